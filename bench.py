@@ -32,6 +32,12 @@ q, k, v resident in HBM (three rotating sets); the projections run for their cos
 Contract: python bench.py --gpus N --steps K --warmup W  ->  ONE JSON line on rank 0.  With ``--gpus N > 1`` and no
 ``WORLD_SIZE`` in the environment the script starts its own N ranks (``torch.distributed.run`` on 127.0.0.1); under an
 external ``torch.distributed.run`` it uses the ranks it is given and checks that N matches.
+
+A plain run sets up, warms up, times the steps and prints the line (``value``, ``ms_per_step``, the step kinds of the timed window
+and, for HunyuanVideo, the whole-schedule figures derived from them).  ``--full`` adds everything else the line can carry: the dense
+GPU comparators, the CPU baseline, the measured legs, per-kernel figures and the roofline, FLUX's tracking figure and Wan's resident
+leg.  ``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float32; inputs are seeded, so two
+builds can be compared output for output; with N > 1 ranks, rank 0's outputs -- its shard of the hidden state under ``hunyuan_sp``).
 """
 from __future__ import annotations
 
@@ -97,7 +103,17 @@ def parse_args():
     ap.add_argument("--sp-no-exchange", action="store_true", help="hunyuan_sp: compute only (probe for the exposed-comm fraction)")
     ap.add_argument("--flux-core", action="store_true", help="flux_c2: attention + image-token MLP only (the step of rounds 1-5) instead of the whole block")
     ap.add_argument("--grid", default="33,45,80", help="hunyuan: latent patch grid T,H,W (default 720x1280x129)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: dense comparators, CPU baseline, legs, roofline / per-kernel figures, FLUX tracking, "
+                         "Wan resident leg (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all: a fixed "
+                         "seeded row sample of larger outputs).  With N > 1 ranks rank 0 writes its own outputs: under hunyuan_sp that is "
+                         "its shard of the hidden state (its rows), comparable between runs at the same N")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ instrumentation
@@ -255,13 +271,16 @@ def build_flux(dev, n_layers, timer, whole_block=True):
         blk = FluxBlock("double" if li < n_double else "single", dev, HID, FFN, H, 3840, 512) if whole_block else None
         layers.append((attn, mlp, (q, k, v, xs), fc1, fc2, act, blk))
     x_state = torch.randn(N, HID, device=dev, dtype=torch.bfloat16, generator=g) if whole_block else None
+    last = {}       # what the last sparse step handed its caller (bench.py --dump-outputs)
 
     def core_step(i):
         """Round 1-5's definition of the FLUX step: every layer's attention + image-token MLP through the sparse modules, nothing else."""
         with torch.no_grad():
             for attn, mlp, (q, k, v, xs), *_ in layers:
-                attn(q, k, v)
-                mlp(xs[i % NX])
+                o = attn(q, k, v)
+                y = mlp(xs[i % NX])
+            last.clear()
+            last.update(attn_out=o, mlp_out=y)     # the last layer's (every layer's outputs are its caller's)
 
     def core_dense_step(i):
         with torch.no_grad():
@@ -284,8 +303,12 @@ def build_flux(dev, n_layers, timer, whole_block=True):
                 mlp_fn = (lambda _xm: dense_mlp(xin, fc1, fc2)[0]) if dense else (lambda _xm: mlp(xin)[0])
                 nb = layers[li + 1][6] if li + 1 < len(layers) else None
                 x, xm = blk.post(x, o, mlp_fn, nb.first_mod() if nb is not None and nb.kind == blk.kind else None)
+            if not dense:
+                last.clear()
+                last.update({"hidden_txt": x[0], "hidden_img": x[1]} if isinstance(x, tuple) else {"hidden": x})
 
     step = block_step if whole_block else core_step
+    step.last_outputs = last
     dense_step = (lambda i: block_step(i, dense=True)) if whole_block else core_dense_step
     desc = {"workload": "flux_c2: FLUX.1-dev 1280x768, B1 H24 D128 N4352, hidden 3072, ffn 12288",
             "layers": n_layers, "double_blocks": n_double, "attn_keep": 672, "mlp_top_keys": 0.3,
@@ -733,6 +756,7 @@ class Hunyuan:
         self.step_events = []
         self.q_scale = 1.0
         self.mlp_only = False
+        self.last_out = None
 
     def _plan_chunks(self, dist_mod, group, heads):
         """Split of the rank's heads into pipeline chunks: explicit (--sp-chunks / --sp-chunk-heads) or from the cost model
@@ -811,7 +835,7 @@ class Hunyuan:
             kind = "skipped"
             inference_step = self.counter.cur_inference_step
             if self.step_cache.should_skip(inference_step):
-                self.step_cache.skip()
+                self.last_out = self.step_cache.skip()
             else:
                 kind = "full" if self.counter.should_do_full_attn_step() else "sparse"
                 if kind == "full":
@@ -832,6 +856,7 @@ class Hunyuan:
                     o = self._attention(li, attn)
                     x, xm = blk.post(x, h, o, self.layers[li + 1][1].first_mod() if li + 1 < L else None)
                 self.step_cache.store(x)
+                self.last_out = x                  # the hidden state after the last block: what the step hands its caller
             self.step_events.append((inference_step, kind, ev))
 
     def dense_step(self, how):
@@ -1292,6 +1317,30 @@ def launch_only(rank, local_rank, world):
 
 
 # ------------------------------------------------------------------------------------------------ main
+DUMP_BUDGET_BYTES = 60 << 20     # all .npy files of --dump-outputs together (64 MB allowed; headers and rounding stay under the rest)
+
+
+def dump_outputs(out_dir, outputs, budget=DUMP_BUDGET_BYTES):
+    """Write each tensor of `outputs` ({name: tensor}) as out_dir/<name>.npy in float32.  A tensor whose float32 copy exceeds its
+    share of `budget` is written as a fixed sample of its rows (leading dimensions flattened): the same seeded, sorted row
+    selection in every run, so two builds compare element for element.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(outputs))
+    written = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        if 4 * t.numel() > share:
+            rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+            keep = max(1, share // (4 * rows.shape[1]))
+            pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = rows.index_select(0, pick.to(rows.device))
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def schedule_honesty_keys(mean, value, steps, step_caching):
     """Top-level keys that let a reader compare the timed window with the WHOLE shipped 50-step schedule without arithmetic
     (reference examples/hunyuan/hyvideo/modules/models.py:732-741,834-835: the skip schedule; step 0 dense, steps 1 / 10 / 40
@@ -1365,6 +1414,7 @@ def main():
         f"{world} ranks need {world} GPUs on this node, found {torch.cuda.device_count()}"
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
+    torch.manual_seed(0)    # weights, modulation vectors, rotary tables, random mask columns: the same inputs in every run with the same arguments
     import torch.distributed as dist
     rccl_info = {}
     if world > 1:
@@ -1392,7 +1442,8 @@ def main():
         # hunyuan_c3: steps 0 (dense), 1 (mask), 2 (sparse) run every kernel of the schedule once; any 50-step window is the whole schedule
         args.warmup = (3 if whole_schedule else 5) if hunyuan else 50 if not wan else 12
     if args.dense_steps < 0:
-        args.dense_steps = 1 if hunyuan else 3 if not wan else 2
+        # the dense comparators are part of --full; a plain run times the sparse steps only (an explicit --dense-steps N still runs them)
+        args.dense_steps = (1 if hunyuan else 3 if not wan else 2) if args.full else 0
 
     timer = KernelTimer()
     timer.period = args.event_period if args.event_period > 0 else (1 if hunyuan else 7)
@@ -1423,6 +1474,8 @@ def main():
     warm_times = wl.step_times() if wl else []
     if wl:
         wl.step_events = []
+    # the HIP-event brackets stay on in a plain run too, although only --full reports them: they add their small bubbles to the timed
+    # steps, and switching them off would move `value` away from what earlier lines measured
     timer.enabled = True
     t0 = time.perf_counter()
     for i in range(args.warmup, args.warmup + args.steps):
@@ -1435,6 +1488,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     timed_times = wl.step_times() if wl else []
+    if args.dump_outputs and rank == 0:
+        outs = {"hidden": wl.last_out} if wl else wan_extra["outputs"]() if wan else dict(step.last_outputs)
+        written = dump_outputs(args.dump_outputs, outs)
+        print(f"bench.py: last timed step's outputs{'' if world == 1 else ' of rank 0 (its shard under hunyuan_sp)'} -> "
+              f"{args.dump_outputs}: {written}", file=sys.stderr)
 
     extra = {}
     mean = {}
@@ -1445,14 +1503,15 @@ def main():
         for _, kind, t in warm_times + timed_times:
             kinds.setdefault(kind, []).append(t)
         mean = {k: sum(v) / len(v) for k, v in kinds.items()}
-        mc = wl.mean_counts()
         extra["timed_steps"] = {"inference_steps": [s for s, _, _ in timed_times],
                                 "kinds": {k: sum(1 for _, kk, _ in timed_times if kk == k) for k in kinds},
                                 "mean_step_s_by_kind (warm-up steps included)": {k: round(v, 4) for k, v in mean.items()}}
-        if args.offload and rank == 0 and "sparse" in mean:
-            extra["offload"] = wl.offload_report(mean["sparse"])
-        extra["mean_kept_keys_per_group"] = mc
-        extra["column_sparsity"] = None if mc is None else round(1.0 - mc / wl.N, 4)
+        if args.full:
+            mc = wl.mean_counts()
+            if args.offload and rank == 0 and "sparse" in mean:
+                extra["offload"] = wl.offload_report(mean["sparse"])
+            extra["mean_kept_keys_per_group"] = mc
+            extra["column_sparsity"] = None if mc is None else round(1.0 - mc / wl.N, 4)
         if all(k in mean for k in ("dense0", "mask", "sparse")):
             full50 = mean["dense0"] + 3 * mean["mask"] + 46 * mean["sparse"]
             cached50 = mean["dense0"] + 3 * mean["mask"] + 21 * mean["sparse"]
@@ -1480,7 +1539,7 @@ def main():
             torch.cuda.synchronize()
             dense_sps = args.dense_steps / (time.perf_counter() - t0)
 
-    if not wl and not wan and not args.flux_core and rank == 0 and world == 1:
+    if args.full and not wl and not wan and not args.flux_core and rank == 0 and world == 1:
         # the step definition of rounds 1-5 (attention + image-token MLP only), measured in this run after the timed region: a key whose
         # meaning does not move between rounds.  20 steps hold the same share of full steps (2 of 20) as the 50-step window (5 of 50).
         core_step, core_dense_step = flux_core
@@ -1506,7 +1565,7 @@ def main():
                              "what": "rounds 1-5's FLUX step (every layer's SparseDiffAttn + SparseDiffMlp call and nothing else), 20 steps after the "
                                      "timed region of this run; `value` is the whole block since round 6"}
 
-    kernels = timer.summary() if rank == 0 else {}
+    kernels = timer.summary() if rank == 0 and args.full else {}    # per-kernel figures and the roofline: --full
     roof = None
     if kernels:
         name, k = max(kernels.items(), key=lambda kv: kv[1]["total_ms"])
@@ -1561,7 +1620,7 @@ def main():
                                          "what": f"hipBLASLt bf16 addmm [{xg.shape[0]}, {blk.fc2.in_features}] x [{blk.fc2.in_features}, {blk.fc2.out_features}] (the block's fc2), 8 launches after the timed region"}
         del hbuf
 
-    if wl and not args.no_legs:
+    if wl and args.full and not args.no_legs:
         if wl.sp and world > 1 and "sparse" in mean:
             t_noex = wl.no_exchange_probe()
             extra["exposed_comm"] = {"sparse_step_s": round(mean["sparse"], 4), "sparse_step_s_without_exchange": round(t_noex, 4),
@@ -1644,7 +1703,7 @@ def main():
         "event_brackets": {"every_nth_call_of_a_timed_op": timer.period,
                            "what": "kernels.*.avg_ms are HIP-event brackets on the launch stream inside the timed region; launches = all calls, timed_launches = the bracketed ones"},
         "dense_gpu_comparator": comparator,
-        "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else (
+        "cpu_baseline": None if (args.no_cpu_baseline or world > 1 or not args.full) else (
             cpu_baseline_hunyuan(n_layers, wl.N, projections=not args.no_projections) if hunyuan else
             wan_extra["cpu_baseline"]() if wan else cpu_baseline_flux(n_layers)),
     }
@@ -1652,7 +1711,7 @@ def main():
         line.update(honesty)     # whole_schedule_steps_per_s, window_bias, tracking: top level, next to `value`
     if wan:
         line.update(wan_extra["line"]())
-        if world == 1 and not args.no_legs and not args.offload and os.environ.get("WAN_RESIDENT") != "1":
+        if args.full and world == 1 and not args.no_legs and not args.offload and os.environ.get("WAN_RESIDENT") != "1":
             # configs[4] as worded keeps the attention caches in pinned host memory (the reference's shipped Wan config, written for 80 GB
             # cards).  The same schedule with the residency policy on (offloading.keep_resident_if_fits: 6 GB of caches in 288 GB of HBM, the
             # kept compact index lists instead of re-deriving them from the packed masks every step), measured by a second process

@@ -28,32 +28,34 @@ def _newer(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _includes(path: str):
+def _includes(path: str, extra_dirs=()):
     """Local headers a source includes (one level is all this tree has)."""
     out = []
     with open(path) as f:
         for line in f:
             if line.startswith('#include "'):
                 h = line.split('"')[1]
-                for base in (CSRC, os.path.join(ROOT, "..", "include")):
+                for base in (CSRC, os.path.join(ROOT, "..", "include"), *extra_dirs):
                     hp = os.path.join(base, h)
                     if os.path.exists(hp):
                         out.append(hp)
     return out
 
 
-def build_hip_lib(force: bool = False, verbose: bool = False) -> str:
-    """One object per source (compiled in parallel, rebuilt only when the source or a header it includes changed), then one link."""
+def build_hip_lib(force: bool = False, verbose: bool = False, out: str = HIP_LIB, flags=(), include_dirs=()) -> str:
+    """One object per source (compiled in parallel, rebuilt only when the source or a header it includes changed), then one link.
+    `out`, `flags` and `include_dirs`: another build of the same sources (tools/probes/mm1_forms: the probe forms)."""
     from concurrent.futures import ThreadPoolExecutor
-    objdir = os.path.join(LIBDIR, "obj")
+    objdir = os.path.join(os.path.dirname(out), "obj")
     os.makedirs(objdir, exist_ok=True)
     common = [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "..", "include", "chipmunk_hip.h")]
     jobs, objs = [], []
     for s in HIP_SOURCES:
         src, obj = os.path.join(CSRC, s), os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(obj)
-        if force or _newer(obj, [src] + common + _includes(src)):
-            jobs.append([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-o", obj, src])
+        if force or _newer(obj, [src] + common + _includes(src, include_dirs)):
+            jobs.append([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", *flags, *[f"-I{d}" for d in include_dirs],
+                         "-c", "-o", obj, src])
 
     def run(cmd):
         if verbose:
@@ -62,9 +64,9 @@ def build_hip_lib(force: bool = False, verbose: bool = False) -> str:
     if jobs:
         with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
             list(ex.map(run, jobs))
-    if jobs or _newer(HIP_LIB, objs):
-        run([HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", HIP_LIB] + objs)
-    return HIP_LIB
+    if jobs or _newer(out, objs):
+        run([HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out] + objs)
+    return out
 
 
 def build_torch_ext(force: bool = False, verbose: bool = False) -> str:

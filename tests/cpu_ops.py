@@ -94,3 +94,34 @@ class recording:
 
     def __exit__(self, *exc):
         RECORD["on"] = False
+
+
+# torch's own bf16 CPU kernels (oneDNN GEMMs, the flash SDPA kernel, vectorised GELU) round differently with the thread count and the
+# CPU's instruction set (AVX2 / AVX-512 / AMX), so their bits are not a fixture.  The modules' dense paths in the pinned runs go through
+# these stand-ins instead: float64 arithmetic, rounded once to the input dtype, the same on every host.
+class ExactLinear(torch.nn.Linear):
+    def forward(self, x):
+        return torch.nn.functional.linear(x.double(), self.weight.double(),
+                                          None if self.bias is None else self.bias.double()).to(x.dtype)
+
+
+class ExactGELU(torch.nn.GELU):
+    def forward(self, x):
+        return torch.nn.functional.gelu(x.double(), approximate=self.approximate).to(x.dtype)
+
+
+def exact_sdpa(q, k, v):
+    s = q.double() @ k.double().transpose(-1, -2) / q.shape[-1] ** 0.5
+    return (torch.softmax(s, dim=-1) @ v.double()).to(q.dtype)
+
+
+class exact_dense_sdpa:
+    """Within the block, torch.nn.functional.scaled_dot_product_attention (the modules' dense eager path) is exact_sdpa."""
+
+    def __enter__(self):
+        self._saved = torch.nn.functional.scaled_dot_product_attention
+        torch.nn.functional.scaled_dot_product_attention = exact_sdpa
+
+    def __exit__(self, *exc):
+        torch.nn.functional.scaled_dot_product_attention = self._saved
+        return False

@@ -161,7 +161,8 @@ def digest(t):
 
 def seeded_linear(fin, fout, seed):
     """nn.Linear with explicit, platform-independent weights (uniform(-1/sqrt(fin), 1/sqrt(fin)) like the default)."""
-    lin = torch.nn.Linear(fin, fout)
+    import cpu_ops
+    lin = cpu_ops.ExactLinear(fin, fout)      # float64 GEMM rounded once: the same bits on every host (see cpu_ops)
     g = torch.Generator().manual_seed(seed)
     bound = 1.0 / fin ** 0.5
     with torch.no_grad():
@@ -228,7 +229,7 @@ def module_runs(ref):
     mlps = []
     for i in range(2):
         fc1, fc2 = seeded_linear(1024, 4096, 4242 + 2 * i), seeded_linear(4096, 1024, 4243 + 2 * i)
-        mlps.append(ref["mmlp"].SparseDiffMlp(i, counter, fc1, torch.nn.GELU(approximate="tanh"), fc2, 6))
+        mlps.append(ref["mmlp"].SparseDiffMlp(i, counter, fc1, cpu_ops.ExactGELU(approximate="tanh"), fc2, 6))
     outs = []
     with cpu_ops.recording() as calls, torch.no_grad():
         for step in range(13):
@@ -246,8 +247,8 @@ def module_runs(ref):
     cfg["attn"]["is_enabled"], cfg["mlp"]["is_enabled"] = False, False
     counter = ref["lc"].LayerCounter(1, 2)
     a = ref["mattn"].SparseDiffAttn(0, counter)
-    m = ref["mmlp"].SparseDiffMlp(0, counter, fc1, torch.nn.GELU(approximate="tanh"), fc2, 6)
-    with torch.no_grad():
+    m = ref["mmlp"].SparseDiffMlp(0, counter, fc1, cpu_ops.ExactGELU(approximate="tanh"), fc2, 6)
+    with torch.no_grad(), cpu_ops.exact_dense_sdpa():     # torch's bf16 CPU kernels are host-dependent: float64 stand-ins (cpu_ops)
         out["c1"] = {"attn_out": a(q, k, v)[:, :, ::4].clone(), "mlp_out": m(x)[:, ::4].clone()}
     cfg["attn"]["is_enabled"], cfg["mlp"]["is_enabled"] = True, True
     return out

@@ -1,6 +1,7 @@
 """bench.py's output contract on the GPU box, at reduced layer counts so the three workloads finish in well under a minute
-each: ONE JSON line with the driver's keys, a `roofline` object for the dominant kernel (HIP-event durations from the timed
-region), a `cpu_baseline` object, the measured legs of the HunyuanVideo line, and the sharded code paths at world size 1."""
+each: ONE JSON line with the driver's keys; with --full a `roofline` object for the dominant kernel (HIP-event durations from the
+timed region), a `cpu_baseline` object and the measured legs of the HunyuanVideo line; the sharded code paths at world size 1; a
+plain run that measures the headline only and dumps the last timed step's outputs."""
 import json
 import os
 import subprocess
@@ -38,7 +39,7 @@ def _check_common(d, steps, warmup):
 
 
 def test_hunyuan_line_with_its_legs():
-    d = _bench("--layers", "4", "--steps", "3", "--warmup", "3")
+    d = _bench("--full", "--layers", "4", "--steps", "3", "--warmup", "3")
     _check_common(d, 3, 3)
     assert d["config"]["workload"].startswith("hunyuan_c3") and d["dtype"] == "bf16" and d["scaling"] == "strong"
     assert set(d["kernels"]) >= {"dense_attn", "csp_128_attn"}
@@ -62,7 +63,7 @@ def test_hunyuan_line_with_its_legs():
 
 
 def test_hunyuan_line_without_the_step_cache_has_the_step_caching_leg():
-    d = _bench("--layers", "4", "--steps", "3", "--warmup", "3", "--no-step-caching", "--no-82", "--dense-steps", "0", "--no-cpu-baseline")
+    d = _bench("--full", "--layers", "4", "--steps", "3", "--warmup", "3", "--no-step-caching", "--no-82", "--dense-steps", "0", "--no-cpu-baseline")
     assert d["config"]["step_caching"] is False
     leg = d["step_caching_leg"]
     assert leg["skipped"] == 6 and leg["kinds"].count("sparse") == 3 and leg["steps_per_s"] > d["value"]
@@ -77,13 +78,13 @@ def test_sharded_paths_at_world_size_one(mode, chunks):
 
 
 def test_wan_and_flux_lines():
-    w = _bench("--workload", "wan_c5", "--layers", "4", "--steps", "3", "--warmup", "12", "--dense-steps", "1")
+    w = _bench("--full", "--workload", "wan_c5", "--layers", "4", "--steps", "3", "--warmup", "12", "--dense-steps", "1")
     _check_common(w, 3, 12)
     assert w["config"]["workload"].startswith("wan_c5") and "fp8" in w["dtype"] and "csp_mlp_mm1_fp8" in w["kernels"]
     assert w["offload"]["modules_offloaded"] >= 1 and w["offload"]["pinned_host_bytes_read_per_sparse_step"] > 0
     assert w["invocation_kinds_seen"]["sparse"] > 0 and w["dense_gpu_comparator"]["sparse_over_dense"] > 0
     assert w["resident_leg"]["value"] > 0 and w["resident_leg"]["over_the_offloaded_run"] > 0.5   # the residency policy, measured by a second process
-    f = _bench("--workload", "flux_c2", "--layers", "6", "--steps", "6", "--warmup", "12", "--dense-steps", "1")
+    f = _bench("--full", "--workload", "flux_c2", "--layers", "6", "--steps", "6", "--warmup", "12", "--dense-steps", "1")
     _check_common(f, 6, 12)
     assert f["config"]["workload"].startswith("flux_c2") and {"csp_attn", "csp_mlp_mm2"} <= set(f["kernels"])
     # microsecond-scale launches: only every 7th call of a timed op carries a HIP-event bracket (a bracket's bubble is ~10 us); all calls are counted
@@ -91,7 +92,7 @@ def test_wan_and_flux_lines():
         assert line["event_brackets"]["every_nth_call_of_a_timed_op"] == 7
         for k in line["kernels"].values():
             assert 1 <= k["timed_launches"] <= k["launches"] and k["timed_launches"] <= k["launches"] // 7 + 1 and k["avg_ms"] > 0
-    g = _bench("--workload", "flux_c2", "--layers", "6", "--steps", "6", "--warmup", "12", "--dense-steps", "0", "--no-cpu-baseline", "--event-period", "1")
+    g = _bench("--full", "--workload", "flux_c2", "--layers", "6", "--steps", "6", "--warmup", "12", "--dense-steps", "0", "--no-cpu-baseline", "--event-period", "1")
     assert all(k["timed_launches"] == k["launches"] for k in g["kernels"].values())
 
 
@@ -100,7 +101,7 @@ def test_two_rank_line_rehearsed_on_one_gpu(mode):
     """`bench.py --gpus 2` end to end on a one-GPU box (BENCH_SHARE_GPU=1: both ranks on cuda:0, gloo with host staging): the
     launcher, the chunk planner fed by a measured exchange, per-chunk modules with their own slots / query-group offsets, the
     max-over-ranks timing, the exposed-communication probe and rank 0's single line."""
-    d = _bench("--gpus", "2", "--sp-mode", mode, "--grid", "8,12,16", "--layers", "3", "--steps", "3", "--warmup", "3", BENCH_SHARE_GPU="1")
+    d = _bench("--full", "--gpus", "2", "--sp-mode", mode, "--grid", "8,12,16", "--layers", "3", "--steps", "3", "--warmup", "3", BENCH_SHARE_GPU="1")
     assert d["n_gpus"] == 2 and d["config"]["dist_world_size"] == 2 and d["config"]["sp_mode"] == mode and d["scaling"] == "strong"
     plan = d["config"]["chunk_plan"]
     assert sum(plan["chunks"]) == (12 if mode == "heads" else 24) and plan["exchange_ms_per_head_measured"] > 0
@@ -141,3 +142,27 @@ def test_block_loop_with_the_fused_rowwise_pass_equals_the_torch_ops():
     scale = b.float().abs().max().item()
     assert (a.float() - b.float()).abs().max().item() <= 2.0 ** -5 * scale, ((a.float() - b.float()).abs().max().item(), scale)
     assert ((a.float() - b.float()).abs() <= 2.0 ** -7 * scale).float().mean().item() > 0.99
+
+
+def test_plain_line_is_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) times the steps and prints the line: no comparators, baseline, legs or per-kernel figures.  Its
+    --dump-outputs files are float32, within 64 MB, and bit-identical from run to run: the inputs are seeded, the library's random key
+    selection starts from its fixed default seed, and its kernels fold in a fixed order."""
+    import numpy as np
+    args = ("--grid", "8,12,16", "--layers", "3", "--steps", "3", "--warmup", "3")
+    d = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"} <= set(d)
+    assert d["steps"] == 3 and d["warmup"] == 3 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["timed_steps"]["inference_steps"] == [3, 4, 5]        # --steps sets the timed steps; --warmup ran 0, 1, 2 before them
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["dense_gpu_comparator"] is None and d["kernels"] == {}
+    assert not any(k.endswith("_leg") for k in d) and "sdpa_flash_libraries" not in d
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) == ["hidden.npy"]
+    total = 0
+    for name in files:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        total += os.path.getsize(tmp_path / "a" / name)
+        assert a.dtype == np.float32 and a.shape == (8 * 12 * 16 + 256, 3072) and np.isfinite(a).all() and np.abs(a).max() > 0
+        np.testing.assert_array_equal(a, b)
+    assert total <= 64 << 20

@@ -1,7 +1,7 @@
 """The forms that were measured against the shipped kernels and live outside the product library (tools/probes/mm1_forms: GEMM tile
-shapes, the two producer / consumer GEMM1 forms, the work-balanced gathered attention launch) stay parity-tested: when
-tools/bin/forms/libchipmunk_hip.so has been built (tools/probes/mm1_forms/build.sh), the MLP parity files and the balanced-launch tests run in a
-subprocess bound to that library with every form enabled.  Skipped when the forms library is absent (it is not part of build())."""
+shapes, the two producer / consumer GEMM1 forms, the work-balanced gathered attention launch) stay parity-tested: build() compiles them into
+tools/bin/forms/libchipmunk_hip.so (tools/probes/mm1_forms/build.sh builds it alone), and the MLP parity files and the balanced-launch tests run
+in a subprocess bound to that library with every form enabled."""
 import os
 import subprocess
 import sys
@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FORMS = os.path.join(ROOT, "tools", "bin", "forms", "libchipmunk_hip.so")
 
 
-@pytest.mark.skipif(not os.path.exists(FORMS), reason="tools/probes/mm1_forms/build.sh has not been run")
 def test_probe_forms_pass_the_mlp_parity_suite():
+    assert os.path.exists(FORMS), f"{FORMS} is missing: run build()"
     env = dict(os.environ, CHIPMUNK_MM1_FORMS="1", CHIPMUNK_HIP_LIB=FORMS,
                LD_LIBRARY_PATH=os.path.dirname(FORMS) + ":" + os.environ.get("LD_LIBRARY_PATH", ""))
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", "tests/test_gpu_mlp.py", "tests/test_gpu_mlp_bench_shape.py",

@@ -112,7 +112,7 @@ def test_bench_two_ranks_over_rccl_reports_transport_and_exposed_communication()
     assert lo["backend"].startswith("nccl") and lo["rank_sum"] == 1 and lo["rccl"]["init"].startswith("nccl")
     assert lo["collectives"]["all_to_all_single"]["payload_ok"] and lo["collectives"]["all_gather_into_tensor"]["payload_ok"]
     for mode in ("heads", "groups"):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--sp-mode", mode, "--grid", "8,12,16", "--layers", "3",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--sp-mode", mode, "--grid", "8,12,16", "--layers", "3",
                             "--steps", "3", "--warmup", "3"], capture_output=True, text=True, timeout=1200)
         assert r.returncode == 0, r.stderr[-2000:]
         d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -32,7 +32,8 @@ def _seeded(shape, seed, scale=1.0):
 
 
 def seeded_linear(fin, fout, seed):
-    lin = torch.nn.Linear(fin, fout)
+    import cpu_ops
+    lin = cpu_ops.ExactLinear(fin, fout)      # float64 GEMM rounded once: the same bits on every host (see cpu_ops)
     g = torch.Generator().manual_seed(seed)
     bound = 1.0 / fin ** 0.5
     with torch.no_grad():
@@ -115,7 +116,7 @@ def test_sparse_mlp_schedule(cpu_chipmunk, gold):
     cpu_chipmunk["mlp"].update(dict(top_keys=0.3, random_keys=0.0, full_step_every=4, block_mask_cache=2,
                                     first_n_dense_layers=1, counts_multiple_of=256))
     counter = LayerCounter(2, 1)
-    mlps = [SparseDiffMlp(i, counter, seeded_linear(1024, 4096, 4242 + 2 * i), torch.nn.GELU(approximate="tanh"),
+    mlps = [SparseDiffMlp(i, counter, seeded_linear(1024, 4096, 4242 + 2 * i), cpu_ops.ExactGELU(approximate="tanh"),
                           seeded_linear(4096, 1024, 4243 + 2 * i), 6) for i in range(2)]
     i = 0
     with cpu_ops.recording() as calls, torch.no_grad():
@@ -132,7 +133,10 @@ def test_sparse_mlp_schedule(cpu_chipmunk, gold):
 
 
 def test_c1_dense_eager_path(cpu_chipmunk, gold):
-    """BASELINE.json configs[0]: FLUX single block, 256 tokens, dim 1024, bf16, dense eager CPU path (is_enabled false)."""
+    """BASELINE.json configs[0]: FLUX single block, 256 tokens, dim 1024, bf16, dense eager CPU path (is_enabled false).  The path's
+    torch calls (SDPA, the Linears, GELU) run as cpu_ops' float64 stand-ins, as in the recorded reference run: bits that do not depend
+    on the host's thread count or instruction set."""
+    import cpu_ops
     from chipmunk_amd.modules import SparseDiffAttn, SparseDiffMlp
     from chipmunk_amd.util.layer_counter import LayerCounter
     cpu_chipmunk["attn"]["is_enabled"] = False
@@ -141,9 +145,9 @@ def test_c1_dense_eager_path(cpu_chipmunk, gold):
     x = _seeded((1, 256, 1024), 73)
     counter = LayerCounter(1, 2)
     a = SparseDiffAttn(0, counter)
-    m = SparseDiffMlp(0, counter, seeded_linear(1024, 4096, 74), torch.nn.GELU(approximate="tanh"),
+    m = SparseDiffMlp(0, counter, seeded_linear(1024, 4096, 74), cpu_ops.ExactGELU(approximate="tanh"),
                       seeded_linear(4096, 1024, 75), 6)
-    with torch.no_grad():
+    with torch.no_grad(), cpu_ops.exact_dense_sdpa():
         assert torch.equal(a(q, k, v)[:, :, ::4], gold["c1"]["attn_out"])
         assert torch.equal(m(x)[:, ::4], gold["c1"]["mlp_out"])
 

@@ -170,6 +170,7 @@ def build_wan(dev, args, timer):
         return torch.addcmul(x, m[5], y), None
 
     stall_probe = [] if os.environ.get("WAN_STALL_PROBE") == "1" else None
+    last_out = {}       # invocation -> the hidden state its last sparse-loop call handed back (bench.py --dump-outputs)
 
     def step(i):
         """One denoise step = n_inv model invocations (reference wan/text2video.py: cond + uncond forward per timestep)."""
@@ -177,7 +178,7 @@ def build_wan(dev, args, timer):
             for inv in range(n_inv):
                 inference_step = counter.cur_inference_step
                 if step_cache.should_skip(inference_step):
-                    step_cache.skip()
+                    last_out[inv] = step_cache.skip()
                     kinds.append("skipped")
                     continue
                 kinds.append("full" if counter.should_do_full_attn_step() else "sparse")
@@ -196,6 +197,7 @@ def build_wan(dev, args, timer):
                     nxt["attn"].storage.load_async()
                     x, xm = block(blk, x, inv, li, "sparse", xm, (nxt["mod"][0], nxt["mod"][1]) if li + 1 < L else None)
                 step_cache.store(x)
+                last_out[inv] = x
 
     def dense_step(i, how="sdpa"):
         with torch.no_grad():
@@ -263,5 +265,6 @@ def build_wan(dev, args, timer):
             out["side_stream_wait_ms_per_block"] = {k: {"mean": round(sum(v) / len(v), 4), "max": round(max(v), 3), "n": len(v)} for k, v in by.items()}
         return out
 
-    extra = {"peak_tflops": {"csp_mlp_mm1_fp8": MFMA_FP8_PEAK_TFS}, "cpu_baseline": cpu_baseline, "line": line}
+    extra = {"peak_tflops": {"csp_mlp_mm1_fp8": MFMA_FP8_PEAK_TFS}, "cpu_baseline": cpu_baseline, "line": line,
+             "outputs": lambda: {f"hidden_inv{inv}": t for inv, t in sorted(last_out.items())}}
     return step, dense_step, desc, extra
