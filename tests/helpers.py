@@ -49,3 +49,281 @@ def structured_qkv(H, N, n_hot, step, layer, seed=31337, gain=6.0):
     for h in range(H):
         k[0, h, hot[h]] += amp * u[h]
     return q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16), hot
+
+
+# --------------------------------------------------------------------------- attention accuracy: exact reference + row metric
+# The attention outputs shrink like sqrt(e / n_keys) with randn inputs, so an absolute tolerance stops seeing defects from a
+# few thousand keys on.  The row-relative error against exact fp64 attention does not: docs/TEST_SENSITIVITY.md.
+#
+# ORACLE_ROW_ERR: the largest row error of the CPU oracle (the reference's roundings: bf16 P, bf16 output) against
+# attn_exact over the case list of tests/test_attn_metric_cpu.py (accumulate form included), rounded up to two digits; that
+# file pins it.
+# ROW_ERR_MARGIN: what a correct kernel may do differently (summation order, tile size, reference point of the
+# exponentials, hardware exp2).  tests/test_attn_metric_cpu.py caps margin * floor at half the weakest mutant's error.
+ORACLE_ROW_ERR = 0.0029
+ROW_ERR_MARGIN = 2.0
+ROW_ERR_BOUND = ROW_ERR_MARGIN * ORACLE_ROW_ERR
+BF16_EPS = 2.0 ** -8          # round-to-nearest bf16 (8 significant bits): relative error of one rounding, per element
+GROUP_ROWS = 192              # query rows that share one index list
+SCALE_LOG2E = 1.4426950408889634 / 128 ** 0.5     # the kernels' constant c: scores in exp2 units are q.k * c
+
+
+def _row_range(rows, n):
+    if rows is None:
+        return 0, n
+    if isinstance(rows, slice):
+        start, stop, step = rows.indices(n)
+        assert step == 1
+        return start, stop
+    return int(rows[0]), int(rows[1])
+
+
+def attn_exact(q, k, v, inds=None, counts=None, rows=None, keep=None, scale_mul=1.0, chunk_bytes=1 << 28, with_top=False):
+    """fp64 ``softmax(q k^T / sqrt(D)) v`` with plain torch on the inputs' device: ``[B, H, rows, D]`` float64.
+
+    inds / counts ``[B, H, G, width]`` / ``[B, H, G]``: per (head, 192-row group) the keys are ``inds[..., :count]`` (count
+    clamped to the key count, as the kernels do), duplicates counted as often as listed.  A group with count 0 has no
+    attention output: its rows are 0 (what every form adds for it) and `row_rel_err` wants them reproduced exactly.
+    rows: ``slice`` or ``(start, stop)`` of query rows.  keep: bool key mask broadcastable to ``[B, H, Nk]`` (dense form) and
+    scale_mul (multiplies the 1/sqrt(D) scale): the defects of tests/test_attn_metric_cpu.py.
+    with_top: also return ``[B, H, rows]`` ``max_j w_ij * ||v_j||`` of the row's heaviest key (w the softmax weights), the
+    ingredient of `top_key_term`."""
+    B, H, Nq, D = q.shape
+    Nk = k.shape[2]
+    r0, r1 = _row_range(rows, Nq)
+    scale = scale_mul / (D ** 0.5)
+    out = torch.zeros(B, H, r1 - r0, D, dtype=torch.float64, device=q.device)
+    tops = torch.zeros(B, H, r1 - r0, dtype=torch.float64, device=q.device)
+    if keep is not None:
+        keep = keep.to(q.device).expand(B, H, Nk)
+
+    def block(qb, kb, vb, mask, top=None):
+        # qb [R, D], kb / vb [n, D] float64; chunked over rows so that the score block stays under chunk_bytes
+        res = torch.empty(qb.shape[0], D, dtype=torch.float64, device=qb.device)
+        step = max(1, chunk_bytes // (8 * max(1, kb.shape[0])))
+        for a in range(0, qb.shape[0], step):
+            s = (qb[a:a + step] @ kb.T) * scale
+            if mask is not None:
+                s = s.masked_fill(~mask[None, :], float("-inf"))
+            w = torch.softmax(s, dim=-1)
+            res[a:a + step] = w @ vb
+            if top is not None:
+                wmax, jmax = w.max(-1)
+                top[a:a + step] = wmax * vb[jmax].norm(dim=-1)
+        return res
+
+    for b in range(B):
+        for h in range(H):
+            qd = q[b, h, r0:r1].double()
+            kd, vd = k[b, h].double(), v[b, h].double()
+            top = tops[b, h] if with_top else None
+            if inds is None:
+                out[b, h] = block(qd, kd, vd, None if keep is None else keep[b, h], top)
+                continue
+            assert keep is None, "defects of a gathered launch are made by editing the index list"
+            for g in range(r0 // GROUP_ROWS, (r1 + GROUP_ROWS - 1) // GROUP_ROWS):
+                a, e = max(r0, g * GROUP_ROWS), min(r1, (g + 1) * GROUP_ROWS)
+                c = min(int(counts[b, h, g]), Nk)
+                if c <= 0 or a >= e:
+                    continue
+                idx = inds[b, h, g, :c].to(q.device).long()
+                out[b, h, a - r0:e - r0] = block(qd[a - r0:e - r0], kd[idx], vd[idx], None, None if top is None else top[a - r0:e - r0])
+    return (out, tops) if with_top else out
+
+
+# --------------------------------------------------------------------------- computed allowance for one documented design rounding
+# Every kernel rounds P to bf16 for the PV product and sums the unrounded p into the normaliser, as the reference (and the
+# oracle) does.  With a running maximum the heaviest key of a row has p = 1 exactly; its rounding is the one rounding the
+# oracle's floor does not contain.  Two kernels take the exponentials against another point when they can prove the scores
+# bounded -- attn64.hip's dense kernel ("Fixed reference point", `nomax`: M_i = |q_i| max|k|) and attn96.hip (`nomax`: no
+# reference point, c folded into Q) -- so there that p is not 1 and its bf16 rounding, up to 2^-8, scales its key's whole
+# contribution: at most 2^-8 w_max ||v_jmax|| / ||x_i|| of row error (w_max the largest softmax weight of the row).  On
+# diffuse rows over thousands of keys that is a tenth of the bound, over a few hundred keys a quarter, on a one-hot row
+# 0.0039; measured: 0.0055 - 0.0058 on the spike / aligned inputs against the oracle's 0.0001.  The term is a function of the inputs alone; it is added to the bound for
+# the rows of the waves that take those paths, and for no other kernel.
+def top_key_term(exact, top):
+    den = exact.norm(dim=-1)
+    return torch.where(den > 0, BF16_EPS * top / den, torch.zeros_like(den))
+
+
+def _wave_all(ok, wave):
+    """ok [B, H, Nq] bool -> the same shape, True where every row of the row's `wave`-row wave is ok (rows past Nq are)"""
+    n = ok.shape[-1]
+    pad = (-n) % wave
+    w = torch.nn.functional.pad(ok, (0, pad), value=True).view(*ok.shape[:-1], -1, wave).all(-1)
+    return w.repeat_interleave(wave, dim=-1)[..., :n]
+
+
+def _score_bound(q, k):
+    """|q_i| max_j |k_j| c per row, exp2 units, fp64 (max over ALL keys of the head, as knorm_max_kernel takes it)"""
+    kmax = k.double().norm(dim=-1).max(-1).values
+    return q.double().norm(dim=-1) * kmax[..., None] * SCALE_LOG2E
+
+
+def attn_exact_dense64(q, k, v, rows=None, running_max=False):
+    """(exact, extra) for attn64.hip's dense kernel: plain exact attention, and per row the `top_key_term` where the row's 64-row
+    wave takes the fixed reference point (2 |q_i| max|k| c <= 64 for all its queries; never with option attn_nomax = 2:
+    running_max), 0 elsewhere.  assert_rows_close takes the pair as its `exact`."""
+    exact, top = attn_exact(q, k, v, rows=rows, with_top=True)
+    r0, r1 = _row_range(rows, q.shape[2])
+    fixed = _wave_all(2.0 * _score_bound(q, k) <= 64.0, 64) & (not running_max) & (q.shape[0] * q.shape[1] * 4 <= (32 << 10))
+    return exact, torch.where(fixed[..., r0:r1], top_key_term(exact, top), torch.zeros_like(top))
+
+
+def attn_exact_csp96(q, k, v, inds, counts, rows=None, running_max=False):
+    """(exact, extra) for attn96.hip.  A 96-row wave whose queries all have |q_i| max|k| c <= 55 drops the reference point and
+    folds c into the bf16 Q fragments (load_q: `pack_bf16x2(lo * SCALE_LOG2E, hi * SCALE_LOG2E)`): for its rows `exact` is
+    attention over bf16(q c) with the rest of the scale in fp64 -- the exact effect of that documented rounding -- and
+    `extra` the `top_key_term`; other waves (and option attn_nomax = 2: running_max): plain exact attention, 0."""
+    plain = attn_exact(q, k, v, inds, counts, rows=rows)
+    r0, r1 = _row_range(rows, q.shape[2])
+    folds = (_wave_all(_score_bound(q, k) <= 55.0, 96) & (not running_max) & (q.shape[0] * q.shape[1] * 4 <= (32 << 10)))[..., r0:r1]
+    if not folds.any():
+        return plain, torch.zeros_like(plain[..., 0])
+    c32 = torch.tensor(0.08838834764, dtype=torch.float32) * torch.tensor(1.44269504089, dtype=torch.float32)   # as compiled
+    qf = (q.float() * c32.to(q.device)).to(torch.bfloat16)
+    folded, top = attn_exact(qf, k, v, inds, counts, rows=rows, scale_mul=0.6931471805599453 * 128 ** 0.5, with_top=True)
+    folds = folds.to(plain.device)
+    return torch.where(folds[..., None], folded, plain), torch.where(folds, top_key_term(folded, top), torch.zeros_like(top))
+
+
+def row_rel_err(o, exact):
+    """Per query row ``||o_i - x_i||_2 / ||x_i||_2`` in fp64, shape ``o.shape[:-1]``.  A NaN / Inf anywhere in ``o_i`` is an
+    infinite error; a row whose exact value is 0 (group without keys) has error 0 if reproduced exactly, else infinite."""
+    o = o.to(exact.device).double()
+    num = (o - exact).norm(dim=-1)
+    den = exact.norm(dim=-1)
+    err = num / den
+    err = torch.where(den == 0, torch.where(num == 0, torch.zeros_like(num), torch.full_like(num, float("inf"))), err)
+    return torch.where(torch.isfinite(o).all(dim=-1) & ~torch.isnan(err), err, torch.full_like(err, float("inf")))
+
+
+def _record_row_err(what, worst, bound):
+    import os
+    path = os.environ.get("CHIPMUNK_ROW_ERR_LOG")      # (how the per-path table of docs/TEST_SENSITIVITY.md is collected)
+    print(f"row error {what}: worst {worst:.5f} (bound {bound:.5f}, {worst / ORACLE_ROW_ERR:.2f} x oracle floor)")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"{what}\t{worst:.6f}\t{bound:.6f}\n")
+
+
+def assert_rows_close(o, exact, bound=ROW_ERR_BOUND, what="", row0=0, extra=None):
+    """Every row of ``o`` ``[B, H, R, D]`` within `bound` (row-relative, see `row_rel_err`) of ``exact``; ``row0`` is the index
+    of the first row in the full launch (for the group / row named in the message); ``extra`` ``[B, H, R]`` widens the bound
+    per row by a derived term.  Returns the worst ``error - extra``."""
+    if isinstance(exact, tuple):           # (exact, per-row term of a design rounding: attn_exact_dense64 / attn_exact_csp96)
+        exact, term = exact
+        extra = term if extra is None else extra.to(term.device) + term
+    assert o.shape == exact.shape, (o.shape, exact.shape)
+    err = row_rel_err(o, exact)
+    if extra is not None:
+        err = err - extra.to(err.device)
+    worst = float(err.max()) if err.numel() else 0.0
+    _record_row_err(what, worst, bound)
+    bad = ~(err <= bound)
+    if bad.any():
+        flat = int(torch.nan_to_num(err, nan=float("inf")).argmax())
+        R = err.shape[2]
+        b, h, r = flat // (err.shape[1] * R), (flat // R) % err.shape[1], flat % R
+        raise AssertionError(
+            f"{what}: row error {worst:.4g} > {bound:.4g} at batch {b} head {h} group {(row0 + r) // GROUP_ROWS} "
+            f"row {row0 + r} (row {(row0 + r) % GROUP_ROWS} of its group); {int(bad.sum())} / {bad.numel()} rows over the "
+            f"bound, {int((~torch.isfinite(o.float())).sum())} non-finite elements")
+    return worst
+
+
+def assert_delta_rows_close(result, base, exact, o_scale=1, bound=ROW_ERR_BOUND, what="", row0=0):
+    """Accumulate forms (``result = base + o_scale * attention``): the error is taken on ``result - base`` against
+    ``o_scale * exact``.  The stored sum is rounded to bf16 once more than a plain output, which moves element e of the
+    difference by at most 2^-8 |result_e| (half of the 2^-7 spacing of 8 significant bits): per row the bound is widened by
+    ``2^-8 ||result_i|| / ||exact_i||``.  Derived, not tuned; with a unit-size base this term is several times the bound
+    itself, which is why the accumulate tests also run on a base of the delta's magnitude."""
+    term = None
+    if isinstance(exact, tuple):
+        exact, term = exact
+    dev = exact.device
+    res, b0 = result.to(dev).double(), base.to(dev).double()
+    den = exact.norm(dim=-1)
+    extra = torch.where(den > 0, BF16_EPS * res.norm(dim=-1) / den, torch.zeros_like(den))
+    delta = torch.where(torch.isfinite(res), res - b0, res)
+    extra = torch.nan_to_num(extra, nan=0.0, posinf=0.0)
+    return assert_rows_close(delta, o_scale * exact, bound, what, row0, extra=extra if term is None else extra + term)
+
+
+# |sum_d o[i, d] - 1| of the oracle with an indicator V (every row of a non-empty group is a probability vector), measured
+# by tests/test_attn_metric_cpu.py::test_indicator_v_row_sums_of_the_oracle on the GPU test's inputs, rounded up
+ORACLE_ROWSUM_ERR = 0.0024
+
+
+def indicator_v(n, kind, device="cpu"):
+    """``v[j, d] = 1 if class(j) == d else 0``, bf16 ``[n, 128]``: o[i, d] is then the softmax mass of class d.
+    kind "key": class(j) = j mod 128; "tile": (j // 32) mod 128 -- a 32-key tile that is skipped, read twice or taken
+    from elsewhere moves ONE column by its whole value, and the column names the tile."""
+    j = torch.arange(n, device=device)
+    cls = j % 128 if kind == "key" else (j // 32) % 128
+    return torch.nn.functional.one_hot(cls, 128).to(torch.bfloat16)
+
+
+# --------------------------------------------------------------------------- inputs shared by test_gpu_attn_accuracy.py and the CPU
+# test that measures the oracle on them (tests/test_attn_metric_cpu.py); all CPU tensors
+
+
+def gathered_matrix_inputs():
+    """3 heads, 4 100 query rows (22 groups, the last of 68 rows), 8 448 keys; per (head, group) a random key order of which a
+    ragged count is kept (0, 7, 33, every key, tails that are no multiple of 16 / 32 / 64); `shared`: one key order per
+    head for all its groups, so that the position in the list is a property of the key and an indicator V can mark it
+    (`v_pos`: class = 32-key tile of the list, mod 128)."""
+    H, nq, nk = 3, 4100, 8448
+    G = (nq + GROUP_ROWS - 1) // GROUP_ROWS
+    q, k, v = [randn_bf16(1, H, n, 128, seed=s) for n, s in ((nq, 211), (nk, 212), (nk, 213))]
+    gen = torch.Generator().manual_seed(214)
+    inds = torch.stack([torch.randperm(nk, generator=gen) for _ in range(H * G)]).view(1, H, G, nk).to(torch.int32)
+    inds[0, 2, 3] = torch.arange(nk, dtype=torch.int32)
+    counts = torch.full((1, H, G), 1100, dtype=torch.int32)          # 1100 = 17 x 64 + 12: a masked tail everywhere
+    counts[0, 0, 1], counts[0, 1, 2], counts[0, 2, 3] = 0, 7, nk      # no key, fewer than a tile, every key (sliced by the plan)
+    counts[0, 0, 5], counts[0, 1, 7], counts[0, 2, 9] = 1093, 2050, 33
+    counts[0, 0, G - 1], counts[0, H - 1, G - 1] = 1055, 4129         # the ragged last group
+    shared = inds[:, :, :1].expand(1, H, G, nk).contiguous()
+    pos = torch.empty(1, H, nk, dtype=torch.long)
+    for h in range(H):
+        pos[0, h, shared[0, h, 0].long()] = torch.arange(nk)
+    v_pos = torch.nn.functional.one_hot((pos // 32) % 128, 128).to(torch.bfloat16)
+    return dict(q=q, k=k, v=v, inds=inds, counts=counts, shared=shared, v_pos=v_pos)
+
+
+STRADDLE_PATTERNS = {"all rows at 0.9": (0.9, None), "all rows at 0.99": (0.99, None), "all rows at 1.01": (1.01, None),
+                     "all rows at 1.1": (1.1, None), "one row per other wave at 1.1, the rest at 0.9": (0.9, 1.1)}
+
+
+def straddle_inputs(align, pattern, threshold, mult, period, nq, nk, seed, planted=False):
+    """q, k, v bf16 ``[1, 2, n, 128]`` with |q_i| set so that mult * |q_i| * max_j |k_j| * c = f_i * threshold, f from the pattern
+    (row 5 of every `period` rows gets the second value); the bound is evaluated in fp64 on the bf16 inputs and returned
+    per row in units of the threshold.
+    align: "random"; "along": every query close to the direction of the largest-norm key (scores at the top of the proven
+    range); "against": all keys share a direction and the queries point the other way (scores near -M: the exponentials at
+    the bottom of the range).  planted: key 0 gets 1.5 x the largest norm (the caller keeps it out of the index lists)."""
+    H = 2
+    g = torch.Generator().manual_seed(seed)
+    q, k, v = [torch.randn(1, H, n, 128, generator=g) for n in (nq, nk, nk)]
+    u = torch.randn(H, 1, 128, generator=g)
+    u = u / u.norm(dim=-1, keepdim=True)
+    if align == "against":
+        k = 0.5 * k + 128 ** 0.5 * u
+    if planted:
+        k[0, :, 0] *= 1.5 * k.norm(dim=-1).max() / k[0, :, 0].norm(dim=-1, keepdim=True)
+    k = k.to(torch.bfloat16)
+    kmax, jmax = k.double().norm(dim=-1).max(-1)                    # [1, H]
+    if align == "along":
+        d = torch.stack([k[0, h, jmax[0, h]].float() / float(kmax[0, h]) for h in range(H)])[:, None]
+        q = d + 0.02 * q
+    elif align == "against":
+        q = -u + 0.02 * q
+    f_lo, f_hi = STRADDLE_PATTERNS[pattern]
+    f = torch.full((nq,), f_lo, dtype=torch.float64)
+    if f_hi is not None:
+        f[5::period] = f_hi
+    target = f[None, None, :] * threshold / (mult * kmax[..., None] * SCALE_LOG2E)
+    q = (q.double() / q.double().norm(dim=-1, keepdim=True) * target[..., None]).to(torch.bfloat16)
+    bound = mult * q.double().norm(dim=-1) * kmax[..., None] * SCALE_LOG2E / threshold
+    assert ((bound - f).abs() < 2e-3).all()
+    return q, k, v.to(torch.bfloat16), bound

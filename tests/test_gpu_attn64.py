@@ -1,10 +1,12 @@
 """The one-wave-per-SIMD dense kernel (csrc/attn64.hip), forced through option attn_dense64 = 1 at sizes the oracle
-finishes in seconds: same tolerances as test_gpu_attn.py (bf16 o: atol = rtol = 2e-2; l: rtol 1e-3 / 2e-3)."""
+finishes in seconds: same tolerances as test_gpu_attn.py (bf16 o: atol = rtol = 2e-2; l: rtol 1e-3 / 2e-3), and the same
+row-relative bound against exact fp64 attention (helpers.assert_rows_close, docs/TEST_SENSITIVITY.md)."""
 import pytest
 import torch
 
 import oracle
-from helpers import assert_close_bf16, randn_bf16
+from helpers import (assert_close_bf16, assert_delta_rows_close, assert_rows_close, attn_exact, attn_exact_csp96, attn_exact_dense64,
+                     randn_bf16)
 
 pytestmark = pytest.mark.gpu
 
@@ -14,6 +16,24 @@ def dev():
     import chipmunk_amd  # noqa: F401
     assert torch.cuda.is_available()
     return torch.device("cuda:0")
+
+
+def _exact(dev, q, k, v, inds=None, counts=None):
+    """exact fp64 attention of CPU inputs, computed on the device"""
+    return attn_exact(q.to(dev), k.to(dev), v.to(dev), inds, counts)
+
+
+def _exact64(dev, q, k, v):
+    """... with the per-row term of the dense kernel's fixed reference point (helpers.attn_exact_dense64)"""
+    return attn_exact_dense64(q.to(dev), k.to(dev), v.to(dev))
+
+
+def _exact_csp(dev, request, q, k, v, inds, counts):
+    """... over bf16(q c) where attn96.hip folds the scale, with its per-row term (helpers.attn_exact_csp96), when that kernel runs: index rows
+    whose width is no multiple of 4 go to the general kernel (attn.hip, `fits96`)"""
+    if request.node.callspec.params["forced_csp"] == "attn_csp96" and inds.shape[-1] % 4 == 0:
+        return attn_exact_csp96(q.to(dev), k.to(dev), v.to(dev), inds, counts)
+    return _exact(dev, q, k, v, inds, counts)
 
 
 @pytest.fixture()
@@ -35,6 +55,7 @@ def test_dense64_vs_oracle(dev, forced, nq, nk):
     o_ref, l_ref = oracle.dense_attn(q, k, v)
     o, l = torch.ops.chipmunk.dense_attn(q.to(dev), k.to(dev), v.to(dev))
     assert_close_bf16(o, o_ref, what=f"dense64 o {nq}x{nk}")
+    assert_rows_close(o, _exact64(dev, q, k, v), what=f"dense64 {nq}x{nk}")
     torch.testing.assert_close(l.cpu(), l_ref, rtol=1e-3, atol=0)
 
 
@@ -45,6 +66,7 @@ def test_dense64_strided_and_batched(dev, forced):
     o, l = torch.ops.chipmunk.dense_attn(q, k, v)
     o_ref, l_ref = oracle.dense_attn(q.cpu().contiguous(), k.cpu().contiguous(), v.cpu().contiguous())
     assert_close_bf16(o, o_ref, what="strided dense64")
+    assert_rows_close(o, attn_exact_dense64(q, k, v), what="dense64, strided and batched")
     torch.testing.assert_close(l.cpu(), l_ref, rtol=1e-3, atol=0)
 
 
@@ -73,6 +95,7 @@ def test_dense64_running_max_update_paths(dev, forced, pattern):
     o_ref, l_ref = oracle.dense_attn(q, k, v)
     o, l = torch.ops.chipmunk.dense_attn(q.to(dev), k.to(dev), v.to(dev))
     assert_close_bf16(o, o_ref, what=f"dense64, {pattern}")
+    assert_rows_close(o, _exact64(dev, q, k, v), what=f"dense64, {pattern}")
     torch.testing.assert_close(l.cpu(), l_ref, rtol=2e-3, atol=0)
 
 
@@ -86,6 +109,10 @@ def test_dense64_matches_general_kernel_at_scale(dev):
     o_b, l_b = torch.ops.chipmunk.dense_attn(q, k, v)
     _native.set_option("attn_dense64", 0)
     assert_close_bf16(o_b, o_a.float().cpu(), what="dense64 vs general kernel")
+    rows = slice(4000, 4400)
+    exact = attn_exact(q, k, v, rows=rows)
+    assert_rows_close(o_a[:, :, rows], exact, what="general dense kernel, 8448 keys", row0=rows.start)
+    assert_rows_close(o_b[:, :, rows], attn_exact_dense64(q, k, v, rows=rows), what="dense64, 8448 keys", row0=rows.start)
     torch.testing.assert_close(l_b, l_a, rtol=1e-3, atol=0)
 
 
@@ -102,7 +129,7 @@ def forced_csp(dev, request):
 
 @pytest.mark.parametrize("n,nk,count", [(384, 384, 128), (1000, 1000, 333), (1152, 1152, 1152), (576, 2000, 64), (200, 640, 7), (960, 960, 0),
                                          (576, 997, 333), (390, 1001, 1001)])   # (index rows that are not 16-byte aligned: the dword load path)
-def test_csp64_random_indices_vs_oracle(dev, forced_csp, n, nk, count):
+def test_csp64_random_indices_vs_oracle(dev, forced_csp, request, n, nk, count):
     """csp_128_attn: ragged query groups, counts that are not multiples of the 64-key tile (masked tail), fewer keys than a
     tile, all keys, no keys"""
     import math
@@ -116,6 +143,7 @@ def test_csp64_random_indices_vs_oracle(dev, forced_csp, n, nk, count):
     o_ref = oracle.csp_128_attn(q, k, v, inds, counts)
     o = torch.ops.chipmunk.csp_128_attn(q.to(dev), k.to(dev), v.to(dev), inds.to(dev), counts.to(dev))
     assert_close_bf16(o, o_ref, what=f"csp64 {n}x{nk} count {count}")
+    assert_rows_close(o, _exact_csp(dev, request, q, k, v, inds, counts), what=f"{request.node.callspec.params['forced_csp'][5:]} {n}x{nk} count {count}")
 
 
 @pytest.mark.parametrize("how", ["option", "large_scores"])
@@ -144,10 +172,12 @@ def test_csp96_running_maximum_schedule_vs_oracle(dev, how):
         _native.set_option("attn_csp96", 0)
         _native.set_option("attn_nomax", 0)
     assert_close_bf16(o, o_ref, what=f"csp96 running-maximum schedule ({how})")
+    assert_rows_close(o, attn_exact_csp96(q.to(dev), k.to(dev), v.to(dev), inds, counts, running_max=how == "option"),
+                      what=f"csp96 running-maximum schedule ({how})")
 
 
 @pytest.mark.parametrize("o_scale", [1, -1])
-def test_csp64_inplace_and_out_forms(dev, forced_csp, o_scale):
+def test_csp64_inplace_and_out_forms(dev, forced_csp, request, o_scale):
     import math
     from helpers import random_index_sets
     H, n = 2, 1344
@@ -161,12 +191,19 @@ def test_csp64_inplace_and_out_forms(dev, forced_csp, o_scale):
     acc = base.clone().to(dev)
     torch.ops.chipmunk.csp_attn(q.to(dev), k.to(dev), v.to(dev), acc, inds.to(dev), counts.to(dev), o_scale)
     assert_close_bf16(acc, ref, atol=3e-2, what="csp64 in place")
+    which = request.node.callspec.params["forced_csp"][5:]
+    exact = _exact_csp(dev, request, q, k, v, inds, counts)
+    assert_delta_rows_close(acc, base, exact, o_scale, what=f"{which} in place, unit base")
+    # a base of the delta's magnitude (randn x the delta's RMS), where the stored sum's rounding hides nothing
+    small = randn_bf16(1, H, n, 128, seed=5, scale=float(_exact(dev, q, k, v, inds, counts).pow(2).mean().sqrt()))
+    out_small = torch.ops.chipmunk.csp_attn_out(q.to(dev), k.to(dev), v.to(dev), small.to(dev), inds.to(dev), counts.to(dev), o_scale)
+    assert_delta_rows_close(out_small, small, exact, o_scale, what=f"{which} out of place, small base")
     out = torch.ops.chipmunk.csp_attn_out(q.to(dev), k.to(dev), v.to(dev), base.to(dev), inds.to(dev), counts.to(dev), o_scale)
     assert torch.equal(out, acc), "the out-of-place form is the in-place form on a copy"
     assert torch.equal(out[0, 1, 2 * 192:3 * 192].cpu(), base[0, 1, 2 * 192:3 * 192]), "a group without keys keeps the base"
 
 
-def test_csp64_sliced_heavy_items_merge(dev, forced_csp):
+def test_csp64_sliced_heavy_items_merge(dev, forced_csp, request):
     """a few groups keep ALL keys while the rest keep few: the plan cuts the heavy items into key slices that different
     workgroups process and the last arriver merges"""
     import math
@@ -183,6 +220,7 @@ def test_csp64_sliced_heavy_items_merge(dev, forced_csp):
     o_ref = oracle.csp_128_attn(q, k, v, inds, counts)
     o = torch.ops.chipmunk.csp_128_attn(q.to(dev), k.to(dev), v.to(dev), inds.to(dev), counts.to(dev))
     assert_close_bf16(o, o_ref, what="csp64 sliced items")
+    assert_rows_close(o, _exact_csp(dev, request, q, k, v, inds, counts), what=f"{request.node.callspec.params['forced_csp'][5:]} sliced items")
     again = torch.ops.chipmunk.csp_128_attn(q.to(dev), k.to(dev), v.to(dev), inds.to(dev), counts.to(dev))
     assert torch.equal(o, again), "slices fold in slice order: run-to-run deterministic"
 
@@ -220,6 +258,10 @@ def test_colsum64_vs_oracle(dev, n, nk, route):
     G = math.ceil(n / 192)
     assert cs.shape == (1, H, G, n) and cs.dtype == torch.bfloat16   # Nq columns, the first Nk meaningful (dense_colsum_attn.cu:580-583)
     assert_close_bf16(o, o_ref, what="colsum64 o")
+    # (every route but the forced running maximum takes a reference point that is not the row maximum where a wave can: the fixed
+    #  one, or -log2 p_i of the unit-weight column sums, attn64.hip "CSUM: with the reference point of query i at -log2 p_i")
+    x = _exact(dev, q2, k, v) if route == "fused_runmax" else _exact64(dev, q2, k, v)
+    assert_rows_close(o, x, what=f"colsum o, {route}, {n}x{nk}")
     torch.testing.assert_close(l.cpu(), l_ref, rtol=1e-3, atol=0)
     assert_close_bf16(cs[..., :nk], cs_ref[..., :nk], atol=2e-3, rtol=3e-2, what="colsum64 cs vs oracle")
     assert torch.equal(cs[..., :nk], again[..., :nk]), "no order-dependent reduction: run-to-run identical"
@@ -247,6 +289,7 @@ def test_fused_colsum_strided_batched_and_degenerate_p(dev):
         _native.set_option("attn_fused_colsum", 0)
     assert torch.equal(o, o4) and torch.equal(cs, cs4) and torch.equal(l, l4), "chunked launches change nothing"
     assert_close_bf16(o, o_ref, what="fused colsum, strided o")
+    assert_rows_close(o, attn_exact_dense64(q, k, v), what="fused colsum o, strided and batched")
     torch.testing.assert_close(l.cpu(), l_ref, rtol=1e-3, atol=0)
     assert_close_bf16(cs, cs_ref, atol=2e-3, rtol=3e-2, what="fused colsum, strided cs")
 
@@ -310,6 +353,9 @@ def test_fused_colsum_running_max_update_paths(dev, pattern):
         for opt in ("attn_colsum64", "attn_dense64", "attn_fused_colsum"):
             _native.set_option(opt, 0)
     assert_close_bf16(o, o_ref, what=f"fused colsum o, {pattern}")
+    exact = _exact64(dev, q, k, v)
+    assert_rows_close(o, exact, what=f"fused colsum o, {pattern}")
+    assert_rows_close(o2, exact, what=f"two-pass colsum o, {pattern}")
     torch.testing.assert_close(l.cpu(), l_ref, rtol=2e-3, atol=0)
     assert_close_bf16(cs, cs_ref, atol=2e-3, rtol=3e-2, what=f"fused cs vs oracle, {pattern}")
     assert_close_bf16(cs, cs2.float().cpu(), atol=2e-3, rtol=3e-2, what=f"fused cs vs two-pass, {pattern}")
@@ -319,7 +365,7 @@ def test_fused_colsum_running_max_update_paths(dev, pattern):
 
 
 @pytest.mark.parametrize("pattern", ["ramp", "spike", "spike_first", "descending"])
-def test_csp64_running_max_update_paths(dev, forced_csp, pattern):
+def test_csp64_running_max_update_paths(dev, forced_csp, request, pattern):
     """the gathered one-wave-per-SIMD kernels on the constructions that force the reference point of the exponentials to
     move (per query block, with the rescale of that block's accumulator registers) for some lanes and not for others"""
     import math
@@ -348,6 +394,7 @@ def test_csp64_running_max_update_paths(dev, forced_csp, pattern):
         inds = order.to(torch.int32).expand(1, H, G, n).contiguous()
         o = torch.ops.chipmunk.csp_128_attn(q.to(dev), k.to(dev), v.to(dev), inds.to(dev), counts.to(dev))
         assert_close_bf16(o, o_ref, what=f"gathered, {name} key order, {pattern}")
+        assert_rows_close(o, _exact_csp(dev, request, q, k, v, inds, counts), what=f"{request.node.callspec.params['forced_csp'][5:]}, {name} key order, {pattern}")
 
 
 @pytest.mark.parametrize("scale,expect", [(1.0, "fixed"), (4.0, "running")])
@@ -363,6 +410,8 @@ def test_dense64_fixed_reference_point_and_its_fallback(dev, forced, scale, expe
     o_ref, l_ref = oracle.dense_attn(q, k, v)
     o, l = torch.ops.chipmunk.dense_attn(q.to(dev), k.to(dev), v.to(dev))
     assert_close_bf16(o, o_ref, what=f"dense64 ({expect} reference)")
+    exact = _exact(dev, q, k, v)
+    assert_rows_close(o, _exact64(dev, q, k, v), what=f"dense64 ({expect} reference point)")
     torch.testing.assert_close(l.cpu(), l_ref, rtol=1e-3, atol=0)
     _native.set_option("attn_nomax", 2)
     try:
@@ -370,6 +419,7 @@ def test_dense64_fixed_reference_point_and_its_fallback(dev, forced, scale, expe
     finally:
         _native.set_option("attn_nomax", 0)
     assert_close_bf16(o2, o_ref, what="dense64, running maximum forced")
+    assert_rows_close(o2, exact, what=f"dense64, running maximum forced, inputs x {scale:g}")
     torch.testing.assert_close(l2.cpu(), l_ref, rtol=1e-3, atol=0)
     if expect == "running":
         assert torch.equal(o, o2) and torch.equal(l, l2), "inputs too large for the bound: both runs take the running-maximum loop"

@@ -2,6 +2,8 @@
 csp_128_attn.cu:355-461): the last `items mod slots` items of a launch run as three 64-row workgroups with one query block per wave.
 
 Same tolerances as tests/test_gpu_attn.py (bf16 outputs atol = rtol = 2e-2 vs the oracle, 3e-2 for the accumulate form); run to run bit-stable.
+Split and unsplit launches share most of their code, so agreeing with each other is not enough: both are also held to the row-relative
+bound against exact fp64 attention (helpers.assert_rows_close / assert_delta_rows_close, docs/TEST_SENSITIVITY.md).
 """
 import math
 
@@ -9,7 +11,7 @@ import pytest
 import torch
 
 import oracle
-from helpers import assert_close_bf16, randn_bf16, random_index_sets
+from helpers import assert_close_bf16, assert_delta_rows_close, assert_rows_close, attn_exact, randn_bf16, random_index_sets
 
 pytestmark = pytest.mark.gpu
 
@@ -72,6 +74,11 @@ def test_row_split_forced_all_forms_bit_equal_and_vs_oracle(dev, o_scale):
         assert_close_bf16(a, b, what="row-split vs unsplit launch")
     assert_close_bf16(outs[1][0], o_ref, atol=3e-2, what="row-split csp_attn")
     assert torch.equal(outs[1][0][0, 0, 192:384].cpu(), o0[0, 0, 192:384])     # the group without keys is left as it was
+    exact = attn_exact(qd, kd, vd, inds, counts)
+    for opt, name in ((1, "row-split"), (2, "unsplit")):
+        assert_delta_rows_close(outs[opt][0], o0, exact, o_scale, what=f"{name} csp_attn, unit base")
+        assert_delta_rows_close(outs[opt][1], o0, exact, o_scale, what=f"{name} csp_attn_out, unit base")
+        assert_rows_close(outs[opt][2], exact, what=f"{name} csp_128_attn")
 
 
 def test_row_split_ragged_index_rows(dev):
@@ -92,6 +99,13 @@ def test_row_split_ragged_index_rows(dev):
         b = torch.ops.chipmunk.csp_attn_out_ragged(qd, kd, vd, base, flat, offs, cntd, 1)
     assert torch.equal(a, b), "ragged and padded index rows through the same row-split launch: same bits"
     assert_close_bf16(b, ref, what="row-split (ragged rows) vs unsplit launch")
+    exact = attn_exact(qd, kd, vd, inds, counts)
+    assert_delta_rows_close(b, base, exact, 1, what="row-split, ragged index rows, unit base")
+    assert_delta_rows_close(ref, base, exact, 1, what="unsplit, padded index rows, unit base")
+    small = randn_bf16(1, H, n, 128, seed=7, scale=float(exact.pow(2).mean().sqrt())).to(dev)    # a base of the delta's magnitude
+    with row_split(1):
+        c = torch.ops.chipmunk.csp_attn_out_ragged(qd, kd, vd, small, flat, offs, cntd, 1)
+    assert_delta_rows_close(c, small, exact, 1, what="row-split, ragged index rows, small base")
 
 
 def test_row_split_flux_launch_by_shape(dev):
@@ -122,3 +136,8 @@ def test_row_split_flux_launch_by_shape(dev):
         assert_close_bf16(out[:, h:h + 1, rows], o_ref, atol=3e-2, what=f"row-split item (head {h}, group {g})")
     for _ in range(10):
         assert torch.equal(torch.ops.chipmunk.csp_attn_out(qd, kd, vd, base, indd, cntd, 1), out)
+    exact = attn_exact(qd, kd, vd, inds, counts)
+    assert_delta_rows_close(out, base, exact, 1, what="FLUX launch, row-split tail by shape, unit base")
+    small = randn_bf16(1, H, n, 128, seed=6, scale=0.06).to(dev)                                  # sqrt(e / 672) = 0.064: the delta's RMS
+    assert_delta_rows_close(torch.ops.chipmunk.csp_attn_out(qd, kd, vd, small, indd, cntd, 1), small, exact, 1,
+                            what="FLUX launch, row-split tail by shape, small base")

@@ -1,14 +1,17 @@
 """Parity on the launches bench.py actually makes (round-2 verdict, weak 1d / next 8): HunyuanVideo C3 size, ALL 24 heads, the
 ragged key counts that the module's own mask pipeline produces (dense_colsum_attn -> top-k + 1 % random + static text columns ->
 bit-packed mask -> sorted indices), HIP `csp_128_attn` / `csp_attn_out` against the C oracle on sampled (head, group) items --
-text groups with all 119 056 keys included -- and the same launch with the running-maximum loop forced."""
+text groups with all 119 056 keys included -- and the same launch with the running-maximum loop forced.
+
+Outputs over ~9 000 keys have an RMS of 0.018, the size of the absolute tolerance: the same items are also held to the
+row-relative bound against exact fp64 attention computed on the device (helpers.assert_rows_close, docs/TEST_SENSITIVITY.md)."""
 import math
 
 import pytest
 import torch
 
 import oracle
-from helpers import assert_close_bf16
+from helpers import assert_close_bf16, assert_delta_rows_close, assert_rows_close, attn_exact_csp96
 
 pytestmark = pytest.mark.gpu
 
@@ -77,6 +80,15 @@ def _oracle_item(launch, h, gi):
     return oracle.csp_128_attn(qg, kh, vh, ind, cnt), rows
 
 
+def _exact_item(launch, h, gi, q=None):
+    """fp64 attention of one (head, group) on the device, as attn96.hip (the kernel of these launches) rounds it where it folds the
+    scale into Q (helpers.attn_exact_csp96)"""
+    r0, r1 = gi * 192, min((gi + 1) * 192, N)
+    q = launch["q"] if q is None else q
+    return attn_exact_csp96(q[:, h:h + 1], launch["k"][:, h:h + 1], launch["v"][:, h:h + 1], launch["inds"][:, h:h + 1],
+                      launch["counts"][:, h:h + 1], rows=(r0, r1)), r0
+
+
 def test_bench_mask_is_ragged_and_has_full_text_groups(bench_launch):
     c = bench_launch["counts"][0].float()
     assert c.max().item() >= N - 192 and c.min().item() < 0.2 * N, "the bench's launch mixes 119 k-key text / tail groups with ~9 k-key ones"
@@ -102,6 +114,12 @@ def test_c3_all_heads_bench_launch_vs_oracle(dev, bench_launch, form):
             # sparse step = cache + sparse = dense (the cache was built as dense - sparse from the same q, k, v): bf16 roundings only
             want = L["cache"][:, h:h + 1, rows].float().cpu() + ref.float()
             assert_close_bf16(o[:, h:h + 1, rows], want, atol=3e-2, what=f"bench launch (cache + delta), head {h} group {gi}")
+        exact, r0 = _exact_item(L, h, gi)
+        what = f"bench launch {form}, head {h} group {gi} ({int(L['counts'][0, h, gi])} keys) vs fp64"
+        if form == "csp_128_attn":
+            assert_rows_close(o[:, h:h + 1, rows], exact, what=what, row0=r0)
+        else:
+            assert_delta_rows_close(o[:, h:h + 1, rows], L["cache"][:, h:h + 1, rows], exact, 1, what=what, row0=r0)
     assert_close_bf16(torch.ops.chipmunk.csp_attn_out(L["q"], L["k"], L["v"], L["cache"], L["inds"], L["counts"], 1)[:, :2],
                       L["o_dense"][:, :2].float().cpu(), atol=6e-2, what="sparse step reproduces the dense step it was cached from")
 
@@ -133,6 +151,8 @@ def test_c3_running_maximum_loop_vs_oracle(dev, bench_launch, how):
         rows = slice(gi * 192, min((gi + 1) * 192, N))
         ref = oracle.csp_128_attn(q[:, :, rows].cpu(), kc, vc, inds[:, :, gi:gi + 1].cpu().contiguous(), counts[:, :, gi:gi + 1].cpu().contiguous())
         assert_close_bf16(o[:, :, rows], ref, what=f"running-maximum loop ({how}), group {gi}")
+        exact = attn_exact_csp96(q, k, v, inds, counts, rows=(rows.start, rows.stop), running_max=how == "option")
+        assert_rows_close(o[:, :, rows], exact, what=f"running-maximum loop ({how}), group {gi} vs fp64", row0=rows.start)
 
 
 def test_bench_launch_is_run_to_run_identical(dev, bench_launch):
@@ -193,3 +213,7 @@ def test_bench_launch_ragged_rows_and_token_major_cache(dev, bench_launch):
     got = ops.csp_attn_out_ragged(L["q"], L["k"], L["v"], cache_tm, flat, offsets, L["counts"], 1)
     assert got.stride() == cache_tm.stride() and got.permute(0, 2, 1, 3).is_contiguous()
     assert torch.equal(got, ref)
+    for h, gi in _sample_items(L["counts"], n_random=4):
+        exact, r0 = _exact_item(L, h, gi)
+        rows = slice(r0, r0 + exact[0].shape[2])
+        assert_delta_rows_close(got[:, h:h + 1, rows], cache[:, h:h + 1, rows], exact, 1, what=f"ragged rows, head {h} group {gi} vs fp64", row0=r0)

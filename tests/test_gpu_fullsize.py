@@ -1,12 +1,16 @@
 """Parity at BASELINE.json's FULL sizes through size-independent properties (the oracle is too slow there), plus the
-domain's edge cases: empty / ragged groups, duplicate (colliding) indices, all-true / all-false mask rows."""
+domain's edge cases: empty / ragged groups, duplicate (colliding) indices, all-true / all-false mask rows.
+
+At these key counts the attention outputs are as small as the absolute tolerances below, so every attention result is
+also held to the row-relative bound against exact fp64 attention on the rows the test slices (helpers.assert_rows_close,
+docs/TEST_SENSITIVITY.md)."""
 import math
 
 import pytest
 import torch
 
 import oracle
-from helpers import assert_close_bf16, randn_bf16
+from helpers import assert_close_bf16, assert_delta_rows_close, assert_rows_close, attn_exact, attn_exact_csp96, randn_bf16
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +39,9 @@ def test_c3_sparse_attention_with_all_keys_equals_dense(dev):
     rows = slice(50000, 50384)
     ref = torch.nn.functional.scaled_dot_product_attention(q[:, :, rows].float(), k.float(), v.float())
     assert_close_bf16(o_dense[:, :, rows], ref, atol=1e-2, rtol=2e-2, what="C3 dense vs SDPA slice")
+    exact = attn_exact(q, k, v, rows=rows)
+    assert_rows_close(o_dense[:, :, rows], exact, what="C3 dense vs fp64 slice", row0=rows.start)
+    assert_rows_close(o_sparse[:, :, rows], exact, what="C3 identity sparse vs fp64 slice", row0=rows.start)
     lref = 1.0 / torch.exp((q[:, :, rows].float() @ k.float().transpose(-1, -2)) / math.sqrt(128)).sum(-1, keepdim=True)
     torch.testing.assert_close(l[:, :, rows], lref, rtol=2e-3, atol=0)
 
@@ -55,6 +62,10 @@ def test_c3_fused_column_sums_are_a_partition_of_unity(dev):
     assert cs.shape == (1, H, G, N)
     assert_close_bf16(o, o_d.float().cpu(), atol=4e-3, rtol=1e-2, what="C3 one-pass o vs dense_attn")
     torch.testing.assert_close(l2, l, rtol=2e-3, atol=0)
+    for rows in (slice(300 * 192, 301 * 192), slice(N - 208, N)):
+        exact = attn_exact(q, k, v, rows=rows)
+        assert_rows_close(o[:, :, rows], exact, what="C3 one-pass o vs fp64 slice", row0=rows.start)
+        assert_rows_close(o_d[:, :, rows], exact, what="C3 dense_attn o vs fp64 slice", row0=rows.start)
     tot = cs.float().sum(-1)
     rows = torch.full((G,), 192.0, device=dev)
     rows[-1] = N - 192 * (G - 1)
@@ -97,6 +108,10 @@ def test_c3_cache_plus_delta_identity(dev):
     assert sparse.shape == q.shape
     back = (o - sparse) + sparse
     assert_close_bf16(back, o, atol=2e-2, rtol=2e-2, what="C3 cache + delta")
+    for rows in ((5 * 192, 6 * 192), (300 * 192, 302 * 192), ((G - 1) * 192, N)):
+        assert_rows_close(sparse[:, :, rows[0]:rows[1]], attn_exact_csp96(q, k, v, inds, counts, rows=rows),   # (attn96.hip at this size)
+                          what="C3 sparse (7 296 of 119 056 keys) vs fp64", row0=rows[0])
+        assert_rows_close(o[:, :, rows[0]:rows[1]], attn_exact(q, k, v, rows=rows), what="C3 dense vs fp64", row0=rows[0])
     # the sparse result is a convex combination of the selected V rows: bounded by their extrema per group
     sel = v[0, 0, inds[0, 0, 5, :count].long()].float()
     grp = sparse[0, 0, 5 * 192:6 * 192].float()
@@ -164,11 +179,14 @@ def test_empty_and_ragged_groups(dev):
     o_ref = oracle.csp_128_attn(q, k, v, inds, counts)
     o = torch.ops.chipmunk.csp_128_attn(q.to(dev), k.to(dev), v.to(dev), inds.to(dev), counts.to(dev))
     assert_close_bf16(o, o_ref, what="ragged counts")
+    exact = attn_exact(q.to(dev), k.to(dev), v.to(dev), inds, counts)
+    assert_rows_close(o, exact, what="ragged counts vs fp64")
     assert (o[0, 0, :192] == 0).all() and (o[0, 1, 192:384] == 0).all()       # empty group -> zeros (documented)
     o0 = randn_bf16(1, H, n, 128, seed=9)
     oi = o0.clone().to(dev)
     torch.ops.chipmunk.csp_attn(q.to(dev), k.to(dev), v.to(dev), oi, inds.to(dev), counts.to(dev), -1)
     assert torch.equal(oi[0, 0, :192].cpu(), o0[0, 0, :192])                   # in place: empty group leaves o alone
+    assert_delta_rows_close(oi, o0, exact, -1, what="ragged counts, in place, vs fp64")
 
 
 def test_duplicate_indices_are_not_deduplicated(dev):
@@ -182,6 +200,7 @@ def test_duplicate_indices_are_not_deduplicated(dev):
     o_ref = oracle.csp_128_attn(q, k, v, inds, counts)
     o = torch.ops.chipmunk.csp_128_attn(q.to(dev), k.to(dev), v.to(dev), inds.to(dev), counts.to(dev))
     assert_close_bf16(o, o_ref, what="duplicates vs oracle")
+    assert_rows_close(o, attn_exact(q.to(dev), k.to(dev), v.to(dev), inds, counts), what="duplicates vs fp64")
     inds1 = inds.clone(); inds1[0, 0, :, 32:] = 0
     o_single = torch.ops.chipmunk.csp_128_attn(q.to(dev), k.to(dev), v.to(dev), inds1.to(dev),
                                               torch.full((1, H, 2), 32, dtype=torch.int32, device=dev))
@@ -288,27 +307,39 @@ def test_sliced_heavy_items_match_unsliced_and_oracle(H):
         r0, r1 = gi * 192, min(N, gi * 192 + 192)
         o_ref = oracle.csp_128_attn(q[:, :, r0:r1].contiguous(), k, v, inds[:, :, gi:gi + 1, :N].contiguous(), counts[:, :, gi:gi + 1].contiguous())
         assert_close_bf16(o[:, :, r0:r1], o_ref, what=f"group {gi} vs oracle")
+    exact = {gi: attn_exact(qd, kd, vd, inds, counts, rows=(gi * 192, min(N, gi * 192 + 192))) for gi in (5, G - 1, 7, 9, 11)}
+    exact96 = {gi: attn_exact_csp96(qd, kd, vd, inds, counts, rows=(gi * 192, min(N, gi * 192 + 192))) for gi in exact}   # (as attn96.hip rounds)
+    for gi, x in exact.items():
+        r0, r1 = gi * 192, min(N, gi * 192 + 192)
+        assert_rows_close(o[:, :, r0:r1], exact96[gi], what=f"sliced items, attn96, group {gi} vs fp64", row0=r0)
+        assert_rows_close(o_gen[:, :, r0:r1], x, what=f"sliced items, general kernel, group {gi} vs fp64", row0=r0)
+        assert_rows_close(o_tail[:, :, r0:r1], x, what=f"sliced items + tail cut, general kernel, group {gi} vs fp64", row0=r0)
     # accumulate forms
     base = randn_bf16(1, H, N, 128, seed=77)
     out = torch.ops.chipmunk.csp_attn_out(qd, kd, vd, base.to(dev), indd, cntd, -1)
     want = (base.float() - o.float().cpu().to(torch.bfloat16).float()).to(torch.bfloat16)
     assert_close_bf16(out, want, atol=1e-2, rtol=1e-2, what="csp_attn_out with sliced items")
+    # the same with a base of the delta's magnitude (what the product adds to: a cached attention output), where the
+    # rounding of the stored sum no longer hides the delta
+    small = randn_bf16(1, H, N, 128, seed=78, scale=0.01)
+    out_small = torch.ops.chipmunk.csp_attn_out(qd, kd, vd, small.to(dev), indd, cntd, -1)
+    for gi, x in exact96.items():
+        r0, r1 = gi * 192, min(N, gi * 192 + 192)
+        assert_delta_rows_close(out[:, :, r0:r1], base[:, :, r0:r1], x, -1, what=f"csp_attn_out, sliced items, unit base, group {gi}", row0=r0)
+        assert_delta_rows_close(out_small[:, :, r0:r1], small[:, :, r0:r1], x, -1, what=f"csp_attn_out, sliced items, small base, group {gi}", row0=r0)
     inpl = base.clone().to(dev)
     torch.ops.chipmunk.csp_attn(qd, kd, vd, inpl, indd, cntd, -1)
     assert torch.equal(inpl, out), "in-place and out-of-place accumulate agree bit for bit"
 
 
 # ------------------------------------------------------------------------------------------------ config-sized cases
-def test_c2_flux_attention_full_size_all_heads(dev):
-    """BASELINE configs[1] at its real size: 24 heads, 4352 tokens, 672 kept keys per 192-query group, in-place delta
-    kernel.  Heads 0, 11 and 23 against the oracle; every head through the cache identity (o - sparse) + sparse == o up to
-    the two bf16 roundings; and `csp_attn_out` == clone + in-place, bit for bit."""
+def _c2_flux_attention_full_size_all_heads(dev, base_scale):
     from helpers import random_index_sets
     H, N, count = 24, 4352, 672
     G = math.ceil(N / 192)
     q, k, v = [randn_bf16(1, H, N, 128, seed=s) for s in (31, 32, 33)]
     inds, counts = random_index_sets(1, H, G, N, count, N, seed=34, multiple_of=112)
-    base = randn_bf16(1, H, N, 128, seed=35)
+    base = randn_bf16(1, H, N, 128, seed=35, scale=base_scale)
     qd, kd, vd, indd, cntd = [t.to(dev) for t in (q, k, v, inds, counts)]
     o = base.clone().to(dev)
     torch.ops.chipmunk.csp_attn(qd, kd, vd, o, indd, cntd, -1)
@@ -322,6 +353,20 @@ def test_c2_flux_attention_full_size_all_heads(dev):
     back = o.clone()
     torch.ops.chipmunk.csp_attn(qd, kd, vd, back, indd, cntd, 1)
     assert_close_bf16(back, base, atol=2e-2, rtol=2e-2, what="C2 (o - sparse) + sparse")
+    assert_delta_rows_close(o, base, attn_exact(qd, kd, vd, inds, counts), -1, what=f"C2 csp_attn, all heads, base x {base_scale:g}, vs fp64")
+
+
+def test_c2_flux_attention_full_size_all_heads(dev):
+    """BASELINE configs[1] at its real size: 24 heads, 4352 tokens, 672 kept keys per 192-query group, in-place delta
+    kernel.  Heads 0, 11 and 23 against the oracle; every head through the cache identity (o - sparse) + sparse == o up to
+    the two bf16 roundings; `csp_attn_out` == clone + in-place, bit for bit; every head's delta against exact fp64."""
+    _c2_flux_attention_full_size_all_heads(dev, 1.0)
+
+
+def test_c2_flux_attention_full_size_all_heads_base_of_the_deltas_magnitude(dev):
+    """the same on a base as small as the delta (an attention output over 672 randn keys has an RMS of sqrt(e / 672) = 0.064;
+    what the product adds to is a cached attention output), where the rounding of the stored sum does not hide the delta"""
+    _c2_flux_attention_full_size_all_heads(dev, 0.06)
 
 
 def test_c5_wan_fp8_gemm1_full_size(dev):
@@ -371,6 +416,7 @@ def test_c5_wan_attention_shapes(dev):
     for rows in (slice(0, 384), slice(N - 300, N)):
         ref = torch.nn.functional.scaled_dot_product_attention(q[:, :, rows].float(), k.float(), v.float())
         assert_close_bf16(o_dense[:, :, rows], ref, atol=1e-2, rtol=2e-2, what="Wan dense vs SDPA")
+        assert_rows_close(o_dense[:, :, rows], attn_exact(q, k, v, rows=rows), what="Wan dense vs fp64", row0=rows.start)
     count = 3328
     inds = torch.zeros(1, H, G, G * 192, dtype=torch.int32, device=dev)
     for h in range(H):
@@ -384,6 +430,9 @@ def test_c5_wan_attention_shapes(dev):
         ref = oracle.csp_128_attn(qc[:, h:h + 1, r0:r1].contiguous(), kc[:, h:h + 1].contiguous(), vc[:, h:h + 1].contiguous(),
                                   ic[:, h:h + 1, gi:gi + 1, :N].contiguous(), counts[:, h:h + 1, gi:gi + 1].cpu().contiguous())
         assert_close_bf16(o[:, h:h + 1, r0:r1], ref, what=f"Wan sparse head {h} group {gi} vs oracle")
+    for gi in (0, 77, G - 1):
+        r0, r1 = gi * 192, min(N, gi * 192 + 192)
+        assert_rows_close(o[:, :, r0:r1], attn_exact_csp96(q, k, v, inds, counts, rows=(r0, r1)), what=f"Wan sparse, all heads, group {gi} vs fp64", row0=r0)
 
 
 @pytest.mark.gpu
@@ -431,6 +480,10 @@ def test_plan_tail_cut_items_match_uncut_and_oracle():
             o_ref = oracle.csp_128_attn(q[:, H - 1:, r0:r1].contiguous(), k[:, H - 1:], v[:, H - 1:], inds[:, H - 1:, gi:gi + 1].contiguous(),
                                         counts[:, H - 1:, gi:gi + 1].contiguous())
             assert_close_bf16(o_cut[:, H - 1:, r0:r1], o_ref, what=f"cut item (head {H - 1}, group {gi}) vs oracle, attn_csp96={opt}")
+        for gi in (G - 5, G - 4, G - 3, G - 2, G - 1):
+            r0, r1 = gi * 192, min(N, gi * 192 + 192)
+            assert_rows_close(o_cut[:, :, r0:r1], (attn_exact if opt else attn_exact_csp96)(qd, kd, vd, inds, counts, rows=(r0, r1)),
+                              what=f"cut items, group {gi} vs fp64, attn_csp96={opt}", row0=r0)
 
 
 def test_c5_wan_cross_attention_shape(dev):
@@ -451,6 +504,7 @@ def test_c5_wan_cross_attention_shape(dev):
     for rows in (slice(0, 256), slice(17000, 17300), slice(M - 192, M)):
         ref = torch.nn.functional.scaled_dot_product_attention(q[:, :, rows].float(), k.float(), v.float())
         assert_close_bf16(o[:, :, rows], ref, atol=1e-2, rtol=2e-2, what="Wan cross-attention vs SDPA")
+        assert_rows_close(o[:, :, rows], attn_exact(q, k, v, rows=rows), what="Wan cross-attention vs fp64", row0=rows.start)
     # the head-major form gives the same values
     o2, _ = torch.ops.chipmunk.dense_attn(q, k, v)
     assert torch.equal(o2, o)
