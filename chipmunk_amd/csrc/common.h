@@ -32,6 +32,10 @@ __device__ __forceinline__ void glds16(const void *gsrc, void *lds_wave_base) {
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base) {
     return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 0xffffffff, 0x00020000);
 }
+// ... with the tensor's real size in bytes: the hardware range check then drops every access whose offset lies at or past `bytes`
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000);
+}
 __device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, uint32_t lane_off_bytes, uint32_t wave_off_bytes,
                                        void *lds_wave_base) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LDS_PTR(lds_wave_base), 16, (int)lane_off_bytes, (int)wave_off_bytes, 0, 0);

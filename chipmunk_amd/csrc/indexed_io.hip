@@ -474,7 +474,8 @@ __global__ __launch_bounds__(256) void bitunpack_kernel(const uint8_t *packed, u
 // =====================================================================================  2-byte transpose
 // [B, R, C] -> [B, C, R] for 16-bit elements (the column-major activation cache of the sparse MLP is act^T,
 // reference modules/mlp.py:56).  64x64 tiles through LDS: 128-byte row segments on both the read and the write side.
-__global__ __launch_bounds__(256) void transpose16_kernel(const uint16_t *src, uint16_t *dst, int R, int C) {
+// The output rows have a pitch of ld >= R elements; elements [R, ld) of every row are written as zeros (the tile rows past R are).
+__global__ __launch_bounds__(256) void transpose16_kernel(const uint16_t *src, uint16_t *dst, int R, int C, int ld) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[64][72];
     const int64_t boff = (int64_t)blockIdx.z * R * C;
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
@@ -501,11 +502,11 @@ __global__ __launch_bounds__(256) void transpose16_kernel(const uint16_t *src, u
     for (int i = 0; i < 2; ++i) {
         const int item = i * 256 + tid, c = item >> 3, ch = item & 7;
         if (c0 + c >= C) continue;
-        uint16_t *d = dst + boff + (int64_t)(c0 + c) * R + r0 + ch * 8;
-        if (r0 + ch * 8 + 8 <= R && ((R & 7) == 0)) *(u32x4 *)d = *(const u32x4 *)&tile[c][ch * 8];
+        uint16_t *d = dst + (int64_t)blockIdx.z * C * ld + (int64_t)(c0 + c) * ld + r0 + ch * 8;
+        if (r0 + ch * 8 + 8 <= ld && ((ld & 7) == 0)) *(u32x4 *)d = *(const u32x4 *)&tile[c][ch * 8];
         else
             for (int e = 0; e < 8; ++e)
-                if (r0 + ch * 8 + e < R) d[e] = tile[c][ch * 8 + e];
+                if (r0 + ch * 8 + e < ld) d[e] = tile[c][ch * 8 + e];
     }
 }
 
@@ -933,7 +934,17 @@ extern "C" int chipmunk_transpose16(const void *src, void *dst, int B, int R, in
     CM_CHECK(src && dst && B > 0 && R > 0 && C > 0, "transpose16: bad arguments");
     CM_CHECK((C & 7) == 0 || true, "unreachable");
     hipLaunchKernelGGL(transpose16_kernel, dim3((C + 63) / 64, (R + 63) / 64, B), dim3(256), 0, (hipStream_t)stream,
-                       (const uint16_t *)src, (uint16_t *)dst, R, C);
+                       (const uint16_t *)src, (uint16_t *)dst, R, C, R);
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+
+extern "C" int chipmunk_transpose16_pitched(const void *src, void *dst, int B, int R, int C, int ld, void *stream) {
+    CM_CHECK(src && dst && B > 0 && R > 0 && C > 0, "transpose16: bad arguments");
+    CM_CHECK(ld >= R, "transpose16: the output pitch ld (%d) must be at least R (%d)", ld, R);
+    // the grid's row tiles cover [0, ld): the tiles past R hold zeros, which is what the padding gets
+    hipLaunchKernelGGL(transpose16_kernel, dim3((C + 63) / 64, (ld + 63) / 64, B), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t *)src, (uint16_t *)dst, R, C, ld);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }

@@ -161,6 +161,7 @@ struct Mm1Params {
     int update_cache;  // 1: also apply the scatter-add of this tile's deltas to the cache block it already holds in LDS;
                        // 2 (fp8): store the new activation into the cache like the reference's Triton kernel
     const float *scale_a, *scale_b;  // fp8 only: reciprocal quantisation scales (one float each)
+    int ldc;           // pitch of the column-major cache in elements: ldc >= M, ldc % 8 == 0 (M itself for the [F, M] contiguous cache)
 };
 
 // One TM x TN output tile (TM rows of group g starting at m_off, packed columns n0 .. n0+TN-1): 4 waves as 2 x 2, each a
@@ -189,12 +190,17 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     const int wm = w / WNC, wn = w % WNC;
     const int32_t *idxg = p.indices + (int64_t)g * p.F;
 
-    const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.a), rb = make_rsrc(p.b);
+    // Ragged last group (M % 128 != 0): `rows` of the tile's TM rows exist.  An A row only feeds its own output row, so the LDS rows
+    // past `rows` may hold anything as long as they are never stored: their DMA pieces re-read the tile's last live row (as the B rows
+    // past the count re-read a live one), and the epilogue masks its stores by row.  The descriptors of a and the cache carry the real
+    // sizes, so an offset past the tensor would be dropped by the range check, not fetched.
+    const int rows = min(TM, p.M - (g * BM + m_off));
+    const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.a, (uint32_t)p.M * p.K * ESZ), rb = make_rsrc(p.b);
     uint32_t aoff[A_INST], boff[B_INST];  // byte offsets
 #pragma unroll
     for (int i = 0; i < A_INST; ++i) {
         const int row = KT::lane_row(w * A_INST + i, lane);
-        aoff[i] = (uint32_t)(g * BM + m_off + row) * p.K * ESZ + KT::src_chunk_elems(row, lane) * 2u;
+        aoff[i] = (uint32_t)(g * BM + m_off + min(row, rows - 1)) * p.K * ESZ + KT::src_chunk_elems(row, lane) * 2u;
     }
 #pragma unroll
     for (int i = 0; i < B_INST; ++i) {
@@ -223,15 +229,19 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     static_assert(!FP8 || STAGED, "the fp8 form is only built for tile shapes with the staged epilogue");
     constexpr int LPR = TM * 2 / 16;                                  // 16-byte chunks per cache row
     constexpr int C_INST = STAGED ? EPI / (1024 * NW) : 1;            // DMA instructions per wave
-    const __amdgpu_buffer_rsrc_t rc = make_rsrc(p.cache);
+    // The cache is [F, ldc]: a 16-byte piece that starts below M lies inside its column (ldc >= ceil8(M)), so the masks are
+    // piece-granular; pieces that start at or past M re-read the column's first piece of this tile and are not written back.
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc(p.cache, (uint32_t)p.F * p.ldc * 2u);
     uint32_t coff[C_INST];
+    auto piece_row = [&](int jj) { return ((lane % LPR) ^ (jj & (LPR - 1))) << 3; };   // first tile row of the lane's piece of column jj
     if constexpr (STAGED) {
 #pragma unroll
         for (int i = 0; i < C_INST; ++i) {
             const int jj = (w * C_INST + i) * (64 / LPR) + lane / LPR;  // tile-local packed column
             const int j = n0 + jj;
             const int col = idxg[j < cnt ? j : n0];
-            coff[i] = ((uint32_t)col * p.M + g * BM + m_off + (((lane % LPR) ^ (jj & (LPR - 1))) << 3)) * 2u;
+            const int ms = piece_row(jj);
+            coff[i] = ((uint32_t)col * p.ldc + g * BM + m_off + (ms < rows ? ms : 0)) * 2u;
         }
     }
     auto issue_cache = [&](int buf) {
@@ -423,6 +433,7 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
             const u32x4 v = *(const u32x4 *)(ot_row(r) + (ch << 4));
             const int j = n0 + ch * 8;
             uint16_t *cp = p.c + (int64_t)(g * BM + m_off + r) * p.F + j;
+            if (r >= rows) continue;   // ragged last group: no row at or past M is stored
             if (j + 8 <= cnt && (p.F & 7) == 0) {
                 *(u32x4 *)cp = v;
             } else {
@@ -435,7 +446,7 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
 #pragma unroll
             for (int i = 0; i < C_INST; ++i) {
                 const int jj = (w * C_INST + i) * (64 / LPR) + lane / LPR;
-                if (n0 + jj < cnt)
+                if (n0 + jj < cnt && piece_row(jj) < rows)
                     *(u32x4 *)((unsigned char *)p.cache + coff[i]) = *(const u32x4 *)(Ct + (w * C_INST + i) * 1024 + lane * 16);
             }
         }
@@ -445,7 +456,7 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
             const int j = n0 + wn * (TN / WNC) + n4 * 32 + (lane & 31);
             const bool live = j < cnt;
             const int col = live ? idxg[j] : 0;
-            const uint16_t *crow = p.cache + (int64_t)col * p.M;
+            const uint16_t *crow = p.cache + (int64_t)col * p.ldc;
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
@@ -487,7 +498,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const Mm1Params p) {
     // (kernel arguments, the live-tile map, wave start-up: 5.4 k of a 41 k-cycle tile at the Wan2.1 fp8 shape, tools/mlp_prof.py) and
     // with the previous tile's stores draining under the next tile's index loads.  (Requesting the NEXT tile's gather indices during
     // the current tile -- one exposed round trip less -- measured no gain at the fp8 shape, 209 vs 209-224 us, for 40 more registers.)
-    const TilePlan pl = plan_tiles<BN>(p.counts, p.M / BM, p.NT, p.NR, p.slots_per_xcd, NSUB);
+    const TilePlan pl = plan_tiles<BN>(p.counts, (p.M + BM - 1) / BM, p.NT, p.NR, p.slots_per_xcd, NSUB);
     const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
     for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
         const TileMap tm = tile_at(pl, slot);
@@ -502,6 +513,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const Mm1Params p) {
             constexpr int SUB_NST = (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
             const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
             if (n0 >= cnt || p.probe == 3) continue;  // probe 3: time the launch without its tail
+            if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
             mm1_tile<64, 64, BK, (SUB_NST > 4 ? 4 : SUB_NST), FP8>(p, smem, g, (tm.sub & 1) * 64, n0, cnt);
         }
         __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
@@ -543,7 +555,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
     const int wm = w / WNG, wn = w % WNG;
 
     // all column tiles of fc2^T are live (N2 is dense); the map only reorders them for L2 reuse (see map_tile)
-    const int G = p.M / BM;
+    const int G = (p.M + BM - 1) / BM;
     const int xcdq = (G * p.NT) >> 3, xcdr = (G * p.NT) & 7;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     if (slot >= xcdq + (xcd < xcdr ? 1 : 0)) return;
@@ -587,12 +599,15 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
     const int nkb = (cnt + BK - 1) / BK;
     if (nkb == 0) return;
 
-    const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.a), rb = make_rsrc(p.b);
+    // ragged last group: `rows` of the 128 rows exist; the A pieces of the others re-read the last live row (a row of A only feeds its
+    // own output row) and the epilogue neither loads nor stores their rows of C
+    const int rows = min(BM, p.M - g * BM);
+    const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.a, (uint32_t)p.M * p.F * 2u), rb = make_rsrc(p.b);
     uint32_t aoff[A_INST];  // byte offsets
 #pragma unroll
     for (int i = 0; i < A_INST; ++i) {
         const int row = KT::lane_row(w * A_INST + i, lane);
-        aoff[i] = ((uint32_t)(g * BM + row) * p.F + KT::src_chunk_elems(row, lane)) * 2u;
+        aoff[i] = ((uint32_t)(g * BM + min(row, rows - 1)) * p.F + KT::src_chunk_elems(row, lane)) * 2u;
     }
     // The gather keys of a tile are wave-uniform per DMA row, so they are fetched with SCALAR loads (lgkmcnt): the
     // vector-memory counter then only counts LDS-DMA and the counted vmcnt pipeline below stays intact.  The keys of
@@ -779,14 +794,14 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
             const int item = it * (NW * 64) + tid;
             const int r = item / CPRO, ch = item % CPRO;
             const int n = n0 + ch * 8;
-            olds[it] = n < p.N2 ? *(const u32x4 *)(p.c + (int64_t)(g * BM + r) * p.N2 + n) : (u32x4){0u, 0u, 0u, 0u};
+            olds[it] = (n < p.N2 && r < rows) ? *(const u32x4 *)(p.c + (int64_t)(g * BM + r) * p.N2 + n) : (u32x4){0u, 0u, 0u, 0u};
         }
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
             const int item = it * (NW * 64) + tid;
             const int r = item / CPRO, ch = item % CPRO;
             const int n = n0 + ch * 8;
-            if (n >= p.N2) continue;  // N2 is a multiple of 8: a chunk is live or dead as a whole
+            if (n >= p.N2 || r >= rows) continue;  // N2 is a multiple of 8: a chunk is live or dead as a whole
             const u32x4 a = *(const u32x4 *)(smem + r * (BN * 2) + ((ch ^ (r & (CPRO - 1) & 31)) << 4));
             uint16_t *cp = p.c + (int64_t)(g * BM + r) * p.N2 + n;
             const u32x4 old = olds[it];
@@ -830,18 +845,19 @@ constexpr int SC_COLS = 64;
 constexpr int SC_LD = 136;  // padded row length of the transposed tile (bf16 elements)
 
 __global__ __launch_bounds__(256) void scatter_add_kernel(const uint16_t *packed, uint16_t *unpacked,
-                                                          const int32_t *indices, const int32_t *counts, int M, int F) {
+                                                          const int32_t *indices, const int32_t *counts, int M, int F, int ldc) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[SC_COLS * SC_LD];
     const int g = blockIdx.y, c0 = blockIdx.x * SC_COLS;
     const int cnt = counts[g];
     if (c0 >= cnt) return;
     const int tid = threadIdx.x;
+    const int rows = min(128, M - g * 128);   // ragged last group: rows past M are neither read from `packed` nor written to the cache
     // load: 128 rows x 8 chunks of 16 B
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int item = i * 256 + tid;
         const int r = item >> 3, ch = item & 7;
-        const u32x4 v = *(const u32x4 *)(packed + (int64_t)(g * 128 + r) * F + c0 + ch * 8);
+        const u32x4 v = r < rows ? *(const u32x4 *)(packed + (int64_t)(g * 128 + r) * F + c0 + ch * 8) : (u32x4){0u, 0u, 0u, 0u};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             tile[(ch * 8 + 2 * e) * SC_LD + r] = (uint16_t)(v[e] & 0xffffu);
@@ -859,9 +875,9 @@ __global__ __launch_bounds__(256) void scatter_add_kernel(const uint16_t *packed
         const int c = item >> 4, ch = item & 15;
         src[i] = nullptr;
         olds[i] = (u32x4){0u, 0u, 0u, 0u};
-        if (c0 + c >= cnt) continue;
+        if (c0 + c >= cnt || ch * 8 >= rows) continue;   // a piece that starts below M lies inside its column (ldc >= ceil8(M))
         const int col = indices[(int64_t)g * F + c0 + c];
-        src[i] = unpacked + (int64_t)col * M + g * 128 + ch * 8;
+        src[i] = unpacked + (int64_t)col * ldc + g * 128 + ch * 8;
         olds[i] = *(const u32x4 *)src[i];
     }
 #pragma unroll
@@ -886,11 +902,26 @@ int check_mlp_common(int M, int F, const int32_t *indices, const int32_t *counts
     CM_CHECK(F > 0 && F % 64 == 0, "mlp: F must be a positive multiple of 64 (got %d)", F);
     return CHIPMUNK_OK;
 }
+// The *_ragged entries: any positive M (G = ceil(M / 128) groups, the last one short) ...
+int check_mlp_ragged(int M, int F, const int32_t *indices, const int32_t *counts) {
+    CM_CHECK(indices && counts, "mlp: indices / counts missing");
+    CM_CHECK(M > 0, "mlp: M must be positive (got %d)", M);
+    CM_CHECK(F > 0 && F % 64 == 0, "mlp: F must be a positive multiple of 64 (got %d)", F);
+    return CHIPMUNK_OK;
+}
+// ... and a pitch for the column-major cache [F, ldc]
+int check_cache_pitch(int M, int F, int ldc) {
+    CM_CHECK(ldc >= M && ldc % 8 == 0,
+             "mlp: the cache pitch ldc must be at least M and a multiple of 8 elements (got ldc = %d, M = %d): a [F, M] cache with M %% 8 != 0 "
+             "needs padded columns", ldc, M);
+    CM_CHECK((int64_t)F * ldc < (1ll << 31), "mlp: F * ldc too large for 32-bit offsets");
+    return CHIPMUNK_OK;
+}
 
-int launch_scatter_add(const void *packed, void *unpacked, const int32_t *indices, const int32_t *counts, int M, int F,
+int launch_scatter_add(const void *packed, void *unpacked, const int32_t *indices, const int32_t *counts, int M, int F, int ldc,
                        hipStream_t s) {
-    hipLaunchKernelGGL(scatter_add_kernel, dim3(F / SC_COLS, M / BM), dim3(256), 0, s, (const uint16_t *)packed,
-                       (uint16_t *)unpacked, indices, counts, M, F);
+    hipLaunchKernelGGL(scatter_add_kernel, dim3(F / SC_COLS, (M + BM - 1) / BM), dim3(256), 0, s, (const uint16_t *)packed,
+                       (uint16_t *)unpacked, indices, counts, M, F, ldc);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }
@@ -907,7 +938,7 @@ int launch_mm2_variant(const Mm2Params &p0, hipStream_t s) {
     if (p.NR > p.NT) p.NR = p.NT;
     // length-aware placement: two-workgroups-per-CU forms only (what the census measured); option mm2_order = 1 keeps tile order
     p.cus_per_xcd = (WPS == 2 && !chipmunk_get_option("mm2_order")) ? device_cu_count() / 8 : 0;
-    hipLaunchKernelGGL(kern, dim3((((p.M / BM) * p.NT + 7) / 8) * 8), dim3(NW * 64), LDS, s, p);
+    hipLaunchKernelGGL(kern, dim3(((((p.M + BM - 1) / BM) * p.NT + 7) / 8) * 8), dim3(NW * 64), LDS, s, p);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }
@@ -918,7 +949,7 @@ int launch_mm2(const void *a, const void *b, void *c, const int32_t *indices, co
     CM_CHECK((int64_t)M * F < (1ll << 31) && (int64_t)F * N2 < (1ll << 31), "mm2: M*F or F*N2 too large for 32-bit offsets");
     Mm2Params p = {(const uint16_t *)a, (const uint16_t *)b, (uint16_t *)c, indices, counts, M, F, N2, 0, 0, chipmunk_get_option("mm1_probe")};
 #ifdef CHIPMUNK_MM1_PROBES
-    switch (chipmunk_get_option("mm2_variant")) {
+    if (M % BM == 0) switch (chipmunk_get_option("mm2_variant")) {   // (the probe forms know whole groups only)
         case 1: return launch_mm2_variant<256, 64, 2, 1>(p, s);
         case 2: return launch_mm2_variant<128, 64, 2, 2>(p, s);
         case 3: return launch_mm2_variant<128, 64, 3, 1>(p, s);
@@ -964,7 +995,7 @@ int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated =
     const int resident_per_xcd = WPS_FIT * device_cu_count() / 8;
     p.slots_per_xcd = (chipmunk_get_option("mm1_no_split") || NW != 4) ? 0 : resident_per_xcd;
     // persistent grid: the resident slots, or fewer when the launch has fewer tiles than slots (every tile gets its own workgroup)
-    const int tiles_per_xcd = ((p.M / BM) * p.NT + 7) / 8;
+    const int tiles_per_xcd = (((p.M + BM - 1) / BM) * p.NT + 7) / 8;
     const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
     hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(NW * 64), LDS, s, p);
     CM_LAUNCH_CHECK();
@@ -974,17 +1005,19 @@ int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated =
 }  // namespace
 
 namespace {
+// `ragged`: the *_ragged entries' contract (any M, cache pitch ldc); otherwise the reference's (M % 128 == 0, ldc == M)
 int mm1_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
-              const int32_t *counts, int M, int K, int F, hipStream_t stream, int update_cache, bool *cache_updated) {
+              const int32_t *counts, int M, int K, int F, int ldc, bool ragged, hipStream_t stream, int update_cache, bool *cache_updated) {
     CM_CHECK(a && b && c && bias && pa_cache, "csp_mlp_mm1: null tensor pointer");
-    if (int e = check_mlp_common(M, F, indices, counts)) return e;
+    if (int e = ragged ? check_mlp_ragged(M, F, indices, counts) : check_mlp_common(M, F, indices, counts)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
     CM_CHECK(K > 0 && K % 64 == 0, "csp_mlp_mm1: K must be a positive multiple of 64 (got %d)", K);
-    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * M < (1ll << 31),
+    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
              "csp_mlp_mm1: operand too large for 32-bit offsets");
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
-                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, chipmunk_get_option("mm1_probe"), 0, update_cache, nullptr, nullptr};
+                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, chipmunk_get_option("mm1_probe"), 0, update_cache, nullptr, nullptr, ldc};
 #ifdef CHIPMUNK_MM1_PROBES
-    switch (chipmunk_get_option("mm1_variant")) {
+    if (M % BM == 0 && ldc == M) switch (chipmunk_get_option("mm1_variant")) {   // (the probe forms know whole groups and ldc == M only)
         case 1: return launch_mm1_variant<256, 64, 2, 1>(p, stream, cache_updated);
         case 3: return launch_mm1_variant<128, 64, 3, 1>(p, stream, cache_updated);
         case 4: return launch_mm1_variant<256, 32, 3, 2>(p, stream, cache_updated);
@@ -1011,20 +1044,57 @@ int mm1_entry(const void *a, const void *b, void *c, const void *bias, void *pa_
 #endif
     return launch_mm1_variant<128, 64, 2, 2>(p, stream, cache_updated);  // measured best (profiles/r01_*); the library's one GEMM1 form
 }
+
+int mm1_scatter_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                      const int32_t *counts, int M, int K, int F, int ldc, bool ragged, hipStream_t stream) {
+    bool done = false;
+    if (int e = mm1_entry(a, b, c, bias, pa_cache, indices, counts, M, K, F, ldc, ragged, stream, 1, &done)) return e;
+    // tile shapes whose epilogue does not hold the cache block in LDS: the separate scatter-add kernel
+    return done ? CHIPMUNK_OK : launch_scatter_add(c, pa_cache, indices, counts, M, F, ldc, stream);
+}
+
+int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                  const int32_t *counts, const float *scale_a, const float *scale_b, int M, int K, int F, int ldc, bool ragged,
+                  int update_cache, hipStream_t stream) {
+    CM_CHECK(a && b && c && bias && pa_cache && scale_a && scale_b, "csp_mlp_mm1_fp8: null tensor pointer");
+    if (int e = ragged ? check_mlp_ragged(M, F, indices, counts) : check_mlp_common(M, F, indices, counts)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
+    CM_CHECK(K > 0 && K % 128 == 0, "csp_mlp_mm1_fp8: K must be a positive multiple of 128 (got %d)", K);
+    CM_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8: update_cache must be 0, 1 or 2");
+    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
+             "csp_mlp_mm1_fp8: operand too large for 32-bit offsets");
+    // same tile machinery as the bf16 kernel (buffer-form DMA, tail split, staged epilogue); a k step is 128 fp8 values
+    Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache, (uint16_t *)c,
+                   indices, counts, M, K, F, 0, 0, chipmunk_get_option("mm1_probe"), 0, update_cache == 1 ? 2 : update_cache == 2 ? 1 : 0, scale_a, scale_b, ldc};
+#ifdef CHIPMUNK_MM1_PROBES
+    if (M % BM == 0 && ldc == M) {
+        if (chipmunk_get_option("mm1_variant") == 10) return launch_mm1_variant<256, 64, 3, 1, true, 8>(p, stream);
+        if (chipmunk_get_option("mm1_variant") == 20 && K >= 256) return launch_mm1pc<true>(p, stream);
+        if (chipmunk_get_option("mm1_variant") == 21 && K >= 768) return launch_mm1pp<true>(p, stream);
+    }
+#endif
+    return launch_mm1_variant<128, 64, 2, 2, true>(p, stream);
+}
 }  // namespace
 
 extern "C" int chipmunk_csp_mlp_mm1(const void *a, const void *b, void *c, const void *bias, const void *pa_cache,
                                     const int32_t *indices, const int32_t *counts, int M, int K, int F, void *stream) {
-    return mm1_entry(a, b, c, bias, const_cast<void *>(pa_cache), indices, counts, M, K, F, (hipStream_t)stream, 0, nullptr);
+    return mm1_entry(a, b, c, bias, const_cast<void *>(pa_cache), indices, counts, M, K, F, M, false, (hipStream_t)stream, 0, nullptr);
+}
+extern "C" int chipmunk_csp_mlp_mm1_ragged(const void *a, const void *b, void *c, const void *bias, const void *pa_cache,
+                                           const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, void *stream) {
+    return mm1_entry(a, b, c, bias, const_cast<void *>(pa_cache), indices, counts, M, K, F, ldc, true, (hipStream_t)stream, 0, nullptr);
 }
 
 extern "C" int chipmunk_csp_mlp_mm1_scatter(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
                                             const int32_t *indices, const int32_t *counts, int M, int K, int F,
                                             void *stream) {
-    bool done = false;
-    if (int e = mm1_entry(a, b, c, bias, pa_cache, indices, counts, M, K, F, (hipStream_t)stream, 1, &done)) return e;
-    // tile shapes whose epilogue does not hold the cache block in LDS: the separate scatter-add kernel
-    return done ? CHIPMUNK_OK : launch_scatter_add(c, pa_cache, indices, counts, M, F, (hipStream_t)stream);
+    return mm1_scatter_entry(a, b, c, bias, pa_cache, indices, counts, M, K, F, M, false, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_scatter_ragged(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                                   const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc,
+                                                   void *stream) {
+    return mm1_scatter_entry(a, b, c, bias, pa_cache, indices, counts, M, K, F, ldc, true, (hipStream_t)stream);
 }
 
 extern "C" int chipmunk_csp_scatter_add(const void *packed, void *unpacked_colmajor, const int32_t *indices,
@@ -1032,13 +1102,26 @@ extern "C" int chipmunk_csp_scatter_add(const void *packed, void *unpacked_colma
     (void)num_sms;
     CM_CHECK(packed && unpacked_colmajor, "csp_scatter_add: null tensor pointer");
     if (int e = check_mlp_common(M, F, indices, counts)) return e;
-    return launch_scatter_add(packed, unpacked_colmajor, indices, counts, M, F, (hipStream_t)stream);
+    return launch_scatter_add(packed, unpacked_colmajor, indices, counts, M, F, M, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_scatter_add_ragged(const void *packed, void *unpacked_colmajor, const int32_t *indices,
+                                               const int32_t *counts, int M, int F, int ldc, void *stream) {
+    CM_CHECK(packed && unpacked_colmajor, "csp_scatter_add: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
+    return launch_scatter_add(packed, unpacked_colmajor, indices, counts, M, F, ldc, (hipStream_t)stream);
 }
 
 extern "C" int chipmunk_csp_mlp_mm2(const void *mma_a, const void *mma_b, void *mma_c, const int32_t *indices,
                                     const int32_t *counts, int M, int F, int N2, void *stream) {
     CM_CHECK(mma_a && mma_b && mma_c, "csp_mlp_mm2: null tensor pointer");
     if (int e = check_mlp_common(M, F, indices, counts)) return e;
+    return launch_mm2(mma_a, mma_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm2_ragged(const void *mma_a, const void *mma_b, void *mma_c, const int32_t *indices,
+                                           const int32_t *counts, int M, int F, int N2, void *stream) {
+    CM_CHECK(mma_a && mma_b && mma_c, "csp_mlp_mm2: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
     return launch_mm2(mma_a, mma_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream);
 }
 
@@ -1049,26 +1132,28 @@ extern "C" int chipmunk_csp_mlp_mm2_and_scatter_add(const void *packed, void *un
     (void)num_sms_scatter_add;
     CM_CHECK(packed && unpacked_colmajor && mma_a && mma_b && mma_c, "csp_mlp_mm2_and_scatter_add: null tensor pointer");
     if (int e = check_mlp_common(M, F, indices, counts)) return e;
-    if (int e = launch_scatter_add(packed, unpacked_colmajor, indices, counts, M, F, (hipStream_t)stream)) return e;
+    if (int e = launch_scatter_add(packed, unpacked_colmajor, indices, counts, M, F, M, (hipStream_t)stream)) return e;
+    return launch_mm2(mma_a, mma_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm2_and_scatter_add_ragged(const void *packed, void *unpacked_colmajor,
+                                                           const int32_t *indices, const int32_t *counts, const void *mma_a,
+                                                           const void *mma_b, void *mma_c, int M, int F, int N2, int ldc,
+                                                           void *stream) {
+    CM_CHECK(packed && unpacked_colmajor && mma_a && mma_b && mma_c, "csp_mlp_mm2_and_scatter_add: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
+    CM_CHECK(N2 > 0 && N2 % 8 == 0, "mm2: N2 must be a positive multiple of 8 (got %d)", N2);   // before the first kernel is enqueued
+    if (int e = launch_scatter_add(packed, unpacked_colmajor, indices, counts, M, F, ldc, (hipStream_t)stream)) return e;
     return launch_mm2(mma_a, mma_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream);
 }
 
 extern "C" int chipmunk_csp_mlp_mm1_fp8(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
                                         const int32_t *indices, const int32_t *counts, const float *scale_a,
                                         const float *scale_b, int M, int K, int F, int update_cache, void *stream) {
-    CM_CHECK(a && b && c && bias && pa_cache && scale_a && scale_b, "csp_mlp_mm1_fp8: null tensor pointer");
-    if (int e = check_mlp_common(M, F, indices, counts)) return e;
-    CM_CHECK(K > 0 && K % 128 == 0, "csp_mlp_mm1_fp8: K must be a positive multiple of 128 (got %d)", K);
-    CM_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8: update_cache must be 0, 1 or 2");
-    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * M < (1ll << 31),
-             "csp_mlp_mm1_fp8: operand too large for 32-bit offsets");
-    // same tile machinery as the bf16 kernel (buffer-form DMA, tail split, staged epilogue); a k step is 128 fp8 values
-    Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache, (uint16_t *)c,
-                   indices, counts, M, K, F, 0, 0, chipmunk_get_option("mm1_probe"), 0, update_cache == 1 ? 2 : update_cache == 2 ? 1 : 0, scale_a, scale_b};
-#ifdef CHIPMUNK_MM1_PROBES
-    if (chipmunk_get_option("mm1_variant") == 10) return launch_mm1_variant<256, 64, 3, 1, true, 8>(p, (hipStream_t)stream);
-    if (chipmunk_get_option("mm1_variant") == 20 && K >= 256) return launch_mm1pc<true>(p, (hipStream_t)stream);
-    if (chipmunk_get_option("mm1_variant") == 21 && K >= 768) return launch_mm1pp<true>(p, (hipStream_t)stream);
-#endif
-    return launch_mm1_variant<128, 64, 2, 2, true>(p, (hipStream_t)stream);
+    return mm1_fp8_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, M, K, F, M, false, update_cache, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_ragged(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                               const int32_t *indices, const int32_t *counts, const float *scale_a,
+                                               const float *scale_b, int M, int K, int F, int ldc, int update_cache, void *stream) {
+    return mm1_fp8_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, M, K, F, ldc, true, update_cache, (hipStream_t)stream);
 }

@@ -112,8 +112,9 @@ void launch_rlm(const void *x, const void *y, const void *gate, const void *shif
 // operation of every sparse MLP step; torch's reshape + mean kernel reads the 27 MB of a FLUX layer's input in 17 us).  One workgroup
 // = (block, 512 columns): the four waves take a quarter of the block's rows each, a lane 8 columns (16 bytes) of every row; fp32
 // sums in row order, the four partial sums added in wave order, one rounding to bf16.  HBM-bound: R * C * 2 bytes.
+// A ragged last block (R % mbm != 0) is the mean over the rows present: every wave keeps its slice of the block and stops at row R.
 template <int NW, int VEC>   // NW waves per workgroup, each takes mbm / NW rows of the block (all requested before the first is added);
-__global__ __launch_bounds__(NW * 64) void block_mean_kernel(const uint16_t *x, uint16_t *out, int C, int mbm) {   // VEC = columns per lane (8 or 4)
+__global__ __launch_bounds__(NW * 64) void block_mean_kernel(const uint16_t *x, uint16_t *out, int64_t rows, int C, int mbm) {   // VEC = columns per lane (8 or 4)
     __shared__ float part[NW - 1][64][VEC];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int c = (blockIdx.x * 64 + lane) * VEC;
@@ -123,9 +124,11 @@ __global__ __launch_bounds__(NW * 64) void block_mean_kernel(const uint16_t *x, 
     for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
     if (c < C) {
         const int per = mbm / NW;
-        const uint16_t *src = x + (blk * mbm + (int64_t)w * per) * C + c;
+        const int64_t first = blk * mbm + (int64_t)w * per;
+        const int mine = (int)min((int64_t)per, max((int64_t)0, rows - first));   // rows of this wave's slice that exist
+        const uint16_t *src = x + first * C + c;
 #pragma unroll 16
-        for (int r = 0; r < per; ++r) {
+        for (int r = 0; r < mine; ++r) {
             uint32_t v[VEC / 2];
             if constexpr (VEC == 8) {
                 const u32x4 t = *(const u32x4 *)(src + (int64_t)r * C);
@@ -144,7 +147,7 @@ __global__ __launch_bounds__(NW * 64) void block_mean_kernel(const uint16_t *x, 
     }
     __syncthreads();
     if (w == 0 && c < C) {
-        const float inv = 1.0f / (float)mbm;
+        const float inv = 1.0f / (float)min((int64_t)mbm, rows - blk * mbm);
 #pragma unroll
         for (int e = 0; e < VEC; ++e)
 #pragma unroll
@@ -180,21 +183,31 @@ extern "C" int chipmunk_residual_ln_modulate(const void *x, const void *y, const
     return CHIPMUNK_OK;
 }
 
-extern "C" int chipmunk_block_mean(const void *x, void *out, int64_t rows, int C, int mbm, void *stream) {
+namespace {
+int block_mean_entry(const void *x, void *out, int64_t rows, int C, int mbm, bool ragged, void *stream) {
     CM_CHECK(x && out, "block_mean: null tensor pointer");
-    CM_CHECK(mbm > 0 && mbm % 4 == 0 && rows > 0 && rows % mbm == 0, "block_mean: rows (%lld) must be a positive multiple of mbm (%d), mbm a multiple of 4",
-             (long long)rows, mbm);
-    CM_CHECK(C > 0 && C % 8 == 0 && rows / mbm < 65536, "block_mean: C must be a positive multiple of 8 and rows / mbm < 65536");
+    CM_CHECK(mbm > 0 && mbm % 4 == 0 && rows > 0 && (ragged || rows % mbm == 0),
+             "block_mean: rows (%lld) must be a positive multiple of mbm (%d), mbm a multiple of 4", (long long)rows, mbm);
+    const int64_t blocks = (rows + mbm - 1) / mbm;
+    CM_CHECK(C > 0 && C % 8 == 0 && blocks < 65536, "block_mean: C must be a positive multiple of 8 and rows / mbm < 65536");
     // 8 waves x mbm / 8 rows x FOUR columns per lane when the block divides (FLUX / Wan: 128 rows): 408 workgroups instead of 204 and 16 loads in
     // flight per lane -- 27 MB of cold rows in 6.5 us (4.2 TB/s); 4 waves x 8 columns measured 17.3 us, 8 x 8: 10.9, 16 x 4: 7.3, 8 x 2: 6.5
     if (mbm % 8 == 0)
-        hipLaunchKernelGGL((block_mean_kernel<8, 4>), dim3((C + 255) / 256, (unsigned)(rows / mbm)), dim3(512), 0, (hipStream_t)stream,
-                           (const uint16_t *)x, (uint16_t *)out, C, mbm);
+        hipLaunchKernelGGL((block_mean_kernel<8, 4>), dim3((C + 255) / 256, (unsigned)blocks), dim3(512), 0, (hipStream_t)stream,
+                           (const uint16_t *)x, (uint16_t *)out, rows, C, mbm);
     else
-        hipLaunchKernelGGL((block_mean_kernel<4, 8>), dim3((C + 511) / 512, (unsigned)(rows / mbm)), dim3(256), 0, (hipStream_t)stream,
-                           (const uint16_t *)x, (uint16_t *)out, C, mbm);
+        hipLaunchKernelGGL((block_mean_kernel<4, 8>), dim3((C + 511) / 512, (unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                           (const uint16_t *)x, (uint16_t *)out, rows, C, mbm);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
+}
+}  // namespace
+
+extern "C" int chipmunk_block_mean(const void *x, void *out, int64_t rows, int C, int mbm, void *stream) {
+    return block_mean_entry(x, out, rows, C, mbm, false, stream);
+}
+extern "C" int chipmunk_block_mean_ragged(const void *x, void *out, int64_t rows, int C, int mbm, void *stream) {
+    return block_mean_entry(x, out, rows, C, mbm, true, stream);
 }
 
 // ---------------------------------------------------------------------------------------------- fp8 input quantisation

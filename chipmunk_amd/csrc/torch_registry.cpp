@@ -255,6 +255,22 @@ std::vector<at::Tensor> dense_colsum_attn(at::Tensor q, at::Tensor k, at::Tensor
 }
 
 // ---------------------------------------------------------------------------------- MLP
+// The column-major activation cache as the MLP operators take it: [F, M] (leading dimensions of size 1 allowed), elements of a column
+// contiguous, columns `ldc` elements apart -- a contiguous tensor (ldc = M) or the [:, :M] view of a buffer with padded columns.
+// M % 128 == 0 with ldc == M goes to the reference's entry points, everything else to the *_ragged ones (include/chipmunk_hip.h).
+int64_t cache_pitch(const at::Tensor &t, int64_t F, int64_t M, const char *name) {
+    if (t.is_contiguous() && t.numel() == F * M) return M;
+    TORCH_CHECK(t.dim() >= 2 && t.size(-2) == F && t.size(-1) == M && t.numel() == F * M, name, " must be [F, M]");
+    TORCH_CHECK(t.stride(-1) == 1, name, ": the M elements of a column must be contiguous");
+    return t.stride(-2);
+}
+void check_pitch(int64_t ldc, int64_t M, const char *name) {
+    TORCH_CHECK(ldc >= M && ldc % 8 == 0, name, ": the column pitch (", ldc, " elements) must be at least M = ", M,
+                " and a multiple of 8: a contiguous [F, M] cache with M % 8 != 0 is not supported, pass the [:, :M] view of a [F, ceil8(M)] buffer");
+}
+bool whole_groups(int64_t M, int64_t ldc) { return M % 128 == 0 && ldc == M; }
+int64_t groups_of(int64_t M) { return (M + 127) / 128; }
+
 // reference csrc/mlp/csp_mlp_mm1.cu:625-702
 void csp_mlp_mm1(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
                  at::Tensor indices, at::Tensor indices_counts) {
@@ -262,20 +278,27 @@ void csp_mlp_mm1(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor b
     CHECK_DEV(indices); CHECK_DEV(indices_counts);
     CHECK_BF16(a); CHECK_BF16(b_colmajor); CHECK_BF16(c); CHECK_BF16(bias); CHECK_BF16(pa_cache_colmajor);
     CHECK_I32(indices); CHECK_I32(indices_counts);
-    CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias); CHECK_CONTIG(pa_cache_colmajor);
+    CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias);
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
     TORCH_CHECK(a.dim() == 2 && b_colmajor.dim() == 2 && c.dim() == 2, "a, b_colmajor, c must be 2D");
     const int64_t M = a.size(0), K = a.size(1), F = b_colmajor.size(0);
     TORCH_CHECK(b_colmajor.size(1) == K, "a and b_colmajor must share the K dimension");
     TORCH_CHECK(c.size(0) == M && c.size(1) == F, "c must be [M, F]");
     TORCH_CHECK(bias.numel() == F, "bias must have F entries");
-    TORCH_CHECK(pa_cache_colmajor.numel() == F * M, "pa_cache_colmajor must be [F, M]");
-    TORCH_CHECK(indices.numel() == (M / 128) * F && indices_counts.numel() == M / 128, "indices must be [M/128, F], counts [M/128]");
+    const int64_t ldc = cache_pitch(pa_cache_colmajor, F, M, "pa_cache_colmajor");
+    check_pitch(ldc, M, "pa_cache_colmajor");
+    TORCH_CHECK(indices.numel() == groups_of(M) * F && indices_counts.numel() == groups_of(M), "indices must be [ceil(M/128), F], counts [ceil(M/128)]");
     c10::DeviceGuard guard(a.device());
-    check(chipmunk_csp_mlp_mm1(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                               pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                               (int)M, (int)K, (int)F, cur_stream(a)),
-          "csp_mlp_mm1");
+    if (whole_groups(M, ldc))
+        check(chipmunk_csp_mlp_mm1(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
+                                   pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
+                                   (int)M, (int)K, (int)F, cur_stream(a)),
+              "csp_mlp_mm1");
+    else
+        check(chipmunk_csp_mlp_mm1_ragged(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
+                                          pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
+                                          (int)M, (int)K, (int)F, (int)ldc, cur_stream(a)),
+              "csp_mlp_mm1");
 }
 
 // addition: GEMM1 + the scatter-add of its output into the activation cache, one kernel
@@ -285,20 +308,27 @@ void csp_mlp_mm1_scatter(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::
     CHECK_DEV(indices); CHECK_DEV(indices_counts);
     CHECK_BF16(a); CHECK_BF16(b_colmajor); CHECK_BF16(c); CHECK_BF16(bias); CHECK_BF16(pa_cache_colmajor);
     CHECK_I32(indices); CHECK_I32(indices_counts);
-    CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias); CHECK_CONTIG(pa_cache_colmajor);
+    CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias);
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
     TORCH_CHECK(a.dim() == 2 && b_colmajor.dim() == 2 && c.dim() == 2, "a, b_colmajor, c must be 2D");
     const int64_t M = a.size(0), K = a.size(1), F = b_colmajor.size(0);
     TORCH_CHECK(b_colmajor.size(1) == K, "a and b_colmajor must share the K dimension");
     TORCH_CHECK(c.size(0) == M && c.size(1) == F, "c must be [M, F]");
     TORCH_CHECK(bias.numel() == F, "bias must have F entries");
-    TORCH_CHECK(pa_cache_colmajor.numel() == F * M, "pa_cache_colmajor must be [F, M]");
-    TORCH_CHECK(indices.numel() == (M / 128) * F && indices_counts.numel() == M / 128, "indices must be [M/128, F], counts [M/128]");
+    const int64_t ldc = cache_pitch(pa_cache_colmajor, F, M, "pa_cache_colmajor");
+    check_pitch(ldc, M, "pa_cache_colmajor");
+    TORCH_CHECK(indices.numel() == groups_of(M) * F && indices_counts.numel() == groups_of(M), "indices must be [ceil(M/128), F], counts [ceil(M/128)]");
     c10::DeviceGuard guard(a.device());
-    check(chipmunk_csp_mlp_mm1_scatter(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                                       pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
-                                       indices_counts.data_ptr<int>(), (int)M, (int)K, (int)F, cur_stream(a)),
-          "csp_mlp_mm1_scatter");
+    if (whole_groups(M, ldc))
+        check(chipmunk_csp_mlp_mm1_scatter(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
+                                           pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
+                                           indices_counts.data_ptr<int>(), (int)M, (int)K, (int)F, cur_stream(a)),
+              "csp_mlp_mm1_scatter");
+    else
+        check(chipmunk_csp_mlp_mm1_scatter_ragged(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
+                                                  pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
+                                                  indices_counts.data_ptr<int>(), (int)M, (int)K, (int)F, (int)ldc, cur_stream(a)),
+              "csp_mlp_mm1_scatter");
 }
 
 // native counterpart of the reference's Triton csp_mlp_mm1_fp8 (src/chipmunk/triton/csp_mlp_mm1.py:143-164)
@@ -311,20 +341,30 @@ static void mm1_fp8_impl(at::Tensor a, at::Tensor b, at::Tensor c, at::Tensor bi
                 "a and b must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
     CHECK_BF16(c); CHECK_BF16(bias); CHECK_BF16(pa_cache_colmajor);
     CHECK_I32(indices); CHECK_I32(indices_counts);
-    CHECK_CONTIG(a); CHECK_CONTIG(b); CHECK_CONTIG(c); CHECK_CONTIG(bias); CHECK_CONTIG(pa_cache_colmajor);
+    CHECK_CONTIG(a); CHECK_CONTIG(b); CHECK_CONTIG(c); CHECK_CONTIG(bias);
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
     TORCH_CHECK(scale_a.scalar_type() == at::kFloat && scale_b.scalar_type() == at::kFloat && scale_a.numel() == 1 &&
                 scale_b.numel() == 1, "scale_a and scale_b must be one-element float32 tensors");
     TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && c.dim() == 2, "a, b, c must be 2D");
     const int64_t M = a.size(0), K = a.size(1), F = b.size(0);
     TORCH_CHECK(b.size(1) == K && c.size(0) == M && c.size(1) == F, "shape mismatch");
-    TORCH_CHECK(bias.numel() == F && pa_cache_colmajor.numel() == F * M, "bias must be [F], pa_cache_colmajor [F, M]");
+    TORCH_CHECK(bias.numel() == F, "bias must be [F]");
+    const int64_t ldc = cache_pitch(pa_cache_colmajor, F, M, "pa_cache_colmajor");
+    check_pitch(ldc, M, "pa_cache_colmajor");
+    TORCH_CHECK(indices.numel() == groups_of(M) * F && indices_counts.numel() == groups_of(M), "indices must be [ceil(M/128), F], counts [ceil(M/128)]");
     c10::DeviceGuard guard(a.device());
-    check(chipmunk_csp_mlp_mm1_fp8(a.data_ptr(), b.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                                   pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
-                                   indices_counts.data_ptr<int>(), scale_a.data_ptr<float>(), scale_b.data_ptr<float>(),
-                                   (int)M, (int)K, (int)F, update_cache, cur_stream(a)),
-          "csp_mlp_mm1_fp8");
+    if (whole_groups(M, ldc))
+        check(chipmunk_csp_mlp_mm1_fp8(a.data_ptr(), b.data_ptr(), c.data_ptr(), bias.data_ptr(),
+                                       pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
+                                       indices_counts.data_ptr<int>(), scale_a.data_ptr<float>(), scale_b.data_ptr<float>(),
+                                       (int)M, (int)K, (int)F, update_cache, cur_stream(a)),
+              "csp_mlp_mm1_fp8");
+    else
+        check(chipmunk_csp_mlp_mm1_fp8_ragged(a.data_ptr(), b.data_ptr(), c.data_ptr(), bias.data_ptr(),
+                                              pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
+                                              indices_counts.data_ptr<int>(), scale_a.data_ptr<float>(), scale_b.data_ptr<float>(),
+                                              (int)M, (int)K, (int)F, (int)ldc, update_cache, cur_stream(a)),
+              "csp_mlp_mm1_fp8");
 }
 
 void csp_mlp_mm1_fp8(at::Tensor a, at::Tensor b, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
@@ -338,11 +378,11 @@ void csp_mlp_mm1_fp8_scatter(at::Tensor a, at::Tensor b, at::Tensor c, at::Tenso
     mm1_fp8_impl(a, b, c, bias, pa_cache_colmajor, indices, indices_counts, scale_a, scale_b, 2);
 }
 
-void check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, const at::Tensor &inds,
-                        const at::Tensor &counts) {
+int64_t check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, const at::Tensor &inds,
+                           const at::Tensor &counts) {   // returns the cache pitch
     // reference csrc/indexed_io/scatter_add.cu:111-142 (B is hard-wired to 1, :58-59,138)
     CHECK_DEV(packed); CHECK_DEV(unpacked); CHECK_DEV(inds); CHECK_DEV(counts);
-    CHECK_CONTIG(packed); CHECK_CONTIG(unpacked); CHECK_CONTIG(inds); CHECK_CONTIG(counts);
+    CHECK_CONTIG(packed); CHECK_CONTIG(inds); CHECK_CONTIG(counts);
     TORCH_CHECK(packed.dim() == 3, "packed must be a 3D tensor");
     TORCH_CHECK(unpacked.dim() == 3, "unpacked_colmajor must be a 3D tensor");
     TORCH_CHECK(inds.dim() == 3, "sp_inds must be a 3D tensor");
@@ -351,19 +391,28 @@ void check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, co
     CHECK_I32(inds); CHECK_I32(counts);
     TORCH_CHECK(packed.size(0) == 1, "batch size must be 1");
     TORCH_CHECK(unpacked.size(1) == packed.size(2) && unpacked.size(2) == packed.size(1), "unpacked_colmajor must be [1, F, M]");
-    TORCH_CHECK(inds.size(1) == packed.size(1) / 128 && inds.size(2) == packed.size(2), "sp_inds must be [1, M/128, F]");
-    TORCH_CHECK(counts.size(1) == packed.size(1) / 128, "sp_counts must be [1, M/128]");
+    TORCH_CHECK(inds.size(1) == groups_of(packed.size(1)) && inds.size(2) == packed.size(2), "sp_inds must be [1, ceil(M/128), F]");
+    TORCH_CHECK(counts.size(1) == groups_of(packed.size(1)), "sp_counts must be [1, ceil(M/128)]");
+    const int64_t ldc = cache_pitch(unpacked, packed.size(2), packed.size(1), "unpacked_colmajor");
+    check_pitch(ldc, packed.size(1), "unpacked_colmajor");
+    return ldc;
 }
 
 // reference csrc/indexed_io/scatter_add.cu:102-181
 void csp_scatter_add(at::Tensor packed, at::Tensor unpacked_colmajor, at::Tensor sp_inds, at::Tensor sp_counts,
                      int64_t num_sms) {
-    check_scatter_args(packed, unpacked_colmajor, sp_inds, sp_counts);
+    const int64_t ldc = check_scatter_args(packed, unpacked_colmajor, sp_inds, sp_counts);
     c10::DeviceGuard guard(packed.device());
-    check(chipmunk_csp_scatter_add(packed.data_ptr(), unpacked_colmajor.data_ptr(), sp_inds.data_ptr<int>(),
-                                   sp_counts.data_ptr<int>(), (int)packed.size(1), (int)packed.size(2), (int)num_sms,
-                                   cur_stream(packed)),
-          "csp_scatter_add");
+    if (whole_groups(packed.size(1), ldc))
+        check(chipmunk_csp_scatter_add(packed.data_ptr(), unpacked_colmajor.data_ptr(), sp_inds.data_ptr<int>(),
+                                       sp_counts.data_ptr<int>(), (int)packed.size(1), (int)packed.size(2), (int)num_sms,
+                                       cur_stream(packed)),
+              "csp_scatter_add");
+    else
+        check(chipmunk_csp_scatter_add_ragged(packed.data_ptr(), unpacked_colmajor.data_ptr(), sp_inds.data_ptr<int>(),
+                                              sp_counts.data_ptr<int>(), (int)packed.size(1), (int)packed.size(2), (int)ldc,
+                                              cur_stream(packed)),
+              "csp_scatter_add");
 }
 
 // reference csrc/mlp/csp_mlp_mm2_and_scatter_add.cu:96-259.  `matmul_kernel` is the reference's Triton CUfunction
@@ -372,7 +421,7 @@ void csp_mlp_mm2_and_scatter_add(at::Tensor packed, at::Tensor unpacked_colmajor
                                  at::Tensor sp_counts, at::Tensor mma_a, at::Tensor mma_b, at::Tensor mma_c,
                                  int64_t num_sms_scatter_add, int64_t matmul_kernel) {
     (void)matmul_kernel;
-    check_scatter_args(packed, unpacked_colmajor, sp_inds, sp_counts);
+    const int64_t ldc = check_scatter_args(packed, unpacked_colmajor, sp_inds, sp_counts);
     CHECK_DEV(mma_a); CHECK_DEV(mma_b); CHECK_DEV(mma_c);
     CHECK_BF16(mma_a); CHECK_BF16(mma_b); CHECK_BF16(mma_c);
     CHECK_CONTIG(mma_a); CHECK_CONTIG(mma_b); CHECK_CONTIG(mma_c);
@@ -382,11 +431,18 @@ void csp_mlp_mm2_and_scatter_add(at::Tensor packed, at::Tensor unpacked_colmajor
     TORCH_CHECK(mma_b.size(1) == F, "mma_b must be [1, F, N]");
     TORCH_CHECK(mma_c.size(1) == M && mma_c.size(2) == N2, "mma_c must be [1, M, N]");
     c10::DeviceGuard guard(packed.device());
-    check(chipmunk_csp_mlp_mm2_and_scatter_add(packed.data_ptr(), unpacked_colmajor.data_ptr(),
-                                               sp_inds.data_ptr<int>(), sp_counts.data_ptr<int>(), mma_a.data_ptr(),
-                                               mma_b.data_ptr(), mma_c.data_ptr(), (int)M, (int)F, (int)N2,
-                                               (int)num_sms_scatter_add, cur_stream(packed)),
-          "csp_mlp_mm2_and_scatter_add");
+    if (whole_groups(M, ldc))
+        check(chipmunk_csp_mlp_mm2_and_scatter_add(packed.data_ptr(), unpacked_colmajor.data_ptr(),
+                                                   sp_inds.data_ptr<int>(), sp_counts.data_ptr<int>(), mma_a.data_ptr(),
+                                                   mma_b.data_ptr(), mma_c.data_ptr(), (int)M, (int)F, (int)N2,
+                                                   (int)num_sms_scatter_add, cur_stream(packed)),
+              "csp_mlp_mm2_and_scatter_add");
+    else
+        check(chipmunk_csp_mlp_mm2_and_scatter_add_ragged(packed.data_ptr(), unpacked_colmajor.data_ptr(),
+                                                          sp_inds.data_ptr<int>(), sp_counts.data_ptr<int>(), mma_a.data_ptr(),
+                                                          mma_b.data_ptr(), mma_c.data_ptr(), (int)M, (int)F, (int)N2, (int)ldc,
+                                                          cur_stream(packed)),
+              "csp_mlp_mm2_and_scatter_add");
 }
 
 // native counterpart of the reference's Triton csp_mlp_mm2 (src/chipmunk/triton/csp_mlp_mm2.py:104-129)
@@ -399,8 +455,10 @@ void csp_mlp_mm2(at::Tensor mma_a, at::Tensor mma_b, at::Tensor indices, at::Ten
     const int64_t M = mma_a.size(0), F = mma_a.size(1), N2 = mma_b.size(1);
     TORCH_CHECK(mma_b.size(0) == F && mma_c.size(0) == M && mma_c.size(1) == N2, "shape mismatch");
     c10::DeviceGuard guard(mma_a.device());
-    check(chipmunk_csp_mlp_mm2(mma_a.data_ptr(), mma_b.data_ptr(), mma_c.data_ptr(), indices.data_ptr<int>(),
-                               counts.data_ptr<int>(), (int)M, (int)F, (int)N2, cur_stream(mma_a)),
+    TORCH_CHECK(indices.numel() == groups_of(M) * F && counts.numel() == groups_of(M), "indices must be [ceil(M/128), F], counts [ceil(M/128)]");
+    check((M % 128 == 0 ? chipmunk_csp_mlp_mm2 : chipmunk_csp_mlp_mm2_ragged)(
+              mma_a.data_ptr(), mma_b.data_ptr(), mma_c.data_ptr(), indices.data_ptr<int>(), counts.data_ptr<int>(), (int)M, (int)F,
+              (int)N2, cur_stream(mma_a)),
           "csp_mlp_mm2");
 }
 
@@ -524,15 +582,38 @@ at::Tensor transpose_last2(at::Tensor x) {
     return out;
 }
 
+// transpose_last2 into rows of `ld` >= R elements: [..., C, ld] with elements [R, ld) of every row zero; [..., :R] is the transpose (the
+// activation cache of a token count that is not a multiple of 8: the MLP operators take that view, its owner keeps the whole tensor)
+at::Tensor transpose_last2_pitched(at::Tensor x, int64_t ld) {
+    CHECK_DEV(x);
+    TORCH_CHECK(x.dim() >= 2 && x.element_size() == 2, "transpose_last2_pitched: need a >=2-D tensor of a 16-bit dtype");
+    x = x.contiguous();
+    const int64_t R = x.size(-2), C = x.size(-1), B = x.numel() / (R * C);
+    TORCH_CHECK(ld >= R, "transpose_last2_pitched: ld must be at least the row count");
+    auto sizes = x.sizes().vec();
+    sizes[sizes.size() - 2] = C;
+    sizes[sizes.size() - 1] = ld;
+    c10::DeviceGuard guard(x.device());
+    at::Tensor out = at::empty(sizes, x.options());
+    check(chipmunk_transpose16_pitched(x.data_ptr(), out.data_ptr(), (int)B, (int)R, (int)C, (int)ld, cur_stream(x)), "transpose_last2_pitched");
+    return out;
+}
+
 // [b, n, c] -> [b, n / mbm, c] mean over consecutive row blocks (reference modules/mlp.py:11-16) in one HBM-rate kernel, bf16
 at::Tensor block_mean(at::Tensor x, int64_t mbm) {
     CHECK_DEV(x);
     TORCH_CHECK(x.dim() == 3 && x.scalar_type() == at::kBFloat16, "block_mean: need a [b, n, c] bfloat16 tensor");
-    TORCH_CHECK(mbm > 0 && x.size(1) % mbm == 0, "block_mean: n must be a multiple of mbm");
+    TORCH_CHECK(mbm > 0 && x.size(1) > 0, "block_mean: mbm and n must be positive");
     x = x.contiguous();
     c10::DeviceGuard guard(x.device());
-    at::Tensor out = at::empty({x.size(0), x.size(1) / mbm, x.size(2)}, x.options());
-    check(chipmunk_block_mean(x.data_ptr(), out.data_ptr(), x.size(0) * x.size(1), (int)x.size(2), (int)mbm, cur_stream(x)), "block_mean");
+    const int64_t n = x.size(1), blocks = (n + mbm - 1) / mbm;
+    at::Tensor out = at::empty({x.size(0), blocks, x.size(2)}, x.options());
+    if (n % mbm == 0) {
+        check(chipmunk_block_mean(x.data_ptr(), out.data_ptr(), x.size(0) * n, (int)x.size(2), (int)mbm, cur_stream(x)), "block_mean");
+    } else {   // a ragged last block (the mean over the rows present) ends every batch entry: one launch each
+        for (int64_t b = 0; b < x.size(0); ++b)
+            check(chipmunk_block_mean_ragged(x[b].data_ptr(), out[b].data_ptr(), n, (int)x.size(2), (int)mbm, cur_stream(x)), "block_mean");
+    }
     return out;
 }
 
@@ -772,6 +853,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_attn_out_ragged(Tensor q, Tensor k, Tensor v, Tensor o_in, Tensor indices, Tensor offsets, Tensor indices_counts, int o_scale) -> Tensor");
     m.def("residual_ln_modulate(Tensor x, Tensor? y, Tensor? gate, Tensor shift, Tensor scale, float eps) -> Tensor[]");
     m.def("transpose_last2(Tensor x) -> Tensor");
+    m.def("transpose_last2_pitched(Tensor x, int ld) -> Tensor");
     m.def("block_mean(Tensor x, int mbm) -> Tensor");
     m.def("quantize_fp8(Tensor x, Tensor scale, float max_value) -> Tensor");
     m.def("bitpack(Tensor mask) -> Tensor");
@@ -808,6 +890,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("mask_to_sorted_indices", &mask_to_sorted_indices);
     m.impl("topk_mask", &topk_mask);
     m.impl("transpose_last2", &transpose_last2);
+    m.impl("transpose_last2_pitched", &transpose_last2_pitched);
     m.impl("block_mean", &block_mean);
     m.impl("quantize_fp8", &quantize_fp8);
     m.impl("bitpack", &bitpack);

@@ -17,14 +17,33 @@ from ..util.storage import MlpStorage
 
 
 def block_mean(x: torch.Tensor, mbm: int) -> torch.Tensor:
-    """[b, n, c] -> [b, n/mbm, c] mean over consecutive row blocks (reference modules/mlp.py:11-16).  bf16 GPU tensors take the
-    one-pass kernel (``mlp.fused_block_mean``: fp32 sums, one rounding -- torch's reduction in another summation order)."""
+    """[b, n, c] -> [b, ceil(n/mbm), c] mean over consecutive row blocks (reference modules/mlp.py:11-16).  bf16 GPU tensors take the
+    one-pass kernel (``mlp.fused_block_mean``: fp32 sums, one rounding -- torch's reduction in another summation order).  A ragged last
+    block (``n % mbm != 0``; the reference has none) is the mean over the rows present."""
     b, n, c = x.shape
-    if (x.is_cuda and x.dtype == torch.bfloat16 and mbm % 4 == 0 and c % 8 == 0 and n % mbm == 0
-            and b * (n // mbm) < 65536       # the kernel's row blocks ride on grid.y
+    if (x.is_cuda and x.dtype == torch.bfloat16 and mbm % 4 == 0 and c % 8 == 0
+            and b * ((n + mbm - 1) // mbm) < 65536       # the kernel's row blocks ride on grid.y
             and amd_key("mlp", "fused_block_mean")):
         return torch.ops.chipmunk.block_mean(x, mbm)
-    return x.reshape(b, n // mbm, mbm, c).mean(dim=2)
+    full = n // mbm * mbm
+    out = x[:, :full].reshape(b, n // mbm, mbm, c).mean(dim=2)
+    if full < n:
+        out = torch.cat([out, x[:, full:].mean(dim=1, keepdim=True)], dim=1)
+    return out
+
+
+def _ceil8(n: int) -> int:
+    return (n + 7) // 8 * 8
+
+
+def _transposed_pitched(x: torch.Tensor, ld: int) -> torch.Tensor:
+    """[..., R, C] -> [..., C, ld] with ``[..., :R]`` the transpose and zeros behind it: the activation cache at a column pitch the
+    sparse-MLP operators accept for a token count that is not a multiple of 8 (``ld >= R``, ``ld % 8 == 0``)."""
+    if x.is_cuda and x.element_size() == 2:
+        return torch.ops.chipmunk.transpose_last2_pitched(x, ld)
+    out = x.new_zeros(x.shape[:-2] + (x.shape[-1], ld))
+    out[..., : x.shape[-2]] = x.transpose(-1, -2)
+    return out
 
 
 def _transposed(x: torch.Tensor) -> torch.Tensor:
@@ -64,7 +83,10 @@ class SparseDiffMlp:
             mid = fc1(x)
             act = self.activation(mid)
             out = fc2(act)
-            self.storage.set_sparse_act_T(_transposed(act))
+            # the module owns the activation cache: [1, F, ld] with ld = ceil8(N) and zeroed padding, stored (and offloaded) whole; the
+            # operators get its [F, N] view.  ld == N for every N % 8 == 0: the contiguous cache of the reference.
+            n = x.shape[1]
+            self.storage.set_sparse_act_T(_transposed(act) if n % 8 == 0 else _transposed_pitched(act, _ceil8(n)))
             self.storage.set_out_cache(out)
             self.storage.set_blockmean_mid_cache(block_mean(mid, mbm))
             return out
@@ -84,7 +106,9 @@ class SparseDiffMlp:
             else:
                 mdiff = (bmfc1 - cache).abs()
                 b, rows, f = mdiff.shape
-                mdiff = mdiff.reshape(b, rows // r, r, f).sum(dim=2)
+                if rows % r:   # ragged last group: it sums the blocks it has
+                    mdiff = torch.nn.functional.pad(mdiff, (0, 0, 0, r - rows % r))
+                mdiff = mdiff.reshape(b, -1, r, f).sum(dim=2)
                 inds = torch.empty_like(mdiff, dtype=torch.int32, device=x.device)
                 counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=x.device)
                 ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
@@ -96,7 +120,7 @@ class SparseDiffMlp:
         indices = self.storage.get_indices()[0]
         counts = self.storage.get_counts()[0]
         out_cache = self.storage.get_out_cache()[0]
-        sparse_act_T = self.storage.get_sparse_act_T()[0]
+        sparse_act_T = self.storage.get_sparse_act_T()[0][:, : x.shape[1]]   # the [F, N] view of the pitched cache
 
         scale_a = scale_b = None
         if fc1.weight.dtype == torch.float8_e4m3fn:

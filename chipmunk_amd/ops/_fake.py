@@ -69,7 +69,15 @@ def _register():
 
     @lib.register_fake("chipmunk::block_mean")
     def _(x, mbm):
-        return x.new_empty((x.shape[0], x.shape[1] // mbm, x.shape[2]))
+        return x.new_empty((x.shape[0], (x.shape[1] + mbm - 1) // mbm, x.shape[2]))   # a ragged last block counts
+
+    @lib.register_fake("chipmunk::transpose_last2")
+    def _(x):
+        return x.new_empty(x.shape[:-2] + (x.shape[-1], x.shape[-2]))
+
+    @lib.register_fake("chipmunk::transpose_last2_pitched")
+    def _(x, ld):
+        return x.new_empty(x.shape[:-2] + (x.shape[-1], ld))
 
     @lib.register_fake("chipmunk::quantize_fp8")
     def _(x, scale, max_value):

@@ -101,6 +101,8 @@ def mm2_unfused(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, cached_out
 def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: torch.Tensor, fc2w_T: torch.Tensor, indices: torch.Tensor,
             counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
             mm1_scale_a: Optional[torch.Tensor] = None, mm1_scale_b: Optional[torch.Tensor] = None) -> None:
+    # M is any positive row count (ceil(M / 128) groups, the last one short); sparse_act_T is [F, M], contiguous or -- required when
+    # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers
     M, K1 = x.shape
     K2, K1_ = fc1w.shape
     assert K1 == K1_, "K1 must match"

@@ -178,6 +178,30 @@ int chipmunk_csp_scatter_add(const void *packed, void *unpacked_colmajor, const 
 int chipmunk_csp_mlp_mm2(const void *mma_a, const void *mma_b, void *mma_c, const int32_t *indices,
                          const int32_t *counts, int M, int F, int N2, void *stream);
 
+/* The sparse-MLP operators for ANY number of token rows (no reference counterpart: the reference requires M % 128 == 0).
+ * M > 0; G = ceil(M / 128) groups, the last one with M - 128 (G - 1) rows; indices [G, F], counts [G].
+ *   - Row-major tensors (a [M,K], c / packed / mma_a [M,F], mma_c [M,N2]) hold exactly M rows: no byte at or past row M is loaded
+ *     or stored, and rows < M get the bits the entries above give them on the problem padded with zero rows.
+ *   - The column-major activation cache is [F, ldc]: column f starts at element f * ldc.  ldc >= M and ldc % 8 == 0; elements
+ *     [M, ldc) of a column are padding the operator may overwrite with anything (nothing read there reaches a row < M), and
+ *     nothing outside F * ldc elements is touched.  ldc == M is allowed when M % 8 == 0 (a contiguous [F, M] cache).
+ * K, F, N2, alignment and 32-bit-offset conditions (with F * ldc in place of F * M) as for the entries they extend. */
+int chipmunk_csp_mlp_mm1_ragged(const void *a, const void *b, void *c, const void *bias, const void *pa_cache,
+                                const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, void *stream);
+int chipmunk_csp_mlp_mm1_scatter_ragged(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                        const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc,
+                                        void *stream);
+int chipmunk_csp_mlp_mm1_fp8_ragged(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                    const int32_t *indices, const int32_t *counts, const float *scale_a,
+                                    const float *scale_b, int M, int K, int F, int ldc, int update_cache, void *stream);
+int chipmunk_csp_mlp_mm2_ragged(const void *mma_a, const void *mma_b, void *mma_c, const int32_t *indices,
+                                const int32_t *counts, int M, int F, int N2, void *stream);
+int chipmunk_csp_mlp_mm2_and_scatter_add_ragged(const void *packed, void *unpacked_colmajor, const int32_t *indices,
+                                                const int32_t *counts, const void *mma_a, const void *mma_b, void *mma_c,
+                                                int M, int F, int N2, int ldc, void *stream);
+int chipmunk_csp_scatter_add_ragged(const void *packed, void *unpacked_colmajor, const int32_t *indices,
+                                    const int32_t *counts, int M, int F, int ldc, void *stream);
+
 /* ---------------------------------------------------------------- indexed IO
  * Replaces chipmunk::topk_indices (reference csrc/indexed_io/topk_indices.cu:145-218; schema chipmunk.cpp:58).
  * activation [B*R, C] of `dtype`; indices [B*R, C] int32; counts [B*R] int32.  Threshold = element
@@ -243,11 +267,16 @@ int chipmunk_copy_indices(const void *src, void *dst, const int32_t *inds, const
 /* [B,R,C] -> [B,C,R] for 16-bit elements: builds the column-major activation cache `pa.transpose(-1,-2).contiguous()`
  * of the sparse MLP's full step (reference src/chipmunk/modules/mlp.py:56) at HBM rate. */
 int chipmunk_transpose16(const void *src, void *dst, int B, int R, int C, void *stream);
+/* ... with an output pitch: dst is [B, C, ld], ld >= R; elements [R, ld) of every output row are written as zeros (the activation
+ * cache of a token count that is not a multiple of 8, see the *_ragged MLP entries). */
+int chipmunk_transpose16_pitched(const void *src, void *dst, int B, int R, int C, int ld, void *stream);
 
 /* [rows, C] bf16 -> [rows / mbm, C] bf16: mean over consecutive blocks of `mbm` rows, fp32 sums, one rounding (the caller's
  * `block_mean(x, mbm)` in front of the fc1 probe of every sparse MLP step, src/chipmunk/modules/mlp.py:11-16,62).  rows % mbm == 0,
  * mbm % 4 == 0, C % 8 == 0. */
 int chipmunk_block_mean(const void *x, void *out, int64_t rows, int C, int mbm, void *stream);
+/* ... for any rows > 0: out is [ceil(rows / mbm), C] and the last block is the mean over the rows present (fp32 sum, one rounding). */
+int chipmunk_block_mean_ragged(const void *x, void *out, int64_t rows, int C, int mbm, void *stream);
 
 /* bf16 [n] -> OCP fp8 e4m3 [n]: F8Linear.quantize_input's `(x * scale).clamp(-max, max).to(float8_e4m3fn)` (reference
  * src/chipmunk/modules/mlp_fp8.py, the input side of csp_mlp_mm1_fp8) as one pass with the same roundings (fp32 product -> bf16 -> clamp ->

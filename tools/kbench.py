@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm2 scatter csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm2 scatter fp8_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -82,7 +82,7 @@ def bench_mlp(which, variants, M=4352, K=3072, F=12288, keep=4096):
         w2t = (torch.randn(F, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
         out = torch.zeros(M, K, device=dev, dtype=torch.bfloat16)
         sets.append((w1, cache, packed, w2t, out))
-    G = M // 128
+    G = (M + 127) // 128      # (a token count that is no multiple of 128: the last group is short)
     inds = rand_rows(G, F, keep, g)
     if os.environ.get("KB_SAME_INDICES") == "1":   # every group selects the same columns: upper bound of L2 sharing
         inds[:] = inds[0:1]
@@ -133,24 +133,25 @@ def bench_mlp(which, variants, M=4352, K=3072, F=12288, keep=4096):
     _native.set_option("mm2_variant", 0)
 
 
-def bench_fp8_wan():
+def bench_fp8_wan(M=32768, ldc=None):
     """BASELINE config C5 (Wan2.1-1.3B, 832x480x81 -> 32 760 tokens padded to 32 768): fp8 e4m3 GEMM1, M = 32768, K = 1536,
-    F = 8960, keep 0.3 (2688 columns); bf16 GEMM1 at the same shape beside it."""
+    F = 8960, keep 0.3 (2688 columns); bf16 GEMM1 at the same shape beside it.  M = 32760: the ragged launch on the tokens as they are
+    (ldc: the cache as the [:, :M] view of a [F, ldc] buffer, default the contiguous [F, M])."""
     g = torch.Generator(device=dev).manual_seed(0)
-    M, K, F, keep = 32768, 1536, 8960, 2688
+    K, F, keep = 1536, 8960, 2688
     a = torch.randn(M, K, device=dev, generator=g)
     w = torch.randn(F, K, device=dev, generator=g) * 0.02
     a8, w8 = (a * 16).clamp(-448, 448).to(torch.float8_e4m3fn), (w * 512).clamp(-448, 448).to(torch.float8_e4m3fn)
     sa, sb = torch.tensor([1 / 16.0], device=dev), torch.tensor([1 / 512.0], device=dev)
     bias = torch.zeros(F, device=dev, dtype=torch.bfloat16)
-    cache = torch.randn(F, M, device=dev, dtype=torch.bfloat16, generator=g)
+    cache = torch.randn(F, ldc or M, device=dev, dtype=torch.bfloat16, generator=g)[:, :M]
     packed = torch.empty(M, F, device=dev, dtype=torch.bfloat16)
-    G = M // 128
+    G = (M + 127) // 128
     inds = rand_rows(G, F, keep, g)
     counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
     flops = 2.0 * M * K * keep
     ms = timeit(lambda: torch.ops.chipmunk.csp_mlp_mm1_fp8(a8, w8, packed, bias, cache, inds, counts, sa, sb, False), reps=5)
-    print(f"mm1_fp8 (Wan C5): {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TFLOP/s   (M={M} K={K} F={F} keep={keep})")
+    print(f"mm1_fp8 (Wan C5): {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TFLOP/s   (M={M} K={K} F={F} keep={keep} ldc={ldc or M})")
     ab, wb = a.to(torch.bfloat16), w.to(torch.bfloat16)
     ms = timeit(lambda: torch.ops.chipmunk.csp_mlp_mm1(ab, wb, packed, bias, cache, inds, counts), reps=5)
     print(f"mm1 bf16 same shape: {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TFLOP/s")
@@ -271,6 +272,14 @@ def main():
             bench_fp8_wan()
         elif w == "mm2_wan":          # GEMM2 at the Wan2.1 1.3B shape (configs[4]): M = 32 768 rows, N2 = 1 536, F = 8 960, 30 % kept
             bench_mlp("mm2", variants, M=32768, K=1536, F=8960, keep=2816)
+        elif w == "fp8_wan_ragged":   # the same launches on Wan2.1's 32 760 tokens as they are: 255 groups + 120 rows
+            bench_fp8_wan(M=32760)
+        elif w == "fp8_wan_ragged_pitched":   # ... with the cache columns on 128-byte lines (ldc = 32 768)
+            bench_fp8_wan(M=32760, ldc=32768)
+        elif w == "mm2_wan_ragged":
+            bench_mlp("mm2", variants, M=32760, K=1536, F=8960, keep=2816)
+        elif w in ("mm1s_hunyuan", "mm2_hunyuan"):   # HunyuanVideo 720x1280x129: 119 056 tokens = 930 groups + 16 rows, 30 % of 12 288 columns kept
+            bench_mlp(w.split("_")[0], variants, M=119056, K=3072, F=12288, keep=3840)
         elif w in ("topk", "topkd", "m2i", "copy"):
             bench_io(w)
         else:
