@@ -1467,7 +1467,7 @@ extern "C" int chipmunk_dense_colsum_topk_mask_strided(const void *q, const void
     if (int e = check_strides(k_strides, "k")) return e;
     if (int e = check_strides(v_strides, "v")) return e;
     hipStream_t st = (hipStream_t)stream;
-    if (!use_dense64(B, H, Nq, Nk) || chipmunk_get_option("attn_fused_colsum") == 2 || (Nk & 3) || Nk > 1024 * 120)
+    if (!use_dense64(B, H, Nq, Nk) || chipmunk_get_option("attn_fused_colsum") == 2 || (Nk & 3) || Nk > CHIPMUNK_TOPK_MASK_MAX_N)
         return CHIPMUNK_ERR_UNSUPPORTED;
     AttnParams p = {};
     p.q = (const uint16_t *)q, p.k = (const uint16_t *)k, p.v = (const uint16_t *)v, p.o = (uint16_t *)o;

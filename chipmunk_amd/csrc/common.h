@@ -155,6 +155,11 @@ inline void ensure_dynamic_lds(const void *kernel, int bytes, uint64_t &done) {
     }
 }
 
+// Longest row chipmunk_topk_mask / the fused mask step take: 1024 threads x 512 keys, the most a thread's two packed u16 counters
+// hold in topk_mask_stream_kernel (indexed_io.hip).  It covers every row mask_to_indices can still turn into indices (its LDS
+// ends at n = 522 240); chipmunk_amd/ops/indexed_io.py (TOPK_MASK_MAX_N) carries the same number.
+#define CHIPMUNK_TOPK_MASK_MAX_N (1024 * 512)
+
 // ---- host-side error plumbing (thread-local message, see chipmunk_last_error) ----
 void chipmunk_set_error(const char *fmt, ...);
 int chipmunk_get_option(const char *name);

@@ -830,6 +830,241 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
     }
 }
 
+// ---- the same selection for rows of any length up to CHIPMUNK_TOPK_MASK_MAX_N: the keys are not kept in registers, every
+// bisection round STREAMS the row again (the workgroup's own row: 2 bytes per column, resident in this XCD's L2 after the first
+// pass).  Same column-to-thread mapping as above (thread t owns columns 4t + 4096j + e), so counts, threshold, tie order
+// (ascending thread, then ascending column) and therefore every mask bit are those of topk_mask_kernel.
+// Passes over a row of n columns: [PARTS: 1 combine pass, 2-3 partial rows in (4-6n bytes, HBM), n keys out] + 16 bisection
+// rounds + 1 pass counting keys above / at the threshold + 1 output pass = 18 reads of 2n bytes from L2, plus n static-mask
+// bytes in and n mask bytes out.  Inactive rows and k = 0 skip all but the output pass, which then reads no keys either.
+// PARTS: the three-row combine is done ONCE; its 16-bit keys are written over the group's first partial row (row r0 of
+// colsum_part_rows belongs to that group alone, and the partial rows are scratch that nothing reads after this kernel), each
+// thread over exactly the columns it read, and the later passes read keys (no conversion, one row instead of three).
+// A thread counts at most 4 * 128 = 512 keys per round: two packed u16 counters of at most 256 each.
+// (Key 0 is bf16 bits 0xffff, a NaN, and the padding past n: only with such a NaN at the threshold would padding enter a tie count.)
+__device__ __forceinline__ uint32_t bf16_key2(uint32_t u) {   // bf16_key on both halves of a word
+    uint32_t s;
+    const uint32_t fifteen2 = 0x000f000fu;
+    asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(s) : "v"(fifteen2), "v"(u));   // 0xffff where the sign bit is set
+    return u ^ (s | 0x80008000u);
+}
+
+template <bool ALIGNED, bool PARTS>
+__global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskParams p) {
+    __shared__ int wave_cnt[16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int row = blockIdx.x;
+    const int n = p.n;
+    const uint16_t *x = nullptr;
+    int prow = 1;
+    int64_t row1 = 0;      // PARTS: elements from the group's first partial row to its second
+    if constexpr (PARTS) {
+        const int bh = row / p.ngroups, g = row - bh * p.ngroups;
+        int r0, r1;
+        prow = colsum_part_rows(g, p.nrb / 2, r0, r1);
+        x = p.parts + ((int64_t)bh * p.nrb + r0) * p.pstride;
+        row1 = (int64_t)(r1 - r0) * p.pstride;
+    } else {
+        x = p.cs + (int64_t)row * p.cs_stride;
+    }
+    const uint32_t lane_off8 = 8u * (uint32_t)tid;
+    const int nsteps = (n + 4095) / 4096;
+    const bool active = p.groups == nullptr || p.groups[row] != 0;
+    const int k = p.k < n ? p.k : n;
+    const bool select = active && k > 0;
+    const bool rnd = active && p.random_amount > 0.f;
+
+    // (PARTS: the combined bf16 values of columns c0..c0+3, the additions in the order of the register form)
+    auto combined4 = [&](int c0, uint32_t &v0, uint32_t &v1) {
+        const u32x2 v = *(const u32x2 *)(x + c0);
+        v0 = v[0], v1 = v[1];
+        if constexpr (PARTS) {
+            if (prow == 2) {
+                float a0 = __uint_as_float(v0 << 16), a1 = __uint_as_float(v0 & 0xffff0000u);
+                float a2 = __uint_as_float(v1 << 16), a3 = __uint_as_float(v1 & 0xffff0000u);
+                const u32x2 y = *(const u32x2 *)(x + row1 + c0);
+                a0 += __uint_as_float(y[0] << 16), a1 += __uint_as_float(y[0] & 0xffff0000u);
+                a2 += __uint_as_float(y[1] << 16), a3 += __uint_as_float(y[1] & 0xffff0000u);
+                v0 = pack_bf16x2(a0, a1), v1 = pack_bf16x2(a2, a3);
+            }
+        }
+    };
+    // the salt's row part, from the row's first (combined) element -- read before the keys overwrite it
+    uint32_t first = 0;
+    if (rnd) {
+        first = x[0];
+        if constexpr (PARTS) {
+            uint32_t f0, f1;
+            combined4(0, f0, f1);
+            first = f0 & 0xffffu;
+        }
+    }
+    const uint32_t salt = p.salt ^ (first * 0x27D4EB2Fu);
+    if constexpr (PARTS) {
+        __syncthreads();   // every thread has read column 0 before thread 0 replaces it
+        if (select) {      // (uniform over the workgroup)
+            uint16_t *xk = const_cast<uint16_t *>(x);
+            for (int j = 0; j < nsteps; ++j) {
+                const int c = 4 * tid + 4096 * j;
+                if (c < n) {
+                    uint32_t v0, v1;
+                    combined4(c, v0, v1);
+                    u32x2 kk = {bf16_key2(v0), bf16_key2(v1)};
+                    *(u32x2 *)(xk + c) = kk;
+                }
+            }
+        }
+        __syncthreads();   // (a thread reads back only what it wrote itself; the barrier's wait drains the stores first)
+    }
+    // the keys of step j (columns 4 * tid + 4096 * j ..+3) as two packed words; columns past n have key 0, below every real key
+    auto load_raw = [&](int j, uint32_t &v0, uint32_t &v1) {
+        const int c = 4 * tid + 4096 * j;
+        if constexpr (ALIGNED) {
+            v0 = v1 = PARTS ? 0u : 0xffffffffu;
+            if (c < n) {
+                const u32x2 v = *(const u32x2 *)((const unsigned char *)(x + 4096 * j) + lane_off8);
+                v0 = v[0], v1 = v[1];
+            }
+        } else {
+            v0 = v1 = 0xffffffffu;
+            if (c < n) {
+                v0 = v1 = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t u = c + e < n ? x[c + e] : 0xffffu;
+                    if (e < 2) v0 |= u << (16 * e);
+                    else v1 |= u << (16 * (e - 2));
+                }
+            }
+        }
+    };
+    auto to_keys = [&](uint32_t &v0, uint32_t &v1) {
+        if constexpr (!PARTS) v0 = bf16_key2(v0), v1 = bf16_key2(v1);
+    };
+    auto block_count = [&](int mine) {  // sum over the 1024 threads, broadcast
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d);
+        if (lane == 0) wave_cnt[w] = mine;
+        __syncthreads();
+        int t = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) t += wave_cnt[i];
+        __syncthreads();
+        return t;
+    };
+    constexpr int U = ALIGNED ? 8 : 2;   // row loads in flight per thread
+    uint32_t thr = 0x10000u;  // keep nothing
+    int ties_to_take = 0, my_ties = 0;
+    if (select) {
+        // ---- largest T with #{key >= T} >= k, most significant bit first; one pass over the row per bit
+        uint32_t res = 0;
+        for (int bit = 15; bit >= 0; --bit) {
+            const uint32_t cand = res | (1u << bit);
+            const uint32_t cm1 = (cand - 1u) | ((cand - 1u) << 16);
+            const uint32_t one2 = 0x00010001u;
+            uint32_t cnt2 = 0;
+            for (int j0 = 0; j0 < nsteps; j0 += U) {
+                uint32_t kw[U][2];
+#pragma unroll
+                for (int jj = 0; jj < U; ++jj) load_raw(j0 + jj, kw[jj][0], kw[jj][1]);
+#pragma unroll
+                for (int jj = 0; jj < U; ++jj) {
+                    to_keys(kw[jj][0], kw[jj][1]);
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        uint32_t d;   // sat(key - (cand - 1)) is non-zero iff key >= cand; min(., 1) makes it a count (see above)
+                        asm volatile("v_pk_sub_u16 %0, %1, %2 clamp\n\tv_pk_min_u16 %0, %0, %3" : "=&v"(d) : "v"(kw[jj][h]), "v"(cm1), "v"(one2));
+                        asm volatile("v_pk_add_u16 %0, %0, %1" : "+v"(cnt2) : "v"(d));
+                    }
+                }
+            }
+            const int mine = (int)(cnt2 & 0xffffu) + (int)(cnt2 >> 16);
+            if (block_count(mine) >= k) res = cand;
+        }
+        thr = res;
+        // ---- keys above the threshold and keys at it, in one pass
+        int gt = 0;
+        for (int j0 = 0; j0 < nsteps; j0 += U) {
+            uint32_t kw[U][2];
+#pragma unroll
+            for (int jj = 0; jj < U; ++jj) load_raw(j0 + jj, kw[jj][0], kw[jj][1]);
+#pragma unroll
+            for (int jj = 0; jj < U; ++jj) {
+                to_keys(kw[jj][0], kw[jj][1]);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const uint32_t lo = kw[jj][h] & 0xffffu, hi = kw[jj][h] >> 16;
+                    gt += (lo > thr ? 1 : 0) + (hi > thr ? 1 : 0);
+                    my_ties += (lo == thr ? 1 : 0) + (hi == thr ? 1 : 0);
+                }
+            }
+        }
+        ties_to_take = k - block_count(gt);  // >= 1 by construction of thr
+    }
+    // ---- ties at the threshold go to the lowest thread ids, inside a thread to its lowest columns
+    int tie_budget = 0;
+    {
+        int incl = my_ties;  // inclusive scan over the block: wave scan, then the 16 wave totals
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(incl, d);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) wave_cnt[w] = incl;
+        __syncthreads();
+        int before = incl - my_ties;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) before += i < w ? wave_cnt[i] : 0;
+        __syncthreads();
+        tie_budget = ties_to_take - before;  // how many of MY ties are taken (clamped below)
+    }
+    // ---- write the mask: (top-k | random) & group | static
+    uint8_t *out = p.mask + (int64_t)row * n;
+    const uint8_t *st = p.stat ? p.stat + (int64_t)(row % p.stat_rows) * p.stat_stride : nullptr;
+    for (int j0 = 0; j0 < nsteps; j0 += U) {
+        uint32_t kw[U][2], sbv[U];
+#pragma unroll
+        for (int jj = 0; jj < U; ++jj) {
+            const int c = 4 * tid + 4096 * (j0 + jj);
+            kw[jj][0] = kw[jj][1] = 0;
+            if (select) load_raw(j0 + jj, kw[jj][0], kw[jj][1]);
+            sbv[jj] = 0;
+            if constexpr (ALIGNED) {
+                if (st && c < n) sbv[jj] = *(const uint32_t *)(st + c);
+            } else if (st) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (c + e < n) sbv[jj] |= (uint32_t)st[c + e] << (8 * e);
+            }
+        }
+#pragma unroll
+        for (int jj = 0; jj < U; ++jj) {
+            const int c = 4 * tid + 4096 * (j0 + jj);
+            if (c >= n) continue;
+            if (select) to_keys(kw[jj][0], kw[jj][1]);
+            uint32_t bytes = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t kv = (kw[jj][e >> 1] >> (16 * (e & 1))) & 0xffffu;
+                bool keep = kv > thr;                      // thr = 0x10000 when the row is inactive or k = 0
+                const bool tie = kv == thr && tie_budget > 0 && c + e < n;
+                tie_budget -= tie ? 1 : 0;
+                keep = keep || tie;
+                if (rnd && !keep) keep = hash_uniform(row, c + e, salt) < p.random_amount;
+                keep = keep || ((sbv[jj] >> (8 * e)) & 0xffu) != 0;
+                bytes |= (keep ? 1u : 0u) << (8 * e);
+            }
+            if constexpr (ALIGNED) {
+                *(uint32_t *)(out + c) = bytes;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (c + e < n) out[c + e] = (uint8_t)(bytes >> (8 * e));
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int chipmunk_mask_to_indices(const void *mask, int32_t *indices, int32_t *counts, int64_t rows, int n,
@@ -991,7 +1226,7 @@ extern "C" int chipmunk_gather_rows(const void *src, void *dst, const int32_t *m
 int chipmunk_topk_mask_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
                              int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double random_amount,
                              hipStream_t s) {
-    CM_CHECK(part && mask && rows >= 0 && n > 0 && (n & 3) == 0 && n <= 1024 * 120 && k >= 0 && part_stride >= n && (part_stride & 3) == 0, "topk_mask_parts: bad arguments");
+    CM_CHECK(part && mask && rows >= 0 && n > 0 && (n & 3) == 0 && n <= CHIPMUNK_TOPK_MASK_MAX_N && k >= 0 && part_stride >= n && (part_stride & 3) == 0, "topk_mask_parts: bad arguments");
     CM_CHECK(!static_mask || (static_rows > 0 && static_stride >= n && (static_stride & 3) == 0 && ((uintptr_t)static_mask & 3) == 0),
              "topk_mask_parts: bad static mask geometry");
     CM_CHECK(((uintptr_t)mask & 3) == 0 && ((uintptr_t)part & 7) == 0, "topk_mask_parts: unaligned buffers");
@@ -1000,7 +1235,9 @@ int chipmunk_topk_mask_parts(const uint16_t *part, int part_stride, int nrb, int
                         rows, n, k, static_mask ? static_rows : 1, (float)random_amount,
                         random_amount > 0.0 ? chipmunk_next_random_salt() : 0u};
     p.parts = part, p.pstride = part_stride, p.nrb = nrb, p.ngroups = groups_per_bh, p.nq = Nq;
-    if (n <= 1024 * 16) hipLaunchKernelGGL((topk_mask_kernel<16, true, true>), dim3(rows), dim3(1024), 0, s, p);
+    // rows past the register form's 122 880 columns (or option topk_mask_stream = 1: every row) take the streaming form
+    if (n > 1024 * 120 || chipmunk_get_option("topk_mask_stream") == 1) hipLaunchKernelGGL((topk_mask_stream_kernel<true, true>), dim3(rows), dim3(1024), 0, s, p);
+    else if (n <= 1024 * 16) hipLaunchKernelGGL((topk_mask_kernel<16, true, true>), dim3(rows), dim3(1024), 0, s, p);
     else if (n <= 1024 * 48) hipLaunchKernelGGL((topk_mask_kernel<48, true, true>), dim3(rows), dim3(1024), 0, s, p);
     else hipLaunchKernelGGL((topk_mask_kernel<120, true, true>), dim3(rows), dim3(1024), 0, s, p);
     CM_LAUNCH_CHECK();
@@ -1087,7 +1324,7 @@ extern "C" int chipmunk_topk_mask(const void *cs, int64_t cs_stride, const void 
     CM_CHECK(cs && mask, "topk_mask: null pointer");
     CM_CHECK(rows >= 0 && n > 0 && k >= 0, "topk_mask: bad sizes (rows=%d n=%d k=%d)", rows, n, k);
     CM_CHECK(cs_stride >= n, "topk_mask: cs row stride %lld < n %d", (long long)cs_stride, n);
-    CM_CHECK(n <= 1024 * 120, "topk_mask: rows of more than 122880 columns are not supported (got %d)", n);
+    CM_CHECK(n <= CHIPMUNK_TOPK_MASK_MAX_N, "topk_mask: rows of more than %d columns are not supported (got %d)", CHIPMUNK_TOPK_MASK_MAX_N, n);
     CM_CHECK(!static_mask || (static_rows > 0 && static_stride >= n), "topk_mask: bad static mask geometry");
     CM_CHECK(random_amount >= 0.0 && random_amount <= 1.0, "topk_mask: random_amount must be in [0,1]");
     if (rows == 0) return CHIPMUNK_OK;
@@ -1102,7 +1339,11 @@ extern "C" int chipmunk_topk_mask(const void *cs, int64_t cs_stride, const void 
         if (aligned) hipLaunchKernelGGL((topk_mask_kernel<KPT, true>), dim3(rows), dim3(1024), 0, s, p);     \
         else hipLaunchKernelGGL((topk_mask_kernel<KPT, false>), dim3(rows), dim3(1024), 0, s, p);            \
     } while (0)
-    if (n <= 1024 * 16) LAUNCH_TM(16);
+    // rows past the register form's 122 880 columns (or option topk_mask_stream = 1: every row) take the streaming form
+    if (n > 1024 * 120 || chipmunk_get_option("topk_mask_stream") == 1) {
+        if (aligned) hipLaunchKernelGGL((topk_mask_stream_kernel<true, false>), dim3(rows), dim3(1024), 0, s, p);
+        else hipLaunchKernelGGL((topk_mask_stream_kernel<false, false>), dim3(rows), dim3(1024), 0, s, p);
+    } else if (n <= 1024 * 16) LAUNCH_TM(16);
     else if (n <= 1024 * 48) LAUNCH_TM(48);
     else LAUNCH_TM(120);
 #undef LAUNCH_TM

@@ -95,7 +95,7 @@ class SparseDiffAttn(nn.Module):
         cfg = GLOBAL_CONFIG["attn"]
         qg, n = cs.shape[-2], cs.shape[-1]
         static, groups = self._static(cs.shape[1], qg, n)
-        if cs.is_cuda and amd_key("attn", "fused_topk_mask") and cs.dtype == torch.bfloat16 and n <= 122880:
+        if cs.is_cuda and amd_key("attn", "fused_topk_mask") and cs.dtype == torch.bfloat16 and n <= ops.TOPK_MASK_MAX_N:
             # one kernel for the whole chain below (the random 1 % comes from a counter-based hash, not torch's RNG)
             return ops.topk_mask(cs, topk, 0.01, groups, static)
         mask = torch.randint(0, 100, cs.shape, device=cs.device, dtype=torch.uint8) == 0
@@ -208,7 +208,7 @@ class SparseDiffAttn(nn.Module):
                 tk = int(multiple_of * round((cfg["top_keys"] * k.shape[-2]) / multiple_of))
                 mask = bs = None
                 if (q.is_cuda and cfg["should_compress_indices"] and tk > 0 and amd_key("attn", "fused_colsum_topk")
-                        and amd_key("attn", "fused_topk_mask") and k.shape[-2] <= 122880):
+                        and amd_key("attn", "fused_topk_mask") and k.shape[-2] <= ops.TOPK_MASK_MAX_N):
                     # dense attention -> column sums -> mask without the column-sum tensor in between (same bits as the two steps)
                     static, groups = self._static(q.shape[1], _cdiv(q.shape[-2], bm), k.shape[-2])
                     o, mask, lse = ops.dense_colsum_topk_mask(q, k, v, prev_lse, tk, 0.01, groups, static, tm)

@@ -5,6 +5,10 @@ from typing import List, Optional, Sequence
 
 import torch
 
+# Longest row (last dimension of ``cs``, key count of the fused mask step) the top-k mask kernels take: CHIPMUNK_TOPK_MASK_MAX_N of
+# ``csrc/common.h``.  Up to 122 880 columns a row's keys stay in registers; longer rows take the streaming form of the kernel.
+TOPK_MASK_MAX_N = 1024 * 512
+
 
 def copy_indices(bm_fc1: torch.Tensor, bm_mid_cache: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor) -> None:
     torch.ops.chipmunk.copy_indices(bm_fc1, bm_mid_cache, indices, counts)
@@ -43,7 +47,8 @@ def topk_mask(cs: torch.Tensor, k: int, random_amount: float = 0.0, groups: Opti
     """``((top-k of cs | random) & groups) | static_mask`` as one kernel: the reference's ``random_and_topk``
     (``modules/attn.py:76-82``: randint + topk + scatter_ + two mask combines).  Exactly ``k`` columns per active row
     come from the top-k part (ties at the k-th value broken deterministically); the random part is a counter-based
-    hash, so only ``random_amount = 0`` is comparable bit for bit with the torch chain."""
+    hash, so only ``random_amount = 0`` is comparable bit for bit with the torch chain.  Rows of up to
+    ``TOPK_MASK_MAX_N`` columns; ties at the k-th value go to the columns lowest in ``((c % 4096) // 4, c)`` order."""
     return torch.ops.chipmunk.topk_mask(cs, k, random_amount, groups, static_mask)
 
 

@@ -224,7 +224,7 @@ int chipmunk_topk_delta_indices(const void *activation, void *cache, int dtype, 
  * dense_colsum_attn, then random_and_topk on its 3.55 GB result at HunyuanVideo size): o, l as chipmunk_dense_colsum_attn,
  * mask [B*H*ceil(Nq/192), Nk] bool bytes as chipmunk_topk_mask would produce from that call's cs -- bit for bit.
  * Returns CHIPMUNK_ERR_UNSUPPORTED without enqueuing anything when the launch would not take the one-pass route in one piece
- * (small launches, Nk % 4 != 0, no room for the partial sums): run the two operators then. */
+ * (small launches, Nk % 4 != 0, Nk > 524 288, no room for the partial sums): run the two operators then. */
 int chipmunk_dense_colsum_topk_mask(const void *q, const void *k, const void *v, const int64_t q_strides[3],
                                     const int64_t k_strides[3], const int64_t v_strides[3], const float *p, void *o, float *l,
                                     int B, int H, int Nq, int Nk, const void *static_mask, int64_t static_stride, int static_rows,
@@ -237,7 +237,9 @@ int chipmunk_dense_colsum_topk_mask(const void *q, const void *k, const void *v,
  * rows modulo static_rows; group_flags (optional) one byte per row; mask [rows, n] bool bytes, fully overwritten.
  * Exactly k columns per active row come from the top-k part; ties at the k-th value are broken deterministically (the
  * reference's torch.topk leaves that choice unspecified); u is a counter-based hash (RNG streams cannot match torch's
- * randint), so results are comparable with the reference chain for random_amount = 0.  n <= 122 880. */
+ * randint), so results are comparable with the reference chain for random_amount = 0.
+ * Ties are taken in ascending order of ((c mod 4096) div 4, c).  n <= 524 288: rows of up to 122 880 columns keep their keys in
+ * registers, longer ones take the streaming form of the kernel (same bits; tuning option topk_mask_stream = 1 sends every row there). */
 int chipmunk_topk_mask(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
                        int static_rows, const void *group_flags, void *mask, int rows, int n, int k,
                        double random_amount, void *stream);
