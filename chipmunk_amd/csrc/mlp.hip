@@ -488,8 +488,19 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     MPROF_END(w, nkb);
 }
 
-template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4>
-__global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const Mm1Params p) {
+// Batched launch (B > 1 sequences in one grid): the operands of sequence b are its slices of dense [B, M, .] tensors, the cache
+// [B, F, ldc] with a batch stride of its own; indices [B, G, F] and counts [B, G] are the per-sequence lists back to back, i.e. one list
+// of B * G groups.  The tile map runs over those B * G groups (group g = sequence g / G, local group g % G), and a tile then sees the
+// Mm1Params of ITS sequence: base pointers advanced in 64-bit arithmetic, so the descriptors keep per-sequence sizes and every 32-bit
+// offset inside a sequence stays what it is in a single-sequence launch.  Every output element is still produced by one workgroup in
+// the same K order: the bits of B separate launches.
+struct Mm1Batch : Mm1Params {
+    int B;
+    int64_t cache_bs;   // elements between the caches of consecutive sequences (>= F * ldc)
+};
+
+template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false>
+__global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     MPROF_ABS(0);
     constexpr int NSUB = NW == 4 ? 2 * (BN / 64) : 1;  // 64 x 64 sub-tiles per tile (the 8-wave form has no tail split)
@@ -498,25 +509,54 @@ __global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const Mm1Params p) {
     // (kernel arguments, the live-tile map, wave start-up: 5.4 k of a 41 k-cycle tile at the Wan2.1 fp8 shape, tools/mlp_prof.py) and
     // with the previous tile's stores draining under the next tile's index loads.  (Requesting the NEXT tile's gather indices during
     // the current tile -- one exposed round trip less -- measured no gain at the fp8 shape, 209 vs 209-224 us, for 40 more registers.)
-    const TilePlan pl = plan_tiles<BN>(p.counts, (p.M + BM - 1) / BM, p.NT, p.NR, p.slots_per_xcd, NSUB);
-    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
-    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
-        const TileMap tm = tile_at(pl, slot);
-        if (!tm.live) continue;
-        const int g = tm.g;
-        const int cnt = p.counts[g];
-        if (tm.sub < 0) {
-            const int n0 = tm.nt * BN;
-            if (n0 >= cnt) continue;  // tiles past counts[g] are skipped (csp_mlp_mm1.cu:233-243)
-            mm1_tile<BM, BN, BK, NST, FP8, NW>(p, smem, g, 0, n0, cnt);
-        } else if constexpr (NW == 4) {
-            constexpr int SUB_NST = (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
-            const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
-            if (n0 >= cnt || p.probe == 3) continue;  // probe 3: time the launch without its tail
-            if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
-            mm1_tile<64, 64, BK, (SUB_NST > 4 ? 4 : SUB_NST), FP8>(p, smem, g, (tm.sub & 1) * 64, n0, cnt);
+    if constexpr (BATCHED) {
+        const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence; the map runs over all B * Gs
+        const TilePlan pl = plan_tiles<BN>(p.counts, p.B * Gs, p.NT, p.NR, p.slots_per_xcd, NSUB);
+        const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+        for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+            const TileMap tm = tile_at(pl, slot);
+            if (!tm.live) continue;
+            const int cnt = p.counts[tm.g];
+            const int b = tm.g / Gs, g = tm.g - b * Gs;   // sequence, group inside it
+            Mm1Params q = p;                              // the tile sees its sequence's operands
+            q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)b * p.M * p.K * (FP8 ? 1 : 2));
+            q.c = p.c + (int64_t)b * p.M * p.F;
+            q.cache = p.cache + (int64_t)b * p.cache_bs;
+            q.indices = p.indices + (int64_t)b * Gs * p.F;
+            if (tm.sub < 0) {
+                const int n0 = tm.nt * BN;
+                if (n0 >= cnt) continue;  // tiles past counts[g] are skipped (csp_mlp_mm1.cu:233-243)
+                mm1_tile<BM, BN, BK, NST, FP8, NW>(q, smem, g, 0, n0, cnt);
+            } else if constexpr (NW == 4) {
+                constexpr int SUB_NST = (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
+                const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
+                if (n0 >= cnt || p.probe == 3) continue;  // probe 3: time the launch without its tail
+                if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
+                mm1_tile<64, 64, BK, (SUB_NST > 4 ? 4 : SUB_NST), FP8>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
+            }
+            __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
         }
-        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
+    } else {
+        const TilePlan pl = plan_tiles<BN>(p.counts, (p.M + BM - 1) / BM, p.NT, p.NR, p.slots_per_xcd, NSUB);
+        const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+        for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+            const TileMap tm = tile_at(pl, slot);
+            if (!tm.live) continue;
+            const int g = tm.g;
+            const int cnt = p.counts[g];
+            if (tm.sub < 0) {
+                const int n0 = tm.nt * BN;
+                if (n0 >= cnt) continue;  // tiles past counts[g] are skipped (csp_mlp_mm1.cu:233-243)
+                mm1_tile<BM, BN, BK, NST, FP8, NW>(p, smem, g, 0, n0, cnt);
+            } else if constexpr (NW == 4) {
+                constexpr int SUB_NST = (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
+                const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
+                if (n0 >= cnt || p.probe == 3) continue;  // probe 3: time the launch without its tail
+                if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
+                mm1_tile<64, 64, BK, (SUB_NST > 4 ? 4 : SUB_NST), FP8>(p, smem, g, (tm.sub & 1) * 64, n0, cnt);
+            }
+            __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
+        }
     }
 }
 
@@ -537,8 +577,13 @@ struct Mm2Params {
     int cus_per_xcd;   // > 0: length-aware placement of a one-round launch (see mm2_kernel), 0: dispatch order = tile order
 };
 
-template <int BN, int BK, int NST, int WPS, int NW = 4>
-__global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2Params p) {
+// Batched launch: as Mm1Batch -- a [B, M, F], c [B, M, N2], indices [B, G, F], counts [B, G]; the map runs over B * G groups
+struct Mm2Batch : Mm2Params {
+    int B;
+};
+
+template <int BN, int BK, int NST, int WPS, int NW = 4, bool BATCHED = false>
+__global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const typename std::conditional<BATCHED, Mm2Batch, Mm2Params>::type p) {
     static_assert(NW == 4 || NW == 8, "4 waves (2 x 2) or 8 waves (2 x 4)");
     constexpr int WNG = NW / 2;                 // waves along n; wave tile = 64 rows x BN/WNG columns
     using KT = KTile<BK>;
@@ -555,7 +600,9 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
     const int wm = w / WNG, wn = w % WNG;
 
     // all column tiles of fc2^T are live (N2 is dense); the map only reorders them for L2 reuse (see map_tile)
-    const int G = (p.M + BM - 1) / BM;
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = Gs * p.B;
     const int xcdq = (G * p.NT) >> 3, xcdr = (G * p.NT) & 7;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     if (slot >= xcdq + (xcd < xcdr ? 1 : 0)) return;
@@ -591,18 +638,32 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
     }
     const int nb = t / (G * NR), rem = t - nb * (G * NR);
     const int nr = min(NR, p.NT - nb * NR);
-    const int g = rem / nr, nt = nb * NR + rem - g * nr;
-    const int cnt = p.counts[g];
+    const int gi = rem / nr, nt = nb * NR + rem - gi * nr;   // gi: the group's place in the index / count lists
+    const int cnt = p.counts[gi];
+    // g: the group inside its sequence; seq_a / seq_c: that sequence's operands (64-bit bases; the offsets below stay per sequence)
+    int g = gi, bseq = 0;
+    if constexpr (BATCHED) {
+        bseq = gi / Gs;
+        g = gi - bseq * Gs;
+    }
+    auto seq_a = [&]() -> const uint16_t * {
+        if constexpr (BATCHED) return p.a + (int64_t)bseq * p.M * p.F;
+        else return p.a;
+    };
+    auto seq_c = [&]() -> uint16_t * {
+        if constexpr (BATCHED) return p.c + (int64_t)bseq * p.M * p.N2;
+        else return p.c;
+    };
     const int n0 = nt * BN;
     const int ncols = min(BN, p.N2 - n0);  // N2 is a multiple of 8 (checked on the host)
-    const int32_t *idxg = p.indices + (int64_t)g * p.F;
+    const int32_t *idxg = p.indices + (int64_t)gi * p.F;
     const int nkb = (cnt + BK - 1) / BK;
     if (nkb == 0) return;
 
     // ragged last group: `rows` of the 128 rows exist; the A pieces of the others re-read the last live row (a row of A only feeds its
     // own output row) and the epilogue neither loads nor stores their rows of C
     const int rows = min(BM, p.M - g * BM);
-    const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.a, (uint32_t)p.M * p.F * 2u), rb = make_rsrc(p.b);
+    const __amdgpu_buffer_rsrc_t ra = make_rsrc(seq_a(), (uint32_t)p.M * p.F * 2u), rb = make_rsrc(p.b);
     uint32_t aoff[A_INST];  // byte offsets
 #pragma unroll
     for (int i = 0; i < A_INST; ++i) {
@@ -794,7 +855,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
             const int item = it * (NW * 64) + tid;
             const int r = item / CPRO, ch = item % CPRO;
             const int n = n0 + ch * 8;
-            olds[it] = (n < p.N2 && r < rows) ? *(const u32x4 *)(p.c + (int64_t)(g * BM + r) * p.N2 + n) : (u32x4){0u, 0u, 0u, 0u};
+            olds[it] = (n < p.N2 && r < rows) ? *(const u32x4 *)(seq_c() + (int64_t)(g * BM + r) * p.N2 + n) : (u32x4){0u, 0u, 0u, 0u};
         }
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
@@ -803,7 +864,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
             const int n = n0 + ch * 8;
             if (n >= p.N2 || r >= rows) continue;  // N2 is a multiple of 8: a chunk is live or dead as a whole
             const u32x4 a = *(const u32x4 *)(smem + r * (BN * 2) + ((ch ^ (r & (CPRO - 1) & 31)) << 4));
-            uint16_t *cp = p.c + (int64_t)(g * BM + r) * p.N2 + n;
+            uint16_t *cp = seq_c() + (int64_t)(g * BM + r) * p.N2 + n;
             const u32x4 old = olds[it];
             u32x4 out;
 #pragma unroll
@@ -816,7 +877,7 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             const int m = g * BM + wm * 64 + mt * 32 + (lane & 31);
-            uint16_t *crow = p.c + (int64_t)m * p.N2;
+            uint16_t *crow = seq_c() + (int64_t)m * p.N2;
 #pragma unroll
             for (int n4 = 0; n4 < NT4; ++n4) {
 #pragma unroll
@@ -844,10 +905,19 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const Mm2
 constexpr int SC_COLS = 64;
 constexpr int SC_LD = 136;  // padded row length of the transposed tile (bf16 elements)
 
+// Batched launch (one trailing argument: the elements between the caches of consecutive sequences): blockIdx.y walks the B * G groups
+// of indices [B, G, F] / counts [B, G]; packed is [B, M, F].  The pointers move to the group's sequence, then everything is as below.
+template <class... BS>
 __global__ __launch_bounds__(256) void scatter_add_kernel(const uint16_t *packed, uint16_t *unpacked,
-                                                          const int32_t *indices, const int32_t *counts, int M, int F, int ldc) {
+                                                          const int32_t *indices, const int32_t *counts, int M, int F, int ldc, BS... cache_bs) {
+    static_assert(sizeof...(BS) <= 1, "at most the cache batch stride");
     __shared__ __attribute__((aligned(16))) uint16_t tile[SC_COLS * SC_LD];
-    const int g = blockIdx.y, c0 = blockIdx.x * SC_COLS;
+    if constexpr (sizeof...(BS) == 1) {
+        const int Gs = (M + 127) / 128, b = blockIdx.y / Gs;
+        packed += (int64_t)b * M * F, unpacked += (int64_t)b * (int64_t)(cache_bs + ...);
+        indices += (int64_t)b * Gs * F, counts += b * Gs;
+    }
+    const int g = sizeof...(BS) == 1 ? blockIdx.y % ((M + 127) / 128) : blockIdx.y, c0 = blockIdx.x * SC_COLS;
     const int cnt = counts[g];
     if (c0 >= cnt) return;
     const int tid = threadIdx.x;
@@ -918,18 +988,39 @@ int check_cache_pitch(int M, int F, int ldc) {
     return CHIPMUNK_OK;
 }
 
+// The *_batched entries: B sequences in one launch, the ragged contract per sequence
+int check_mlp_batch(int B, int M) {
+    CM_CHECK(B >= 1, "mlp: the batch size B must be at least 1 (got %d)", B);
+    CM_CHECK((int64_t)B * ((M + BM - 1) / BM) <= 65535, "mlp: B * ceil(M / 128) groups must not exceed 65535 (got B = %d, M = %d)", B, M);
+    return CHIPMUNK_OK;
+}
+int check_cache_batch_stride(int F, int ldc, int64_t cache_bs) {
+    CM_CHECK(cache_bs >= (int64_t)F * ldc && cache_bs % 8 == 0,
+             "mlp: the cache batch stride must be at least F * ldc and a multiple of 8 elements (got %lld, F * ldc = %lld)",
+             (long long)cache_bs, (long long)F * ldc);
+    return CHIPMUNK_OK;
+}
+
 int launch_scatter_add(const void *packed, void *unpacked, const int32_t *indices, const int32_t *counts, int M, int F, int ldc,
                        hipStream_t s) {
-    hipLaunchKernelGGL(scatter_add_kernel, dim3(F / SC_COLS, (M + BM - 1) / BM), dim3(256), 0, s, (const uint16_t *)packed,
+    hipLaunchKernelGGL(scatter_add_kernel<>, dim3(F / SC_COLS, (M + BM - 1) / BM), dim3(256), 0, s, (const uint16_t *)packed,
                        (uint16_t *)unpacked, indices, counts, M, F, ldc);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }
+int launch_scatter_add_batched(const void *packed, void *unpacked, const int32_t *indices, const int32_t *counts, int B, int M, int F,
+                               int ldc, int64_t cache_bs, hipStream_t s) {
+    hipLaunchKernelGGL(scatter_add_kernel<int64_t>, dim3(F / SC_COLS, B * ((M + BM - 1) / BM)), dim3(256), 0, s, (const uint16_t *)packed,
+                       (uint16_t *)unpacked, indices, counts, M, F, ldc, cache_bs);
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
 
-template <int BN, int BK, int NST, int WPS, int NW = 4>
-int launch_mm2_variant(const Mm2Params &p0, hipStream_t s) {
+// B > 0: the batched instantiation over B * G groups
+template <int BN, int BK, int NST, int WPS, int NW = 4, bool BATCHED = false>
+int launch_mm2_variant(const Mm2Params &p0, hipStream_t s, int B = 1) {
     constexpr int LDS = NST * (BM * BK * 2 + BK * BN * 2);
-    auto kern = mm2_kernel<BN, BK, NST, WPS, NW>;
+    auto kern = mm2_kernel<BN, BK, NST, WPS, NW, BATCHED>;
     static uint64_t lds_set = 0;
     ensure_dynamic_lds((const void *)kern, LDS, lds_set);
     Mm2Params p = p0;
@@ -938,16 +1029,25 @@ int launch_mm2_variant(const Mm2Params &p0, hipStream_t s) {
     if (p.NR > p.NT) p.NR = p.NT;
     // length-aware placement: two-workgroups-per-CU forms only (what the census measured); option mm2_order = 1 keeps tile order
     p.cus_per_xcd = (WPS == 2 && !chipmunk_get_option("mm2_order")) ? device_cu_count() / 8 : 0;
-    hipLaunchKernelGGL(kern, dim3(((((p.M + BM - 1) / BM) * p.NT + 7) / 8) * 8), dim3(NW * 64), LDS, s, p);
+    const dim3 grid(((B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8) * 8);
+    if constexpr (BATCHED) {
+        Mm2Batch q;
+        static_cast<Mm2Params &>(q) = p;
+        q.B = B;
+        hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS, s, q);
+    } else {
+        hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS, s, p);
+    }
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }
 
 int launch_mm2(const void *a, const void *b, void *c, const int32_t *indices, const int32_t *counts, int M, int F, int N2,
-               hipStream_t s) {
+               hipStream_t s, int B = 0) {
     CM_CHECK(N2 > 0 && N2 % 8 == 0, "mm2: N2 must be a positive multiple of 8 (got %d)", N2);
     CM_CHECK((int64_t)M * F < (1ll << 31) && (int64_t)F * N2 < (1ll << 31), "mm2: M*F or F*N2 too large for 32-bit offsets");
     Mm2Params p = {(const uint16_t *)a, (const uint16_t *)b, (uint16_t *)c, indices, counts, M, F, N2, 0, 0, chipmunk_get_option("mm1_probe")};
+    if (B > 0) return launch_mm2_variant<256, 32, 3, 2, 8, true>(p, s, B);   // the *_batched entries: the shipped form only
 #ifdef CHIPMUNK_MM1_PROBES
     if (M % BM == 0) switch (chipmunk_get_option("mm2_variant")) {   // (the probe forms know whole groups only)
         case 1: return launch_mm2_variant<256, 64, 2, 1>(p, s);
@@ -973,12 +1073,12 @@ int launch_mm2(const void *a, const void *b, void *c, const int32_t *indices, co
     return launch_mm2_variant<256, 32, 3, 2, 8>(p, s);
 }
 
-template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4>
-int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated = nullptr) {
+template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false>
+int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated = nullptr, int B = 1, int64_t cache_bs = 0) {
     constexpr int STAGE = BM * BK * 2 + BN * BK * 2, LDS = NST * STAGE, EPI = BM * BN * 2;
     // mm1_tile's staged epilogue (the one that can scatter): one stage each for cache block and outputs, or the FLAT layout
     constexpr bool STAGED = EPI <= STAGE || (NW == 8 && EPI <= (NST - 1) * STAGE && 2 * EPI <= NST * STAGE && STAGE % (BN * 2) == 0);
-    auto kern = mm1_kernel<BN, BK, NST, WPS, FP8, NW>;
+    auto kern = mm1_kernel<BN, BK, NST, WPS, FP8, NW, BATCHED>;
     static uint64_t lds_set = 0;
     ensure_dynamic_lds((const void *)kern, LDS, lds_set);
     Mm1Params p = p0;
@@ -995,9 +1095,16 @@ int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated =
     const int resident_per_xcd = WPS_FIT * device_cu_count() / 8;
     p.slots_per_xcd = (chipmunk_get_option("mm1_no_split") || NW != 4) ? 0 : resident_per_xcd;
     // persistent grid: the resident slots, or fewer when the launch has fewer tiles than slots (every tile gets its own workgroup)
-    const int tiles_per_xcd = (((p.M + BM - 1) / BM) * p.NT + 7) / 8;
+    const int tiles_per_xcd = (B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8;
     const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
-    hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(NW * 64), LDS, s, p);
+    if constexpr (BATCHED) {
+        Mm1Batch q;
+        static_cast<Mm1Params &>(q) = p;
+        q.B = B, q.cache_bs = cache_bs;
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(NW * 64), LDS, s, q);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(NW * 64), LDS, s, p);
+    }
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }
@@ -1007,15 +1114,20 @@ int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated =
 namespace {
 // `ragged`: the *_ragged entries' contract (any M, cache pitch ldc); otherwise the reference's (M % 128 == 0, ldc == M)
 int mm1_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
-              const int32_t *counts, int M, int K, int F, int ldc, bool ragged, hipStream_t stream, int update_cache, bool *cache_updated) {
+              const int32_t *counts, int M, int K, int F, int ldc, bool ragged, hipStream_t stream, int update_cache, bool *cache_updated,
+              int B = 0, int64_t cache_bs = 0) {   // B > 0: the *_batched entries
     CM_CHECK(a && b && c && bias && pa_cache, "csp_mlp_mm1: null tensor pointer");
     if (int e = ragged ? check_mlp_ragged(M, F, indices, counts) : check_mlp_common(M, F, indices, counts)) return e;
     if (int e = check_cache_pitch(M, F, ldc)) return e;
+    if (B > 0) {
+        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
+    }
     CM_CHECK(K > 0 && K % 64 == 0, "csp_mlp_mm1: K must be a positive multiple of 64 (got %d)", K);
     CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
              "csp_mlp_mm1: operand too large for 32-bit offsets");
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, chipmunk_get_option("mm1_probe"), 0, update_cache, nullptr, nullptr, ldc};
+    if (B > 0) return launch_mm1_variant<128, 64, 2, 2, false, 4, true>(p, stream, cache_updated, B, cache_bs);   // the shipped form only
 #ifdef CHIPMUNK_MM1_PROBES
     if (M % BM == 0 && ldc == M) switch (chipmunk_get_option("mm1_variant")) {   // (the probe forms know whole groups and ldc == M only)
         case 1: return launch_mm1_variant<256, 64, 2, 1>(p, stream, cache_updated);
@@ -1046,19 +1158,24 @@ int mm1_entry(const void *a, const void *b, void *c, const void *bias, void *pa_
 }
 
 int mm1_scatter_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
-                      const int32_t *counts, int M, int K, int F, int ldc, bool ragged, hipStream_t stream) {
+                      const int32_t *counts, int M, int K, int F, int ldc, bool ragged, hipStream_t stream, int B = 0, int64_t cache_bs = 0) {
     bool done = false;
-    if (int e = mm1_entry(a, b, c, bias, pa_cache, indices, counts, M, K, F, ldc, ragged, stream, 1, &done)) return e;
+    if (int e = mm1_entry(a, b, c, bias, pa_cache, indices, counts, M, K, F, ldc, ragged, stream, 1, &done, B, cache_bs)) return e;
     // tile shapes whose epilogue does not hold the cache block in LDS: the separate scatter-add kernel
-    return done ? CHIPMUNK_OK : launch_scatter_add(c, pa_cache, indices, counts, M, F, ldc, stream);
+    if (done) return CHIPMUNK_OK;
+    if (B > 0) return launch_scatter_add_batched(c, pa_cache, indices, counts, B, M, F, ldc, cache_bs, stream);
+    return launch_scatter_add(c, pa_cache, indices, counts, M, F, ldc, stream);
 }
 
 int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
                   const int32_t *counts, const float *scale_a, const float *scale_b, int M, int K, int F, int ldc, bool ragged,
-                  int update_cache, hipStream_t stream) {
+                  int update_cache, hipStream_t stream, int B = 0, int64_t cache_bs = 0) {
     CM_CHECK(a && b && c && bias && pa_cache && scale_a && scale_b, "csp_mlp_mm1_fp8: null tensor pointer");
     if (int e = ragged ? check_mlp_ragged(M, F, indices, counts) : check_mlp_common(M, F, indices, counts)) return e;
     if (int e = check_cache_pitch(M, F, ldc)) return e;
+    if (B > 0) {
+        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
+    }
     CM_CHECK(K > 0 && K % 128 == 0, "csp_mlp_mm1_fp8: K must be a positive multiple of 128 (got %d)", K);
     CM_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8: update_cache must be 0, 1 or 2");
     CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
@@ -1066,6 +1183,7 @@ int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void 
     // same tile machinery as the bf16 kernel (buffer-form DMA, tail split, staged epilogue); a k step is 128 fp8 values
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache, (uint16_t *)c,
                    indices, counts, M, K, F, 0, 0, chipmunk_get_option("mm1_probe"), 0, update_cache == 1 ? 2 : update_cache == 2 ? 1 : 0, scale_a, scale_b, ldc};
+    if (B > 0) return launch_mm1_variant<128, 64, 2, 2, true, 4, true>(p, stream, nullptr, B, cache_bs);
 #ifdef CHIPMUNK_MM1_PROBES
     if (M % BM == 0 && ldc == M) {
         if (chipmunk_get_option("mm1_variant") == 10) return launch_mm1_variant<256, 64, 3, 1, true, 8>(p, stream);
@@ -1156,4 +1274,59 @@ extern "C" int chipmunk_csp_mlp_mm1_fp8_ragged(const void *a, const void *b, voi
                                                const int32_t *indices, const int32_t *counts, const float *scale_a,
                                                const float *scale_b, int M, int K, int F, int ldc, int update_cache, void *stream) {
     return mm1_fp8_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, M, K, F, ldc, true, update_cache, (hipStream_t)stream);
+}
+
+// ---- B sequences in one launch (include/chipmunk_hip.h, "Batches")
+extern "C" int chipmunk_csp_mlp_mm1_batched(const void *a, const void *b, void *c, const void *bias, const void *pa_cache,
+                                            const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int B,
+                                            int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_entry(a, b, c, bias, const_cast<void *>(pa_cache), indices, counts, M, K, F, ldc, true, (hipStream_t)stream, 0, nullptr, B,
+                     cache_batch_stride);
+}
+extern "C" int chipmunk_csp_mlp_mm1_scatter_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                                    const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int B,
+                                                    int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_scatter_entry(a, b, c, bias, pa_cache, indices, counts, M, K, F, ldc, true, (hipStream_t)stream, B, cache_batch_stride);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                                const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                                int M, int K, int F, int ldc, int update_cache, int B, int64_t cache_batch_stride,
+                                                void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_fp8_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, M, K, F, ldc, true, update_cache, (hipStream_t)stream, B,
+                         cache_batch_stride);
+}
+extern "C" int chipmunk_csp_mlp_mm2_batched(const void *mma_a, const void *mma_b, void *mma_c, const int32_t *indices,
+                                            const int32_t *counts, int M, int F, int N2, int B, void *stream) {
+    CM_CHECK(mma_a && mma_b && mma_c, "csp_mlp_mm2: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_mlp_batch(B, M)) return e;
+    return launch_mm2(mma_a, mma_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream, B);
+}
+extern "C" int chipmunk_csp_scatter_add_batched(const void *packed, void *unpacked_colmajor, const int32_t *indices,
+                                                const int32_t *counts, int M, int F, int ldc, int B, int64_t cache_batch_stride,
+                                                void *stream) {
+    CM_CHECK(packed && unpacked_colmajor, "csp_scatter_add: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_mlp_batch(B, M)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
+    if (int e = check_cache_batch_stride(F, ldc, cache_batch_stride)) return e;
+    return launch_scatter_add_batched(packed, unpacked_colmajor, indices, counts, B, M, F, ldc, cache_batch_stride, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm2_and_scatter_add_batched(const void *packed, void *unpacked_colmajor, const int32_t *indices,
+                                                            const int32_t *counts, const void *mma_a, const void *mma_b, void *mma_c,
+                                                            int M, int F, int N2, int ldc, int B, int64_t cache_batch_stride,
+                                                            void *stream) {
+    CM_CHECK(packed && unpacked_colmajor && mma_a && mma_b && mma_c, "csp_mlp_mm2_and_scatter_add: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_mlp_batch(B, M)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
+    if (int e = check_cache_batch_stride(F, ldc, cache_batch_stride)) return e;
+    CM_CHECK(N2 > 0 && N2 % 8 == 0, "mm2: N2 must be a positive multiple of 8 (got %d)", N2);   // before the first kernel is enqueued
+    CM_CHECK((int64_t)M * F < (1ll << 31) && (int64_t)F * N2 < (1ll << 31), "mm2: M*F or F*N2 too large for 32-bit offsets");
+    if (int e = launch_scatter_add_batched(packed, unpacked_colmajor, indices, counts, B, M, F, ldc, cache_batch_stride, (hipStream_t)stream))
+        return e;
+    return launch_mm2(mma_a, mma_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream, B);
 }

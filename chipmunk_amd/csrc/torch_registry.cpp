@@ -271,6 +271,41 @@ void check_pitch(int64_t ldc, int64_t M, const char *name) {
 bool whole_groups(int64_t M, int64_t ldc) { return M % 128 == 0 && ldc == M; }
 int64_t groups_of(int64_t M) { return (M + 127) / 128; }
 
+// Batches (B > 1 sequences in one launch): a [B, M, K], c [B, M, F], the cache [B, F, M] (or the [..., :M] view of [B, F, ldc], any batch
+// stride the C entry accepts), indices [B, G, F], counts [B, G].  2-D operands and B == 1 take exactly the entries they always took.
+struct Mm1Shape {
+    int64_t B, M, K, F, ldc, cache_bs;
+    bool batched() const { return B > 1; }
+};
+Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c, const at::Tensor &bias, const at::Tensor &cache,
+                   const at::Tensor &indices, const at::Tensor &counts) {
+    TORCH_CHECK((a.dim() == 2 || a.dim() == 3) && b.dim() == 2 && c.dim() == a.dim(), "a and c must both be 2D ([M, .]) or 3D ([B, M, .]), b 2D");
+    Mm1Shape s;
+    s.B = a.dim() == 3 ? a.size(0) : 1;
+    s.M = a.size(-2), s.K = a.size(-1), s.F = b.size(0);
+    TORCH_CHECK(s.B >= 1, "the batch size must be at least 1");
+    TORCH_CHECK(b.size(1) == s.K, "a and b must share the K dimension");
+    TORCH_CHECK(c.size(-2) == s.M && c.size(-1) == s.F && c.numel() == s.B * s.M * s.F, "c must be [M, F] ([B, M, F] with the batch size of a)");
+    TORCH_CHECK(bias.numel() == s.F, "bias must have F entries");
+    if (!s.batched()) {
+        s.ldc = cache_pitch(cache, s.F, s.M, "pa_cache_colmajor");
+        s.cache_bs = s.F * s.ldc;
+    } else {
+        TORCH_CHECK(cache.dim() == 3 && cache.size(0) == s.B && cache.size(1) == s.F && cache.size(2) == s.M,
+                    "pa_cache_colmajor must be [B, F, M] with the batch size of a (B = ", s.B, ")");
+        TORCH_CHECK(cache.stride(2) == 1, "pa_cache_colmajor: the M elements of a column must be contiguous");
+        s.ldc = cache.stride(1), s.cache_bs = cache.stride(0);
+        TORCH_CHECK(s.cache_bs >= s.F * s.ldc && s.cache_bs % 8 == 0, "pa_cache_colmajor: the batch stride (", s.cache_bs,
+                    " elements) must be at least F * ldc = ", s.F * s.ldc, " and a multiple of 8");
+    }
+    check_pitch(s.ldc, s.M, "pa_cache_colmajor");
+    const int64_t G = groups_of(s.M);
+    TORCH_CHECK(indices.numel() == s.B * G * s.F && counts.numel() == s.B * G,
+                "indices must be [ceil(M/128), F], counts [ceil(M/128)] ([B, ceil(M/128), F] and [B, ceil(M/128)] with the batch size of a)");
+    TORCH_CHECK(s.B * G <= 65535, "B * ceil(M/128) groups must not exceed 65535 (got ", s.B * G, ")");
+    return s;
+}
+
 // reference csrc/mlp/csp_mlp_mm1.cu:625-702
 void csp_mlp_mm1(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
                  at::Tensor indices, at::Tensor indices_counts) {
@@ -280,16 +315,15 @@ void csp_mlp_mm1(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor b
     CHECK_I32(indices); CHECK_I32(indices_counts);
     CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias);
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
-    TORCH_CHECK(a.dim() == 2 && b_colmajor.dim() == 2 && c.dim() == 2, "a, b_colmajor, c must be 2D");
-    const int64_t M = a.size(0), K = a.size(1), F = b_colmajor.size(0);
-    TORCH_CHECK(b_colmajor.size(1) == K, "a and b_colmajor must share the K dimension");
-    TORCH_CHECK(c.size(0) == M && c.size(1) == F, "c must be [M, F]");
-    TORCH_CHECK(bias.numel() == F, "bias must have F entries");
-    const int64_t ldc = cache_pitch(pa_cache_colmajor, F, M, "pa_cache_colmajor");
-    check_pitch(ldc, M, "pa_cache_colmajor");
-    TORCH_CHECK(indices.numel() == groups_of(M) * F && indices_counts.numel() == groups_of(M), "indices must be [ceil(M/128), F], counts [ceil(M/128)]");
+    const Mm1Shape sh = mm1_shape(a, b_colmajor, c, bias, pa_cache_colmajor, indices, indices_counts);
+    const int64_t M = sh.M, K = sh.K, F = sh.F, ldc = sh.ldc;
     c10::DeviceGuard guard(a.device());
-    if (whole_groups(M, ldc))
+    if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_batched(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
+                                           pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
+                                           (int)M, (int)K, (int)F, (int)ldc, (int)sh.B, sh.cache_bs, cur_stream(a)),
+              "csp_mlp_mm1");
+    else if (whole_groups(M, ldc))
         check(chipmunk_csp_mlp_mm1(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
                                    pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
                                    (int)M, (int)K, (int)F, cur_stream(a)),
@@ -310,16 +344,15 @@ void csp_mlp_mm1_scatter(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::
     CHECK_I32(indices); CHECK_I32(indices_counts);
     CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias);
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
-    TORCH_CHECK(a.dim() == 2 && b_colmajor.dim() == 2 && c.dim() == 2, "a, b_colmajor, c must be 2D");
-    const int64_t M = a.size(0), K = a.size(1), F = b_colmajor.size(0);
-    TORCH_CHECK(b_colmajor.size(1) == K, "a and b_colmajor must share the K dimension");
-    TORCH_CHECK(c.size(0) == M && c.size(1) == F, "c must be [M, F]");
-    TORCH_CHECK(bias.numel() == F, "bias must have F entries");
-    const int64_t ldc = cache_pitch(pa_cache_colmajor, F, M, "pa_cache_colmajor");
-    check_pitch(ldc, M, "pa_cache_colmajor");
-    TORCH_CHECK(indices.numel() == groups_of(M) * F && indices_counts.numel() == groups_of(M), "indices must be [ceil(M/128), F], counts [ceil(M/128)]");
+    const Mm1Shape sh = mm1_shape(a, b_colmajor, c, bias, pa_cache_colmajor, indices, indices_counts);
+    const int64_t M = sh.M, K = sh.K, F = sh.F, ldc = sh.ldc;
     c10::DeviceGuard guard(a.device());
-    if (whole_groups(M, ldc))
+    if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_scatter_batched(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
+                                                   pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
+                                                   (int)M, (int)K, (int)F, (int)ldc, (int)sh.B, sh.cache_bs, cur_stream(a)),
+              "csp_mlp_mm1_scatter");
+    else if (whole_groups(M, ldc))
         check(chipmunk_csp_mlp_mm1_scatter(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
                                            pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
                                            indices_counts.data_ptr<int>(), (int)M, (int)K, (int)F, cur_stream(a)),
@@ -345,15 +378,16 @@ static void mm1_fp8_impl(at::Tensor a, at::Tensor b, at::Tensor c, at::Tensor bi
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
     TORCH_CHECK(scale_a.scalar_type() == at::kFloat && scale_b.scalar_type() == at::kFloat && scale_a.numel() == 1 &&
                 scale_b.numel() == 1, "scale_a and scale_b must be one-element float32 tensors");
-    TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && c.dim() == 2, "a, b, c must be 2D");
-    const int64_t M = a.size(0), K = a.size(1), F = b.size(0);
-    TORCH_CHECK(b.size(1) == K && c.size(0) == M && c.size(1) == F, "shape mismatch");
-    TORCH_CHECK(bias.numel() == F, "bias must be [F]");
-    const int64_t ldc = cache_pitch(pa_cache_colmajor, F, M, "pa_cache_colmajor");
-    check_pitch(ldc, M, "pa_cache_colmajor");
-    TORCH_CHECK(indices.numel() == groups_of(M) * F && indices_counts.numel() == groups_of(M), "indices must be [ceil(M/128), F], counts [ceil(M/128)]");
+    const Mm1Shape sh = mm1_shape(a, b, c, bias, pa_cache_colmajor, indices, indices_counts);
+    const int64_t M = sh.M, K = sh.K, F = sh.F, ldc = sh.ldc;
     c10::DeviceGuard guard(a.device());
-    if (whole_groups(M, ldc))
+    if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_fp8_batched(a.data_ptr(), b.data_ptr(), c.data_ptr(), bias.data_ptr(), pa_cache_colmajor.data_ptr(),
+                                               indices.data_ptr<int>(), indices_counts.data_ptr<int>(), scale_a.data_ptr<float>(),
+                                               scale_b.data_ptr<float>(), (int)M, (int)K, (int)F, (int)ldc, update_cache, (int)sh.B,
+                                               sh.cache_bs, cur_stream(a)),
+              "csp_mlp_mm1_fp8");
+    else if (whole_groups(M, ldc))
         check(chipmunk_csp_mlp_mm1_fp8(a.data_ptr(), b.data_ptr(), c.data_ptr(), bias.data_ptr(),
                                        pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
                                        indices_counts.data_ptr<int>(), scale_a.data_ptr<float>(), scale_b.data_ptr<float>(),
@@ -379,7 +413,7 @@ void csp_mlp_mm1_fp8_scatter(at::Tensor a, at::Tensor b, at::Tensor c, at::Tenso
 }
 
 int64_t check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, const at::Tensor &inds,
-                           const at::Tensor &counts) {   // returns the cache pitch
+                           const at::Tensor &counts, int64_t *cache_bs) {   // returns the cache pitch; *cache_bs: the cache's batch stride
     // reference csrc/indexed_io/scatter_add.cu:111-142 (B is hard-wired to 1, :58-59,138)
     CHECK_DEV(packed); CHECK_DEV(unpacked); CHECK_DEV(inds); CHECK_DEV(counts);
     CHECK_CONTIG(packed); CHECK_CONTIG(inds); CHECK_CONTIG(counts);
@@ -389,21 +423,41 @@ int64_t check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked,
     TORCH_CHECK(counts.dim() == 2, "sp_counts must be a 2D tensor");
     CHECK_BF16(packed); CHECK_BF16(unpacked);
     CHECK_I32(inds); CHECK_I32(counts);
-    TORCH_CHECK(packed.size(0) == 1, "batch size must be 1");
-    TORCH_CHECK(unpacked.size(1) == packed.size(2) && unpacked.size(2) == packed.size(1), "unpacked_colmajor must be [1, F, M]");
-    TORCH_CHECK(inds.size(1) == groups_of(packed.size(1)) && inds.size(2) == packed.size(2), "sp_inds must be [1, ceil(M/128), F]");
-    TORCH_CHECK(counts.size(1) == groups_of(packed.size(1)), "sp_counts must be [1, ceil(M/128)]");
-    const int64_t ldc = cache_pitch(unpacked, packed.size(2), packed.size(1), "unpacked_colmajor");
-    check_pitch(ldc, packed.size(1), "unpacked_colmajor");
+    // (the reference hard-wires a batch of 1; here the leading dimension is the number of sequences of one launch)
+    const int64_t B = packed.size(0), M = packed.size(1), F = packed.size(2);
+    TORCH_CHECK(B >= 1, "batch size must be at least 1");
+    TORCH_CHECK(unpacked.size(0) == B && inds.size(0) == B && counts.size(0) == B,
+                "packed, unpacked_colmajor, sp_inds and sp_counts must share the batch size (packed has B = ", B, ")");
+    TORCH_CHECK(unpacked.size(1) == F && unpacked.size(2) == M, "unpacked_colmajor must be [B, F, M]");
+    TORCH_CHECK(inds.size(1) == groups_of(M) && inds.size(2) == F, "sp_inds must be [B, ceil(M/128), F]");
+    TORCH_CHECK(counts.size(1) == groups_of(M), "sp_counts must be [B, ceil(M/128)]");
+    TORCH_CHECK(B * groups_of(M) <= 65535, "B * ceil(M/128) groups must not exceed 65535 (got ", B * groups_of(M), ")");
+    int64_t ldc;
+    if (B == 1) {
+        ldc = cache_pitch(unpacked, F, M, "unpacked_colmajor");
+        *cache_bs = F * ldc;
+    } else {
+        TORCH_CHECK(unpacked.stride(2) == 1, "unpacked_colmajor: the M elements of a column must be contiguous");
+        ldc = unpacked.stride(1), *cache_bs = unpacked.stride(0);
+        TORCH_CHECK(*cache_bs >= F * ldc && *cache_bs % 8 == 0, "unpacked_colmajor: the batch stride (", *cache_bs,
+                    " elements) must be at least F * ldc = ", F * ldc, " and a multiple of 8");
+    }
+    check_pitch(ldc, M, "unpacked_colmajor");
     return ldc;
 }
 
 // reference csrc/indexed_io/scatter_add.cu:102-181
 void csp_scatter_add(at::Tensor packed, at::Tensor unpacked_colmajor, at::Tensor sp_inds, at::Tensor sp_counts,
                      int64_t num_sms) {
-    const int64_t ldc = check_scatter_args(packed, unpacked_colmajor, sp_inds, sp_counts);
+    int64_t cache_bs = 0;
+    const int64_t ldc = check_scatter_args(packed, unpacked_colmajor, sp_inds, sp_counts, &cache_bs);
     c10::DeviceGuard guard(packed.device());
-    if (whole_groups(packed.size(1), ldc))
+    if (packed.size(0) > 1)
+        check(chipmunk_csp_scatter_add_batched(packed.data_ptr(), unpacked_colmajor.data_ptr(), sp_inds.data_ptr<int>(),
+                                               sp_counts.data_ptr<int>(), (int)packed.size(1), (int)packed.size(2), (int)ldc,
+                                               (int)packed.size(0), cache_bs, cur_stream(packed)),
+              "csp_scatter_add");
+    else if (whole_groups(packed.size(1), ldc))
         check(chipmunk_csp_scatter_add(packed.data_ptr(), unpacked_colmajor.data_ptr(), sp_inds.data_ptr<int>(),
                                        sp_counts.data_ptr<int>(), (int)packed.size(1), (int)packed.size(2), (int)num_sms,
                                        cur_stream(packed)),
@@ -421,17 +475,23 @@ void csp_mlp_mm2_and_scatter_add(at::Tensor packed, at::Tensor unpacked_colmajor
                                  at::Tensor sp_counts, at::Tensor mma_a, at::Tensor mma_b, at::Tensor mma_c,
                                  int64_t num_sms_scatter_add, int64_t matmul_kernel) {
     (void)matmul_kernel;
-    const int64_t ldc = check_scatter_args(packed, unpacked_colmajor, sp_inds, sp_counts);
+    int64_t cache_bs = 0;
+    const int64_t ldc = check_scatter_args(packed, unpacked_colmajor, sp_inds, sp_counts, &cache_bs);
     CHECK_DEV(mma_a); CHECK_DEV(mma_b); CHECK_DEV(mma_c);
     CHECK_BF16(mma_a); CHECK_BF16(mma_b); CHECK_BF16(mma_c);
     CHECK_CONTIG(mma_a); CHECK_CONTIG(mma_b); CHECK_CONTIG(mma_c);
     TORCH_CHECK(mma_a.dim() == 3 && mma_b.dim() == 3 && mma_c.dim() == 3, "mma_a, mma_b, mma_c must be 3D tensors");
-    const int64_t M = packed.size(1), F = packed.size(2), N2 = mma_b.size(2);
-    TORCH_CHECK(mma_a.size(1) == M && mma_a.size(2) == F, "mma_a must be [1, M, F]");
-    TORCH_CHECK(mma_b.size(1) == F, "mma_b must be [1, F, N]");
-    TORCH_CHECK(mma_c.size(1) == M && mma_c.size(2) == N2, "mma_c must be [1, M, N]");
+    const int64_t B = packed.size(0), M = packed.size(1), F = packed.size(2), N2 = mma_b.size(2);
+    TORCH_CHECK(mma_a.size(0) == B && mma_a.size(1) == M && mma_a.size(2) == F, "mma_a must be [B, M, F] with the batch size of packed (B = ", B, ")");
+    TORCH_CHECK(mma_b.size(0) == 1 && mma_b.size(1) == F, "mma_b must be [1, F, N]");
+    TORCH_CHECK(mma_c.size(0) == B && mma_c.size(1) == M && mma_c.size(2) == N2, "mma_c must be [B, M, N] with the batch size of packed (B = ", B, ")");
     c10::DeviceGuard guard(packed.device());
-    if (whole_groups(M, ldc))
+    if (B > 1)
+        check(chipmunk_csp_mlp_mm2_and_scatter_add_batched(packed.data_ptr(), unpacked_colmajor.data_ptr(), sp_inds.data_ptr<int>(),
+                                                           sp_counts.data_ptr<int>(), mma_a.data_ptr(), mma_b.data_ptr(), mma_c.data_ptr(),
+                                                           (int)M, (int)F, (int)N2, (int)ldc, (int)B, cache_bs, cur_stream(packed)),
+              "csp_mlp_mm2_and_scatter_add");
+    else if (whole_groups(M, ldc))
         check(chipmunk_csp_mlp_mm2_and_scatter_add(packed.data_ptr(), unpacked_colmajor.data_ptr(),
                                                    sp_inds.data_ptr<int>(), sp_counts.data_ptr<int>(), mma_a.data_ptr(),
                                                    mma_b.data_ptr(), mma_c.data_ptr(), (int)M, (int)F, (int)N2,
@@ -451,11 +511,23 @@ void csp_mlp_mm2(at::Tensor mma_a, at::Tensor mma_b, at::Tensor indices, at::Ten
     CHECK_BF16(mma_a); CHECK_BF16(mma_b); CHECK_BF16(mma_c);
     CHECK_I32(indices); CHECK_I32(counts);
     CHECK_CONTIG(mma_a); CHECK_CONTIG(mma_b); CHECK_CONTIG(mma_c); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
-    TORCH_CHECK(mma_a.dim() == 2 && mma_b.dim() == 2 && mma_c.dim() == 2, "mma_a, mma_b, mma_c must be 2D tensors");
-    const int64_t M = mma_a.size(0), F = mma_a.size(1), N2 = mma_b.size(1);
-    TORCH_CHECK(mma_b.size(0) == F && mma_c.size(0) == M && mma_c.size(1) == N2, "shape mismatch");
+    TORCH_CHECK((mma_a.dim() == 2 || mma_a.dim() == 3) && mma_b.dim() == 2 && mma_c.dim() == mma_a.dim(),
+                "mma_a and mma_c must both be 2D ([M, .]) or 3D ([B, M, .]) tensors, mma_b 2D");
+    const int64_t B = mma_a.dim() == 3 ? mma_a.size(0) : 1;
+    const int64_t M = mma_a.size(-2), F = mma_a.size(-1), N2 = mma_b.size(1);
+    TORCH_CHECK(B >= 1, "the batch size must be at least 1");
+    TORCH_CHECK(mma_b.size(0) == F && mma_c.size(-2) == M && mma_c.size(-1) == N2 && mma_c.numel() == B * M * N2,
+                "shape mismatch (mma_c must be [M, N2], or [B, M, N2] with the batch size of mma_a)");
     c10::DeviceGuard guard(mma_a.device());
-    TORCH_CHECK(indices.numel() == groups_of(M) * F && counts.numel() == groups_of(M), "indices must be [ceil(M/128), F], counts [ceil(M/128)]");
+    TORCH_CHECK(indices.numel() == B * groups_of(M) * F && counts.numel() == B * groups_of(M),
+                "indices must be [ceil(M/128), F], counts [ceil(M/128)] ([B, ceil(M/128), F] and [B, ceil(M/128)] with the batch size of mma_a)");
+    TORCH_CHECK(B * groups_of(M) <= 65535, "B * ceil(M/128) groups must not exceed 65535 (got ", B * groups_of(M), ")");
+    if (B > 1) {
+        check(chipmunk_csp_mlp_mm2_batched(mma_a.data_ptr(), mma_b.data_ptr(), mma_c.data_ptr(), indices.data_ptr<int>(),
+                                           counts.data_ptr<int>(), (int)M, (int)F, (int)N2, (int)B, cur_stream(mma_a)),
+              "csp_mlp_mm2");
+        return;
+    }
     check((M % 128 == 0 ? chipmunk_csp_mlp_mm2 : chipmunk_csp_mlp_mm2_ragged)(
               mma_a.data_ptr(), mma_b.data_ptr(), mma_c.data_ptr(), indices.data_ptr<int>(), counts.data_ptr<int>(), (int)M, (int)F,
               (int)N2, cur_stream(mma_a)),

@@ -73,7 +73,7 @@ class SparseDiffMlp:
 
         do_full = self.layer_counter.should_do_full_mlp_step()
         inference_step, layer, _submodule = self.layer_counter.increment()
-        assert x.ndim == 3 and x.shape[0] == 1, "x must be (1, N, C)"
+        assert x.ndim == 3 and x.shape[0] >= 1, "x must be (B, N, C)"
         mbm, bm = cfg["mbm"], cfg["bm"]
 
         if layer < cfg["first_n_dense_layers"]:
@@ -83,13 +83,22 @@ class SparseDiffMlp:
             mid = fc1(x)
             act = self.activation(mid)
             out = fc2(act)
-            # the module owns the activation cache: [1, F, ld] with ld = ceil8(N) and zeroed padding, stored (and offloaded) whole; the
-            # operators get its [F, N] view.  ld == N for every N % 8 == 0: the contiguous cache of the reference.
+            # the module owns the activation cache: [B, F, ld] with ld = ceil8(N) and zeroed padding, stored (and offloaded) whole; the
+            # operators get its [F, N] view ([B, F, N] for a batch).  ld == N for every N % 8 == 0: the contiguous cache of the reference.
             n = x.shape[1]
             self.storage.set_sparse_act_T(_transposed(act) if n % 8 == 0 else _transposed_pitched(act, _ceil8(n)))
             self.storage.set_out_cache(out)
             self.storage.set_blockmean_mid_cache(block_mean(mid, mbm))
             return out
+
+        # the stored state (activation cache [B, F, ld], output cache [B, N, C], block means, indices [B, G, F], counts [B, G]) is per
+        # sequence: a sparse step continues the B sequences of the last full step and nothing else
+        stored = self.storage.get_out_cache()
+        if stored is None or stored.shape[0] != x.shape[0] or stored.shape[1] != x.shape[1]:
+            raise RuntimeError(
+                f"SparseDiffMlp: a sparse step got x of shape {tuple(x.shape)} but the state of the last full step is for "
+                f"{'no input at all' if stored is None else f'batch size {stored.shape[0]} with {stored.shape[1]} tokens'}: the batch size "
+                "and token count may only change on a full step")
 
         reuse_mask = (inference_step % cfg["block_mask_cache"] != 0 and self.storage.get_indices() is not None
                       and inference_step >= 10)
@@ -117,21 +126,31 @@ class SparseDiffMlp:
             self.storage.set_indices(inds)
             self.storage.set_counts(counts)
 
-        indices = self.storage.get_indices()[0]
-        counts = self.storage.get_counts()[0]
-        out_cache = self.storage.get_out_cache()[0]
-        sparse_act_T = self.storage.get_sparse_act_T()[0][:, : x.shape[1]]   # the [F, N] view of the pitched cache
+        batched = x.shape[0] > 1     # B == 1 passes the 2-D operands it always passed
+        indices = self.storage.get_indices() if batched else self.storage.get_indices()[0]
+        counts = self.storage.get_counts() if batched else self.storage.get_counts()[0]
+        out_cache = stored if batched else stored[0]
+        sparse_act_T = self.storage.get_sparse_act_T()
+        sparse_act_T = sparse_act_T[..., : x.shape[1]] if batched else sparse_act_T[0][:, : x.shape[1]]   # the [F, N] view of the pitched cache
 
         scale_a = scale_b = None
         if fc1.weight.dtype == torch.float8_e4m3fn:
             x = fc1.quantize_input(x)
             scale_a, scale_b = fc1.input_scale_reciprocal, fc1.scale_reciprocal
 
-        ops.mlp(x=x[0], fc1w=fc1.weight.data, fc1b=fc1.bias.data, fc2w_T=self.fc2w_T[0], indices=indices,
+        ops.mlp(x=x if batched else x[0], fc1w=fc1.weight.data, fc1b=fc1.bias.data, fc2w_T=self.fc2w_T[0], indices=indices,
                 counts=counts, sparse_act_T=sparse_act_T, cached_out=out_cache,
                 num_sms_scatter_add=self.num_sms_scatter_add, mm1_scale_a=scale_a, mm1_scale_b=scale_b)
 
-        out_cache = out_cache.unsqueeze(0)
+        # the operators updated the LOADED activation cache in place.  When it lives in host memory (offloading on, not kept resident) the
+        # host copy has to follow, or the next step's load brings back the cache of the last full step and that step's deltas are taken
+        # against activations the output cache has long moved on from
+        holder = self.storage.sparse_act_T
+        if holder is not None and not holder.is_resident():
+            holder.offload_cur_value()
+
+        if not batched:
+            out_cache = out_cache.unsqueeze(0)
         self.storage.set_out_cache(out_cache)
         return out_cache
 

@@ -21,6 +21,9 @@ def topk_indices(activations: torch.Tensor, indices_out: torch.Tensor, counts_ou
 
 def scatter_add(packed: torch.Tensor, unpacked: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
                 num_sms: int) -> None:
+    if packed.ndim == 3:   # a batch [B, M, F] with unpacked [B, F, M], indices [B, G, F], counts [B, G]: one launch
+        torch.ops.chipmunk.csp_scatter_add(packed, unpacked, indices, counts, num_sms)
+        return
     torch.ops.chipmunk.csp_scatter_add(packed.unsqueeze(0), unpacked.unsqueeze(0), indices.unsqueeze(0),
                                        counts.unsqueeze(0), num_sms)
 

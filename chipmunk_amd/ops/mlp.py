@@ -75,6 +75,10 @@ def mm2_fused(packed: torch.Tensor, unpacked_colmajor: torch.Tensor, indices: to
     assert sparse_act_packed.dtype == torch.bfloat16
     assert fc2wT.dtype == torch.bfloat16
     assert cached_out.dtype == torch.bfloat16
+    if packed.ndim == 3:   # a batch [B, M, F]: the operator's leading dimension is the batch; the weight stays [1, F, N]
+        torch.ops.chipmunk.csp_mlp_mm2_and_scatter_add(packed, unpacked_colmajor, indices, counts, sparse_act_packed,
+                                                       fc2wT.unsqueeze(0), cached_out, num_sms_scatter_add, csp_mlp_mm2_function_ptr)
+        return
     torch.ops.chipmunk.csp_mlp_mm2_and_scatter_add(
         packed.unsqueeze(0), unpacked_colmajor.unsqueeze(0), indices.unsqueeze(0), counts.unsqueeze(0),
         sparse_act_packed.unsqueeze(0), fc2wT.unsqueeze(0), cached_out.unsqueeze(0), num_sms_scatter_add,
@@ -102,13 +106,22 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: torch.Tensor, fc2w_T: tor
             counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
             mm1_scale_a: Optional[torch.Tensor] = None, mm1_scale_b: Optional[torch.Tensor] = None) -> None:
     # M is any positive row count (ceil(M / 128) groups, the last one short); sparse_act_T is [F, M], contiguous or -- required when
-    # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers
-    M, K1 = x.shape
+    # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers.
+    # A batch: x [B, M, K1] with indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] (or the [..., :M] view of [B, F, ldc]) and
+    # cached_out [B, M, N] -- one launch per kernel for all B sequences, the bits of B calls on the slices.
+    assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
+    if x.ndim == 3:
+        B = x.shape[0]
+        assert indices.ndim == 3 and counts.ndim == 2 and sparse_act_T.ndim == 3 and cached_out.ndim == 3, \
+            "a batched x [B, M, K] takes indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] and cached_out [B, M, N]"
+        assert indices.shape[0] == B and counts.shape[0] == B and sparse_act_T.shape[0] == B and cached_out.shape[0] == B, \
+            f"the batch size of indices / counts / sparse_act_T / cached_out must be that of x ({B})"
+    M, K1 = x.shape[-2:]
     K2, K1_ = fc1w.shape
     assert K1 == K1_, "K1 must match"
     K2_, _N = fc2w_T.shape
     assert K2 == K2_, "K2 must match"
-    sparse_act_packed = torch.empty((M, K2), device=x.device, dtype=sparse_act_T.dtype)  # bf16 also when x is fp8
+    sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)  # bf16 also when x is fp8
     if (x.is_cuda and fc1w.dtype == torch.bfloat16
             and amd_key("mlp", "fused_scatter")):
         # GEMM1 applies the scatter-add of its own deltas (same bits as the two-kernel form), GEMM2 runs alone
@@ -116,7 +129,7 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: torch.Tensor, fc2w_T: tor
         csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out)
         return
     if (x.is_cuda and fc1w.dtype == torch.float8_e4m3fn and x.dtype == torch.float8_e4m3fn and amd_key("mlp", "fused_scatter")
-            and not FP8_MM1_UPDATES_CACHE and x.shape[1] % 128 == 0):
+            and not FP8_MM1_UPDATES_CACHE and K1 % 128 == 0):
         mm1_fp8_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b)
         csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out)
         return

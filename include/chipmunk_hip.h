@@ -202,6 +202,37 @@ int chipmunk_csp_mlp_mm2_and_scatter_add_ragged(const void *packed, void *unpack
 int chipmunk_csp_scatter_add_ragged(const void *packed, void *unpacked_colmajor, const int32_t *indices,
                                     const int32_t *counts, int M, int F, int ldc, void *stream);
 
+/* Batches: the same operators over B sequences of M rows in ONE launch (no reference counterpart: the reference hard-wires B = 1).
+ * The ragged contract above holds per sequence (any M > 0, ldc >= M, ldc % 8 == 0); the argument order is that of the *_ragged entry
+ * followed by `int B` and, where a cache is passed, `int64_t cache_batch_stride`.
+ *   - Row-major tensors are dense [B, M, .]: a [B,M,K], c / packed / mma_a [B,M,F], mma_c [B,M,N2].
+ *   - indices [B, G, F] and counts [B, G], G = ceil(M / 128): what chipmunk_topk_indices writes for B * G rows.
+ *   - The cache is [B, F, ldc]; sequence b's starts at element b * cache_batch_stride, with cache_batch_stride >= F * ldc and a
+ *     multiple of 8 (elements).  Nothing outside the F * ldc elements of each sequence is touched.
+ *   - Weights (b, mma_b) and bias are shared by all sequences.
+ *   - B >= 1 and B * G <= 65535.  The 32-bit-offset conditions apply per sequence: B * M * F may exceed 2^31.
+ * Every output element gets the bits B calls of the *_ragged entry on the sequences' slices give it.  Each failed check returns
+ * CHIPMUNK_ERR_INVALID with a message that names the rule, before anything is enqueued. */
+int chipmunk_csp_mlp_mm1_batched(const void *a, const void *b, void *c, const void *bias, const void *pa_cache,
+                                 const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int B,
+                                 int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_scatter_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                         const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int B,
+                                         int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_fp8_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                     const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                     int M, int K, int F, int ldc, int update_cache, int B, int64_t cache_batch_stride,
+                                     void *stream);
+int chipmunk_csp_mlp_mm2_batched(const void *mma_a, const void *mma_b, void *mma_c, const int32_t *indices,
+                                 const int32_t *counts, int M, int F, int N2, int B, void *stream);
+int chipmunk_csp_mlp_mm2_and_scatter_add_batched(const void *packed, void *unpacked_colmajor, const int32_t *indices,
+                                                 const int32_t *counts, const void *mma_a, const void *mma_b, void *mma_c,
+                                                 int M, int F, int N2, int ldc, int B, int64_t cache_batch_stride,
+                                                 void *stream);
+int chipmunk_csp_scatter_add_batched(const void *packed, void *unpacked_colmajor, const int32_t *indices,
+                                     const int32_t *counts, int M, int F, int ldc, int B, int64_t cache_batch_stride,
+                                     void *stream);
+
 /* ---------------------------------------------------------------- indexed IO
  * Replaces chipmunk::topk_indices (reference csrc/indexed_io/topk_indices.cu:145-218; schema chipmunk.cpp:58).
  * activation [B*R, C] of `dtype`; indices [B*R, C] int32; counts [B*R] int32.  Threshold = element

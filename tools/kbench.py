@@ -66,51 +66,69 @@ def rand_rows(G, F, count, g):
     return inds.contiguous()
 
 
+def batch_env():
+    """(KB_BATCH, KB_BATCH_LOOP): sequences per call, and whether a call is one batched launch (default) or a loop of launches"""
+    return int(os.environ.get("KB_BATCH", "1")), os.environ.get("KB_BATCH_LOOP") == "1"
+
+
+def batch_tag(B, loop):
+    return "" if B == 1 else f" batch={B} as {B} launches" if loop else f" batch={B} in one launch"
+
+
 def bench_mlp(which, variants, M=4352, K=3072, F=12288, keep=4096):
     """KB_LAYERS=n rotates n independent sets of weights / caches / outputs per launch (n = 8: 1.7 GB, far beyond the
     256 MB Infinity Cache) -- the in-pipeline condition, where every layer's weights come from HBM.  Default 1: the
-    same buffers every launch, which the Infinity Cache then serves."""
+    same buffers every launch, which the Infinity Cache then serves.
+    KB_BATCH=n: n sequences of M rows (operands [n, M, .], cache [n, F, M], indices [n, G, F]) in ONE batched launch per call;
+    with KB_BATCH_LOOP=1 the same operands as n back-to-back single-sequence launches on the slices.  The time is per call: all n."""
     g = torch.Generator(device=dev).manual_seed(0)
     L = int(os.environ.get("KB_LAYERS", "1"))
-    a = torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g)
+    B, loop = batch_env()
+    a = torch.randn(B, M, K, device=dev, dtype=torch.bfloat16, generator=g)
     bias = torch.zeros(F, device=dev, dtype=torch.bfloat16)
     sets = []
     for _ in range(L):
         w1 = (torch.randn(F, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
-        cache = torch.randn(F, M, device=dev, dtype=torch.bfloat16, generator=g)
-        packed = torch.randn(M, F, device=dev, dtype=torch.bfloat16, generator=g) * 0.1
+        cache = torch.randn(B, F, M, device=dev, dtype=torch.bfloat16, generator=g)
+        packed = torch.randn(B, M, F, device=dev, dtype=torch.bfloat16, generator=g) * 0.1
         w2t = (torch.randn(F, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
-        out = torch.zeros(M, K, device=dev, dtype=torch.bfloat16)
+        out = torch.zeros(B, M, K, device=dev, dtype=torch.bfloat16)
         sets.append((w1, cache, packed, w2t, out))
     G = (M + 127) // 128      # (a token count that is no multiple of 128: the last group is short)
-    inds = rand_rows(G, F, keep, g)
+    inds = rand_rows(B * G, F, keep, g)
     if os.environ.get("KB_SAME_INDICES") == "1":   # every group selects the same columns: upper bound of L2 sharing
         inds[:] = inds[0:1]
-    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
-    flops = 2.0 * M * K * keep
+    inds = inds.view(B, G, F)
+    counts = torch.full((B, G), keep, dtype=torch.int32, device=dev)
+    flops = 2.0 * B * M * K * keep
     state = {"i": 0}
 
     def nxt():
         state["i"] = (state["i"] + 1) % L
         return sets[state["i"]]
 
+    def each(op):
+        """op on the operands of every launch of one call: the whole batch at once, or one sequence at a time"""
+        for b in (range(B) if loop or B == 1 else [slice(None)]):
+            op(b)
+
     def run_mm1():
         w1, cache, packed, _, _ = nxt()
-        torch.ops.chipmunk.csp_mlp_mm1(a, w1, packed, bias, cache, inds, counts)
+        each(lambda b: torch.ops.chipmunk.csp_mlp_mm1(a[b], w1, packed[b], bias, cache[b], inds[b], counts[b]))
 
     def run_mm1s():
         w1, cache, packed, _, _ = nxt()
-        torch.ops.chipmunk.csp_mlp_mm1_scatter(a, w1, packed, bias, cache, inds, counts)
+        each(lambda b: torch.ops.chipmunk.csp_mlp_mm1_scatter(a[b], w1, packed[b], bias, cache[b], inds[b], counts[b]))
 
     def run_mm2():
         _, _, packed, w2t, out = nxt()
-        torch.ops.chipmunk.csp_mlp_mm2(packed, w2t, inds, counts, out)
+        each(lambda b: torch.ops.chipmunk.csp_mlp_mm2(packed[b], w2t, inds[b], counts[b], out[b]))
 
     def run_scatter():
         _, cache, packed, _, _ = nxt()
-        torch.ops.chipmunk.csp_scatter_add(packed[None], cache[None], inds[None], counts[None], 6)
+        torch.ops.chipmunk.csp_scatter_add(packed[:1], cache[:1], inds[:1], counts[:1], 6)
 
-    tag = f"(M={M} K={K} keep={keep} layers={L})"
+    tag = f"(M={M} K={K} keep={keep} layers={L}{batch_tag(B, loop)})"
     for v in variants:
         if which == "mm1":
             _native.set_option("mm1_variant", v)
@@ -139,21 +157,31 @@ def bench_fp8_wan(M=32768, ldc=None):
     (ldc: the cache as the [:, :M] view of a [F, ldc] buffer, default the contiguous [F, M])."""
     g = torch.Generator(device=dev).manual_seed(0)
     K, F, keep = 1536, 8960, 2688
-    a = torch.randn(M, K, device=dev, generator=g)
+    B, loop = batch_env()     # KB_BATCH / KB_BATCH_LOOP as in bench_mlp
+    a = torch.randn(B, M, K, device=dev, generator=g)
     w = torch.randn(F, K, device=dev, generator=g) * 0.02
     a8, w8 = (a * 16).clamp(-448, 448).to(torch.float8_e4m3fn), (w * 512).clamp(-448, 448).to(torch.float8_e4m3fn)
     sa, sb = torch.tensor([1 / 16.0], device=dev), torch.tensor([1 / 512.0], device=dev)
     bias = torch.zeros(F, device=dev, dtype=torch.bfloat16)
-    cache = torch.randn(F, ldc or M, device=dev, dtype=torch.bfloat16, generator=g)[:, :M]
-    packed = torch.empty(M, F, device=dev, dtype=torch.bfloat16)
+    cache = torch.randn(B, F, ldc or M, device=dev, dtype=torch.bfloat16, generator=g)[..., :M]
+    packed = torch.empty(B, M, F, device=dev, dtype=torch.bfloat16)
     G = (M + 127) // 128
-    inds = rand_rows(G, F, keep, g)
-    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
-    flops = 2.0 * M * K * keep
-    ms = timeit(lambda: torch.ops.chipmunk.csp_mlp_mm1_fp8(a8, w8, packed, bias, cache, inds, counts, sa, sb, False), reps=5)
-    print(f"mm1_fp8 (Wan C5): {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TFLOP/s   (M={M} K={K} F={F} keep={keep} ldc={ldc or M})")
+    inds = rand_rows(B * G, F, keep, g).view(B, G, F)
+    counts = torch.full((B, G), keep, dtype=torch.int32, device=dev)
+    flops = 2.0 * B * M * K * keep
+    sel = list(range(B)) if loop or B == 1 else [slice(None)]     # the operands of every launch of one call
+
+    def run_fp8():
+        for b in sel:
+            torch.ops.chipmunk.csp_mlp_mm1_fp8(a8[b], w8, packed[b], bias, cache[b], inds[b], counts[b], sa, sb, False)
+    ms = timeit(run_fp8, reps=5)
+    print(f"mm1_fp8 (Wan C5): {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TFLOP/s   (M={M} K={K} F={F} keep={keep} ldc={ldc or M}{batch_tag(B, loop)})")
     ab, wb = a.to(torch.bfloat16), w.to(torch.bfloat16)
-    ms = timeit(lambda: torch.ops.chipmunk.csp_mlp_mm1(ab, wb, packed, bias, cache, inds, counts), reps=5)
+
+    def run_bf16():
+        for b in sel:
+            torch.ops.chipmunk.csp_mlp_mm1(ab[b], wb, packed[b], bias, cache[b], inds[b], counts[b])
+    ms = timeit(run_bf16, reps=5)
     print(f"mm1 bf16 same shape: {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TFLOP/s")
 
 
