@@ -1,5 +1,6 @@
 // Row-wise passes of the transformer block around the attention / MLP operators (model code in the reference, torch ops there):
-// gated residual + LayerNorm + modulate in one pass over the hidden state.
+// gated residual + LayerNorm + modulate in one pass over the hidden state; block means; fp8 input quantisation; Wan's row-wide q / k
+// RMSNorm + rotary + head-major layout (split_heads_rownorm_kernel, at the end of the file).
 //
 // The blocks of the DiT models the reference patches do, between any two GEMMs,
 //     x  = x + gate * y                      (torch.addcmul; examples/hunyuan/hyvideo/modules/models.py:262-275, 431)
@@ -260,6 +261,218 @@ extern "C" int chipmunk_quantize_fp8(const void *x, const float *scale, void *ou
     const int64_t blocks = (n8 + 255) / 256;
     hipLaunchKernelGGL(quantize_fp8_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t *)x, scale, (uint8_t *)out, n8, max_value);
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- Wan attention operands
+// Wan's blocks (reference examples/wan/wan/modules/model.py:81-97, 154-164, 195-196, 236-239) normalise q and k over the WHOLE
+// projection row -- WanRMSNorm(dim), dim = heads * 128 channels, a dim-entry weight -- then rotate (rope_apply, :49-78: complex
+// product in fp64, three-axis table), permute to [B, H, L, D] and cast to bf16 (:164): about ten torch passes per layer, two of
+// them in fp64.  Here: one pass.  One wave per (batch, token, part) item; a part is one of up to three consecutive heads * 128
+// column blocks of the row (q | k | v).  A lane owns the 16-byte pieces at columns (j * 64 + lane) * 8, j < NV = ceil(heads / 4):
+// a 16-lane group is one head's 256-byte segment, four heads per iteration, the row in registers as packed bf16.  The sum of
+// squares is a per-lane fp32 fma chain in column order, then row16_sum + sum_across_rows: a fixed order, and a row's result does
+// not depend on which wave took it.  Rounding points are torch's: bf16(x * r) (.type_as, :94); a bf16 weight rounds the product
+// to bf16, an fp32 weight keeps it in fp32 (torch's promotion); rotated or not, one rounding to bf16 at the end (:164).  The
+// rotation of pair (2i, 2i+1) is lane-local (a lane holds 4 whole pairs) and evaluated in fp32; a lane's position inside its
+// head is the same in every iteration (64 is a multiple of 16), so it reads its 8 cos + 8 sin values once per row.  A part
+// that is neither normalised nor rotated is a bit copy (v).  The four waves of a workgroup take consecutive items, so the q and k
+// of one token read the same table lines together.  No LDS; every global access is 16 bytes; stores are whole 256-byte head rows.
+// HBM-bound: (read + write) 4 bytes per element + one read of the tables.
+namespace {
+struct RownormArgs {
+    const uint16_t *x;
+    int64_t batch_stride, row_stride;   // elements
+    const void *w0, *w1, *w2;           // per part: nullptr, bf16 [heads * 128] or fp32 [heads * 128]
+    uint16_t *o0, *o1, *o2;             // per part: [B, heads, n, 128]
+    const float *fcos, *fsin;           // [rope_rows, 128]
+    int64_t n, rows, rope_rows;         // rows = B * n
+    int parts, heads;
+    uint32_t norm_mask, rope_mask, fp32_mask;   // bit p: part p is normalised / rotated / has an fp32 weight
+    float eps;
+};
+
+// (batch, token) of the rows a wave walks, row0 + i * step, without a 64-bit division per row
+struct RowWalk {
+    int64_t b, tok, b_step, tok_step, n;
+    __device__ RowWalk(int64_t row0, int64_t step, int64_t n_) : b(row0 / n_), tok(row0 % n_), b_step(step / n_), tok_step(step % n_), n(n_) {}
+    __device__ void next() {
+        b += b_step, tok += tok_step;
+        if (tok >= n) tok -= n, ++b;
+    }
+};
+
+// A wave's rows of one part.  WK: the part's weight (0 none, 1 bf16, 2 fp32), in registers for all of the wave's rows, as
+// residual_ln_modulate_kernel keeps its vectors.  NV = ceil(heads / 4) exactly, so only the last vector can lie past the row (heads not a
+// multiple of 4): it reads the row's last vector instead -- every load is unconditional and they all issue together -- and counts
+// as zero; its store alone is conditional (a condition on every store has the compiler sink the loads behind it, one wait each).
+template <int NV, int WK>
+__device__ __forceinline__ void rownorm_rows(const RownormArgs &a, int part, int64_t row0, int64_t row_step, const void *wp, uint16_t *out,
+                                             bool normed, bool rope) {
+    const int lane = threadIdx.x & 63, l15 = lane & 15, hq = lane >> 4;
+    const int H = a.heads, C = H * 128;
+    const int64_t rows = a.rows, dstep = a.n * 512;   // dstep: four heads further
+    const bool tail_in = (NV - 1) * 4 + hq < H;                   // NV = ceil(heads / 4): only the last vector can lie past the row
+    int col[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) col[j] = min((j * 64 + lane) * 8, C - 8);
+    constexpr bool HELD = WK == 1 || (WK == 2 && NV <= 10);   // fp32 weights of a longer row (8 registers per vector) are read per row instead
+    u32x4 wb[WK == 1 ? NV : 1];
+    f32x4 wf[WK == 2 && HELD ? NV : 1][2];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        if constexpr (WK == 1) wb[j] = *(const u32x4 *)((const uint16_t *)wp + col[j]);
+        if constexpr (WK == 2 && HELD) wf[j][0] = *(const f32x4 *)((const float *)wp + col[j]), wf[j][1] = *(const f32x4 *)((const float *)wp + col[j] + 4);
+    }
+    RowWalk w(row0, row_step, a.n);
+    for (int64_t row = row0; row < rows; row += row_step, w.next()) {
+        const int64_t b = w.b, tok = w.tok;
+        const uint16_t *src = a.x + b * a.batch_stride + tok * a.row_stride + (int64_t)part * C;
+        uint16_t *dst = out + ((b * H + hq) * a.n + tok) * 128 + l15 * 8;
+        const bool rotated = rope && tok < a.rope_rows;
+        u32x4 xv[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) xv[j] = *(const u32x4 *)(src + col[j]);
+        f32x4 c0 = {1.f, 1.f, 1.f, 1.f}, c1 = c0, s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
+        if (rotated) {   // a lane's place in its head is the same for every j: its 8 cos + 8 sin values, once per row
+            const float *pc = a.fcos + tok * 128 + l15 * 8, *ps = a.fsin + tok * 128 + l15 * 8;
+            c0 = *(const f32x4 *)pc, c1 = *(const f32x4 *)(pc + 4), s0 = *(const f32x4 *)ps, s1 = *(const f32x4 *)(ps + 4);
+        }
+        float r = 1.0f;   // (a part that is not normalised: x * 1 and its rounding to bf16 are exact)
+        if (normed) {
+            float ss = 0.f;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const bool in = j < NV - 1 || tail_in;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float lo = __uint_as_float(xv[j][e] << 16), hi = __uint_as_float(xv[j][e] & 0xffff0000u);
+                    ss = in ? __builtin_fmaf(hi, hi, __builtin_fmaf(lo, lo, ss)) : ss;
+                }
+            }
+            ss = sum_across_rows(row16_sum(ss));
+            r = 1.0f / __builtin_sqrtf(ss / (float)C + a.eps);   // (IEEE divide and sqrt: torch's mean and rsqrt on the host)
+        }
+        // Registers: the row stays packed (4 per vector) across the reduction, the bf16 weights stay packed across rows.  The empty
+        // asm statements hide the values' origin, or the compiler keeps the unpacked floats instead: 8 per vector each, and spills.
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            asm volatile("" : "+v"(xv[j]));
+            if constexpr (WK == 1) asm volatile("" : "+v"(wb[j]));
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            u32x4 o;
+            f32x4 w2[2];
+            if constexpr (WK == 2 && HELD) w2[0] = wf[j][0], w2[1] = wf[j][1];
+            if constexpr (WK == 2 && !HELD) w2[0] = *(const f32x4 *)((const float *)wp + col[j]), w2[1] = *(const f32x4 *)((const float *)wp + col[j] + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float re = __uint_as_float(xv[j][e] << 16) * r, im = __uint_as_float(xv[j][e] & 0xffff0000u) * r;
+                round_bf16_pair(re, im);                                    // .type_as(x)
+                if constexpr (WK == 1) {                                    // bf16 * bf16: the product is rounded to bf16
+                    re *= __uint_as_float(wb[j][e] << 16), im *= __uint_as_float(wb[j][e] & 0xffff0000u);
+                    round_bf16_pair(re, im);
+                }
+                if constexpr (WK == 2) re *= w2[e >> 1][2 * (e & 1)], im *= w2[e >> 1][2 * (e & 1) + 1];   // bf16 * fp32 parameter: stays fp32
+                // (re, im) -> (re * c - im * s, re * s + im * c); both table entries of a pair carry its angle
+                const float c = e < 2 ? c0[2 * e] : c1[2 * e - 4], sn = e < 2 ? s0[2 * e] : s1[2 * e - 4];
+                o[e] = rotated ? pack_bf16x2(re * c - im * sn, re * sn + im * c) : pack_bf16x2(re, im);
+            }
+            if (j < NV - 1 || tail_in) *(u32x4 *)(dst + j * dstep) = o;
+            __builtin_amdgcn_sched_barrier(0);   // one vector at a time: left to itself the scheduler widens all NV at once and runs out of registers
+        }
+    }
+}
+
+template <int NV>   // NV 16-byte vectors per lane: heads in 4 * NV - 3 .. 4 * NV
+__global__ __launch_bounds__(256) void split_heads_rownorm_kernel(const RownormArgs a) {
+    // item = (row, part); the launch makes the number of waves a multiple of parts, so a wave stays with one part
+    const int64_t wave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    const int part = (int)(wave % a.parts);
+    const int64_t row0 = wave / a.parts, row_step = nwaves / a.parts;
+    const void *wp = part == 0 ? a.w0 : part == 1 ? a.w1 : a.w2;
+    uint16_t *out = part == 0 ? a.o0 : part == 1 ? a.o1 : a.o2;
+    const bool normed = a.norm_mask >> part & 1, rope = a.rope_mask >> part & 1;
+    if (!normed && !rope) {   // bit copy into the head-major layout
+        const int lane = threadIdx.x & 63, l15 = lane & 15, hq = lane >> 4, H = a.heads;
+        RowWalk w(row0, row_step, a.n);
+        for (int64_t row = row0; row < a.rows; row += row_step, w.next()) {
+            const int64_t b = w.b, tok = w.tok;
+            const uint16_t *src = a.x + b * a.batch_stride + tok * a.row_stride + (int64_t)part * H * 128;
+            uint16_t *dst = out + ((b * H + hq) * a.n + tok) * 128 + l15 * 8;
+            u32x4 xv[NV];
+#pragma unroll
+            for (int j = 0; j < NV; ++j) xv[j] = *(const u32x4 *)(src + min((j * 64 + lane) * 8, H * 128 - 8));   // (see rownorm_rows)
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (j < NV - 1 || (NV - 1) * 4 + hq < H) *(u32x4 *)(dst + j * a.n * 512) = xv[j];
+        }
+    } else if (!wp) rownorm_rows<NV, 0>(a, part, row0, row_step, wp, out, normed, rope);
+    else if (a.fp32_mask >> part & 1) rownorm_rows<NV, 2>(a, part, row0, row_step, wp, out, normed, rope);
+    else rownorm_rows<NV, 1>(a, part, row0, row_step, wp, out, normed, rope);
+}
+
+template <int NV>
+void launch_rownorm(const RownormArgs &a, hipStream_t s) {
+    // 4 items per workgroup at a time; enough workgroups for 8 per CU, the rest of the items by stride; waves a multiple of parts
+    int64_t grid = (a.rows * a.parts + 3) / 4;
+    grid = grid < 256 * 8 ? grid : 256 * 8;
+    if (a.parts == 3) grid = (grid + 2) / 3 * 3;
+    hipLaunchKernelGGL((split_heads_rownorm_kernel<NV>), dim3((unsigned)grid), dim3(256), 0, s, a);
+}
+}  // namespace
+
+extern "C" int chipmunk_split_heads_rownorm(const void *x, int64_t batch_stride, int64_t row_stride, int parts, const void *w0, int w0_dtype,
+                                            const void *w1, int w1_dtype, const void *w2, int w2_dtype, void *out0, void *out1, void *out2,
+                                            unsigned norm_mask, unsigned rope_mask, int64_t B, int64_t n, int heads, float eps,
+                                            const float *freqs_cos, const float *freqs_sin, int64_t rope_rows, void *stream) {
+    CM_CHECK(parts >= 1 && parts <= 3, "split_heads_rownorm: parts must be 1, 2 or 3 (got %d)", parts);
+    CM_CHECK(heads >= 1 && heads <= 64, "split_heads_rownorm: heads must be in 1 .. 64 (got %d)", heads);
+    CM_CHECK(B >= 1 && B < (1 << 24) && n >= 0 && n < ((int64_t)1 << 31), "split_heads_rownorm: B must be in 1 .. 2^24 - 1 and n in 0 .. 2^31 - 1 (got B=%lld n=%lld)",
+             (long long)B, (long long)n);
+    const void *w[3] = {w0, w1, w2};
+    const int wd[3] = {w0_dtype, w1_dtype, w2_dtype};
+    void *out[3] = {out0, out1, out2};
+    CM_CHECK(x, "split_heads_rownorm: null input pointer");
+    CM_CHECK((norm_mask >> parts) == 0 && (rope_mask >> parts) == 0, "split_heads_rownorm: norm_mask / rope_mask name a part past parts=%d", parts);
+    uint32_t fp32_mask = 0;
+    for (int p = 0; p < 3; ++p) {
+        CM_CHECK(p >= parts || out[p], "split_heads_rownorm: null output pointer for part %d", p);
+        CM_CHECK(wd[p] >= 0 && wd[p] <= 2 && (wd[p] == 0) == (w[p] == nullptr),
+                 "split_heads_rownorm: weight %d: dtype code must be 0 (none, null pointer), 1 (bf16) or 2 (fp32)", p);
+        CM_CHECK(wd[p] == 0 || (p < parts && (norm_mask >> p & 1)), "split_heads_rownorm: weight %d belongs to a part that is not normalised", p);
+        if (wd[p] == 2) fp32_mask |= 1u << p;
+    }
+    CM_CHECK(row_stride >= (int64_t)parts * heads * 128 && batch_stride >= 0,
+             "split_heads_rownorm: the row stride (%lld) must cover parts * heads * 128 = %lld columns", (long long)row_stride,
+             (long long)parts * heads * 128);
+    CM_CHECK((((uintptr_t)x | (uintptr_t)w0 | (uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)out2 |
+               (uintptr_t)freqs_cos | (uintptr_t)freqs_sin) & 15) == 0 && (row_stride & 7) == 0 && (batch_stride & 7) == 0,
+             "split_heads_rownorm: pointers must be 16-byte aligned, the batch and row strides multiples of 8 elements");
+    CM_CHECK((freqs_cos == nullptr) == (freqs_sin == nullptr), "split_heads_rownorm: freqs_cos and freqs_sin come together (both or neither)");
+    CM_CHECK(rope_mask == 0 || freqs_cos, "split_heads_rownorm: a rotated part needs freqs_cos / freqs_sin");
+    CM_CHECK(rope_rows >= 0 && rope_rows <= n && (freqs_cos || rope_rows == 0), "split_heads_rownorm: rope_rows (%lld) must be in 0 .. n (%lld), 0 without tables",
+             (long long)rope_rows, (long long)n);
+    if (n == 0) return CHIPMUNK_OK;
+    RownormArgs a;
+    a.x = (const uint16_t *)x, a.batch_stride = batch_stride, a.row_stride = row_stride;
+    a.w0 = w0, a.w1 = w1, a.w2 = w2;
+    a.o0 = (uint16_t *)out0, a.o1 = (uint16_t *)out1, a.o2 = (uint16_t *)out2;
+    a.fcos = freqs_cos, a.fsin = freqs_sin;
+    a.n = n, a.rows = B * n, a.rope_rows = rope_rows;
+    a.parts = parts, a.heads = heads;
+    a.norm_mask = norm_mask, a.rope_mask = rope_rows > 0 ? rope_mask : 0u, a.fp32_mask = fp32_mask;
+    a.eps = eps;
+    hipStream_t s = (hipStream_t)stream;
+    switch ((heads + 3) / 4) {
+#define CM_ROWNORM_CASE(NV) case NV: launch_rownorm<NV>(a, s); break;
+        CM_ROWNORM_CASE(1) CM_ROWNORM_CASE(2) CM_ROWNORM_CASE(3) CM_ROWNORM_CASE(4) CM_ROWNORM_CASE(5) CM_ROWNORM_CASE(6)
+        CM_ROWNORM_CASE(7) CM_ROWNORM_CASE(8) CM_ROWNORM_CASE(9) CM_ROWNORM_CASE(10) CM_ROWNORM_CASE(11) CM_ROWNORM_CASE(12)
+        CM_ROWNORM_CASE(13) CM_ROWNORM_CASE(14) CM_ROWNORM_CASE(15) CM_ROWNORM_CASE(16)
+#undef CM_ROWNORM_CASE
+    }
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }

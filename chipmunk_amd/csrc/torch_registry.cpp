@@ -869,6 +869,58 @@ std::vector<at::Tensor> qkv_split_norm(at::Tensor qkv, const c10::optional<at::T
     return {out[0], out[1], out[2]};
 }
 
+// [B, n, >= parts*heads*128] (or [n, ...]) -> parts x [B, heads, n, 128]: row-wide RMSNorm, weight, rotary per part (see
+// chipmunk_split_heads_rownorm); norm_mask / rope_mask: bit p = part p
+std::vector<at::Tensor> split_heads_rownorm(at::Tensor x, int64_t heads, int64_t parts, const c10::optional<at::Tensor> &w0,
+                                            const c10::optional<at::Tensor> &w1, const c10::optional<at::Tensor> &w2, int64_t norm_mask,
+                                            int64_t rope_mask, double eps, const c10::optional<at::Tensor> &freqs_cos,
+                                            const c10::optional<at::Tensor> &freqs_sin) {
+    CHECK_DEV(x); CHECK_BF16(x);
+    TORCH_CHECK(parts >= 1 && parts <= 3 && heads >= 1 && heads <= 64, "split_heads_rownorm: parts must be in 1 .. 3 and heads in 1 .. 64");
+    TORCH_CHECK((x.dim() == 2 || x.dim() == 3) && x.stride(-1) == 1 && x.size(-1) >= parts * heads * 128,
+                "split_heads_rownorm: x must be [B, n, >= parts*heads*128] or [n, >= parts*heads*128] with a contiguous last dim");
+    TORCH_CHECK(norm_mask >= 0 && rope_mask >= 0 && (norm_mask >> parts) == 0 && (rope_mask >> parts) == 0, "split_heads_rownorm: a mask names a part past parts");
+    const int64_t B = x.dim() == 3 ? x.size(0) : 1, n = x.size(-2), C = heads * 128;
+    TORCH_CHECK(B >= 1, "split_heads_rownorm: empty batch");
+    const c10::optional<at::Tensor> *ws[3] = {&w0, &w1, &w2};
+    at::Tensor wc[3];
+    const void *wp[3] = {nullptr, nullptr, nullptr};
+    int wd[3] = {0, 0, 0};
+    for (int p = 0; p < 3; ++p) {
+        if (!(ws[p]->has_value() && (*ws[p])->defined())) continue;
+        TORCH_CHECK(p < parts && (norm_mask >> p & 1), "split_heads_rownorm: weight ", p, " belongs to a part that is not normalised");
+        wc[p] = (*ws[p])->contiguous();
+        CHECK_DEV(wc[p]);
+        TORCH_CHECK((wc[p].scalar_type() == at::kBFloat16 || wc[p].scalar_type() == at::kFloat) && wc[p].numel() == C,
+                    "split_heads_rownorm: a weight must be bfloat16 or float32 with heads*128 entries");
+        wp[p] = wc[p].data_ptr(), wd[p] = wc[p].scalar_type() == at::kFloat ? 2 : 1;
+    }
+    const float *fc = nullptr, *fs = nullptr;
+    int64_t rope_rows = 0;
+    at::Tensor fcc, fsc;
+    const bool has_cos = freqs_cos.has_value() && freqs_cos->defined(), has_sin = freqs_sin.has_value() && freqs_sin->defined();
+    TORCH_CHECK(has_cos == has_sin, "split_heads_rownorm: freqs_cos and freqs_sin come together");
+    TORCH_CHECK(rope_mask == 0 || has_cos, "split_heads_rownorm: a rotated part needs freqs_cos / freqs_sin");
+    if (has_cos) {
+        fcc = freqs_cos->contiguous(), fsc = freqs_sin->contiguous();
+        CHECK_DEV(fcc); CHECK_DEV(fsc);
+        TORCH_CHECK(fcc.scalar_type() == at::kFloat && fsc.scalar_type() == at::kFloat && fcc.dim() == 2 && fcc.size(1) == 128 &&
+                    fsc.sizes() == fcc.sizes() && fcc.size(0) <= n, "split_heads_rownorm: freqs must be float32 [rows <= n, 128]");
+        fc = fcc.data_ptr<float>(), fs = fsc.data_ptr<float>(), rope_rows = fcc.size(0);
+    }
+    c10::DeviceGuard guard(x.device());
+    at::Tensor out = at::empty({parts, B, heads, n, 128}, x.options());
+    void *op[3] = {nullptr, nullptr, nullptr};
+    std::vector<at::Tensor> res;
+    for (int p = 0; p < parts; ++p) res.push_back(out[p]), op[p] = res.back().data_ptr();
+    if (n == 0) return res;
+    check(chipmunk_split_heads_rownorm(x.data_ptr(), x.dim() == 3 ? x.stride(0) : 0, x.stride(-2), (int)parts, wp[0], wd[0], wp[1], wd[1], wp[2],
+                                       wd[2], op[0], op[1], op[2], (unsigned)norm_mask, (unsigned)rope_mask, B, n, (int)heads, (float)eps, fc,
+                                       fs, rope_rows, cur_stream(x)),
+          "split_heads_rownorm");
+    return res;
+}
+
 // dst[..., i, :] = src[..., map[i], :] over the second-to-last axis (token reorder; see chipmunk_gather_rows)
 at::Tensor gather_rows(at::Tensor src, at::Tensor map) {
     CHECK_DEV(src);
@@ -932,10 +984,12 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("bitunpack(Tensor packed, int[] shape) -> Tensor");
     m.def("gather_rows(Tensor src, Tensor map) -> Tensor");
     m.def("qkv_split_norm(Tensor qkv, Tensor? q_weight, Tensor? k_weight, int heads, float eps, Tensor? freqs_cos=None, Tensor? freqs_sin=None) -> Tensor[]");
+    m.def("split_heads_rownorm(Tensor x, int heads, int parts, Tensor? w0, Tensor? w1, Tensor? w2, int norm_mask, int rope_mask, float eps, Tensor? freqs_cos=None, Tensor? freqs_sin=None) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("qkv_split_norm", &qkv_split_norm);
+    m.impl("split_heads_rownorm", &split_heads_rownorm);
     m.impl("csp_mlp_mm1_fp8_scatter", &csp_mlp_mm1_fp8_scatter);
     m.impl("dense_colsum_topk_mask", &dense_colsum_topk_mask);
     m.impl("csp_mlp_mm1", &csp_mlp_mm1);

@@ -109,5 +109,10 @@ def _register():
         out = qkv.new_empty((3, 1, heads, qkv.shape[0], 128))
         return [out[0], out[1], out[2]]
 
+    @lib.register_fake("chipmunk::split_heads_rownorm")
+    def _(x, heads, parts, w0, w1, w2, norm_mask, rope_mask, eps, freqs_cos=None, freqs_sin=None):
+        out = x.new_empty((parts, x.shape[0] if x.dim() == 3 else 1, heads, x.shape[-2], 128))
+        return [out[p] for p in range(parts)]
+
 
 _register()

@@ -360,6 +360,26 @@ int chipmunk_qkv_split_norm(const void *qkv, int64_t row_stride, const void *q_w
                             void *v, int64_t n, int heads, float eps, const float *freqs_cos, const float *freqs_sin,
                             int64_t rope_rows, void *stream);
 
+/* ---------------------------------------------------------------- Wan attention operands: row-wide RMSNorm + rotary, one pass
+ * x [B, n rows of row_stride elements, batch_stride elements apart] bf16; the first parts * heads * 128 columns of a row are
+ * `parts` (1 .. 3) consecutive blocks of C = heads * 128 columns (q | k | v), columns behind them are never read.  Part p goes to
+ * out_p [B, heads, n, 128] bf16 (contiguous).  Per part, independently:
+ *   - bit p of norm_mask: WanRMSNorm over the WHOLE row of C values (examples/wan/wan/modules/model.py:81-97, not per head as
+ *     chipmunk_qkv_split_norm): r = 1 / sqrt(mean(x^2) + eps) in fp32, y = bf16(x * r);
+ *   - a weight [C] for a normalised part, w_p with dtype code 0 (none, w_p NULL), 1 (bf16: bf16(y * w)) or 2 (fp32: y * w kept in
+ *     fp32, torch's promotion -- what Wan computes with fp32 parameters);
+ *   - bit p of rope_mask: for tokens < rope_rows the pair (2i, 2i+1) = (re, im) becomes (re * c - im * s, re * s + im * c) in fp32
+ *     (rope_apply, model.py:49-78, which multiplies in fp64), c / s from freqs_cos / freqs_sin fp32 [rope_rows, 128] -- both
+ *     entries of a pair carry the pair's angle, the table format of chipmunk_qkv_split_norm -- shared by all heads and batches.
+ * Every value is rounded once more, to bf16, when it is stored (model.py:164).  A part with neither bit set is a bit copy into
+ * the head-major layout (v).  heads in 1 .. 64; pointers 16-byte aligned, strides multiples of 8 elements; both tables or
+ * neither; rope_rows <= n.  Sums run in a fixed order: launches are bit-reproducible, and a row's result does not depend on B.
+ * The cross-attention operands (model.py:195-196, 236-239) are the same call without a rotation. */
+int chipmunk_split_heads_rownorm(const void *x, int64_t batch_stride, int64_t row_stride, int parts, const void *w0, int w0_dtype,
+                                 const void *w1, int w1_dtype, const void *w2, int w2_dtype, void *out0, void *out1, void *out2,
+                                 unsigned norm_mask, unsigned rope_mask, int64_t B, int64_t n, int heads, float eps,
+                                 const float *freqs_cos, const float *freqs_sin, int64_t rope_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
