@@ -34,12 +34,17 @@ struct M2IParams {
     int32_t *indices;
     int32_t *counts;
     int n, pad_n, multiple_of;
+    const int64_t *offsets;  // RAGGED: row r goes to indices + offsets[r], offsets[r + 1] - offsets[r] entries wide
 };
 
 // SORTED = true emits the kept columns in ASCENDING order instead (same set, same counts, same padding columns): not
 // the reference's order, but the attention result does not depend on it and ascending keys turn the K/V gather into
 // near-sequential DRAM pages (measured 1.6x on the C3 sparse step).  Used by SparseDiffAttn's fused path only.
-template <bool PACKED, bool SORTED = false>
+// RAGGED = true writes the row into ragged rows (the layout of compact_indices_kernel below) instead of a row of the padded
+// [rows, pad_n] tensor: same entries in the same order, then ZEROS from the last valid entry (kept + padding columns, at most
+// n) to the end of the row; counts are mask_row_counts_kernel's and are not written again.  Nothing is written past the row's
+// width, whatever the offsets say, and a row of width 0 is not even read.
+template <bool PACKED, bool SORTED = false, bool RAGGED = false>
 __global__ __launch_bounds__(256) void mask_to_indices_kernel(const M2IParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int n = p.n;
@@ -53,6 +58,22 @@ __global__ __launch_bounds__(256) void mask_to_indices_kernel(const M2IParams p)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t row = blockIdx.x;
     int32_t *out = p.indices + row * p.pad_n;
+    int width = 0;
+    if constexpr (RAGGED) {
+        const int64_t o = p.offsets[row];
+        out = p.indices + o;
+        width = (int)min((int64_t)0x7fffffff, p.offsets[row + 1] - o);
+        if (width <= 0) return;
+    }
+    auto put = [&](int pos, int col) {
+        if (!RAGGED || pos < width) out[pos] = col;
+    };
+    // RAGGED: zeros behind the `total` kept columns and the padding columns (which run out at n)
+    auto zero_rest = [&](int total) {
+        const int rem = total % p.multiple_of;
+        const int64_t padded = rem ? (int64_t)total - rem + p.multiple_of : total;
+        for (int i = (int)min(padded, (int64_t)n) + tid; i < width; i += 256) out[i] = 0;
+    };
 
     // ---- A: bit words
     if constexpr (PACKED) {
@@ -135,9 +156,10 @@ __global__ __launch_bounds__(256) void mask_to_indices_kernel(const M2IParams p)
             while (v) {
                 const int bit = __builtin_ctz(v);
                 v &= v - 1;
-                out[pos++] = col0 + bit;
+                put(pos++, col0 + bit);
             }
         }
+        if constexpr (RAGGED) zero_rest(total);
         if (tid == 0) {
             const int padded = ((total + p.multiple_of - 1) / p.multiple_of) * p.multiple_of;
             int pp = total;
@@ -148,10 +170,10 @@ __global__ __launch_bounds__(256) void mask_to_indices_kernel(const M2IParams p)
                 while (z && pp < padded) {
                     const int bit = __builtin_ctz(z);
                     z &= z - 1;
-                    out[pp++] = i * 32 + bit;
+                    put(pp++, i * 32 + bit);
                 }
             }
-            p.counts[row] = padded;
+            if constexpr (!RAGGED) p.counts[row] = padded;
         }
         return;
     }
@@ -198,9 +220,10 @@ __global__ __launch_bounds__(256) void mask_to_indices_kernel(const M2IParams p)
         while (v) {
             const int bit = __builtin_ctzll(v);
             v &= v - 1;
-            out[pos++] = ((blk * 64 + bit) << 5) + t;
+            put(pos++, ((blk * 64 + bit) << 5) + t);
         }
     }
+    if constexpr (RAGGED) zero_rest(total);
 
     // ---- E: padding with the first False columns (lane 0 only, <= multiple_of-1 columns)
     if (tid == 0) {
@@ -213,10 +236,52 @@ __global__ __launch_bounds__(256) void mask_to_indices_kernel(const M2IParams p)
             while (z && pos < padded) {
                 const int bit = __builtin_ctz(z);
                 z &= z - 1;
-                out[pos++] = i * 32 + bit;
+                put(pos++, i * 32 + bit);
             }
         }
-        p.counts[row] = padded;
+        if constexpr (!RAGGED) p.counts[row] = padded;
+    }
+}
+
+// kept columns per row, rounded as mask_to_indices_kernel rounds them, and the width the row takes in ragged rows -- what the caller
+// needs to lay the rows out before anything is emitted.  One wave per row, four rows per workgroup: 16 bytes per lane and step (head
+// and tail bytes one per lane: packed rows of n % 32 != 0 columns start at any byte), popcounts, one DPP reduction.
+struct RowCountParams {
+    const uint8_t *mask;  // as M2IParams
+    int32_t *counts;      // [rows] kept columns rounded up to multiple_of (may exceed n)
+    int64_t *lengths;     // [rows] min(counts, pad_n) rounded up to 32
+    int64_t rows;
+    int n, pad_n, multiple_of;
+};
+
+template <bool PACKED>
+__global__ __launch_bounds__(256) void mask_row_counts_kernel(const RowCountParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= p.rows) return;   // the whole wave
+    const int nbytes = PACKED ? p.n >> 3 : p.n;
+    const uint8_t *src = p.mask + (PACKED ? (row * p.n) >> 3 : row * p.n);
+    auto set_in_byte = [](uint32_t b) { return PACKED ? (uint32_t)__popc(b) : (uint32_t)(b != 0); };
+    auto set_in_word = [](uint32_t x) {
+        if constexpr (!PACKED) x = (x | (x >> 1) | (x >> 2) | (x >> 3) | (x >> 4) | (x >> 5) | (x >> 6) | (x >> 7)) & 0x01010101u;
+        return (uint32_t)__popc(x);
+    };
+    const int head = min(nbytes, (int)((16 - ((uintptr_t)src & 15)) & 15));
+    uint32_t cnt = lane < head ? set_in_byte(src[lane]) : 0u;
+    const int nvec = (nbytes - head) >> 4;
+    const u32x4 *vec = (const u32x4 *)(src + head);
+#pragma unroll 4
+    for (int i = lane; i < nvec; i += 64) {
+        const u32x4 x = vec[i];
+        cnt += set_in_word(x[0]) + set_in_word(x[1]) + set_in_word(x[2]) + set_in_word(x[3]);
+    }
+    const int tail = head + (nvec << 4) + lane;   // fewer than 16 bytes are left
+    if (tail < nbytes) cnt += set_in_byte(src[tail]);
+    const int64_t kept = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(cnt), 63);
+    if (lane == 0) {
+        const int64_t padded = ((kept + p.multiple_of - 1) / p.multiple_of) * p.multiple_of;
+        p.counts[row] = (int32_t)padded;
+        p.lengths[row] = (min(padded, (int64_t)p.pad_n) + 31) / 32 * 32;
     }
 }
 
@@ -538,10 +603,10 @@ size_t m2i_lds_bytes(int n, bool sorted) {
     return (size_t)NB * 64 * 4 + (size_t)32 * NB * 8 + (size_t)32 * NB * 4 + 33 * 4 + 16;
 }
 
-template <bool PACKED, bool SORTED = false>
+template <bool PACKED, bool SORTED = false, bool RAGGED = false>
 int launch_m2i(const void *mask, int32_t *indices, int32_t *counts, int64_t rows, int n, int pad_n, int multiple_of,
-               void *stream) {
-    CM_CHECK(mask && indices && counts, "mask_to_indices: null pointer");
+               void *stream, const int64_t *offsets = nullptr) {
+    CM_CHECK(mask && indices && (RAGGED ? (const void *)offsets : (const void *)counts), "mask_to_indices: null pointer");
     CM_CHECK(rows >= 0 && n > 0 && pad_n >= n && multiple_of > 0, "mask_to_indices: bad sizes rows=%lld n=%d pad_n=%d multiple_of=%d",
              (long long)rows, n, pad_n, multiple_of);
     CM_CHECK(rows < (1ll << 31), "mask_to_indices: too many rows");
@@ -549,9 +614,9 @@ int launch_m2i(const void *mask, int32_t *indices, int32_t *counts, int64_t rows
     const size_t lds = m2i_lds_bytes(n, SORTED);
     CM_CHECK(lds <= 160 * 1024, "mask_to_indices: row length %d needs %zu B of LDS (> 160 KiB)", n, lds);
     if (rows == 0) return CHIPMUNK_OK;
-    auto kern = mask_to_indices_kernel<PACKED, SORTED>;
+    auto kern = mask_to_indices_kernel<PACKED, SORTED, RAGGED>;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    M2IParams p = {(const uint8_t *)mask, indices, counts, n, pad_n, multiple_of};
+    M2IParams p = {(const uint8_t *)mask, indices, counts, n, pad_n, multiple_of, offsets};
     hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, p);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
@@ -1107,6 +1172,33 @@ extern "C" int chipmunk_mask_to_sorted_indices(const void *mask, int packed, int
                                                int64_t rows, int n, int pad_n, int multiple_of, void *stream) {
     return packed ? launch_m2i<true, true>(mask, indices, counts, rows, n, pad_n, multiple_of, stream)
                   : launch_m2i<false, true>(mask, indices, counts, rows, n, pad_n, multiple_of, stream);
+}
+
+extern "C" int chipmunk_mask_row_counts(const void *mask, int packed, int32_t *counts, int64_t *lengths, int64_t rows, int n,
+                                        int pad_n, int multiple_of, void *stream) {
+    CM_CHECK(mask && counts && lengths, "mask_row_counts: null pointer");
+    CM_CHECK(rows >= 0 && n > 0 && pad_n >= n && multiple_of > 0, "mask_row_counts: bad sizes rows=%lld n=%d pad_n=%d multiple_of=%d",
+             (long long)rows, n, pad_n, multiple_of);
+    CM_CHECK(rows < (1ll << 31), "mask_row_counts: too many rows");
+    CM_CHECK(!packed || n % 8 == 0, "mask_row_counts: n must be a multiple of 8 for a packed mask (got %d)", n);
+    // this kernel uses no LDS; a row that neither emission order can take (the sorted one takes the longer rows) is refused here already
+    const size_t lds = m2i_lds_bytes(n, true);
+    CM_CHECK(lds <= 160 * 1024, "mask_to_indices: row length %d needs %zu B of LDS (> 160 KiB)", n, lds);
+    if (rows == 0) return CHIPMUNK_OK;
+    RowCountParams p = {(const uint8_t *)mask, counts, lengths, rows, n, pad_n, multiple_of};
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (packed) hipLaunchKernelGGL(mask_row_counts_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(mask_row_counts_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+
+extern "C" int chipmunk_mask_to_ragged_indices(const void *mask, int packed, int sorted, const int64_t *offsets, int32_t *flat,
+                                               int64_t rows, int n, int multiple_of, void *stream) {
+    if (packed) return sorted ? launch_m2i<true, true, true>(mask, flat, nullptr, rows, n, n, multiple_of, stream, offsets)
+                              : launch_m2i<true, false, true>(mask, flat, nullptr, rows, n, n, multiple_of, stream, offsets);
+    return sorted ? launch_m2i<false, true, true>(mask, flat, nullptr, rows, n, n, multiple_of, stream, offsets)
+                  : launch_m2i<false, false, true>(mask, flat, nullptr, rows, n, n, multiple_of, stream, offsets);
 }
 
 extern "C" int chipmunk_topk_indices(const void *activation, int dtype, int32_t *indices, int32_t *counts, int rows,

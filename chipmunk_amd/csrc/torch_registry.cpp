@@ -724,6 +724,38 @@ std::vector<at::Tensor> mask_to_sorted_indices(at::Tensor mask, at::IntArrayRef 
     return {indices, counts};
 }
 
+// addition: the rows of (packed_)mask_to_indices / mask_to_sorted_indices followed by compact_indices, without the padded [b, h, m, pad_n]
+// tensor between them: {flat, offsets, counts}.  The size of flat depends on the mask, hence one host sync and no fake kernel.
+std::vector<at::Tensor> mask_to_ragged_indices(at::Tensor mask, at::IntArrayRef shape, int64_t multiple_of, int64_t pad_to_multiple_of,
+                                               bool sorted) {
+    CHECK_DEV(mask);
+    const bool packed = mask.scalar_type() == at::kByte;
+    TORCH_CHECK(packed || mask.scalar_type() == at::kBool, "mask must be bool, or uint8 bit-packed with a shape");
+    TORCH_CHECK(multiple_of > 0 && pad_to_multiple_of > 0, "multiple_of and pad_to_multiple_of must be positive");
+    mask = mask.contiguous();
+    std::vector<int64_t> shp = packed ? shape.vec() : mask.sizes().vec();
+    TORCH_CHECK(shp.size() == 4, "shape must be [b, h, m, n]");
+    const int64_t b = shp[0], h = shp[1], m = shp[2], n = shp[3], rows = b * h * m;
+    if (packed) TORCH_CHECK(n % 8 == 0 && mask.numel() * 8 >= rows * n, "bad packed mask");
+    const int64_t pad_n = ((n + pad_to_multiple_of - 1) / pad_to_multiple_of) * pad_to_multiple_of;
+    TORCH_CHECK(n > 0 && pad_n <= INT_MAX, "rows must have between 1 and 2^31 - 1 columns");
+    c10::DeviceGuard guard(mask.device());
+    at::Tensor counts = at::empty({b, h, m}, mask.options().dtype(at::kInt));
+    at::Tensor len = at::empty({rows}, mask.options().dtype(at::kLong));
+    check(chipmunk_mask_row_counts(mask.data_ptr(), packed ? 1 : 0, counts.data_ptr<int>(), len.data_ptr<int64_t>(), rows, (int)n,
+                                   (int)pad_n, (int)multiple_of, cur_stream(mask)),
+          "mask_to_ragged_indices");
+    at::Tensor offsets = at::zeros({rows + 1}, len.options());
+    if (rows) offsets.narrow(0, 1, rows).copy_(len.cumsum(0));
+    const int64_t total = rows ? offsets[rows].item<int64_t>() : 0;      // the one host sync (as compact_indices)
+    at::Tensor flat = at::empty({total + 64}, counts.options());
+    flat.narrow(0, total, 64).zero_();
+    check(chipmunk_mask_to_ragged_indices(mask.data_ptr(), packed ? 1 : 0, sorted ? 1 : 0, offsets.data_ptr<int64_t>(), flat.data_ptr<int>(),
+                                          rows, (int)n, (int)multiple_of, cur_stream(mask)),
+          "mask_to_ragged_indices");
+    return {flat, offsets, counts};
+}
+
 // addition: randint + topk + scatter_ + the two mask combines of modules/attn.py:76-82 in one kernel
 // dense_colsum_attn + topk_mask without the cs tensor between them (see chipmunk_dense_colsum_topk_mask); falls back to the two
 // operators when the fused entry does not apply to the launch
@@ -974,6 +1006,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("dense_attn_layout(Tensor q, Tensor k, Tensor v, bool token_major_o) -> Tensor[]");
     m.def("dense_colsum_attn_layout(Tensor q, Tensor k, Tensor v, Tensor p, bool token_major_o) -> Tensor[]");
     m.def("compact_indices(Tensor indices, Tensor counts) -> Tensor[]");
+    m.def("mask_to_ragged_indices(Tensor mask, int[] shape, int multiple_of, int pad_to_multiple_of, bool sorted) -> Tensor[]");
     m.def("csp_attn_out_ragged(Tensor q, Tensor k, Tensor v, Tensor o_in, Tensor indices, Tensor offsets, Tensor indices_counts, int o_scale) -> Tensor");
     m.def("residual_ln_modulate(Tensor x, Tensor? y, Tensor? gate, Tensor shift, Tensor scale, float eps) -> Tensor[]");
     m.def("transpose_last2(Tensor x) -> Tensor");
@@ -1014,6 +1047,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("topk_delta_indices", &topk_delta_indices);
     m.impl("packed_mask_to_indices", &packed_mask_to_indices);
     m.impl("mask_to_sorted_indices", &mask_to_sorted_indices);
+    m.impl("mask_to_ragged_indices", &mask_to_ragged_indices);
     m.impl("topk_mask", &topk_mask);
     m.impl("transpose_last2", &transpose_last2);
     m.impl("transpose_last2_pitched", &transpose_last2_pitched);

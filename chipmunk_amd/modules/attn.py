@@ -128,21 +128,22 @@ class SparseDiffAttn(nn.Module):
             pass
 
     @torch.compiler.disable
-    def _remember_indices(self, inds: Tensor, counts: Tensor) -> None:
+    def _remember_indices(self, inds: Optional[Tensor], counts: Tensor, ragged=None) -> None:
         """``attn.keep_unpacked_indices``: keep what the bit-packed mask just stored unpacks to -- while that mask itself stays in
         HBM, or (``attn.keep_unpacked_indices_offloaded``) also when it travels to pinned host memory -- as ragged rows (``ops.compact_indices``: the kept keys back to back; the padded ``[B, H, G, N]`` int32 tensor is 7 GB per
-        HunyuanVideo layer because the text groups keep every key).  One host sync per mask recompute for the total."""
+        HunyuanVideo layer because the text groups keep every key).  One host sync per mask recompute for the total.
+        ``ragged``: the (flat, offsets) the mask step made itself (``attn.ragged_mask_to_indices``); they are only booked here or dropped."""
         inv = self.layer_counter.cur_model_invocation_per_step
         old, self._unpacked[inv] = self._unpacked[inv], None
         if old is not None:
             self._release_kept(old)
         self.storage.indices.suppress_current(False)
-        if not (inds.is_cuda and amd_key("attn", "keep_unpacked_indices") and amd_key("attn", "fused_residual")
+        if not (counts.is_cuda and amd_key("attn", "keep_unpacked_indices") and amd_key("attn", "fused_residual")
                 and (self.storage.indices.is_resident() or amd_key("attn", "keep_unpacked_indices_offloaded"))):
             return
         if not reserve_resident(0):
             return
-        flat, offsets = ops.compact_indices(inds, counts)
+        flat, offsets = ragged if ragged is not None else ops.compact_indices(inds, counts)
         nbytes = 4 * flat.numel() + 8 * offsets.numel() + 4 * counts.numel()
         # rows whose mask goes to the host also count against the small dedicated budget (attn.kept_indices_offloaded_budget_gb)
         off_mode = not self.storage.indices.is_resident()
@@ -165,17 +166,34 @@ class SparseDiffAttn(nn.Module):
             return kept[:3]
         return None
 
+    def _stored_mask(self):
+        """(bit-packed mask, its shape) of the current model invocation."""
+        if self.storage.indices.is_suppressed():
+            # the kept index rows were expected to serve this step and the mask's host copy was not brought back (configuration changed in
+            # between): fetch it now, on the spot
+            self.storage.indices.suppress_current(False)
+            self.storage.indices.load_async()
+            self.storage.indices.load_async_wait()
+        return self.storage.get_indices(), self.mask_shape[self.layer_counter.cur_model_invocation_per_step]
+
+    @staticmethod
+    def _ragged_enabled(x: Tensor) -> bool:
+        """``attn.ragged_mask_to_indices``: the kept keys go from the mask straight to ragged rows (flat, offsets, counts) and the sparse
+        attention reads those; the padded ``[B, H, G, pad192(N)]`` index tensor is never allocated.  Needs the fused paths it is built from."""
+        return bool(x.is_cuda and GLOBAL_CONFIG["attn"]["should_compress_indices"] and amd_key("attn", "fused_residual")
+                    and amd_key("attn", "fused_packed_mask_to_indices") and amd_key("attn", "ragged_mask_to_indices"))
+
+    @torch.compiler.disable
+    def _ragged_indices(self, packed: Tensor, shape, multiple_of: int, bm: int, mask: Optional[Tensor] = None):
+        """(flat, offsets, counts) from the bit-packed mask; a mask whose rows do not end on a byte goes in as bools."""
+        if shape[-1] % 8 != 0:
+            packed = mask if mask is not None else ops.bitunpack(packed, shape)
+        return ops.mask_to_ragged_indices(packed, shape, multiple_of, bm, bool(amd_key("attn", "sorted_indices")))
+
     def _stored_indices(self, multiple_of: int, bm: int):
         cfg = GLOBAL_CONFIG["attn"]
         if cfg["should_compress_indices"]:
-            if self.storage.indices.is_suppressed():
-                # the kept index rows were expected to serve this step and the mask's host copy was not brought back (configuration changed in
-                # between): fetch it now, on the spot
-                self.storage.indices.suppress_current(False)
-                self.storage.indices.load_async()
-                self.storage.indices.load_async_wait()
-            packed = self.storage.get_indices()
-            shape = self.mask_shape[self.layer_counter.cur_model_invocation_per_step]
+            packed, shape = self._stored_mask()
             if amd_key("attn", "fused_packed_mask_to_indices") and packed.is_cuda and shape[-1] % 8 == 0:
                 if amd_key("attn", "sorted_indices"):
                     return ops.mask_to_sorted_indices(packed, shape, multiple_of, bm)
@@ -192,6 +210,7 @@ class SparseDiffAttn(nn.Module):
         multiple_of = 128 if do_padding else cfg["counts_multiple_of"]
 
         tm = bool(q.is_cuda and amd_key("attn", "token_major_output"))     # output layout of the dense calls; the sparse ones follow the cache
+        use_ragged = self._ragged_enabled(q)
         if self.layer_num < cfg["first_n_dense_layers"]:
             o, _ = ops.dense_attn(q, k, v, tm)
             return o
@@ -203,6 +222,7 @@ class SparseDiffAttn(nn.Module):
                 self.storage.set_lse_constants(lse)
                 return o
 
+            ragged = None
             if inference_step == 1 or cfg["recompute_mask"]:
                 prev_lse = self.storage.get_lse_constants()
                 tk = int(multiple_of * round((cfg["top_keys"] * k.shape[-2]) / multiple_of))
@@ -229,11 +249,15 @@ class SparseDiffAttn(nn.Module):
                     packed, mask_shape = ops.bitpack(mask)
                     self.mask_shape[self.layer_counter.cur_model_invocation_per_step] = mask_shape
                     self.storage.set_indices(packed)
-                    if mask.is_cuda and amd_key("attn", "fused_packed_mask_to_indices") and amd_key("attn", "sorted_indices"):
-                        inds, counts = ops.mask_to_sorted_indices(mask, mask.shape, multiple_of, bm)
+                    if use_ragged:
+                        ragged = self._ragged_indices(packed, mask_shape, multiple_of, bm, mask)
+                        self._remember_indices(None, ragged[2], ragged[:2])
                     else:
-                        inds, counts = ops.mask_to_indices(mask, multiple_of, bm)
-                    self._remember_indices(inds, counts)
+                        if mask.is_cuda and amd_key("attn", "fused_packed_mask_to_indices") and amd_key("attn", "sorted_indices"):
+                            inds, counts = ops.mask_to_sorted_indices(mask, mask.shape, multiple_of, bm)
+                        else:
+                            inds, counts = ops.mask_to_indices(mask, multiple_of, bm)
+                        self._remember_indices(inds, counts)
                 else:
                     kseq = k.shape[-2]
                     bs = bs[..., :_cdiv(kseq, bm), :kseq]
@@ -247,10 +271,15 @@ class SparseDiffAttn(nn.Module):
             else:
                 o, _ = ops.dense_attn(q, k, v, tm)
 
-            if not cfg["recompute_mask"]:
+            if use_ragged:
+                if ragged is None:      # a full step that reads the stored mask (no recompute_mask)
+                    ragged = self._ragged_indices(*self._stored_mask(), multiple_of, bm)
+            elif not cfg["recompute_mask"]:
                 inds, counts = self._stored_indices(multiple_of, bm)
 
-            if o.is_cuda and amd_key("attn", "fused_residual"):
+            if ragged is not None:
+                o_cache = ops.csp_attn_out_ragged(q, k, v, o, ragged[0], ragged[1], ragged[2], -1)
+            elif o.is_cuda and amd_key("attn", "fused_residual"):
                 # dense - sparse in the attention kernel's epilogue (bf16(o - bf16(sparse)), the same two roundings as the
                 # reference's `o - csp_attn(...)`), no 731 MB intermediate at HunyuanVideo size
                 o_cache = ops.csp_attn_out(q, k, v, o, inds, counts, -1)
@@ -267,6 +296,9 @@ class SparseDiffAttn(nn.Module):
         kept = self._kept_indices() if (o.is_cuda and amd_key("attn", "fused_residual")) else None
         if kept is not None:
             return ops.csp_attn_out_ragged(q, k, v, o, kept[0], kept[1], kept[2], 1)    # cache + delta, index rows as kept
+        if use_ragged:
+            flat, offsets, counts = self._ragged_indices(*self._stored_mask(), multiple_of, bm)
+            return ops.csp_attn_out_ragged(q, k, v, o, flat, offsets, counts, 1)
         inds, counts = self._stored_indices(multiple_of, bm)
         if do_padding:
             if o.is_cuda and amd_key("attn", "fused_residual"):

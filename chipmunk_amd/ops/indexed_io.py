@@ -45,6 +45,39 @@ def mask_to_sorted_indices(mask: torch.Tensor, shape: Sequence[int], multiple_of
     return torch.ops.chipmunk.mask_to_sorted_indices(mask, list(shape), multiple_of, pad_to_multiple_of)
 
 
+def mask_to_ragged_indices(mask: torch.Tensor, shape: Sequence[int], multiple_of: int, pad_to_multiple_of: int,
+                           sorted: bool = True) -> List[torch.Tensor]:
+    """The kept keys of every mask row as ragged rows, without the padded ``[b, h, m, pad_n]`` tensor: ``[flat, offsets, counts]``.
+    ``mask`` bool ``[b, h, m, n]``, or uint8 bit-packed with ``shape`` (``n % 8 == 0``).  ``counts [b, h, m]`` int32: kept columns
+    rounded up to ``multiple_of`` (it may exceed ``n``).  ``offsets [b*h*m + 1]`` int64: row ``r`` is ``flat[offsets[r]:offsets[r + 1]]``,
+    ``min(counts[r], pad_n)`` rounded up to 32 entries wide.  ``flat`` int32, 64 spare zero entries at its end.  A row holds its True
+    columns -- ascending (``sorted``), or the reference's order: classes ``c % 32`` one after the other, ascending inside a class --
+    then the first False columns ascending up to ``counts[r]`` entries while there are any, then zeros.  What ``mask_to_sorted_indices``
+    / ``(packed_)mask_to_indices`` followed by ``compact_indices`` give.  CPU tensors take the torch statement of that contract below."""
+    if mask.is_cuda:
+        return torch.ops.chipmunk.mask_to_ragged_indices(mask, list(shape), multiple_of, pad_to_multiple_of, sorted)
+    if mask.dtype == torch.uint8:
+        from .bitpack import bitunpack
+        mask = bitunpack(mask, shape)
+    b, h, m, n = mask.shape
+    pad_n = (n + pad_to_multiple_of - 1) // pad_to_multiple_of * pad_to_multiple_of
+    rows = mask.reshape(-1, n) != 0
+    kept = rows.sum(dim=1)
+    counts = (kept + multiple_of - 1) // multiple_of * multiple_of
+    lengths = (counts.clamp(max=pad_n) + 31) // 32 * 32
+    offsets = torch.zeros(rows.shape[0] + 1, dtype=torch.int64)
+    offsets[1:] = lengths.cumsum(0)
+    flat = torch.zeros(int(offsets[-1]) + 64, dtype=torch.int32)
+    cols = torch.arange(n, dtype=torch.int32)
+    for r in range(rows.shape[0]):
+        true = cols[rows[r]]
+        if not sorted:
+            true = true[torch.argsort(true % 32, stable=True)]
+        row = torch.cat([true, cols[~rows[r]][:int(counts[r] - kept[r])]])
+        flat[int(offsets[r]):int(offsets[r]) + row.numel()] = row
+    return [flat, offsets, counts.to(torch.int32).view(b, h, m)]
+
+
 def topk_mask(cs: torch.Tensor, k: int, random_amount: float = 0.0, groups: Optional[torch.Tensor] = None,
               static_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``((top-k of cs | random) & groups) | static_mask`` as one kernel: the reference's ``random_and_topk``

@@ -114,6 +114,10 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # this much derived state in HBM: HunyuanVideo's rows would be 32 GB, Wan2.1's are 1.6 GB); beyond it a layer re-derives its rows
     # from the bits as the reference does.  With the masks resident the rows count against hbm_budget_gb only.
     "attn.kept_indices_offloaded_budget_gb": 8.0,
+    # should_compress_indices with fused_residual and fused_packed_mask_to_indices: the kept keys go from the mask straight to ragged rows
+    # (ops.mask_to_ragged_indices), in the mask step and in every sparse step whose rows were not kept; the padded [B, H, G, pad192(N)]
+    # int32 tensor (7.1 GB per HunyuanVideo layer, 137 GB at 524 288 keys) and its compaction are not made.  Same bits.
+    "attn.ragged_mask_to_indices": True,
 }
 BASE_CONFIG["offloading"]["keep_resident_if_fits"] = AMD_EXTRA_KEYS["offloading.keep_resident_if_fits"]
 BASE_CONFIG["offloading"]["hbm_budget_gb"] = AMD_EXTRA_KEYS["offloading.hbm_budget_gb"]
@@ -129,6 +133,7 @@ BASE_CONFIG["attn"]["token_major_output"] = AMD_EXTRA_KEYS["attn.token_major_out
 BASE_CONFIG["attn"]["keep_unpacked_indices"] = AMD_EXTRA_KEYS["attn.keep_unpacked_indices"]
 BASE_CONFIG["attn"]["keep_unpacked_indices_offloaded"] = AMD_EXTRA_KEYS["attn.keep_unpacked_indices_offloaded"]
 BASE_CONFIG["attn"]["kept_indices_offloaded_budget_gb"] = AMD_EXTRA_KEYS["attn.kept_indices_offloaded_budget_gb"]
+BASE_CONFIG["attn"]["ragged_mask_to_indices"] = AMD_EXTRA_KEYS["attn.ragged_mask_to_indices"]
 
 GLOBAL_CONFIG: Dict[str, Any] = copy.deepcopy(BASE_CONFIG)
 

@@ -292,6 +292,18 @@ int chipmunk_packed_mask_to_indices(const void *packed, int32_t *indices, int32_
 int chipmunk_mask_to_sorted_indices(const void *mask, int packed, int32_t *indices, int32_t *counts, int64_t rows,
                                     int n, int pad_n, int multiple_of, void *stream);
 
+/* The same rows written straight into the ragged layout of chipmunk_csp_attn_out_ragged, without the padded [rows, pad_n] tensor
+ * (no reference counterpart).  chipmunk_mask_row_counts: counts[r] = kept columns of row r rounded up to multiple_of (what the three
+ * entries above write; it may exceed n) and lengths[r] = min(counts[r], pad_n) rounded up to 32, the row's width in `flat`.  The
+ * caller turns the lengths into offsets (offsets[0] = 0, offsets[r + 1] = offsets[r] + lengths[r]) and allocates flat.
+ * chipmunk_mask_to_ragged_indices: flat[offsets[r] ...] = the kept columns of row r (sorted != 0: ascending, else the reference's
+ * order), then the first False columns ascending up to counts[r] while there are any, then zeros up to offsets[r + 1]; nothing
+ * is written past a row's width.  packed != 0: the mask is bit-packed, n % 8 == 0.  flat 16-byte aligned. */
+int chipmunk_mask_row_counts(const void *mask, int packed, int32_t *counts, int64_t *lengths, int64_t rows, int n, int pad_n,
+                             int multiple_of, void *stream);
+int chipmunk_mask_to_ragged_indices(const void *mask, int packed, int sorted, const int64_t *offsets, int32_t *flat, int64_t rows,
+                                    int n, int multiple_of, void *stream);
+
 /* Replaces chipmunk::copy_indices (reference csrc/indexed_io/copy_indices.cu:82-154; schema chipmunk.cpp:57).
  * dst[b,row,idx] = src[b,row,idx] for the first counts[b,row/R] entries of inds[b,row/R,:]; elem_size 2 or 4. */
 int chipmunk_copy_indices(const void *src, void *dst, const int32_t *inds, const int32_t *counts, int B, int M, int R,
