@@ -446,8 +446,18 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
 #pragma unroll
             for (int i = 0; i < C_INST; ++i) {
                 const int jj = (w * C_INST + i) * (64 / LPR) + lane / LPR;
-                if (n0 + jj < cnt && piece_row(jj) < rows)
-                    *(u32x4 *)((unsigned char *)p.cache + coff[i]) = *(const u32x4 *)(Ct + (w * C_INST + i) * 1024 + lane * 16);
+                const int ms = piece_row(jj);
+                if (n0 + jj < cnt && ms < rows) {
+                    const u32x4 v = *(const u32x4 *)(Ct + (w * C_INST + i) * 1024 + lane * 16);
+                    if (ms + 8 <= rows) {
+                        *(u32x4 *)((unsigned char *)p.cache + coff[i]) = v;
+                    } else {   // the piece that straddles M: the elements at or past M (the padding of a pitched cache) keep what they hold
+                        uint16_t *cp = (uint16_t *)((unsigned char *)p.cache + coff[i]);
+#pragma unroll
+                        for (int e = 0; e < 8; ++e)
+                            if (ms + e < rows) cp[e] = (uint16_t)(v[e >> 1] >> ((e & 1) * 16));
+                    }
+                }
             }
         }
     } else {

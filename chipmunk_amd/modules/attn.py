@@ -274,7 +274,10 @@ class SparseDiffAttn(nn.Module):
             if use_ragged:
                 if ragged is None:      # a full step that reads the stored mask (no recompute_mask)
                     ragged = self._ragged_indices(*self._stored_mask(), multiple_of, bm)
-            elif not cfg["recompute_mask"]:
+            elif not (inference_step == 1 or cfg["recompute_mask"]):
+                # (a step that made the selection itself holds it in `inds`, `counts`.  The reference reads it back from the storage here,
+                # attn.py:150-160: with `attn.indices` on the host that getter shows the pipeline slot -- empty at step 1, or another
+                # layer's rows -- and not what was stored a moment ago.)
                 inds, counts = self._stored_indices(multiple_of, bm)
 
             if ragged is not None:

@@ -100,8 +100,8 @@ class SparseDiffMlp:
                 f"{'no input at all' if stored is None else f'batch size {stored.shape[0]} with {stored.shape[1]} tokens'}: the batch size "
                 "and token count may only change on a full step")
 
-        reuse_mask = (inference_step % cfg["block_mask_cache"] != 0 and self.storage.get_indices() is not None
-                      and inference_step >= 10)
+        reuse_mask = (inference_step % cfg["block_mask_cache"] != 0 and inference_step >= 10
+                      and self.storage.get_indices() is not None)
         if not reuse_mask:
             bmfc1 = fc1(block_mean(x, mbm))
             r = bm // mbm
@@ -123,12 +123,22 @@ class SparseDiffMlp:
                 ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
                                  cfg["random_keys"])
                 ops.copy_indices(bmfc1, cache, inds, counts)
+            # the selected columns of the block means were refreshed in the LOADED tensor; a host copy has to follow (as for the activation
+            # cache below), or the next selection is made against the block means of the last full step
+            holder = self.storage.blockmean_mid_cache
+            if holder is not None and not holder.is_resident():
+                holder.offload_cur_value()
             self.storage.set_indices(inds)
             self.storage.set_counts(counts)
 
+        else:
+            inds, counts = self.storage.get_indices(), self.storage.get_counts()
+
+        # (a step that made the selection uses it as it made it: read back through the storage, a selection that was just sent to the host
+        # -- offloading["mlp.indices"] -- is not what the getter shows, which is the pipeline slot as last loaded)
         batched = x.shape[0] > 1     # B == 1 passes the 2-D operands it always passed
-        indices = self.storage.get_indices() if batched else self.storage.get_indices()[0]
-        counts = self.storage.get_counts() if batched else self.storage.get_counts()[0]
+        indices = inds if batched else inds[0]
+        counts = counts if batched else counts[0]
         out_cache = stored if batched else stored[0]
         sparse_act_T = self.storage.get_sparse_act_T()
         sparse_act_T = sparse_act_T[..., : x.shape[1]] if batched else sparse_act_T[0][:, : x.shape[1]]   # the [F, N] view of the pitched cache

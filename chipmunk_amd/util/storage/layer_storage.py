@@ -81,8 +81,14 @@ def _accessors(cls):
 class MlpStorage(_NamedStorage):
     _prefix = "mlp"
     _fields = ["sparse_act_T", "out_cache", "indices", "counts", "blockmean_mid_cache"]
-    _async_fields = ["sparse_act_T", "out_cache", "indices", "counts"]  # reference layer_storage.py:76-95
-    _complete_fields = ["blockmean_mid_cache", "out_cache", "indices", "counts"]  # reference :15-23
+    # reference layer_storage.py:76-95 loads four fields and never the block means: flagged for the host
+    # (offloading["mlp.blockmean_mid_cache"]) they could be stored and not read again.  All five are loaded.
+    _async_fields = ["sparse_act_T", "out_cache", "indices", "counts", "blockmean_mid_cache"]
+    # reference :15-23 lists four fields and leaves sparse_act_T out: its invocation key then never advances and, with more than one model
+    # invocation per step, every invocation reads and updates ONE activation cache while out_cache / indices / counts / the block means
+    # are per invocation -- the deltas of one invocation are taken against the other's activations.  (The reference's Wan model never
+    # advances the MLP storage at all, so it cannot show there.)  Departure from the reference: all five fields advance.
+    _complete_fields = ["sparse_act_T", "blockmean_mid_cache", "out_cache", "indices", "counts"]
 
 
 @_accessors

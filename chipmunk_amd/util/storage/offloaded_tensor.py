@@ -230,6 +230,10 @@ class MaybeOffloadedTensor:
     def get_loaded_value(self) -> Optional[torch.Tensor]:
         if self._is_resident_now():
             return self.gpu_tensor[self.get_cur_model_invocation_key()]
+        if self.real_shape[self.get_cur_model_invocation_key()] is None:
+            # nothing stored for THIS model invocation yet: None, as with offloading off -- not the slot, which holds nothing or what
+            # another invocation or layer loaded (the reference asserts or hands that tensor back, offloaded_tensor.py:120-132)
+            return None
         assert not self.is_suppressed(), (
             f"Tensor {self.name} (layer {self.layer_num}): its load was suppressed for this model invocation -- the pipeline slot "
             "holds another tensor; clear the flag (suppress_current(False)) and load it first")
