@@ -63,6 +63,23 @@ __device__ __forceinline__ f32x2 gelu_tanh2(f32x2 x) {
     return __builtin_elementwise_fma(-x, r, x);
 }
 
+// Activations of the gated GEMM1 (CHIPMUNK_ACT_*): 0 is the tanh-GeLU above, the same code; 1 SiLU x / (1 + exp(-x)); 2 the exact GeLU
+// 0.5 x (1 + erf(x / sqrt 2)).
+template <int ACT>
+__device__ __forceinline__ f32x2 glu_act2(f32x2 x) {
+    static_assert(ACT >= 0 && ACT <= 2, "unknown activation");
+    if constexpr (ACT == 0) {
+        return gelu_tanh2(x);
+    } else if constexpr (ACT == 1) {
+        const f32x2 u = x * (f32x2){-1.44269504089f, -1.44269504089f};
+        const f32x2 d = (f32x2){__builtin_amdgcn_exp2f(u[0]), __builtin_amdgcn_exp2f(u[1])} + (f32x2){1.0f, 1.0f};
+        return x * (f32x2){__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+    } else {
+        const f32x2 e = {erff(x[0] * 0.70710678118654752f), erff(x[1] * 0.70710678118654752f)};
+        return (x * (f32x2){0.5f, 0.5f}) * (e + (f32x2){1.0f, 1.0f});
+    }
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt immediate out of range");
@@ -160,7 +177,11 @@ struct Mm1Params {
     int M, K, F, NT, NR, probe, slots_per_xcd;
     int update_cache;  // 1: also apply the scatter-add of this tile's deltas to the cache block it already holds in LDS;
                        // 2 (fp8): store the new activation into the cache like the reference's Triton kernel
-    const float *scale_a, *scale_b;  // fp8 only: reciprocal quantisation scales (one float each)
+    // fp8 only: reciprocal quantisation scales (one float each).  The gated form (GLU; bf16 only, so it has no scales) keeps the up
+    // projection's weight and bias in the same two slots -- b / bias are then the gate projection's, either bias may be null (= zero):
+    // the parameter block keeps its size, and with it every kernel-argument offset of the ungated instantiations
+    union { const float *scale_a; const uint16_t *b_up; };
+    union { const float *scale_b; const uint16_t *bias_up; };
     int ldc;           // pitch of the column-major cache in elements: ldc >= M, ldc % 8 == 0 (M itself for the [F, M] contiguous cache)
 };
 
@@ -176,7 +197,12 @@ struct Mm1Params {
 // Neither the second wave of a SIMD issuing its DMA pieces after its MFMAs (2 200 per step) nor the pieces spread between the MFMA
 // groups (no change; the 4-wave form 125 -> 131 us bf16, 219 -> 212 us fp8, inside box noise) helps: the loop waits on the
 // landing of the gathered rows, not on their bytes or their issue.
-template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4>
+// GLU (gated feed-forward, c = bf16(act(x Wg + bg) * (x Wu + bu) - cache)): the B tile keeps its TN rows but holds TN/2 packed columns x
+// {gate, up}.  A wave's 64-row slab is split by n4: n4 = 0 holds the gate rows of packed columns n0 + wn*32 + (lane&31), n4 = 1 the up rows of
+// the same 32 columns, so a lane holds acc[mt][0][r] (gate) and acc[mt][1][r] (up) of one (row, column) and the epilogue combines them
+// without cross-lane traffic, on today's accumulator budget.  One DMA instruction covers KTile::RPI consecutive tile rows, so the half
+// (and with it the weight the rows are gathered from) is uniform per instruction.  Cache block and output image are TN/2 columns wide.
+template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0>
 __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
     using KT = KTile<BK>;
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
@@ -185,6 +211,9 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     constexpr int WNC = NW / 2;                                     // waves across the tile's columns (2 down its rows)
     constexpr int MT = TM / 64, NT4 = TN / (32 * WNC);              // 32-wide m / n tiles per wave
     static_assert(A_INST >= 1 && B_INST >= 1, "tile too small for one DMA instruction per wave");
+    constexpr int PW = GLU ? TN / 2 : TN;                           // packed columns of the tile
+    constexpr int NP4 = GLU ? 1 : NT4;                              // 32-wide tiles of packed columns per wave
+    static_assert(!GLU || (!FP8 && NW == 4 && NT4 == 2 && 32 % KT::RPI == 0), "the gated form: bf16, 4 waves, a 64-row B slab per wave");
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = w / WNC, wn = w % WNC;
@@ -196,6 +225,7 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     // sizes, so an offset past the tensor would be dropped by the range check, not fetched.
     const int rows = min(TM, p.M - (g * BM + m_off));
     const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.a, (uint32_t)p.M * p.K * ESZ), rb = make_rsrc(p.b);
+    const __amdgpu_buffer_rsrc_t rb_up = make_rsrc(GLU ? p.b_up : p.b);   // (gated form: the weight the up rows are gathered from)
     uint32_t aoff[A_INST], boff[B_INST];  // byte offsets
 #pragma unroll
     for (int i = 0; i < A_INST; ++i) {
@@ -205,7 +235,7 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
 #pragma unroll
     for (int i = 0; i < B_INST; ++i) {
         const int row = KT::lane_row(w * B_INST + i, lane);
-        const int j = n0 + row;
+        const int j = GLU ? n0 + (row >> 6) * 32 + (row & 31) : n0 + row;   // gated: tile rows [64 wn + 32 half, +32) = packed columns [32 wn, +32)
         const int key = idxg[j < cnt ? j : n0];  // rows past the count re-read a live row and are never stored
         boff[i] = (uint32_t)key * p.K * ESZ + KT::src_chunk_elems(row, lane) * 2u;
     }
@@ -214,7 +244,14 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
 #pragma unroll
         for (int i = 0; i < A_INST; ++i) blds16(ra, aoff[i], kb * BK * 2, st + (w * A_INST + i) * 1024);
 #pragma unroll
-        for (int i = 0; i < B_INST; ++i) blds16(rb, boff[i], kb * BK * 2, st + A_TILE + (w * B_INST + i) * 1024);
+        for (int i = 0; i < B_INST; ++i) {
+            if constexpr (GLU) {
+                const bool up = (((w * B_INST + i) * KT::RPI) >> 5) & 1;   // wave-uniform: the instruction's rows lie in one half
+                blds16(up ? rb_up : rb, boff[i], kb * BK * 2, st + A_TILE + (w * B_INST + i) * 1024);
+            } else {
+                blds16(rb, boff[i], kb * BK * 2, st + A_TILE + (w * B_INST + i) * 1024);
+            }
+        }
     };
     // Epilogue operands staged through LDS when the tile's slice of the activation cache fits one ring stage: the
     // TN x TM block cache[idx[n0..], g*BM+m_off ..] (TN rows of TM*2 contiguous bytes) is fetched by LDS-DMA during
@@ -223,10 +260,11 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     // measured 34 us of a 148 us launch.)
     // FLAT (tiles whose outputs exceed one stage): the ring starts at the stage that makes the LAST k step compute out of stage 0, the
     // cache block lands behind it in [STAGE, STAGE + TM*TN*2) and the outputs leave through stage 0 plus the bytes behind the cache block.
-    constexpr int EPI = TM * TN * 2;
+    constexpr int EPI = TM * PW * 2;   // (gated form: half the columns -- cache block PW columns x TM rows, output image TM x PW)
     constexpr bool FLAT = NW == 8 && EPI > STAGE && EPI <= (NST - 1) * STAGE && 2 * EPI <= NST * STAGE && STAGE % (TN * 2) == 0;
     constexpr bool STAGED = EPI <= STAGE || FLAT;
     static_assert(!FP8 || STAGED, "the fp8 form is only built for tile shapes with the staged epilogue");
+    static_assert(!GLU || (STAGED && !FLAT), "the gated form is only built for tile shapes with the staged epilogue");
     constexpr int LPR = TM * 2 / 16;                                  // 16-byte chunks per cache row
     constexpr int C_INST = STAGED ? EPI / (1024 * NW) : 1;            // DMA instructions per wave
     // The cache is [F, ldc]: a 16-byte piece that starts below M lies inside its column (ldc >= ceil8(M)), so the masks are
@@ -259,8 +297,13 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     f32x16 acc[MT][NT4];
 #pragma unroll
     for (int n4 = 0; n4 < NT4; ++n4) {
-        const int j = n0 + wn * (TN / WNC) + n4 * 32 + (lane & 31);
-        bias_v[n4] = bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]);
+        const int j = GLU ? n0 + wn * 32 + (lane & 31) : n0 + wn * (TN / WNC) + n4 * 32 + (lane & 31);
+        if constexpr (GLU) {   // n4 = 0: the gate's bias, 1: the up projection's; a null vector is zero
+            const uint16_t *bp = n4 ? p.bias_up : p.bias;
+            bias_v[n4] = bp ? bf16_bits_to_f32(bp[idxg[j < cnt ? j : n0]]) : 0.f;
+        } else {
+            bias_v[n4] = bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]);
+        }
         const float seed = SEED_BIAS ? bias_v[n4] : 0.f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -362,8 +405,8 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
         const int cst = last + NST - 1 >= NST ? last - 1 : last + NST - 1;  // nbuf at kb = nkb-1
         unsigned char *Ct = smem + (FLAT ? 1 : cst) * STAGE, *Ot = smem + (FLAT ? 0 : last) * STAGE;
         // output row r of the stage image (FLAT: the rows that do not fit stage 0 continue behind the cache block)
-        auto ot_row = [&](int r) { return Ot + r * (TN * 2) + ((FLAT && r >= STAGE / (TN * 2)) ? EPI : 0); };
-        constexpr int LPO = TN * 2 / 16;  // 16-byte chunks per output row
+        auto ot_row = [&](int r) { return Ot + r * (PW * 2) + ((FLAT && r >= STAGE / (TN * 2)) ? EPI : 0); };
+        constexpr int LPO = PW * 2 / 16;  // 16-byte chunks per output row
         wait_vmcnt<0>();
         __syncthreads();  // cache block landed; every wave is done reading the last tile
         // The output stage is plain row-major: a ds_write_b16 puts 32 consecutive columns of one row (64 contiguous bytes) per half
@@ -375,7 +418,7 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
             constexpr int UPD = decltype(upd_)::value;
             u32x2 cv[2][MT][4];
             auto cptr = [&](int n4, int mt, int q4) {
-                const int jl = wn * (TN / WNC) + n4 * 32 + (lane & 31), ml = wm * (TM / 2) + mt * 32 + q4 * 8 + (lane >> 5) * 4;
+                const int jl = wn * (PW / WNC) + n4 * 32 + (lane & 31), ml = wm * (TM / 2) + mt * 32 + q4 * 8 + (lane >> 5) * 4;
                 return Ct + jl * (TM * 2) + (((ml >> 3) ^ (jl & (LPR - 1))) << 4) + (ml & 7) * 2;
             };
             auto load = [&](int n4) {
@@ -386,9 +429,9 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
             };
             load(0);
 #pragma unroll
-            for (int n4 = 0; n4 < NT4; ++n4) {
-                if (n4 + 1 < NT4) load(n4 + 1);
-                const int jl = wn * (TN / WNC) + n4 * 32 + (lane & 31);
+            for (int n4 = 0; n4 < NP4; ++n4) {
+                if (n4 + 1 < NP4) load(n4 + 1);
+                const int jl = wn * (PW / WNC) + n4 * 32 + (lane & 31);
                 const float bia = bias_v[n4];
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
@@ -406,12 +449,17 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
                             const uint32_t t23 = pack_bf16x2_v(gelu_tanh2((a23 * sav) * sbv + bv));
                             d01 = pack_bf16x2_v(unpack_bf16x2(t01) - c01), d23 = pack_bf16x2_v(unpack_bf16x2(t23) - c23);
                             if constexpr (UPD == 2) n01 = t01, n23 = t23;   // 2: cache = new activation, what the reference's Triton kernel does (csp_mlp_mm1.py:140)
+                        } else if constexpr (GLU) {
+                            // act(gate) * up - cache in fp32, one rounding (both biases are already in the sums); a01 / a23 are the gate's
+                            const f32x2 u01 = {acc[mt][1][q4 * 4 + 0], acc[mt][1][q4 * 4 + 1]}, u23 = {acc[mt][1][q4 * 4 + 2], acc[mt][1][q4 * 4 + 3]};
+                            d01 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>(a01), u01, -c01));
+                            d23 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>(a23), u23, -c23));
                         } else {
                             // the bias is already in the sum (SEED_BIAS)
                             d01 = pack_bf16x2_v(gelu_tanh2(a01) - c01), d23 = pack_bf16x2_v(gelu_tanh2(a23) - c23);
                         }
                         uint16_t *op = (uint16_t *)(ot_row(ml) + jl * 2);   // (rows ml .. ml+3: on one side of the split, a multiple of 4)
-                        op[0] = (uint16_t)d01, op[TN] = (uint16_t)(d01 >> 16), op[2 * TN] = (uint16_t)d23, op[3 * TN] = (uint16_t)(d23 >> 16);
+                        op[0] = (uint16_t)d01, op[PW] = (uint16_t)(d01 >> 16), op[2 * PW] = (uint16_t)d23, op[3 * PW] = (uint16_t)(d23 >> 16);
                         if constexpr (UPD != 0) {
                             // 1: cache += delta in bf16, exactly what csp_scatter_add does (scatter_add.cu:43-98)
                             if constexpr (!(FP8 && UPD == 2))
@@ -423,6 +471,7 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
             }
         };
         if (p.update_cache == 0) arith(ic<0>{});
+        else if constexpr (GLU) arith(ic<1>{});   // (the gated entry admits 0 and 1 only: no third copy of its epilogue)
         else if (p.update_cache == 1) arith(ic<1>{});
         else arith(ic<2>{});
         __syncthreads();
@@ -567,6 +616,40 @@ __global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const typename std::c
             }
             __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
         }
+    }
+}
+
+// The gated GEMM1 (mm1_tile's GLU form; bf16, 4 waves): a kernel of its own, so that mm1_kernel's instantiations keep their names and their
+// code.  The same persistent walk over the same live-tile map, with a whole tile covering BN / 2 packed columns and without the tail
+// split (slots_per_xcd = 0: the launch is correct either way); ragged M through mm1_tile's `rows`, a batch through the pointer advance of
+// mm1_kernel's BATCHED form.
+template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED = false>
+__global__ __launch_bounds__(256, WPS) void mm1_glu_kernel(const typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int PBN = BN / 2;           // packed columns of a tile: its BN B-tile rows are {gate, up} pairs
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
+    const TilePlan pl = plan_tiles<PBN>(p.counts, G, p.NT, p.NR, 0, 1);
+    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+        const TileMap tm = tile_at(pl, slot);
+        if (!tm.live) continue;
+        const int cnt = p.counts[tm.g];
+        const int n0 = tm.nt * PBN;
+        if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
+        if constexpr (BATCHED) {
+            const int b = tm.g / Gs, g = tm.g - b * Gs;   // sequence, group inside it
+            Mm1Params q = p;                              // the tile sees its sequence's operands
+            q.a = p.a + (int64_t)b * p.M * p.K;
+            q.c = p.c + (int64_t)b * p.M * p.F;
+            q.cache = p.cache + (int64_t)b * p.cache_bs;
+            q.indices = p.indices + (int64_t)b * Gs * p.F;
+            mm1_tile<BM, BN, BK, NST, false, 4, true, ACT>(q, smem, g, 0, n0, cnt);
+        } else {
+            mm1_tile<BM, BN, BK, NST, false, 4, true, ACT>(p, smem, tm.g, 0, n0, cnt);
+        }
+        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
     }
 }
 
@@ -1083,18 +1166,23 @@ int launch_mm2(const void *a, const void *b, void *c, const int32_t *indices, co
     return launch_mm2_variant<256, 32, 3, 2, 8>(p, s);
 }
 
-template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false>
+template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false, bool GLU = false, int ACT = 0>
 int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated = nullptr, int B = 1, int64_t cache_bs = 0) {
-    constexpr int STAGE = BM * BK * 2 + BN * BK * 2, LDS = NST * STAGE, EPI = BM * BN * 2;
+    constexpr int PBN = GLU ? BN / 2 : BN;   // packed columns per whole tile (gated form: the B tile's rows are {gate, up} pairs)
+    constexpr int STAGE = BM * BK * 2 + BN * BK * 2, LDS = NST * STAGE, EPI = BM * PBN * 2;
     // mm1_tile's staged epilogue (the one that can scatter): one stage each for cache block and outputs, or the FLAT layout
     constexpr bool STAGED = EPI <= STAGE || (NW == 8 && EPI <= (NST - 1) * STAGE && 2 * EPI <= NST * STAGE && STAGE % (BN * 2) == 0);
-    auto kern = mm1_kernel<BN, BK, NST, WPS, FP8, NW, BATCHED>;
+    auto kern = [] {
+        if constexpr (GLU) return mm1_glu_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+        else return mm1_kernel<BN, BK, NST, WPS, FP8, NW, BATCHED>;
+    }();
+    static_assert(!GLU || (!FP8 && NW == 4), "the gated GEMM1 is bf16 with 4 waves");
     static uint64_t lds_set = 0;
     ensure_dynamic_lds((const void *)kern, LDS, lds_set);
     Mm1Params p = p0;
     if (!STAGED) p.update_cache = 0;
     if (cache_updated) *cache_updated = p.update_cache != 0;
-    p.NT = (p.F + BN - 1) / BN;
+    p.NT = (p.F + PBN - 1) / PBN;
     p.NR = chipmunk_get_option("mm1_nr") > 0 ? chipmunk_get_option("mm1_nr") : 4;
     if (p.NR > p.NT) p.NR = p.NT;
     // tail split: WPS workgroups per CU are resident; an XCD's leftover tiles are handed out as sub-tiles at the end of its list.  The
@@ -1103,7 +1191,7 @@ int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated =
     constexpr int WPS_FIT = (160 * 1024 / LDS) < WPS ? (160 * 1024 / LDS) : WPS;
     static_assert(WPS_FIT >= 1, "a variant's ring must fit the 160 KiB of a CU");
     const int resident_per_xcd = WPS_FIT * device_cu_count() / 8;
-    p.slots_per_xcd = (chipmunk_get_option("mm1_no_split") || NW != 4) ? 0 : resident_per_xcd;
+    p.slots_per_xcd = (chipmunk_get_option("mm1_no_split") || NW != 4 || GLU) ? 0 : resident_per_xcd;   // (the gated form has no tail split)
     // persistent grid: the resident slots, or fewer when the launch has fewer tiles than slots (every tile gets its own workgroup)
     const int tiles_per_xcd = (B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8;
     const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
@@ -1203,7 +1291,51 @@ int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void 
 #endif
     return launch_mm1_variant<128, 64, 2, 2, true>(p, stream);
 }
+
+// Gated GEMM1 (SwiGLU / GEGLU): the *_ragged / *_batched contract, bf16 only, the shipped tile shape only
+template <bool BATCHED>
+int launch_mm1_glu(const Mm1Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
+    switch (act) {
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, false, 4, BATCHED, true, 0>(p, stream, nullptr, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, false, 4, BATCHED, true, 1>(p, stream, nullptr, B, cache_bs);
+        default: return launch_mm1_variant<128, 64, 2, 2, false, 4, BATCHED, true, 2>(p, stream, nullptr, B, cache_bs);
+    }
+}
+int mm1_glu_entry(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
+                  const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream,
+                  int B = 0, int64_t cache_bs = 0) {   // B > 0: the *_batched entry
+    CM_CHECK(a && b_gate && b_up && c && pa_cache, "csp_mlp_mm1_glu: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
+    if (B > 0) {
+        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
+    }
+    CM_CHECK(act == CHIPMUNK_ACT_GELU_TANH || act == CHIPMUNK_ACT_SILU || act == CHIPMUNK_ACT_GELU_ERF,
+             "csp_mlp_mm1_glu: unknown activation %d (0 = gelu_tanh, 1 = silu, 2 = gelu)", act);
+    CM_CHECK(update_cache == 0 || update_cache == 1, "csp_mlp_mm1_glu: update_cache must be 0 or 1 (got %d)", update_cache);
+    CM_CHECK(K > 0 && K % 64 == 0, "csp_mlp_mm1_glu: K must be a positive multiple of 64 (got %d)", K);
+    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
+             "csp_mlp_mm1_glu: operand too large for 32-bit offsets");
+    Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b_gate, (const uint16_t *)bias_gate, (uint16_t *)pa_cache,
+                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
+    p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
+    return B > 0 ? launch_mm1_glu<true>(p, act, stream, B, cache_bs) : launch_mm1_glu<false>(p, act, stream, 1, 0);
+}
 }  // namespace
+
+extern "C" int chipmunk_csp_mlp_mm1_glu(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                        const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K,
+                                        int F, int ldc, int act, int update_cache, void *stream) {
+    return mm1_glu_entry(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache, indices, counts, M, K, F, ldc, act, update_cache, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_glu_batched(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                                const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M,
+                                                int K, int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                                void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_glu_entry(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache, indices, counts, M, K, F, ldc, act, update_cache,
+                         (hipStream_t)stream, B, cache_batch_stride);
+}
 
 extern "C" int chipmunk_csp_mlp_mm1(const void *a, const void *b, void *c, const void *bias, const void *pa_cache,
                                     const int32_t *indices, const int32_t *counts, int M, int K, int F, void *stream) {

@@ -277,7 +277,8 @@ struct Mm1Shape {
     int64_t B, M, K, F, ldc, cache_bs;
     bool batched() const { return B > 1; }
 };
-Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c, const at::Tensor &bias, const at::Tensor &cache,
+// (bias: null for the gated operator, which checks its two optional vectors itself)
+Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c, const at::Tensor *bias, const at::Tensor &cache,
                    const at::Tensor &indices, const at::Tensor &counts) {
     TORCH_CHECK((a.dim() == 2 || a.dim() == 3) && b.dim() == 2 && c.dim() == a.dim(), "a and c must both be 2D ([M, .]) or 3D ([B, M, .]), b 2D");
     Mm1Shape s;
@@ -286,7 +287,7 @@ Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c
     TORCH_CHECK(s.B >= 1, "the batch size must be at least 1");
     TORCH_CHECK(b.size(1) == s.K, "a and b must share the K dimension");
     TORCH_CHECK(c.size(-2) == s.M && c.size(-1) == s.F && c.numel() == s.B * s.M * s.F, "c must be [M, F] ([B, M, F] with the batch size of a)");
-    TORCH_CHECK(bias.numel() == s.F, "bias must have F entries");
+    if (bias) TORCH_CHECK(bias->numel() == s.F, "bias must have F entries");
     if (!s.batched()) {
         s.ldc = cache_pitch(cache, s.F, s.M, "pa_cache_colmajor");
         s.cache_bs = s.F * s.ldc;
@@ -304,6 +305,11 @@ Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c
                 "indices must be [ceil(M/128), F], counts [ceil(M/128)] ([B, ceil(M/128), F] and [B, ceil(M/128)] with the batch size of a)");
     TORCH_CHECK(s.B * G <= 65535, "B * ceil(M/128) groups must not exceed 65535 (got ", s.B * G, ")");
     return s;
+}
+
+Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c, const at::Tensor &bias, const at::Tensor &cache,
+                   const at::Tensor &indices, const at::Tensor &counts) {
+    return mm1_shape(a, b, c, &bias, cache, indices, counts);
 }
 
 // reference csrc/mlp/csp_mlp_mm1.cu:625-702
@@ -362,6 +368,51 @@ void csp_mlp_mm1_scatter(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::
                                                   pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
                                                   indices_counts.data_ptr<int>(), (int)M, (int)K, (int)F, (int)ldc, cur_stream(a)),
               "csp_mlp_mm1_scatter");
+}
+
+// addition: gated GEMM1 (SwiGLU / GEGLU), c = bf16(act(a b_gate^T + bias_gate) * (a b_up^T + bias_up) - cache); update_cache also applies
+// the scatter-add of c to the cache.  2-D operands or the 3-D batch, the cache checks of csp_mlp_mm1; bf16 only.
+void csp_mlp_mm1_glu(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor c, const c10::optional<at::Tensor> &bias_gate,
+                     const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache_colmajor, at::Tensor indices, at::Tensor indices_counts,
+                     std::string act, bool update_cache) {
+    CHECK_DEV(a); CHECK_DEV(b_gate); CHECK_DEV(b_up); CHECK_DEV(c); CHECK_DEV(pa_cache_colmajor);
+    CHECK_DEV(indices); CHECK_DEV(indices_counts);
+    CHECK_BF16(a); CHECK_BF16(b_gate); CHECK_BF16(b_up); CHECK_BF16(c); CHECK_BF16(pa_cache_colmajor);
+    CHECK_I32(indices); CHECK_I32(indices_counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(b_gate); CHECK_CONTIG(b_up); CHECK_CONTIG(c);
+    CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
+    const Mm1Shape sh = mm1_shape(a, b_gate, c, nullptr, pa_cache_colmajor, indices, indices_counts);
+    TORCH_CHECK(b_up.dim() == 2 && b_up.size(0) == sh.F && b_up.size(1) == sh.K, "b_up must have the shape of b_gate ([F, K])");
+    const void *bg = nullptr, *bu = nullptr;
+    if (bias_gate.has_value()) {
+        const at::Tensor &t = *bias_gate;
+        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
+        TORCH_CHECK(t.numel() == sh.F, "bias_gate must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
+        bg = t.data_ptr();
+    }
+    if (bias_up.has_value()) {
+        const at::Tensor &t = *bias_up;
+        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
+        TORCH_CHECK(t.numel() == sh.F, "bias_up must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
+        bu = t.data_ptr();
+    }
+    int code = -1;
+    if (act == "gelu_tanh") code = CHIPMUNK_ACT_GELU_TANH;
+    else if (act == "silu") code = CHIPMUNK_ACT_SILU;
+    else if (act == "gelu") code = CHIPMUNK_ACT_GELU_ERF;
+    TORCH_CHECK(code >= 0, "csp_mlp_mm1_glu: unknown activation '", act, "' (one of gelu_tanh, silu, gelu)");
+    c10::DeviceGuard guard(a.device());
+    if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_glu_batched(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
+                                               pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
+                                               (int)sh.M, (int)sh.K, (int)sh.F, (int)sh.ldc, code, update_cache ? 1 : 0, (int)sh.B,
+                                               sh.cache_bs, cur_stream(a)),
+              "csp_mlp_mm1_glu");
+    else
+        check(chipmunk_csp_mlp_mm1_glu(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
+                                       pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
+                                       (int)sh.M, (int)sh.K, (int)sh.F, (int)sh.ldc, code, update_cache ? 1 : 0, cur_stream(a)),
+              "csp_mlp_mm1_glu");
 }
 
 // native counterpart of the reference's Triton csp_mlp_mm1_fp8 (src/chipmunk/triton/csp_mlp_mm1.py:143-164)
@@ -997,6 +1048,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm2(Tensor mma_a, Tensor mma_b, Tensor indices, Tensor counts, Tensor(mma_c!) mma_c) -> ()");
     m.def("csp_mlp_mm1_fp8(Tensor a, Tensor b, Tensor(c!) c, Tensor bias, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_fp8_scatter(Tensor a, Tensor b, Tensor(c!) c, Tensor bias, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b) -> ()");
+    m.def("csp_mlp_mm1_glu(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, str act, bool update_cache) -> ()");
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
     m.def("packed_mask_to_indices(Tensor packed, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
     m.def("mask_to_sorted_indices(Tensor mask, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
@@ -1044,6 +1096,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_scatter", &csp_mlp_mm1_scatter);
     m.impl("csp_mlp_mm2", &csp_mlp_mm2);
     m.impl("csp_mlp_mm1_fp8", &csp_mlp_mm1_fp8);
+    m.impl("csp_mlp_mm1_glu", &csp_mlp_mm1_glu);
     m.impl("topk_delta_indices", &topk_delta_indices);
     m.impl("packed_mask_to_indices", &packed_mask_to_indices);
     m.impl("mask_to_sorted_indices", &mask_to_sorted_indices);

@@ -1,0 +1,201 @@
+"""Sparse-delta state machine for gated feed-forwards, ``fc2(act(gate_proj(x)) * up_proj(x))`` (SwiGLU / GEGLU; no reference counterpart:
+the reference's ``SparseDiffMlp`` knows ``fc2(act(fc1(x)))`` only).
+
+The method carries over unchanged: a hidden column ``j`` is recomputed or kept as a whole, its activation-cache entry is the gated product,
+and GEMM2 and the scatter-add see the same packed deltas as in ``SparseDiffMlp``.  Only GEMM1 differs (``csp_mlp_mm1_glu``: two gathered
+weight rows per kept column) and the movement of a column is the movement of its two inputs: the block means of BOTH pre-activations are
+cached as one ``[B, 2 Gm, F]`` tensor (rows ``2i`` / ``2i + 1`` = gate / up means of block ``i``) and the score of a column in a group is
+the sum of ``|delta block mean|`` over the group's rows of that tensor -- the ``r > 1`` branch of ``SparseDiffMlp`` with ``r = 2 bm / mbm``.
+State, storage (``MlpStorage``), schedule and offload handling are those of ``SparseDiffMlp``.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from .. import ops
+from ..util.config import GLOBAL_CONFIG
+from ..util.layer_counter import LayerCounter
+from ..util.storage import MlpStorage
+from .mlp import _ceil8, _transposed, _transposed_pitched, block_mean
+
+
+def activation_code(activation: torch.nn.Module) -> str:
+    """The GEMM1 kernel's name for an activation module; anything the kernel does not compute raises."""
+    if isinstance(activation, torch.nn.SiLU):
+        return "silu"
+    if isinstance(activation, torch.nn.GELU) and activation.approximate in ("tanh", "none"):
+        return "gelu_tanh" if activation.approximate == "tanh" else "gelu"
+    raise ValueError(f"SparseDiffGatedMlp: unsupported activation {activation!r}: the gated GEMM1 computes nn.SiLU(), "
+                     "nn.GELU(approximate='tanh') and nn.GELU() only")
+
+
+def _params(lin: torch.nn.Linear, rows: Optional[slice] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(weight, bias | None) of a Linear as it is NOW (``model.to(...)`` rebinds ``param.data``), optionally a slice of its output rows"""
+    w, b = lin.weight.data, None if lin.bias is None else lin.bias.data
+    return (w, b) if rows is None else (w[rows], None if b is None else b[rows])
+
+
+class SparseDiffGatedMlp:
+    """``gate_proj`` / ``up_proj`` / ``fc2``: ``nn.Linear`` with or without bias, bf16 for the sparse steps (there is no fp8 gated GEMM1).
+    Their parameters are read at every call, so the model may be moved or cast after wrapping.  The sparse steps select columns with
+    ``topk_indices``, which takes rows of 1024 columns or more: the hidden width ``F`` must be at least 1024."""
+
+    def __init__(self, layer_num: int, layer_counter: LayerCounter, gate_proj: torch.nn.Linear, up_proj: torch.nn.Linear,
+                 activation: torch.nn.Module, fc2: torch.nn.Linear, heuristic_sms_scatter_add: int = 6):
+        self._init(layer_num, layer_counter, [gate_proj, up_proj], None, activation, fc2, heuristic_sms_scatter_add)
+
+    @classmethod
+    def from_fused(cls, layer_num: int, layer_counter: LayerCounter, fc1: torch.nn.Linear, activation: torch.nn.Module,
+                   fc2: torch.nn.Linear, gate_first: bool = True, heuristic_sms_scatter_add: int = 6) -> "SparseDiffGatedMlp":
+        """One ``[2F, K]`` projection whose output is split in two halves: ``gate_first`` says which half is the gate.  The halves are
+        used as views of ``fc1``'s parameters, nothing is copied."""
+        f2 = fc1.weight.shape[0]
+        if f2 % 2:
+            raise ValueError(f"SparseDiffGatedMlp.from_fused: fc1 has {f2} output features, not two halves")
+        self = cls.__new__(cls)
+        self._init(layer_num, layer_counter, [fc1], gate_first, activation, fc2, heuristic_sms_scatter_add)
+        return self
+
+    def _init(self, layer_num, layer_counter, projs, gate_first, activation, fc2, heuristic_sms_scatter_add):
+        self.act_code = activation_code(activation)      # raises for an activation the sparse steps could not honour
+        self.projs = projs              # (lists keep the Linear modules out of any parent nn.Module's parameter registry)
+        self.gate_first = gate_first    # None: two projections; True / False: the halves of projs[0], and which of them is the gate
+        gate, up = self.gate, self.up
+        if gate[0].shape != up[0].shape or gate[0].ndim != 2:
+            raise ValueError(f"SparseDiffGatedMlp: gate and up projections must have one shape [F, K] (got {tuple(gate[0].shape)} and "
+                             f"{tuple(up[0].shape)})")
+        if fc2.weight.shape[1] != gate[0].shape[0]:
+            raise ValueError(f"SparseDiffGatedMlp: fc2 takes {fc2.weight.shape[1]} features, the projections give {gate[0].shape[0]}")
+        if torch.float8_e4m3fn in (gate[0].dtype, up[0].dtype):
+            raise ValueError("SparseDiffGatedMlp: there is no fp8 gated GEMM1; keep the gate / up projections in bf16")
+        self.fc2 = [fc2]
+        self._fc2w_T = None             # ((address, dtype, device) of the fc2.weight it was made from, its transpose)
+        self.layer_counter = layer_counter
+        self.activation = activation
+        self.storage = MlpStorage(layer_num)
+        self.num_sms_scatter_add = heuristic_sms_scatter_add
+
+    def _half(self, which: int) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """which = 0: the gate projection's (weight, bias), 1: the up projection's"""
+        if self.gate_first is None:
+            return _params(self.projs[which])
+        f = self.projs[0].weight.shape[0] // 2
+        first = which == (0 if self.gate_first else 1)
+        return _params(self.projs[0], slice(0, f) if first else slice(f, 2 * f))
+
+    @property
+    def gate(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        return self._half(0)
+
+    @property
+    def up(self) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        return self._half(1)
+
+    @property
+    def fc2w_T(self) -> torch.Tensor:
+        """fc2.weight^T, contiguous ``[F, C]``: made once per weight tensor (again after the module was moved or cast)"""
+        w = self.fc2[0].weight.data
+        key = (w.data_ptr(), w.dtype, w.device)
+        if self._fc2w_T is None or self._fc2w_T[0] != key:
+            self._fc2w_T = (key, w.transpose(0, 1).contiguous())
+        return self._fc2w_T[1]
+
+    def _pre(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        return torch.nn.functional.linear(x, *self.gate), torch.nn.functional.linear(x, *self.up)
+
+    def _dense(self, x: torch.Tensor) -> torch.Tensor:
+        g, u = self._pre(x)
+        return self.fc2[0](self.activation(g) * u)
+
+    @staticmethod
+    def _paired_block_means(g: torch.Tensor, u: torch.Tensor, rows: int) -> torch.Tensor:
+        """[B, Gm, F] gate and up block means -> [B, 2 * rows, F], rows 2i / 2i + 1 = gate / up of block i (zero rows behind the Gm blocks
+        present, so that every 128-row group owns the same number of rows)."""
+        pair = torch.stack([g, u], dim=2)
+        if pair.shape[1] < rows:
+            pair = torch.nn.functional.pad(pair, (0, 0, 0, 0, 0, rows - pair.shape[1]))
+        return pair.reshape(pair.shape[0], 2 * rows, pair.shape[-1]).contiguous()
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        cfg = GLOBAL_CONFIG["mlp"]
+        if not cfg["is_enabled"]:
+            return self._dense(x)
+
+        do_full = self.layer_counter.should_do_full_mlp_step()
+        inference_step, layer, _submodule = self.layer_counter.increment()
+        assert x.ndim == 3 and x.shape[0] >= 1, "x must be (B, N, C)"
+        mbm, bm = cfg["mbm"], cfg["bm"]
+        assert bm % mbm == 0, "mlp.bm must be a multiple of mlp.mbm"
+
+        if layer < cfg["first_n_dense_layers"]:
+            return self._dense(x)
+
+        n = x.shape[1]
+        r = bm // mbm                              # block means per 128-row group and branch
+        bm_rows = (n + bm - 1) // bm * r           # ... over all groups (a ragged last group has zero rows for the blocks it lacks)
+        if do_full:
+            g, u = self._pre(x)
+            act = self.activation(g) * u
+            out = self.fc2[0](act)
+            # the module owns the activation cache: [B, F, ld] with ld = ceil8(N) and zeroed padding (see SparseDiffMlp)
+            self.storage.set_sparse_act_T(_transposed(act) if n % 8 == 0 else _transposed_pitched(act, _ceil8(n)))
+            self.storage.set_out_cache(out)
+            self.storage.set_blockmean_mid_cache(self._paired_block_means(block_mean(g, mbm), block_mean(u, mbm), bm_rows))
+            return out
+
+        stored = self.storage.get_out_cache()
+        if stored is None or stored.shape[0] != x.shape[0] or stored.shape[1] != x.shape[1]:
+            raise RuntimeError(
+                f"SparseDiffGatedMlp: a sparse step got x of shape {tuple(x.shape)} but the state of the last full step is for "
+                f"{'no input at all' if stored is None else f'batch size {stored.shape[0]} with {stored.shape[1]} tokens'}: the batch size "
+                "and token count may only change on a full step")
+
+        reuse_mask = (inference_step % cfg["block_mask_cache"] != 0 and inference_step >= 10
+                      and self.storage.get_indices() is not None)
+        if not reuse_mask:
+            bmx = block_mean(x, mbm)
+            bmpre = self._paired_block_means(*self._pre(bmx), bm_rows)
+            cache = self.storage.get_blockmean_mid_cache()
+            # a column's movement is the movement of its two inputs: |delta| summed over the group's 2 r rows (gate and up means)
+            mdiff = (bmpre - cache).abs()
+            b, _rows, f = mdiff.shape
+            mdiff = mdiff.reshape(b, -1, 2 * r, f).sum(dim=2)
+            inds = torch.empty_like(mdiff, dtype=torch.int32, device=x.device)
+            counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=x.device)
+            ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"], cfg["random_keys"])
+            ops.copy_indices(bmpre, cache, inds, counts)     # rows [2 r g, 2 r (g + 1)) take group g's list
+            # the selected columns of the block means were refreshed in the LOADED tensor; a host copy has to follow
+            holder = self.storage.blockmean_mid_cache
+            if holder is not None and not holder.is_resident():
+                holder.offload_cur_value()
+            self.storage.set_indices(inds)
+            self.storage.set_counts(counts)
+        else:
+            inds, counts = self.storage.get_indices(), self.storage.get_counts()
+
+        batched = x.shape[0] > 1     # B == 1 passes 2-D operands
+        indices = inds if batched else inds[0]
+        counts = counts if batched else counts[0]
+        out_cache = stored if batched else stored[0]
+        sparse_act_T = self.storage.get_sparse_act_T()
+        sparse_act_T = sparse_act_T[..., :n] if batched else sparse_act_T[0][:, :n]   # the [F, N] view of the pitched cache
+
+        gate, up = self.gate, self.up
+        ops.mlp_glu(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], b_gate=gate[1], b_up=up[1],
+                    act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
+                    cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add)
+
+        # the operators updated the LOADED activation cache in place: its host copy has to follow (see SparseDiffMlp)
+        holder = self.storage.sparse_act_T
+        if holder is not None and not holder.is_resident():
+            holder.offload_cur_value()
+
+        if not batched:
+            out_cache = out_cache.unsqueeze(0)
+        self.storage.set_out_cache(out_cache)
+        return out_cache
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)

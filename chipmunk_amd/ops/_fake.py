@@ -114,5 +114,13 @@ def _register():
         out = x.new_empty((parts, x.shape[0] if x.dim() == 3 else 1, heads, x.shape[-2], 128))
         return [out[p] for p in range(parts)]
 
+    @lib.register_fake("chipmunk::csp_mlp_mm1_glu")
+    def _(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache_colmajor, indices, indices_counts, act, update_cache):
+        # writes c (and the cache) in place and returns nothing: the shapes are checked, so that a trace fails where the operator would
+        torch._check(a.shape[-1] == b_gate.shape[1] and b_gate.shape == b_up.shape, lambda: "a, b_gate and b_up must share K; b_up the shape of b_gate")
+        torch._check(c.shape == a.shape[:-1] + (b_gate.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_glu: unknown activation '{act}'")
+        return None
+
 
 _register()

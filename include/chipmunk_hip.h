@@ -233,6 +233,26 @@ int chipmunk_csp_scatter_add_batched(const void *packed, void *unpacked_colmajor
                                      const int32_t *counts, int M, int F, int ldc, int B, int64_t cache_batch_stride,
                                      void *stream);
 
+/* Gated GEMM1 (SwiGLU / GEGLU feed-forwards, fc2(act(x Wg + bg) * (x Wu + bu)); no reference counterpart).  For group g and packed
+ * column j < counts[g], with i = idx[g,j]:
+ *   c[m,j] = bf16( act(a[m,:].b_gate[i,:] + bias_gate[i]) * (a[m,:].b_up[i,:] + bias_up[i]) - pa_cache[i, m] )
+ * in fp32 with one rounding.  b_gate and b_up are [F,K] bf16 with row stride K: two weights, or the two halves of one fused [2F,K]
+ * projection in either order.  bias_gate / bias_up are bf16 [F] or NULL (= zero).  act is one of the CHIPMUNK_ACT_* codes below.
+ * update_cache = 1 also applies pa_cache[i, m] = bf16(pa_cache[i, m] + c[m,j]), the arithmetic of chipmunk_csp_scatter_add on c;
+ * 0 leaves the cache as it is.  Contract of the *_ragged entries (any M >= 1, ldc >= M, ldc % 8 == 0, K % 64 == 0, F % 64 == 0) and,
+ * for *_batched, of the batch entries above (weights and biases shared by all sequences).  bf16 only: there is no fp8 gated form.
+ * A failed check returns CHIPMUNK_ERR_INVALID with a message, before anything is enqueued. */
+#define CHIPMUNK_ACT_GELU_TANH 0 /* x * 0.5 * (1 + tanh(0.79788456 (x + 0.044715 x^3))): the code of chipmunk_csp_mlp_mm1 */
+#define CHIPMUNK_ACT_SILU 1      /* x / (1 + exp(-x)) */
+#define CHIPMUNK_ACT_GELU_ERF 2  /* 0.5 x (1 + erf(x / sqrt 2)) */
+int chipmunk_csp_mlp_mm1_glu(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                             const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K,
+                             int F, int ldc, int act, int update_cache, void *stream);
+int chipmunk_csp_mlp_mm1_glu_batched(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                     const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M,
+                                     int K, int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                     void *stream);
+
 /* ---------------------------------------------------------------- indexed IO
  * Replaces chipmunk::topk_indices (reference csrc/indexed_io/topk_indices.cu:145-218; schema chipmunk.cpp:58).
  * activation [B*R, C] of `dtype`; indices [B*R, C] int32; counts [B*R] int32.  Threshold = element

@@ -79,6 +79,9 @@ def main(argv):
             same = ko[k][0] == kt[k][0]
             bad += not same
             print(f"{'IDENTICAL' if same else 'DIFFERENT'}  {k}: {len(ko[k][0])} / {len(kt[k][0])} lines; other {ko[k][1]}; this {kt[k][1]}")
+            if not same and len(ko[k][0]) == len(kt[k][0]):     # same length: show what moved (e.g. kernel-argument offsets of a grown struct)
+                for a, b in [(a, b) for a, b in zip(ko[k][0], kt[k][0]) if a != b][:8]:
+                    print(f"           - {a}\n           + {b}")
         else:
             side, v = ("other only", ko[k]) if k in ko else ("this only", kt[k])
             print(f"{side:10} {k}: {len(v[0])} lines; {v[1]}")
