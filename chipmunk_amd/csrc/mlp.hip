@@ -177,12 +177,18 @@ struct Mm1Params {
     int M, K, F, NT, NR, probe, slots_per_xcd;
     int update_cache;  // 1: also apply the scatter-add of this tile's deltas to the cache block it already holds in LDS;
                        // 2 (fp8): store the new activation into the cache like the reference's Triton kernel
-    // fp8 only: reciprocal quantisation scales (one float each).  The gated form (GLU; bf16 only, so it has no scales) keeps the up
+    // fp8 only: reciprocal quantisation scales (one float each).  The gated form (GLU; its bf16 form has no scales, its fp8 form its own block below) keeps the up
     // projection's weight and bias in the same two slots -- b / bias are then the gate projection's, either bias may be null (= zero):
     // the parameter block keeps its size, and with it every kernel-argument offset of the ungated instantiations
     union { const float *scale_a; const uint16_t *b_up; };
     union { const float *scale_b; const uint16_t *bias_up; };
     int ldc;           // pitch of the column-major cache in elements: ldc >= M, ldc % 8 == 0 (M itself for the [F, M] contiguous cache)
+};
+// The gated fp8 form needs both at once -- the up projection's weight / bias AND scales -- so it has a parameter block of its own behind the
+// shared one (which keeps its size): b / bias / b_up / bias_up as in the gated bf16 form (weights e4m3 bytes), then the three reciprocal
+// quantisation scales, one float each.  mm1_tile takes its parameter block as a template type and reads these only in its FP8 && GLU form.
+struct Mm1GluF8Params : Mm1Params {
+    const float *scale_x, *scale_gate, *scale_up;
 };
 
 // One TM x TN output tile (TM rows of group g starting at m_off, packed columns n0 .. n0+TN-1): 4 waves as 2 x 2, each a
@@ -202,8 +208,10 @@ struct Mm1Params {
 // the same 32 columns, so a lane holds acc[mt][0][r] (gate) and acc[mt][1][r] (up) of one (row, column) and the epilogue combines them
 // without cross-lane traffic, on today's accumulator budget.  One DMA instruction covers KTile::RPI consecutive tile rows, so the half
 // (and with it the weight the rows are gathered from) is uniform per instruction.  Cache block and output image are TN/2 columns wide.
-template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0>
-__device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
+// FP8 && GLU (P = Mm1GluF8Params): the k loop of the fp8 form (e4m3 fragments, 32x32x64 MFMA, accumulators from zero) under the B-row gather
+// and the epilogue of the gated form; each branch's sum is scaled by scale_x and its own weight scale, then biased, in the fp8 form's order.
+template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params>
+__device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
     using KT = KTile<BK>;
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
     constexpr int A_TILE = TM * BK * 2, B_TILE = TN * BK * 2, STAGE = A_TILE + B_TILE;
@@ -213,7 +221,8 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     static_assert(A_INST >= 1 && B_INST >= 1, "tile too small for one DMA instruction per wave");
     constexpr int PW = GLU ? TN / 2 : TN;                           // packed columns of the tile
     constexpr int NP4 = GLU ? 1 : NT4;                              // 32-wide tiles of packed columns per wave
-    static_assert(!GLU || (!FP8 && NW == 4 && NT4 == 2 && 32 % KT::RPI == 0), "the gated form: bf16, 4 waves, a 64-row B slab per wave");
+    static_assert(!GLU || (NW == 4 && NT4 == 2 && 32 % KT::RPI == 0), "the gated form: 4 waves, a 64-row B slab per wave");
+    static_assert(!(FP8 && GLU) || std::is_base_of<Mm1GluF8Params, P>::value, "the gated fp8 form reads its scales from Mm1GluF8Params");
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = w / WNC, wn = w % WNC;
@@ -293,7 +302,9 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
     // then bias) fly during the prologue instead of in front of the epilogue.  fp8 scales the sum first, so it starts from zero.
     constexpr bool SEED_BIAS = !FP8;
     float bias_v[NT4], sa = 1.f, sb = 1.f;   // loaded here for both forms: in front of the epilogue the round trips would be exposed
-    if constexpr (FP8) sa = p.scale_a[0], sb = p.scale_b[0];
+    float sb_up = 1.f;                       // (gated fp8 form: sb is the gate weight's scale, sb_up the up weight's)
+    if constexpr (FP8 && GLU) sa = p.scale_x[0], sb = p.scale_gate[0], sb_up = p.scale_up[0];
+    else if constexpr (FP8) sa = p.scale_a[0], sb = p.scale_b[0];
     f32x16 acc[MT][NT4];
 #pragma unroll
     for (int n4 = 0; n4 < NT4; ++n4) {
@@ -442,7 +453,14 @@ __device__ __forceinline__ void mm1_tile(const Mm1Params &p, unsigned char *smem
                         const f32x2 c01 = unpack_bf16x2(c[0]), c23 = unpack_bf16x2(c[1]);
                         f32x2 a01 = {acc[mt][n4][q4 * 4 + 0], acc[mt][n4][q4 * 4 + 1]}, a23 = {acc[mt][n4][q4 * 4 + 2], acc[mt][n4][q4 * 4 + 3]};
                         uint32_t d01, d23, n01 = 0, n23 = 0;   // packed deltas as stored (bf16 pairs); the cache block's new values
-                        if constexpr (FP8) {
+                        if constexpr (FP8 && GLU) {
+                            // each branch as the fp8 form makes its pre-activation, (acc * scale_a) * scale_b + bias, then the gated form's
+                            // one rounding: fma(act(gate), up, -cache); a01 / a23 are the gate's sums, bias_v[1] the up projection's bias
+                            const f32x2 u01 = {acc[mt][1][q4 * 4 + 0], acc[mt][1][q4 * 4 + 1]}, u23 = {acc[mt][1][q4 * 4 + 2], acc[mt][1][q4 * 4 + 3]};
+                            const f32x2 sav = {sa, sa}, sgv = {sb, sb}, suv = {sb_up, sb_up}, bgv = {bia, bia}, buv = {bias_v[1], bias_v[1]};
+                            d01 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>((a01 * sav) * sgv + bgv), (u01 * sav) * suv + buv, -c01));
+                            d23 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>((a23 * sav) * sgv + bgv), (u23 * sav) * suv + buv, -c23));
+                        } else if constexpr (FP8) {
                             // (acc * scale_a) * scale_b + bias in the reference's order -> gelu -> bf16, then a bf16 subtract (csp_mlp_mm1.py:121-133)
                             const f32x2 sav = {sa, sa}, sbv = {sb, sb}, bv = {bia, bia};
                             const uint32_t t01 = pack_bf16x2_v(gelu_tanh2((a01 * sav) * sbv + bv));
@@ -648,6 +666,42 @@ __global__ __launch_bounds__(256, WPS) void mm1_glu_kernel(const typename std::c
             mm1_tile<BM, BN, BK, NST, false, 4, true, ACT>(q, smem, g, 0, n0, cnt);
         } else {
             mm1_tile<BM, BN, BK, NST, false, 4, true, ACT>(p, smem, tm.g, 0, n0, cnt);
+        }
+        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
+    }
+}
+
+// The gated fp8 GEMM1 (mm1_tile's FP8 && GLU form): mm1_glu_kernel's walk with a parameter block and a name of its own -- the operands of
+// a and the weights are e4m3 bytes, so a sequence of a batch starts M * K bytes behind the one before.
+struct Mm1GluF8Batch : Mm1GluF8Params {
+    int B;
+    int64_t cache_bs;   // as Mm1Batch
+};
+template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED = false>
+__global__ __launch_bounds__(256, WPS) void mm1_glu_fp8_kernel(const typename std::conditional<BATCHED, Mm1GluF8Batch, Mm1GluF8Params>::type p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int PBN = BN / 2;           // packed columns of a tile: its BN B-tile rows are {gate, up} pairs
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
+    const TilePlan pl = plan_tiles<PBN>(p.counts, G, p.NT, p.NR, 0, 1);
+    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+        const TileMap tm = tile_at(pl, slot);
+        if (!tm.live) continue;
+        const int cnt = p.counts[tm.g];
+        const int n0 = tm.nt * PBN;
+        if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
+        if constexpr (BATCHED) {
+            const int b = tm.g / Gs, g = tm.g - b * Gs;   // sequence, group inside it
+            Mm1GluF8Params q = p;                         // the tile sees its sequence's operands
+            q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)b * p.M * p.K);
+            q.c = p.c + (int64_t)b * p.M * p.F;
+            q.cache = p.cache + (int64_t)b * p.cache_bs;
+            q.indices = p.indices + (int64_t)b * Gs * p.F;
+            mm1_tile<BM, BN, BK, NST, true, 4, true, ACT>(q, smem, g, 0, n0, cnt);
+        } else {
+            mm1_tile<BM, BN, BK, NST, true, 4, true, ACT>(p, smem, tm.g, 0, n0, cnt);
         }
         __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
     }
@@ -1166,20 +1220,26 @@ int launch_mm2(const void *a, const void *b, void *c, const int32_t *indices, co
     return launch_mm2_variant<256, 32, 3, 2, 8>(p, s);
 }
 
-template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false, bool GLU = false, int ACT = 0>
-int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated = nullptr, int B = 1, int64_t cache_bs = 0) {
+// (parameter block -> its batched form)
+template <class P> struct Mm1BatchOf { using type = Mm1Batch; };
+template <> struct Mm1BatchOf<Mm1GluF8Params> { using type = Mm1GluF8Batch; };
+
+template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false, bool GLU = false, int ACT = 0, class P = Mm1Params>
+int launch_mm1_variant(const P &p0, hipStream_t s, bool *cache_updated = nullptr, int B = 1, int64_t cache_bs = 0) {
     constexpr int PBN = GLU ? BN / 2 : BN;   // packed columns per whole tile (gated form: the B tile's rows are {gate, up} pairs)
     constexpr int STAGE = BM * BK * 2 + BN * BK * 2, LDS = NST * STAGE, EPI = BM * PBN * 2;
     // mm1_tile's staged epilogue (the one that can scatter): one stage each for cache block and outputs, or the FLAT layout
     constexpr bool STAGED = EPI <= STAGE || (NW == 8 && EPI <= (NST - 1) * STAGE && 2 * EPI <= NST * STAGE && STAGE % (BN * 2) == 0);
     auto kern = [] {
-        if constexpr (GLU) return mm1_glu_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+        if constexpr (GLU && FP8) return mm1_glu_fp8_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+        else if constexpr (GLU) return mm1_glu_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
         else return mm1_kernel<BN, BK, NST, WPS, FP8, NW, BATCHED>;
     }();
-    static_assert(!GLU || (!FP8 && NW == 4), "the gated GEMM1 is bf16 with 4 waves");
+    static_assert(!GLU || NW == 4, "the gated GEMM1 has 4 waves");
+    static_assert(std::is_same<P, Mm1GluF8Params>::value == (GLU && FP8), "the gated fp8 form, and only it, takes Mm1GluF8Params");
     static uint64_t lds_set = 0;
     ensure_dynamic_lds((const void *)kern, LDS, lds_set);
-    Mm1Params p = p0;
+    P p = p0;
     if (!STAGED) p.update_cache = 0;
     if (cache_updated) *cache_updated = p.update_cache != 0;
     p.NT = (p.F + PBN - 1) / PBN;
@@ -1196,8 +1256,8 @@ int launch_mm1_variant(const Mm1Params &p0, hipStream_t s, bool *cache_updated =
     const int tiles_per_xcd = (B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8;
     const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
     if constexpr (BATCHED) {
-        Mm1Batch q;
-        static_cast<Mm1Params &>(q) = p;
+        typename Mm1BatchOf<P>::type q;
+        static_cast<P &>(q) = p;
         q.B = B, q.cache_bs = cache_bs;
         hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(NW * 64), LDS, s, q);
     } else {
@@ -1292,7 +1352,7 @@ int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void 
     return launch_mm1_variant<128, 64, 2, 2, true>(p, stream);
 }
 
-// Gated GEMM1 (SwiGLU / GEGLU): the *_ragged / *_batched contract, bf16 only, the shipped tile shape only
+// Gated GEMM1 (SwiGLU / GEGLU): the *_ragged / *_batched contract, bf16 (the e4m3 form is mm1_glu_fp8_entry below), the shipped tile shape only
 template <bool BATCHED>
 int launch_mm1_glu(const Mm1Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
     switch (act) {
@@ -1321,7 +1381,57 @@ int mm1_glu_entry(const void *a, const void *b_gate, const void *b_up, void *c, 
     p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
     return B > 0 ? launch_mm1_glu<true>(p, act, stream, B, cache_bs) : launch_mm1_glu<false>(p, act, stream, 1, 0);
 }
+
+// Gated fp8 GEMM1: the contract of mm1_glu_entry with e4m3 a / weights (1 byte per element), K % 128 as csp_mlp_mm1_fp8, and the three
+// reciprocal quantisation scales; the shipped tile shape only (option mm1_variant is ignored)
+template <bool BATCHED>
+int launch_mm1_glu_fp8(const Mm1GluF8Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
+    switch (act) {
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, true, 4, BATCHED, true, 0>(p, stream, nullptr, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, true, 4, BATCHED, true, 1>(p, stream, nullptr, B, cache_bs);
+        default: return launch_mm1_variant<128, 64, 2, 2, true, 4, BATCHED, true, 2>(p, stream, nullptr, B, cache_bs);
+    }
+}
+int mm1_glu_fp8_entry(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
+                      const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b_gate, const float *scale_b_up,
+                      int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream, int B = 0, int64_t cache_bs = 0) {
+    CM_CHECK(a && b_gate && b_up && c && pa_cache && scale_a && scale_b_gate && scale_b_up, "csp_mlp_mm1_glu_fp8: null tensor or scale pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
+    if (B > 0) {
+        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
+    }
+    CM_CHECK(act == CHIPMUNK_ACT_GELU_TANH || act == CHIPMUNK_ACT_SILU || act == CHIPMUNK_ACT_GELU_ERF,
+             "csp_mlp_mm1_glu_fp8: unknown activation %d (0 = gelu_tanh, 1 = silu, 2 = gelu)", act);
+    CM_CHECK(update_cache == 0 || update_cache == 1, "csp_mlp_mm1_glu_fp8: update_cache must be 0 or 1 (got %d)", update_cache);
+    CM_CHECK(K > 0 && K % 128 == 0, "csp_mlp_mm1_glu_fp8: K must be a positive multiple of 128 (got %d)", K);
+    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
+             "csp_mlp_mm1_glu_fp8: operand too large for 32-bit offsets");
+    Mm1GluF8Params p;
+    static_cast<Mm1Params &>(p) = {(const uint16_t *)a, (const uint16_t *)b_gate, (const uint16_t *)bias_gate, (uint16_t *)pa_cache,
+                                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
+    p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
+    p.scale_x = scale_a, p.scale_gate = scale_b_gate, p.scale_up = scale_b_up;
+    return B > 0 ? launch_mm1_glu_fp8<true>(p, act, stream, B, cache_bs) : launch_mm1_glu_fp8<false>(p, act, stream, 1, 0);
+}
 }  // namespace
+
+extern "C" int chipmunk_csp_mlp_mm1_glu_fp8(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                            const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts,
+                                            const float *scale_a, const float *scale_b_gate, const float *scale_b_up, int M, int K, int F,
+                                            int ldc, int act, int update_cache, void *stream) {
+    return mm1_glu_fp8_entry(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache, indices, counts, scale_a, scale_b_gate, scale_b_up, M, K, F, ldc,
+                             act, update_cache, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_glu_fp8_batched(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                                    const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts,
+                                                    const float *scale_a, const float *scale_b_gate, const float *scale_b_up, int M, int K,
+                                                    int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                                    void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_glu_fp8_entry(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache, indices, counts, scale_a, scale_b_gate, scale_b_up, M, K, F, ldc,
+                             act, update_cache, (hipStream_t)stream, B, cache_batch_stride);
+}
 
 extern "C" int chipmunk_csp_mlp_mm1_glu(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
                                         const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K,

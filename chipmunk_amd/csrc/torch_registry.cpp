@@ -415,6 +415,58 @@ void csp_mlp_mm1_glu(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tenso
               "csp_mlp_mm1_glu");
 }
 
+// addition: the gated GEMM1 over fp8 projections -- a, b_gate, b_up float8_e4m3fn, the three reciprocal quantisation scales as
+// one-element float32 device tensors; everything else as csp_mlp_mm1_glu (which keeps refusing fp8 operands)
+void csp_mlp_mm1_glu_fp8(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor c, const c10::optional<at::Tensor> &bias_gate,
+                         const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache_colmajor, at::Tensor indices, at::Tensor indices_counts,
+                         at::Tensor scale_a, at::Tensor scale_b_gate, at::Tensor scale_b_up, std::string act, bool update_cache) {
+    CHECK_DEV(a); CHECK_DEV(b_gate); CHECK_DEV(b_up); CHECK_DEV(c); CHECK_DEV(pa_cache_colmajor);
+    CHECK_DEV(indices); CHECK_DEV(indices_counts);
+    TORCH_CHECK(a.scalar_type() == at::kFloat8_e4m3fn && b_gate.scalar_type() == at::kFloat8_e4m3fn && b_up.scalar_type() == at::kFloat8_e4m3fn,
+                "csp_mlp_mm1_glu_fp8: a, b_gate and b_up must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+    CHECK_BF16(c); CHECK_BF16(pa_cache_colmajor);
+    CHECK_I32(indices); CHECK_I32(indices_counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(b_gate); CHECK_CONTIG(b_up); CHECK_CONTIG(c);
+    CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
+    for (const at::Tensor *s : {&scale_a, &scale_b_gate, &scale_b_up})
+        TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->numel() == 1,
+                    "csp_mlp_mm1_glu_fp8: scale_a, scale_b_gate and scale_b_up must be one-element float32 tensors on the GPU");
+    const Mm1Shape sh = mm1_shape(a, b_gate, c, nullptr, pa_cache_colmajor, indices, indices_counts);
+    TORCH_CHECK(b_up.dim() == 2 && b_up.size(0) == sh.F && b_up.size(1) == sh.K, "b_up must have the shape of b_gate ([F, K])");
+    const void *bg = nullptr, *bu = nullptr;
+    if (bias_gate.has_value()) {
+        const at::Tensor &t = *bias_gate;
+        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
+        TORCH_CHECK(t.numel() == sh.F, "bias_gate must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
+        bg = t.data_ptr();
+    }
+    if (bias_up.has_value()) {
+        const at::Tensor &t = *bias_up;
+        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
+        TORCH_CHECK(t.numel() == sh.F, "bias_up must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
+        bu = t.data_ptr();
+    }
+    int code = -1;
+    if (act == "gelu_tanh") code = CHIPMUNK_ACT_GELU_TANH;
+    else if (act == "silu") code = CHIPMUNK_ACT_SILU;
+    else if (act == "gelu") code = CHIPMUNK_ACT_GELU_ERF;
+    TORCH_CHECK(code >= 0, "csp_mlp_mm1_glu_fp8: unknown activation '", act, "' (one of gelu_tanh, silu, gelu)");
+    c10::DeviceGuard guard(a.device());
+    if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_glu_fp8_batched(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
+                                                   pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
+                                                   scale_a.data_ptr<float>(), scale_b_gate.data_ptr<float>(), scale_b_up.data_ptr<float>(),
+                                                   (int)sh.M, (int)sh.K, (int)sh.F, (int)sh.ldc, code, update_cache ? 1 : 0, (int)sh.B,
+                                                   sh.cache_bs, cur_stream(a)),
+              "csp_mlp_mm1_glu_fp8");
+    else
+        check(chipmunk_csp_mlp_mm1_glu_fp8(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
+                                           pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
+                                           scale_a.data_ptr<float>(), scale_b_gate.data_ptr<float>(), scale_b_up.data_ptr<float>(),
+                                           (int)sh.M, (int)sh.K, (int)sh.F, (int)sh.ldc, code, update_cache ? 1 : 0, cur_stream(a)),
+              "csp_mlp_mm1_glu_fp8");
+}
+
 // native counterpart of the reference's Triton csp_mlp_mm1_fp8 (src/chipmunk/triton/csp_mlp_mm1.py:143-164)
 static void mm1_fp8_impl(at::Tensor a, at::Tensor b, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
                          at::Tensor indices, at::Tensor indices_counts, at::Tensor scale_a, at::Tensor scale_b,
@@ -1049,6 +1101,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_fp8(Tensor a, Tensor b, Tensor(c!) c, Tensor bias, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_fp8_scatter(Tensor a, Tensor b, Tensor(c!) c, Tensor bias, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b) -> ()");
     m.def("csp_mlp_mm1_glu(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, str act, bool update_cache) -> ()");
+    m.def("csp_mlp_mm1_glu_fp8(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b_gate, Tensor scale_b_up, str act, bool update_cache) -> ()");
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
     m.def("packed_mask_to_indices(Tensor packed, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
     m.def("mask_to_sorted_indices(Tensor mask, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
@@ -1097,6 +1150,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm2", &csp_mlp_mm2);
     m.impl("csp_mlp_mm1_fp8", &csp_mlp_mm1_fp8);
     m.impl("csp_mlp_mm1_glu", &csp_mlp_mm1_glu);
+    m.impl("csp_mlp_mm1_glu_fp8", &csp_mlp_mm1_glu_fp8);
     m.impl("topk_delta_indices", &topk_delta_indices);
     m.impl("packed_mask_to_indices", &packed_mask_to_indices);
     m.impl("mask_to_sorted_indices", &mask_to_sorted_indices);

@@ -7,6 +7,12 @@ weight rows per kept column) and the movement of a column is the movement of its
 cached as one ``[B, 2 Gm, F]`` tensor (rows ``2i`` / ``2i + 1`` = gate / up means of block ``i``) and the score of a column in a group is
 the sum of ``|delta block mean|`` over the group's rows of that tensor -- the ``r > 1`` branch of ``SparseDiffMlp`` with ``r = 2 bm / mbm``.
 State, storage (``MlpStorage``), schedule and offload handling are those of ``SparseDiffMlp``.
+
+fp8 projections (``F8Linear``: two layers, or one fused ``[2F, K]`` layer) take ``csp_mlp_mm1_glu_fp8`` on the sparse steps: ``x`` is quantised
+ONCE, with the gate projection's (or the fused projection's) ``quantize_input``, and the kernel multiplies both sums by that layer's
+``input_scale_reciprocal`` and each by its own layer's ``scale_reciprocal``.  Dequantising with the gate's input scale is exact arithmetic for
+both products -- the e4m3 values ARE ``x * input_scale`` rounded, whichever weight they meet -- so the up layer's own input scale is used only
+by its dense forward (full steps, the block means of the selection), which is also what calibrates it.
 """
 from __future__ import annotations
 
@@ -19,6 +25,8 @@ from ..util.config import GLOBAL_CONFIG
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
 from .mlp import _ceil8, _transposed, _transposed_pitched, block_mean
+
+_F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
 
 def activation_code(activation: torch.nn.Module) -> str:
@@ -38,7 +46,9 @@ def _params(lin: torch.nn.Linear, rows: Optional[slice] = None) -> Tuple[torch.T
 
 
 class SparseDiffGatedMlp:
-    """``gate_proj`` / ``up_proj`` / ``fc2``: ``nn.Linear`` with or without bias, bf16 for the sparse steps (there is no fp8 gated GEMM1).
+    """``gate_proj`` / ``up_proj`` / ``fc2``: ``nn.Linear`` with or without bias, bf16 for the sparse steps; or ``gate_proj`` / ``up_proj``
+    (or the fused ``fc1``) BOTH ``F8Linear`` with e4m3 weights and e4m3 inputs (``input_float8_dtype=torch.float8_e4m3fn``;
+    ``F8Linear.from_linear`` defaults to e5m2, which the kernel does not read) and ``fc2`` bf16 (GEMM2 gathers bf16 rows).
     Their parameters are read at every call, so the model may be moved or cast after wrapping.  The sparse steps select columns with
     ``topk_indices``, which takes rows of 1024 columns or more: the hidden width ``F`` must be at least 1024."""
 
@@ -68,8 +78,18 @@ class SparseDiffGatedMlp:
                              f"{tuple(up[0].shape)})")
         if fc2.weight.shape[1] != gate[0].shape[0]:
             raise ValueError(f"SparseDiffGatedMlp: fc2 takes {fc2.weight.shape[1]} features, the projections give {gate[0].shape[0]}")
-        if torch.float8_e4m3fn in (gate[0].dtype, up[0].dtype):
-            raise ValueError("SparseDiffGatedMlp: there is no fp8 gated GEMM1; keep the gate / up projections in bf16")
+        f8 = [p.weight.dtype in _F8 for p in projs]
+        if any(f8) != all(f8):
+            raise ValueError("SparseDiffGatedMlp: a mixed pair -- one projection is fp8, the other is not; the gated GEMM1 takes both "
+                             "projections in bf16 or both as F8Linear")
+        self.fp8 = all(f8)
+        for p in projs if self.fp8 else ():
+            if p.weight.dtype != torch.float8_e4m3fn or getattr(p, "input_float8_dtype", None) != torch.float8_e4m3fn:
+                raise ValueError(f"SparseDiffGatedMlp: the gated fp8 GEMM1 reads float8_e4m3fn weights and inputs only (got weight "
+                                 f"{p.weight.dtype}, input_float8_dtype {getattr(p, 'input_float8_dtype', None)}); build the projection with "
+                                 "F8Linear.from_linear(..., input_float8_dtype=torch.float8_e4m3fn)")
+        if fc2.weight.dtype in _F8:
+            raise ValueError("SparseDiffGatedMlp: fc2 must stay bf16 (GEMM2 gathers bf16 rows of fc2.weight^T); an fp8 fc2 is refused")
         self.fc2 = [fc2]
         self._fc2w_T = None             # ((address, dtype, device) of the fc2.weight it was made from, its transpose)
         self.layer_counter = layer_counter
@@ -103,6 +123,11 @@ class SparseDiffGatedMlp:
         return self._fc2w_T[1]
 
     def _pre(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.fp8:   # the projections' own forward (torch._scaled_mm), which also feeds their input-scale calibration
+            if self.gate_first is None:
+                return self.projs[0](x), self.projs[1](x)
+            first, second = self.projs[0](x).chunk(2, dim=-1)   # one call of the fused projection, its output split
+            return (first, second) if self.gate_first else (second, first)
         return torch.nn.functional.linear(x, *self.gate), torch.nn.functional.linear(x, *self.up)
 
     def _dense(self, x: torch.Tensor) -> torch.Tensor:
@@ -183,9 +208,17 @@ class SparseDiffGatedMlp:
         sparse_act_T = sparse_act_T[..., :n] if batched else sparse_act_T[0][:, :n]   # the [F, N] view of the pitched cache
 
         gate, up = self.gate, self.up
-        ops.mlp_glu(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], b_gate=gate[1], b_up=up[1],
-                    act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
-                    cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add)
+        if self.fp8:
+            qgate, qup = self.projs[0], self.projs[-1]     # (the same layer twice for a fused projection)
+            xq = qgate.quantize_input(x)                   # once, with the gate's input scale: see the module docstring
+            ops.mlp_glu_fp8(x=xq if batched else xq[0], w_gate=gate[0], w_up=up[0], b_gate=gate[1], b_up=up[1],
+                            act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
+                            cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add,
+                            scale_a=qgate.input_scale_reciprocal, scale_b_gate=qgate.scale_reciprocal, scale_b_up=qup.scale_reciprocal)
+        else:
+            ops.mlp_glu(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], b_gate=gate[1], b_up=up[1],
+                        act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
+                        cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add)
 
         # the operators updated the LOADED activation cache in place: its host copy has to follow (see SparseDiffMlp)
         holder = self.storage.sparse_act_T

@@ -122,5 +122,19 @@ def _register():
         torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_glu: unknown activation '{act}'")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm1_glu_fp8")
+    def _(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache_colmajor, indices, indices_counts, scale_a, scale_b_gate, scale_b_up, act,
+          update_cache):
+        # as csp_mlp_mm1_glu, with e4m3 a / weights and three one-element float32 scales
+        f8 = torch.float8_e4m3fn
+        torch._check(a.dtype == f8 and b_gate.dtype == f8 and b_up.dtype == f8, lambda: "a, b_gate and b_up must be float8_e4m3fn")
+        torch._check(c.dtype == torch.bfloat16 and pa_cache_colmajor.dtype == torch.bfloat16, lambda: "c and pa_cache_colmajor must be bfloat16")
+        torch._check(a.shape[-1] == b_gate.shape[1] and b_gate.shape == b_up.shape, lambda: "a, b_gate and b_up must share K; b_up the shape of b_gate")
+        torch._check(c.shape == a.shape[:-1] + (b_gate.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        for s in (scale_a, scale_b_gate, scale_b_up):
+            torch._check(s.dtype == torch.float32 and s.numel() == 1, lambda: "scale_a, scale_b_gate and scale_b_up must be one-element float32 tensors")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_glu_fp8: unknown activation '{act}'")
+        return None
+
 
 _register()

@@ -150,7 +150,7 @@ def mm1_glu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sparse_ac
     """Gated GEMM1: ``packed = bf16(act(x Wg^T + bg) * (x Wu^T + bu) - cache)`` on the kept columns; ``update_cache`` also applies the
     scatter-add of the packed deltas to ``sparse_act_T`` (the bits of ``csp_scatter_add`` afterwards).  ``w_gate`` / ``w_up`` are
     ``[F, K]`` bf16 with contiguous rows K apart -- two weights or the halves of one fused ``[2F, K]`` projection; either bias may be
-    ``None``.  bf16 only: there is no fp8 gated form."""
+    ``None``.  bf16 only: e4m3 operands go to ``mm1_glu_fp8``."""
     if act not in GLU_ACTS:
         raise ValueError(f"mm1_glu: unknown activation {act!r} (one of {', '.join(GLU_ACTS)})")
     if x.dtype != torch.bfloat16 or w_gate.dtype != torch.bfloat16 or w_up.dtype != torch.bfloat16:
@@ -190,5 +190,54 @@ def run_e2e_glu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b_gat
         mm2_unfused(sparse_act_packed, fc2w_T, cached_out, sparse_act_T, indices, counts, num_sms_scatter_add)
 
 
+def mm1_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sparse_act_packed: torch.Tensor,
+                b_gate: Optional[torch.Tensor], b_up: Optional[torch.Tensor], act: str, sparse_act_T: torch.Tensor,
+                indices: torch.Tensor, counts: torch.Tensor, scale_a: torch.Tensor, scale_b_gate: torch.Tensor,
+                scale_b_up: torch.Tensor, update_cache: bool = False) -> None:
+    """``mm1_glu`` over fp8 projections: ``x``, ``w_gate`` and ``w_up`` are ``float8_e4m3fn`` (K a multiple of 128) and each branch's sum is
+    multiplied by ``scale_a`` and its own weight scale before its bias -- the RECIPROCAL quantisation scales, one float each, as
+    ``csp_mlp_mm1_fp8`` takes them.  Biases, packed deltas and the cache are bf16."""
+    if act not in GLU_ACTS:
+        raise ValueError(f"mm1_glu_fp8: unknown activation {act!r} (one of {', '.join(GLU_ACTS)})")
+    f8 = torch.float8_e4m3fn
+    if x.dtype != f8 or w_gate.dtype != f8 or w_up.dtype != f8:
+        raise ValueError(f"mm1_glu_fp8: float8_e4m3fn operands only (got x {x.dtype}, w_gate {w_gate.dtype}, w_up {w_up.dtype})")
+    assert sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
+    torch.ops.chipmunk.csp_mlp_mm1_glu_fp8(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, sparse_act_T, indices, counts,
+                                           scale_a.reshape(1).float(), scale_b_gate.reshape(1).float(), scale_b_up.reshape(1).float(),
+                                           act, bool(update_cache))
+
+
+@torch.compiler.disable
+def run_e2e_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b_gate: Optional[torch.Tensor],
+                    b_up: Optional[torch.Tensor], act: str, fc2w_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
+                    sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int, scale_a: torch.Tensor,
+                    scale_b_gate: torch.Tensor, scale_b_up: torch.Tensor) -> None:
+    """``run_e2e_glu`` with the gated fp8 GEMM1 (``x`` already quantised to e4m3): the packed deltas are bf16, so GEMM2 (bf16 ``fc2w_T``) and
+    the scatter-add are the operators of the bf16 route."""
+    assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
+    if x.ndim == 3:
+        B = x.shape[0]
+        assert indices.ndim == 3 and counts.ndim == 2 and sparse_act_T.ndim == 3 and cached_out.ndim == 3, \
+            "a batched x [B, M, K] takes indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] and cached_out [B, M, N]"
+        assert indices.shape[0] == B and counts.shape[0] == B and sparse_act_T.shape[0] == B and cached_out.shape[0] == B, \
+            f"the batch size of indices / counts / sparse_act_T / cached_out must be that of x ({B})"
+    K1 = x.shape[-1]
+    K2, K1_ = w_gate.shape
+    assert K1 == K1_ and tuple(w_up.shape) == (K2, K1), "K1 must match, w_up must have the shape of w_gate"
+    assert fc2w_T.shape[0] == K2, "K2 must match"
+    scales = (scale_a, scale_b_gate, scale_b_up)
+    sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)   # bf16: x is fp8
+    if amd_key("mlp", "fused_scatter"):
+        mm1_glu_fp8(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, *scales, update_cache=True)
+        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out)
+        return
+    mm1_glu_fp8(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, *scales, update_cache=False)
+    if USE_FUSED_MLP_MATMUL_2:
+        mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out, num_sms_scatter_add)
+    else:
+        mm2_unfused(sparse_act_packed, fc2w_T, cached_out, sparse_act_T, indices, counts, num_sms_scatter_add)
+
+
 __all__ = ["mm1", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
-           "mm1_glu", "run_e2e_glu"]
+           "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8"]

@@ -240,7 +240,8 @@ int chipmunk_csp_scatter_add_batched(const void *packed, void *unpacked_colmajor
  * projection in either order.  bias_gate / bias_up are bf16 [F] or NULL (= zero).  act is one of the CHIPMUNK_ACT_* codes below.
  * update_cache = 1 also applies pa_cache[i, m] = bf16(pa_cache[i, m] + c[m,j]), the arithmetic of chipmunk_csp_scatter_add on c;
  * 0 leaves the cache as it is.  Contract of the *_ragged entries (any M >= 1, ldc >= M, ldc % 8 == 0, K % 64 == 0, F % 64 == 0) and,
- * for *_batched, of the batch entries above (weights and biases shared by all sequences).  bf16 only: there is no fp8 gated form.
+ * for *_batched, of the batch entries above (weights and biases shared by all sequences).  bf16 only: e4m3 operands take the *_glu_fp8
+ * entries below.
  * A failed check returns CHIPMUNK_ERR_INVALID with a message, before anything is enqueued. */
 #define CHIPMUNK_ACT_GELU_TANH 0 /* x * 0.5 * (1 + tanh(0.79788456 (x + 0.044715 x^3))): the code of chipmunk_csp_mlp_mm1 */
 #define CHIPMUNK_ACT_SILU 1      /* x / (1 + exp(-x)) */
@@ -252,6 +253,22 @@ int chipmunk_csp_mlp_mm1_glu_batched(const void *a, const void *b_gate, const vo
                                      const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M,
                                      int K, int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
                                      void *stream);
+/* The gated GEMM1 with fp8 projections: a [M,K], b_gate / b_up [F,K] are OCP e4m3 bytes (float8_e4m3fn; two weights or the halves of one
+ * [2F,K] tensor, row stride K), scale_a / scale_b_gate / scale_b_up one device float each -- the RECIPROCAL quantisation scales, as
+ * chipmunk_csp_mlp_mm1_fp8 takes them.  In fp32, accumulators from zero:
+ *   gate = (a[m,:].b_gate[i,:]) * scale_a * scale_b_gate + bias_gate[i],   up = (a[m,:].b_up[i,:]) * scale_a * scale_b_up + bias_up[i]
+ *   c[m,j] = bf16( fma(act(gate), up, -pa_cache[i, m]) )
+ * Biases (NULL = zero), the cache and c are bf16; update_cache 0 / 1 and every other rule as chipmunk_csp_mlp_mm1_glu[_batched], except
+ * K % 128 == 0 and 1 byte per element of a and the weights in the 32-bit-offset limits. */
+int chipmunk_csp_mlp_mm1_glu_fp8(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                 const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts,
+                                 const float *scale_a, const float *scale_b_gate, const float *scale_b_up, int M, int K, int F,
+                                 int ldc, int act, int update_cache, void *stream);
+int chipmunk_csp_mlp_mm1_glu_fp8_batched(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                         const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts,
+                                         const float *scale_a, const float *scale_b_gate, const float *scale_b_up, int M, int K,
+                                         int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                         void *stream);
 
 /* ---------------------------------------------------------------- indexed IO
  * Replaces chipmunk::topk_indices (reference csrc/indexed_io/topk_indices.cu:145-218; schema chipmunk.cpp:58).

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_glu mm2 scatter fp8_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_glu mm1_glu_fp8 mm2 scatter fp8_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -187,6 +187,45 @@ def bench_mm1_glu(M=4352, K=3072, F=12288, keep=3840, act="silu"):
     print(f"mm1_glu / mm1   : {med['glu'] / med['mm1']:8.3f}")
 
 
+def bench_mm1_glu_fp8(M=32768, K=1536, F=8960, keep=2816, act="silu"):
+    """The gated fp8 GEMM1 (csp_mlp_mm1_glu_fp8) at the Wan fp8 shape, 30 % of the columns kept (rounded to 256), against the ungated
+    csp_mlp_mm1_fp8 with twice the kept columns over a [2F, K] e4m3 weight: equal matrix work and equal gathered weight bytes, as
+    bench_mm1_glu.  Same process, the two alternating (KB_ROUNDS pairs, default 5); per launch the median bracket of `timeit`, then the
+    median and the range over the rounds.  KB_GLU_UPDATE=1 times the scatter forms of both."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    upd = os.environ.get("KB_GLU_UPDATE") == "1"
+    a8 = (torch.randn(M, K, device=dev, generator=g) * 16).clamp(-448, 448).to(torch.float8_e4m3fn)
+    w8 = (torch.randn(2 * F, K, device=dev, generator=g) * 0.02 * 512).clamp(-448, 448).to(torch.float8_e4m3fn)   # gated: its halves
+    sa, sb, sb2 = (torch.tensor([v], device=dev) for v in (1 / 16.0, 1 / 512.0, 1 / 256.0))
+    bias = torch.zeros(2 * F, device=dev, dtype=torch.bfloat16)
+    cache = torch.randn(2 * F, M, device=dev, dtype=torch.bfloat16, generator=g)
+    packed = torch.empty(M, 2 * F, device=dev, dtype=torch.bfloat16)
+    G = (M + 127) // 128
+    inds1, inds2 = rand_rows(G, F, keep, g), rand_rows(G, 2 * F, 2 * keep, g)
+    c1, c2 = torch.full((G,), keep, dtype=torch.int32, device=dev), torch.full((G,), 2 * keep, dtype=torch.int32, device=dev)
+    packed1 = packed[:, :F].contiguous()
+
+    def run_glu():
+        torch.ops.chipmunk.csp_mlp_mm1_glu_fp8(a8, w8[:F], w8[F:], packed1, None, None, cache[:F], inds1, c1, sa, sb, sb2, act, upd)
+
+    def run_ungated():
+        if upd:
+            torch.ops.chipmunk.csp_mlp_mm1_fp8_scatter(a8, w8, packed, bias, cache, inds2, c2, sa, sb)
+        else:
+            torch.ops.chipmunk.csp_mlp_mm1_fp8(a8, w8, packed, bias, cache, inds2, c2, sa, sb, False)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {"glu": [], "mm1": []}
+    for _ in range(rounds):
+        t["glu"].append(timeit(run_glu) * 1e3)
+        t["mm1"].append(timeit(run_ungated) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * K * 2 * keep
+    tag = f"(M={M} K={K} F={F} keep={keep} {'scatter' if upd else 'update off'}, {rounds} alternating rounds)"
+    print(f"mm1_glu_fp8 {act:9s}: {med['glu']:8.1f} us  [{min(t['glu']):.1f} .. {max(t['glu']):.1f}]  {flops/med['glu']/1e6:7.1f} TFLOP/s   {tag}")
+    print(f"mm1_fp8 2x keep, 2F : {med['mm1']:8.1f} us  [{min(t['mm1']):.1f} .. {max(t['mm1']):.1f}]  {flops/med['mm1']/1e6:7.1f} TFLOP/s")
+    print(f"mm1_glu_fp8 / mm1_fp8: {med['glu'] / med['mm1']:7.3f}")
+
+
 def bench_fp8_wan(M=32768, ldc=None):
     """BASELINE config C5 (Wan2.1-1.3B, 832x480x81 -> 32 760 tokens padded to 32 768): fp8 e4m3 GEMM1, M = 32768, K = 1536,
     F = 8960, keep 0.3 (2688 columns); bf16 GEMM1 at the same shape beside it.  M = 32760: the ragged launch on the tokens as they are
@@ -334,6 +373,8 @@ def main():
             bench_mlp(w, variants, keep=int(os.environ.get("KB_KEEP", "4096")))   # KB_KEEP: kept columns per group (FLUX: 0.3 * 12288 -> 3840)
         elif w == "mm1_glu":          # gated GEMM1 at the FLUX MLP shape against the ungated launch of equal work (KB_GLU_ACT: silu, gelu_tanh, gelu)
             bench_mm1_glu(act=os.environ.get("KB_GLU_ACT", "silu"))
+        elif w == "mm1_glu_fp8":      # gated fp8 GEMM1 at the Wan fp8 shape against the ungated fp8 launch of equal work (KB_GLU_ACT as mm1_glu)
+            bench_mm1_glu_fp8(act=os.environ.get("KB_GLU_ACT", "silu"))
         elif w == "fp8_wan":
             bench_fp8_wan()
         elif w == "mm2_wan":          # GEMM2 at the Wan2.1 1.3B shape (configs[4]): M = 32 768 rows, N2 = 1 536, F = 8 960, 30 % kept
