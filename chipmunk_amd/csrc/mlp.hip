@@ -11,6 +11,9 @@
 // source chunk index so the lane-linear LDS image is conflict-free for ds_read_b128 (k-contiguous operands) and
 // ds_read_b64_tr_b16 (fc2^T, which is n-contiguous in memory and must be fed k-contiguous to the MFMA).  Epilogues go
 // through the freed ring so that global memory only sees 16-byte accesses over whole row segments.
+// GEMM2 also exists over e4m3 rows of fc2^T (mm2_w8_kernel, weight-only fp8): the gathered row slice is N2 BYTES, the transpose read runs over
+// the byte image with a column pair as its 16-bit element, v_perm_b32 + v_cvt_scalef32_pk_bf16_fp8 widen to bf16 in registers in front of the
+// same bf16 MFMA, and the freed half of the B tile is a fourth ring stage <256, 32, 4, 2, 8 waves>.
 #include "common.h"
 #include "attn64_util.h"
 #include <type_traits>
@@ -1044,6 +1047,289 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_kernel(const typ
     }
 }
 
+// ------------------------------------------------------------------------------------------------ mm2, e4m3 weights
+// (not in the probe-forms build: its entries answer with an error there)
+#ifndef CHIPMUNK_MM1_PROBES
+// GEMM2 over e4m3 rows of fc2^T (weight-only fp8): C = bf16(bf16((A_packed x f(fc2^T[idx])) * scale_b) + C).  mm2_kernel's loop -- the same
+// ring, keys, waits, placement, ragged rows and epilogue staging -- with three differences:
+//   * a gathered row slice is BN bytes, so a B tile is half of mm2_kernel's and the freed LDS is a fourth ring stage (4 x 16 KiB = the
+//     64 KiB the staged epilogue needs);
+//   * ds_read_b64_tr_b16 runs over the BYTE image: one 16-bit element is the column pair (2j, 2j + 1), so lane l & 31 of a read pair
+//     receives 8 k-consecutive bytes of columns 2 (l & 31) and 2 (l & 31) + 1 of a 64-column block.  v_perm_b32 separates the two columns,
+//     v_cvt_scalef32_pk_bf16_fp8 with scale 1.0 widens them (exact: every e4m3 value is a bf16 value) -- two MFMA fragments, "even" and
+//     "odd", whose accumulator row i is column 2 i (+ 1) of the block.  k sits where mm2_kernel puts it (lane half = k half, 8 consecutive k
+//     per lane, slices in order), so the fp32 sums are mm2_kernel's on the widened weights;
+//   * the epilogue interleaves the even and the odd accumulator (one lane then owns 8 consecutive columns, a whole 16-byte chunk of the
+//     staged tile) and multiplies by scale_b before bf16(acc).
+struct Mm2W8Params {
+    const uint16_t *a;       // packed [M,F] bf16
+    const uint8_t *b;        // fc2^T [F,N2] e4m3
+    const float *scale_b;    // the weight's reciprocal quantisation scale (device)
+    uint16_t *c;             // [M,N2] bf16, accumulated in place
+    const int32_t *indices, *counts;
+    int M, F, N2, NT, NR;
+    int cus_per_xcd;         // as Mm2Params
+};
+struct Mm2W8Batch : Mm2W8Params {
+    int B;
+};
+
+template <int BN, int BK, int NST, int WPS, int NW, bool BATCHED>
+__global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_w8_kernel(const typename std::conditional<BATCHED, Mm2W8Batch, Mm2W8Params>::type p) {
+    static_assert(NW == 4 || NW == 8, "4 waves (2 x 2) or 8 waves (2 x 4)");
+    constexpr int WNG = NW / 2;                 // waves along n; wave tile = 64 rows x BN/WNG columns
+    using KT = KTile<BK>;
+    constexpr int A_TILE = BM * BK * 2, B_TILE = BK * BN, STAGE = A_TILE + B_TILE;
+    constexpr int A_INST = A_TILE / (1024 * NW), B_INST = B_TILE / (1024 * NW);
+    constexpr int NP = BN / WNG / 64;        // 64-column blocks per wave: one transpose-read pair and two accumulator tiles each
+    static_assert(A_INST >= 1 && B_INST >= 1 && NP >= 1 && BN % (WNG * 64) == 0, "tile too small for this many waves");
+    static_assert(BM * BN * 2 <= NST * STAGE, "the epilogue stages the bf16 output tile in the ring");
+    constexpr int BROWB = BN;                // bytes per gathered fc2^T row slice
+    constexpr int BCPR = BN / 16;            // 16-byte chunks per row
+    constexpr int BRPI = 1024 / BROWB;       // rows per DMA instruction (4 for BN=256)
+    static_assert(BCPR == 16 && BRPI == 4, "the chunk swizzle and the key select below are written for 256-byte row slices");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = w / WNG, wn = w % WNG;
+
+    // tile map and length-aware placement: mm2_kernel's
+    const int Gs = (p.M + BM - 1) / BM;
+    int G = Gs;
+    if constexpr (BATCHED) G = Gs * p.B;
+    const int xcdq = (G * p.NT) >> 3, xcdr = (G * p.NT) & 7;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    if (slot >= xcdq + (xcd < xcdr ? 1 : 0)) return;
+    const int NR = p.NR;
+    const int mine = xcdq + (xcd < xcdr ? 1 : 0);
+    const int tbase = xcd < xcdr ? xcd * (xcdq + 1) : xcdr * (xcdq + 1) + (xcd - xcdr) * xcdq;
+    auto group_of = [&](int tt) {
+        const int nb_ = tt / (G * NR), rem_ = tt - nb_ * (G * NR);
+        return rem_ / min(NR, p.NT - nb_ * NR);
+    };
+    int t = tbase + slot;
+    const int cap = p.cus_per_xcd;
+    if (cap > 0 && mine > cap && mine <= 64 && mine <= 2 * cap) {
+        const int nl = 2 * cap - mine;
+        const int want = slot < mine - cap ? nl + slot : slot < cap ? slot - (mine - cap) : mine - 1 - (slot - cap);
+        const int len = lane < mine ? p.counts[group_of(tbase + lane)] : -1;
+        int rank = 0;
+        for (int j = 0; j < mine; ++j) {
+            const int lj = __shfl(len, j);
+            rank += (lj > len || (lj == len && j < lane)) ? 1 : 0;
+        }
+        const unsigned long long hit = __ballot(lane < mine && rank == want);
+        t = tbase + (int)__builtin_ctzll(hit);
+    }
+    const int nb = t / (G * NR), rem = t - nb * (G * NR);
+    const int nr = min(NR, p.NT - nb * NR);
+    const int gi = rem / nr, nt = nb * NR + rem - gi * nr;
+    const int cnt = p.counts[gi];
+    int g = gi, bseq = 0;
+    if constexpr (BATCHED) {
+        bseq = gi / Gs;
+        g = gi - bseq * Gs;
+    }
+    auto seq_a = [&]() -> const uint16_t * {
+        if constexpr (BATCHED) return p.a + (int64_t)bseq * p.M * p.F;
+        else return p.a;
+    };
+    auto seq_c = [&]() -> uint16_t * {
+        if constexpr (BATCHED) return p.c + (int64_t)bseq * p.M * p.N2;
+        else return p.c;
+    };
+    const int n0 = nt * BN;
+    const int ncols = min(BN, p.N2 - n0);  // N2 is a multiple of 16 (checked on the host): a 16-byte chunk is live or dead as a whole
+    const int32_t *idxg = p.indices + (int64_t)gi * p.F;
+    const int nkb = (cnt + BK - 1) / BK;
+    if (nkb == 0) return;
+    const float sb = *p.scale_b;
+
+    const int rows = min(BM, p.M - g * BM);   // ragged last group, as mm2_kernel
+    const __amdgpu_buffer_rsrc_t ra = make_rsrc(seq_a(), (uint32_t)p.M * p.F * 2u), rb = make_rsrc(p.b, (uint32_t)p.F * p.N2);
+    uint32_t aoff[A_INST];  // byte offsets
+#pragma unroll
+    for (int i = 0; i < A_INST; ++i) {
+        const int row = KT::lane_row(w * A_INST + i, lane);
+        aoff[i] = ((uint32_t)(g * BM + min(row, rows - 1)) * p.F + KT::src_chunk_elems(row, lane)) * 2u;
+    }
+    constexpr int NKEY = B_INST * BRPI;          // keys per wave per tile (4): consecutive entries of the index list, scalar loads
+    static_assert(NKEY % 4 == 0, "a wave's keys are fetched as whole s_load_dwordx4/x8");
+    int keys[NKEY];
+    auto load_keys = [&](int kb) {
+        // counts are multiples of 8 and the block start one of 4: the block is live or dead as a whole
+        const int base = kb * BK + w * NKEY;
+        const __attribute__((address_space(4))) int32_t *kp =
+            (const __attribute__((address_space(4))) int32_t *)(idxg + __builtin_amdgcn_readfirstlane(base < cnt ? base : 0));
+#pragma unroll
+        for (int j = 0; j < NKEY; ++j) keys[j] = kp[j];
+    };
+    const int rsel = lane / BCPR;                  // which of the instruction's BRPI rows this lane stages
+    auto issue = [&](int kb, int buf) {
+        unsigned char *st = smem + buf * STAGE;
+#pragma unroll
+        for (int i = 0; i < A_INST; ++i) blds16(ra, aoff[i], kb * BK * 2, st + (w * A_INST + i) * 1024);
+#pragma unroll
+        for (int i = 0; i < B_INST; ++i) {
+            // (a two-level select on the bits of rsel: the chain `rsel == rr ? keys[rr] : key` over four keys is compiled into an indexed
+            // load from a scratch copy of the keys)
+            const int klo = (rsel & 1) ? keys[i * BRPI + 1] : keys[i * BRPI], khi = (rsel & 1) ? keys[i * BRPI + 3] : keys[i * BRPI + 2];
+            const int key = (rsel & 2) ? khi : klo;
+            const int r = (w * B_INST + i) * BRPI + rsel;
+            int chunk = (lane % BCPR) ^ ((r & 3) << 2);
+            chunk = chunk * 16 < ncols ? chunk : 0;  // partial last column tile: stay inside the row
+            blds16(rb, (uint32_t)key * p.N2 + n0 + chunk * 16, 0, st + A_TILE + (w * B_INST + i) * 1024);
+        }
+    };
+
+    f32x16 acc[NP][2][2];  // [64-column block][even / odd columns][m tile]: MFMA rows = n, MFMA cols = m
+#pragma unroll
+    for (int np = 0; np < NP; ++np)
+#pragma unroll
+        for (int eo = 0; eo < 2; ++eo)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[np][eo][mt][r] = 0.f;
+
+#pragma unroll
+    for (int s = 0; s < NST - 1; ++s)
+        if (s < nkb) {
+            load_keys(s);
+            issue(s, s);
+        }
+    if (NST - 1 < nkb) load_keys(NST - 1);
+    const int li = lane & 15, grp = lane >> 4;
+    int buf = 0, nbuf = NST - 1;
+    for (int kb = 0; kb < nkb; ++kb) {
+        if (kb + NST - 1 <= nkb) wait_vmcnt<(NST - 2) * (A_INST + B_INST)>();
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        const bool late = NW == 8 && w >= NW / 2;   // the second wave of each SIMD issues its pieces after its MFMAs (see mm2_kernel)
+        if (!late && kb + NST - 1 < nkb) {
+            issue(kb + NST - 1, nbuf);
+            if (kb + NST < nkb) load_keys(kb + NST);
+        }
+        // every LDS read of the loop in inline asm with hand-counted lgkmcnt (see mm2_kernel)
+        constexpr int KK = BK / 16;
+        constexpr int RD = 2 + 2 * NP;   // LDS reads per k slice: two A fragments, two halves per 64-column block
+        const uint32_t stage_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem + buf * STAGE;
+        u32x4 pf[KK][2];
+        u32x2 wlo[KK][NP], whi[KK][NP];
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                const int row = wm * 64 + mt * 32 + (lane & 31);
+                const uint32_t ad = stage_lds + row * KT::ROWB + (((kk * 2 + (lane >> 5)) ^ KT::swz(row)) << 4);
+                asm volatile("ds_read_b128 %0, %1" : "=&v"(pf[kk][mt]) : "v"(ad) : "memory");
+            }
+#pragma unroll
+            for (int np = 0; np < NP; ++np) {
+                // lane group grp: column half = grp&1 (32 columns = 32 bytes), k half = grp>>1; lane li addresses block row li>>2, bytes (li&3)*8
+                const int row = kk * 16 + (grp >> 1) * 8 + (li >> 2);
+                const int chunk = (wn * (BN / WNG / 16) + np * 4 + (grp & 1) * 2 + ((li & 3) >> 1)) ^ ((row & 3) << 2);
+                const uint32_t ad = stage_lds + A_TILE + row * BROWB + chunk * 16 + (li & 1) * 8;
+                asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%c3"
+                             : "=&v"(wlo[kk][np]), "=&v"(whi[kk][np]) : "v"(ad), "i"(4 * BROWB) : "memory");
+            }
+        }
+        if (kb == nkb - 1) {   // packed columns past the count hold garbage: only the last k step can see them (counts are multiples of 8)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) {
+                const bool kdead = kb * BK + kk * 16 + (lane >> 5) * 8 >= cnt;
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    asm volatile("" : "+v"(pf[kk][mt]));
+                    if (kdead) pf[kk][mt] = (u32x4){0u, 0u, 0u, 0u};
+                }
+            }
+        }
+        static_for<0, KK>([&](auto kc) {
+            constexpr int kk = decltype(kc)::value;
+            constexpr int YOUNGER = RD * (KK - 1 - kk);
+            asm volatile("s_waitcnt lgkmcnt(%c0)" ::"i"(YOUNGER > 15 ? 15 : YOUNGER) : "memory");
+#pragma unroll
+            for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(pf[kk][i]));
+#pragma unroll
+            for (int i = 0; i < NP; ++i) asm volatile("" : "+v"(wlo[kk][i]), "+v"(whi[kk][i]));
+#pragma unroll
+            for (int np = 0; np < NP; ++np) {
+                // wlo = {k0 | k1 << 16, k2 | k3 << 16}, each 16 bits = {even column, odd column}; whi: k4 .. k7
+#pragma unroll
+                for (int eo = 0; eo < 2; ++eo) {
+                    const uint32_t sel = eo ? 0x07050301u : 0x06040200u;
+                    const uint32_t k03 = __builtin_amdgcn_perm(wlo[kk][np][1], wlo[kk][np][0], sel);
+                    const uint32_t k47 = __builtin_amdgcn_perm(whi[kk][np][1], whi[kk][np][0], sel);
+                    const bf16x2 f0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(k03, 1.0f, false);
+                    const bf16x2 f1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(k03, 1.0f, true);
+                    const bf16x2 f2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(k47, 1.0f, false);
+                    const bf16x2 f3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(k47, 1.0f, true);
+                    const bf16x8 wfr = {f0[0], f0[1], f1[0], f1[1], f2[0], f2[1], f3[0], f3[1]};
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt) acc[np][eo][mt] = mfma32(wfr, __builtin_bit_cast(bf16x8, pf[kk][mt]), acc[np][eo][mt]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        if (late && kb + NST - 1 < nkb) {
+            issue(kb + NST - 1, nbuf);
+            if (kb + NST < nkb) load_keys(kb + NST);
+        }
+        buf = buf + 1 == NST ? 0 : buf + 1;
+        nbuf = nbuf + 1 == NST ? 0 : nbuf + 1;
+    }
+
+    // ---- epilogue: lane owns row m = lane&31 of each tile; accumulator register q4*4 + j is block column 2 (q4*8 + (lane>>5)*4 + j)
+    //      (+ 1 in the odd tile), so j = 0..3 of both tiles are 8 consecutive columns.  C = bf16(acc * scale_b) + C in bf16, staged
+    //      through the ring as in mm2_kernel (row-major [128][BN] bf16, chunk c of row m at chunk c ^ (m & 31))
+    constexpr int CPRO = BN / 8;  // 16-byte chunks per output row
+    __syncthreads();              // every wave is done reading the last operand stage
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        const int ml = wm * 64 + mt * 32 + (lane & 31);
+#pragma unroll
+        for (int np = 0; np < NP; ++np) {
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const int nl = wn * (BN / WNG) + np * 64 + q4 * 16 + (lane >> 5) * 8;
+                u32x4 v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = pack_bf16x2(acc[np][0][mt][q4 * 4 + j] * sb, acc[np][1][mt][q4 * 4 + j] * sb);
+                *(u32x4 *)(smem + ml * (BN * 2) + (((nl >> 3) ^ (ml & (CPRO - 1) & 31)) << 4)) = v;
+            }
+        }
+    }
+    __syncthreads();
+    constexpr int ITEMS = BM * CPRO / (NW * 64);  // 16-byte pieces per thread; all requested before the first is used (see mm2_kernel)
+    u32x4 olds[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        const int item = it * (NW * 64) + tid;
+        const int r = item / CPRO, ch = item % CPRO;
+        const int n = n0 + ch * 8;
+        olds[it] = (n < p.N2 && r < rows) ? *(const u32x4 *)(seq_c() + (int64_t)(g * BM + r) * p.N2 + n) : (u32x4){0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        const int item = it * (NW * 64) + tid;
+        const int r = item / CPRO, ch = item % CPRO;
+        const int n = n0 + ch * 8;
+        if (n >= p.N2 || r >= rows) continue;  // N2 is a multiple of 16: a chunk is live or dead as a whole
+        const u32x4 a = *(const u32x4 *)(smem + r * (BN * 2) + ((ch ^ (r & (CPRO - 1) & 31)) << 4));
+        uint16_t *cp = seq_c() + (int64_t)(g * BM + r) * p.N2 + n;
+        const u32x4 old = olds[it];
+        u32x4 out;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            out[e] = pack_bf16x2(__uint_as_float(a[e] << 16) + __uint_as_float(old[e] << 16),
+                                 __uint_as_float(a[e] & 0xffff0000u) + __uint_as_float(old[e] & 0xffff0000u));
+        *(u32x4 *)cp = out;
+    }
+}
+#endif   // CHIPMUNK_MM1_PROBES
+
 // ------------------------------------------------------------------------------------------------ scatter-add
 // unpacked[idx[g,c], g*128 + r] += packed[g*128 + r, c]   (scatter_add.cu:43-98).  One workgroup = (group, 64 packed
 // columns): the 128x64 packed tile is transposed through LDS so both the read (128 B per row) and the read-modify-write
@@ -1219,6 +1505,52 @@ int launch_mm2(const void *a, const void *b, void *c, const int32_t *indices, co
     // isolation, 2 % faster inside the bench loop (A/B on one box: 170.5 -> 167.3 us, twice)
     return launch_mm2_variant<256, 32, 3, 2, 8>(p, s);
 }
+
+#ifndef CHIPMUNK_MM1_PROBES
+// GEMM2 over e4m3 weights: the shipped shape of launch_mm2 with the halved B tile spent on a fourth ring stage; B > 0: the batched form
+template <bool BATCHED>
+int launch_mm2_w8_variant(Mm2W8Params p, hipStream_t s, int B) {
+    constexpr int BN = 256, BK = 32, NST = 4, WPS = 2, NW = 8;
+    constexpr int LDS = NST * (BM * BK * 2 + BK * BN);
+    auto kern = mm2_w8_kernel<BN, BK, NST, WPS, NW, BATCHED>;
+    static uint64_t lds_set = 0;
+    ensure_dynamic_lds((const void *)kern, LDS, lds_set);
+    p.NT = (p.N2 + BN - 1) / BN;
+    const int nr_option = chipmunk_get_option("mm2_nr");   // column tiles per walk and placement: launch_mm2_variant's
+    p.NR = nr_option > 0 ? nr_option : 4;
+    if (p.NR > p.NT) p.NR = p.NT;
+    p.cus_per_xcd = !chipmunk_get_option("mm2_order") ? device_cu_count() / 8 : 0;
+    const dim3 grid(((B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8) * 8);
+    if constexpr (BATCHED) {
+        Mm2W8Batch q;
+        static_cast<Mm2W8Params &>(q) = p;
+        q.B = B;
+        hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS, s, q);
+    } else {
+        hipLaunchKernelGGL(kern, grid, dim3(NW * 64), LDS, s, p);
+    }
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+
+int launch_mm2_w8(const void *a, const void *b, const float *scale_b, void *c, const int32_t *indices, const int32_t *counts, int M, int F,
+                  int N2, hipStream_t s, int B = 0) {
+    CM_CHECK(a && b && scale_b && c, "csp_mlp_mm2_w8: null tensor or scale pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (B > 0) {
+        if (int e = check_mlp_batch(B, M)) return e;
+    }
+    CM_CHECK(N2 > 0 && N2 % 16 == 0, "csp_mlp_mm2_w8: N2 must be a positive multiple of 16 (got %d): a 16-byte chunk of an e4m3 row is 16 columns", N2);
+    CM_CHECK((int64_t)M * F < (1ll << 31) && (int64_t)F * N2 < (1ll << 31) && (int64_t)M * N2 < (1ll << 31),
+             "csp_mlp_mm2_w8: M*F, F*N2 or M*N2 too large for 32-bit offsets");
+    Mm2W8Params p = {(const uint16_t *)a, (const uint8_t *)b, scale_b, (uint16_t *)c, indices, counts, M, F, N2, 0, 0, 0};
+    return B > 0 ? launch_mm2_w8_variant<true>(p, s, B) : launch_mm2_w8_variant<false>(p, s, 1);
+}
+#else
+int launch_mm2_w8(const void *, const void *, const float *, void *, const int32_t *, const int32_t *, int, int, int, hipStream_t, int = 0) {
+    CM_CHECK(false, "csp_mlp_mm2_w8: not part of the probe-forms build");
+}
+#endif   // CHIPMUNK_MM1_PROBES
 
 // (parameter block -> its batched form)
 template <class P> struct Mm1BatchOf { using type = Mm1Batch; };
@@ -1581,4 +1913,15 @@ extern "C" int chipmunk_csp_mlp_mm2_and_scatter_add_batched(const void *packed, 
     if (int e = launch_scatter_add_batched(packed, unpacked_colmajor, indices, counts, B, M, F, ldc, cache_batch_stride, (hipStream_t)stream))
         return e;
     return launch_mm2(mma_a, mma_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream, B);
+}
+
+// ---- GEMM2 over e4m3 rows of fc2^T (include/chipmunk_hip.h, "fp8 fc2")
+extern "C" int chipmunk_csp_mlp_mm2_w8(const void *mma_a, const void *mma_b, const float *scale_b, void *mma_c, const int32_t *indices,
+                                       const int32_t *counts, int M, int F, int N2, void *stream) {
+    return launch_mm2_w8(mma_a, mma_b, scale_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm2_w8_batched(const void *mma_a, const void *mma_b, const float *scale_b, void *mma_c,
+                                               const int32_t *indices, const int32_t *counts, int M, int F, int N2, int B, void *stream) {
+    CM_CHECK(B >= 1, "mlp: the batch size B must be at least 1 (got %d)", B);
+    return launch_mm2_w8(mma_a, mma_b, scale_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream, B);
 }

@@ -637,6 +637,38 @@ void csp_mlp_mm2(at::Tensor mma_a, at::Tensor mma_b, at::Tensor indices, at::Ten
           "csp_mlp_mm2");
 }
 
+// GEMM2 over e4m3 rows of fc2^T (weight-only fp8, chipmunk_csp_mlp_mm2_w8): csp_mlp_mm2 with mma_b float8_e4m3fn and its reciprocal scale
+void csp_mlp_mm2_w8(at::Tensor mma_a, at::Tensor mma_b, at::Tensor scale_b, at::Tensor indices, at::Tensor counts, at::Tensor mma_c) {
+    CHECK_DEV(mma_a); CHECK_DEV(mma_b); CHECK_DEV(mma_c); CHECK_DEV(indices); CHECK_DEV(counts);
+    TORCH_CHECK(mma_b.scalar_type() == at::kFloat8_e4m3fn, "mma_b must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+    TORCH_CHECK(scale_b.is_cuda() && scale_b.scalar_type() == at::kFloat && scale_b.numel() == 1,
+                "scale_b must be a one-element float32 tensor on the GPU");
+    CHECK_BF16(mma_a); CHECK_BF16(mma_c);
+    CHECK_I32(indices); CHECK_I32(counts);
+    CHECK_CONTIG(mma_a); CHECK_CONTIG(mma_b); CHECK_CONTIG(mma_c); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
+    TORCH_CHECK((mma_a.dim() == 2 || mma_a.dim() == 3) && mma_b.dim() == 2 && mma_c.dim() == mma_a.dim(),
+                "mma_a and mma_c must both be 2D ([M, .]) or 3D ([B, M, .]) tensors, mma_b 2D");
+    const int64_t B = mma_a.dim() == 3 ? mma_a.size(0) : 1;
+    const int64_t M = mma_a.size(-2), F = mma_a.size(-1), N2 = mma_b.size(1);
+    TORCH_CHECK(B >= 1, "the batch size must be at least 1");
+    TORCH_CHECK(mma_b.size(0) == F && mma_c.size(-2) == M && mma_c.size(-1) == N2 && mma_c.numel() == B * M * N2,
+                "shape mismatch (mma_b must be [F, N2], mma_c [M, N2], or [B, M, N2] with the batch size of mma_a)");
+    c10::DeviceGuard guard(mma_a.device());
+    TORCH_CHECK(indices.numel() == B * groups_of(M) * F && counts.numel() == B * groups_of(M),
+                "indices must be [ceil(M/128), F], counts [ceil(M/128)] ([B, ceil(M/128), F] and [B, ceil(M/128)] with the batch size of mma_a)");
+    TORCH_CHECK(B * groups_of(M) <= 65535, "B * ceil(M/128) groups must not exceed 65535 (got ", B * groups_of(M), ")");
+    if (B > 1) {
+        check(chipmunk_csp_mlp_mm2_w8_batched(mma_a.data_ptr(), mma_b.data_ptr(), scale_b.data_ptr<float>(), mma_c.data_ptr(),
+                                              indices.data_ptr<int>(), counts.data_ptr<int>(), (int)M, (int)F, (int)N2, (int)B,
+                                              cur_stream(mma_a)),
+              "csp_mlp_mm2_w8");
+        return;
+    }
+    check(chipmunk_csp_mlp_mm2_w8(mma_a.data_ptr(), mma_b.data_ptr(), scale_b.data_ptr<float>(), mma_c.data_ptr(), indices.data_ptr<int>(),
+                                  counts.data_ptr<int>(), (int)M, (int)F, (int)N2, cur_stream(mma_a)),
+          "csp_mlp_mm2_w8");
+}
+
 // ---------------------------------------------------------------------------------- indexed IO
 // reference csrc/indexed_io/copy_indices.cu:82-154
 void copy_indices(at::Tensor bmfc1, at::Tensor bm_mid_cache, at::Tensor sp_inds, at::Tensor sp_counts) {
@@ -1098,6 +1130,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_attn_out(Tensor q, Tensor k, Tensor v, Tensor o_in, Tensor indices, Tensor indices_counts, int o_scale) -> Tensor");
     m.def("csp_mlp_mm1_scatter(Tensor a, Tensor b_colmajor, Tensor(c!) c, Tensor bias, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts) -> ()");
     m.def("csp_mlp_mm2(Tensor mma_a, Tensor mma_b, Tensor indices, Tensor counts, Tensor(mma_c!) mma_c) -> ()");
+    m.def("csp_mlp_mm2_w8(Tensor mma_a, Tensor mma_b, Tensor scale_b, Tensor indices, Tensor counts, Tensor(mma_c!) mma_c) -> ()");
     m.def("csp_mlp_mm1_fp8(Tensor a, Tensor b, Tensor(c!) c, Tensor bias, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_fp8_scatter(Tensor a, Tensor b, Tensor(c!) c, Tensor bias, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b) -> ()");
     m.def("csp_mlp_mm1_glu(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, str act, bool update_cache) -> ()");
@@ -1148,6 +1181,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_attn_out", &csp_attn_out);
     m.impl("csp_mlp_mm1_scatter", &csp_mlp_mm1_scatter);
     m.impl("csp_mlp_mm2", &csp_mlp_mm2);
+    m.impl("csp_mlp_mm2_w8", &csp_mlp_mm2_w8);
     m.impl("csp_mlp_mm1_fp8", &csp_mlp_mm1_fp8);
     m.impl("csp_mlp_mm1_glu", &csp_mlp_mm1_glu);
     m.impl("csp_mlp_mm1_glu_fp8", &csp_mlp_mm1_glu_fp8);

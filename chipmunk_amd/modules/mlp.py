@@ -5,6 +5,9 @@ Full step: dense ``fc2(act(fc1(x)))``; cache the transposed activations (column-
 most since they were last computed (``topk_indices`` on |delta|), recompute only those columns (``csp_mlp_mm1``),
 scatter the activation deltas into the cache and add ``delta @ fc2^T`` onto the cached output
 (``csp_mlp_mm2_and_scatter_add``).  The fc2 bias is already inside the cached output.
+
+``fc2`` is bf16, or -- with ``mlp.fp8_fc2`` on -- an ``F8Linear`` with e4m3 weights: dense and full steps call its forward as it is
+(``torch._scaled_mm``), the sparse steps gather e4m3 rows of ``fc2.weight^T`` (``csp_mlp_mm2_w8``) with ``fc2.scale_reciprocal``.
 """
 from __future__ import annotations
 
@@ -53,10 +56,32 @@ def _transposed(x: torch.Tensor) -> torch.Tensor:
     return x.transpose(-1, -2).contiguous()
 
 
+_F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
+
+
+def check_fc2(who: str, fc2: torch.nn.Module) -> None:
+    """An fp8 ``fc2`` is taken with ``mlp.fp8_fc2`` on, as an ``F8Linear`` with e4m3 weights: the sparse steps' GEMM2 then gathers e4m3
+    rows of ``fc2.weight^T`` and multiplies its sums by ``fc2.scale_reciprocal``.  Everything else raises at construction."""
+    if fc2.weight.dtype not in _F8:
+        return
+    if not amd_key("mlp", "fp8_fc2"):
+        raise ValueError(f"{who}: fc2 must stay bf16 (GEMM2 gathers bf16 rows of fc2.weight^T); an fp8 fc2 is refused unless the config "
+                         "key mlp.fp8_fc2 is on")
+    if fc2.weight.dtype != torch.float8_e4m3fn or getattr(fc2, "scale_reciprocal", None) is None:
+        raise ValueError(f"{who}: with mlp.fp8_fc2 the fp8 fc2 must be an F8Linear with float8_e4m3fn weights and their scale_reciprocal "
+                         f"(got weight {fc2.weight.dtype}); e5m2 weights are refused")
+
+
+def fc2_scale_of(fc2: torch.nn.Module):
+    """``fc2.scale_reciprocal`` for an e4m3 ``fc2``, ``None`` for a bf16 one"""
+    return fc2.scale_reciprocal if fc2.weight.dtype == torch.float8_e4m3fn else None
+
+
 class SparseDiffMlp:
     def __init__(self, layer_num: int, layer_counter: LayerCounter, fc1: torch.nn.Linear,
                  activation: torch.nn.Module, fc2: torch.nn.Linear, heuristic_sms_scatter_add: int = 6):
         # lists keep the Linear modules out of any parent nn.Module's parameter registry (reference mlp.py:21-23)
+        check_fc2("SparseDiffMlp", fc2)
         self.fc1 = [fc1]
         self.fc2 = [fc2]
         self.fc2w_T = [fc2.weight.data.transpose(0, 1).contiguous()]
@@ -150,7 +175,7 @@ class SparseDiffMlp:
 
         ops.mlp(x=x if batched else x[0], fc1w=fc1.weight.data, fc1b=fc1.bias.data, fc2w_T=self.fc2w_T[0], indices=indices,
                 counts=counts, sparse_act_T=sparse_act_T, cached_out=out_cache,
-                num_sms_scatter_add=self.num_sms_scatter_add, mm1_scale_a=scale_a, mm1_scale_b=scale_b)
+                num_sms_scatter_add=self.num_sms_scatter_add, mm1_scale_a=scale_a, mm1_scale_b=scale_b, fc2_scale=fc2_scale_of(fc2))
 
         # the operators updated the LOADED activation cache in place.  When it lives in host memory (offloading on, not kept resident) the
         # host copy has to follow, or the next step's load brings back the cache of the last full step and that step's deltas are taken

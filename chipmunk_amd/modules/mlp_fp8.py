@@ -175,13 +175,15 @@ def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
     (mlp_fp8.py:295-350): children named in ``ignore_keys``, children whose name contains ``mod`` (the modulation
     layers -- skipped regardless of ``quantize_modulation``, exactly as the reference does), and ``fc2`` of a sparse
     image MLP (child ``"2"`` of an ``nn.Sequential`` named ``img_mlp``) while ``mlp.is_enabled``: the sparse step's
-    GEMM2 gathers bf16 rows of ``fc2.weight.T``."""
+    GEMM2 gathers bf16 rows of ``fc2.weight.T``.  With ``mlp.fp8_fc2`` on (and e4m3 weights asked for) that ``fc2`` is swapped too:
+    the sparse step's GEMM2 then gathers e4m3 rows (``csp_mlp_mm2_w8``)."""
     from ..util.config import GLOBAL_CONFIG
     for name, child in list(model.named_children()):
         if name in ignore_keys or "mod" in name:
             continue
         if (isinstance(model, nn.Sequential) and str(name) == "2" and isinstance(child, nn.Linear)
-                and parent_name == "img_mlp" and GLOBAL_CONFIG["mlp"]["is_enabled"]):
+                and parent_name == "img_mlp" and GLOBAL_CONFIG["mlp"]["is_enabled"]
+                and not (amd_key("mlp", "fp8_fc2") and float8_dtype == torch.float8_e4m3fn)):
             print("skipping fc2 of sparse img mlp")
             continue
         if isinstance(child, nn.Linear) and not isinstance(child, F8Linear):

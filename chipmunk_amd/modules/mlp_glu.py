@@ -24,7 +24,7 @@ from .. import ops
 from ..util.config import GLOBAL_CONFIG
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
-from .mlp import _ceil8, _transposed, _transposed_pitched, block_mean
+from .mlp import _ceil8, _transposed, _transposed_pitched, block_mean, check_fc2, fc2_scale_of
 
 _F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
@@ -48,7 +48,8 @@ def _params(lin: torch.nn.Linear, rows: Optional[slice] = None) -> Tuple[torch.T
 class SparseDiffGatedMlp:
     """``gate_proj`` / ``up_proj`` / ``fc2``: ``nn.Linear`` with or without bias, bf16 for the sparse steps; or ``gate_proj`` / ``up_proj``
     (or the fused ``fc1``) BOTH ``F8Linear`` with e4m3 weights and e4m3 inputs (``input_float8_dtype=torch.float8_e4m3fn``;
-    ``F8Linear.from_linear`` defaults to e5m2, which the kernel does not read) and ``fc2`` bf16 (GEMM2 gathers bf16 rows).
+    ``F8Linear.from_linear`` defaults to e5m2, which the kernel does not read).  ``fc2`` is bf16 (GEMM2 gathers bf16 rows) or, with
+    ``mlp.fp8_fc2`` on, an ``F8Linear`` with e4m3 weights (GEMM2 gathers e4m3 rows, ``fc2.scale_reciprocal`` on its sums).
     Their parameters are read at every call, so the model may be moved or cast after wrapping.  The sparse steps select columns with
     ``topk_indices``, which takes rows of 1024 columns or more: the hidden width ``F`` must be at least 1024."""
 
@@ -88,8 +89,7 @@ class SparseDiffGatedMlp:
                 raise ValueError(f"SparseDiffGatedMlp: the gated fp8 GEMM1 reads float8_e4m3fn weights and inputs only (got weight "
                                  f"{p.weight.dtype}, input_float8_dtype {getattr(p, 'input_float8_dtype', None)}); build the projection with "
                                  "F8Linear.from_linear(..., input_float8_dtype=torch.float8_e4m3fn)")
-        if fc2.weight.dtype in _F8:
-            raise ValueError("SparseDiffGatedMlp: fc2 must stay bf16 (GEMM2 gathers bf16 rows of fc2.weight^T); an fp8 fc2 is refused")
+        check_fc2("SparseDiffGatedMlp", fc2)    # bf16, or an e4m3 F8Linear with mlp.fp8_fc2 on
         self.fc2 = [fc2]
         self._fc2w_T = None             # ((address, dtype, device) of the fc2.weight it was made from, its transpose)
         self.layer_counter = layer_counter
@@ -214,11 +214,12 @@ class SparseDiffGatedMlp:
             ops.mlp_glu_fp8(x=xq if batched else xq[0], w_gate=gate[0], w_up=up[0], b_gate=gate[1], b_up=up[1],
                             act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
                             cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add,
-                            scale_a=qgate.input_scale_reciprocal, scale_b_gate=qgate.scale_reciprocal, scale_b_up=qup.scale_reciprocal)
+                            scale_a=qgate.input_scale_reciprocal, scale_b_gate=qgate.scale_reciprocal, scale_b_up=qup.scale_reciprocal,
+                            fc2_scale=fc2_scale_of(self.fc2[0]))
         else:
             ops.mlp_glu(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], b_gate=gate[1], b_up=up[1],
                         act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
-                        cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add)
+                        cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add, fc2_scale=fc2_scale_of(self.fc2[0]))
 
         # the operators updated the LOADED activation cache in place: its host copy has to follow (see SparseDiffMlp)
         holder = self.storage.sparse_act_T

@@ -136,5 +136,14 @@ def _register():
         torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_glu_fp8: unknown activation '{act}'")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm2_w8")
+    def _(mma_a, mma_b, scale_b, indices, counts, mma_c):
+        # accumulates into mma_c in place and returns nothing
+        torch._check(mma_b.dtype == torch.float8_e4m3fn, lambda: "mma_b must be float8_e4m3fn")
+        torch._check(scale_b.dtype == torch.float32 and scale_b.numel() == 1, lambda: "scale_b must be a one-element float32 tensor on the GPU")
+        torch._check(mma_b.ndim == 2 and mma_b.shape[0] == mma_a.shape[-1] and mma_c.shape == mma_a.shape[:-1] + (mma_b.shape[1],),
+                     lambda: "shape mismatch (mma_b must be [F, N2], mma_c [M, N2], or [B, M, N2] with the batch size of mma_a)")
+        return None
+
 
 _register()

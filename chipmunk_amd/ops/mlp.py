@@ -86,9 +86,24 @@ def mm2_fused(packed: torch.Tensor, unpacked_colmajor: torch.Tensor, indices: to
 
 
 def csp_mlp_mm2(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
-                cached_out: torch.Tensor, num_sms: int = 0) -> None:
-    """Native counterpart of the reference's Triton ``csp_mlp_mm2`` (triton/csp_mlp_mm2.py:104-129)."""
+                cached_out: torch.Tensor, num_sms: int = 0, fc2_scale: Optional[torch.Tensor] = None) -> None:
+    """Native counterpart of the reference's Triton ``csp_mlp_mm2`` (triton/csp_mlp_mm2.py:104-129).  An e4m3 ``fc2wT`` (``[F, N]``
+    ``float8_e4m3fn``, plain row-major) takes the weight-only fp8 GEMM2 and needs ``fc2_scale``, the weight's RECIPROCAL quantisation scale
+    (``F8Linear.scale_reciprocal``), which multiplies the fp32 sums before they are rounded to bf16."""
+    if fc2wT.dtype == torch.float8_e4m3fn:
+        if fc2_scale is None:
+            raise ValueError("csp_mlp_mm2: an e4m3 fc2wT needs fc2_scale, the weight's reciprocal quantisation scale (F8Linear.scale_reciprocal)")
+        torch.ops.chipmunk.csp_mlp_mm2_w8(sparse_act_packed, fc2wT, fc2_scale.reshape(1).float(), indices, counts, cached_out)
+        return
     torch.ops.chipmunk.csp_mlp_mm2(sparse_act_packed, fc2wT, indices, counts, cached_out)
+
+
+def _mm2_w8_after_gemm1(sparse_act_packed: torch.Tensor, fc2w_T: torch.Tensor, fc2_scale: Optional[torch.Tensor], indices: torch.Tensor,
+                        counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int) -> None:
+    """The tail of a sparse step with an e4m3 ``fc2w_T`` whose GEMM1 left the cache alone: the scatter-add of the packed deltas, then the
+    weight-only fp8 GEMM2 (``csp_mlp_mm2_and_scatter_add`` is bf16-only)."""
+    scatter_add(sparse_act_packed, sparse_act_T, indices, counts, num_sms_scatter_add)
+    csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
 
 
 def mm2_unfused(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, cached_out: torch.Tensor,
@@ -104,11 +119,14 @@ def mm2_unfused(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, cached_out
 @torch.compiler.disable
 def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: torch.Tensor, fc2w_T: torch.Tensor, indices: torch.Tensor,
             counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
-            mm1_scale_a: Optional[torch.Tensor] = None, mm1_scale_b: Optional[torch.Tensor] = None) -> None:
+            mm1_scale_a: Optional[torch.Tensor] = None, mm1_scale_b: Optional[torch.Tensor] = None,
+            fc2_scale: Optional[torch.Tensor] = None) -> None:
     # M is any positive row count (ceil(M / 128) groups, the last one short); sparse_act_T is [F, M], contiguous or -- required when
     # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers.
     # A batch: x [B, M, K1] with indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] (or the [..., :M] view of [B, F, ldc]) and
     # cached_out [B, M, N] -- one launch per kernel for all B sequences, the bits of B calls on the slices.
+    # fc2w_T float8_e4m3fn with fc2_scale (F8Linear.scale_reciprocal): the scatter-add is GEMM1's own (or csp_scatter_add with
+    # mlp.fused_scatter off) and GEMM2 gathers e4m3 rows.
     assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
     if x.ndim == 3:
         B = x.shape[0]
@@ -126,14 +144,19 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: torch.Tensor, fc2w_T: tor
             and amd_key("mlp", "fused_scatter")):
         # GEMM1 applies the scatter-add of its own deltas (same bits as the two-kernel form), GEMM2 runs alone
         mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
-        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out)
+        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
         return
     if (x.is_cuda and fc1w.dtype == torch.float8_e4m3fn and x.dtype == torch.float8_e4m3fn and amd_key("mlp", "fused_scatter")
             and not FP8_MM1_UPDATES_CACHE and K1 % 128 == 0):
         mm1_fp8_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b)
-        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out)
+        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
         return
     mm1(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b)
+    if fc2w_T.dtype == torch.float8_e4m3fn:
+        if fc1w.dtype == torch.float8_e4m3fn and FP8_MM1_UPDATES_CACHE:
+            raise ValueError("run_e2e: FP8_MM1_UPDATES_CACHE (GEMM1 stores the activation, the scatter-add adds the delta again) has no e4m3 fc2 form")
+        _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
+        return
     if USE_FUSED_MLP_MATMUL_2:
         mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out,
                   num_sms_scatter_add)
@@ -163,9 +186,10 @@ def mm1_glu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sparse_ac
 @torch.compiler.disable
 def run_e2e_glu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b_gate: Optional[torch.Tensor],
                 b_up: Optional[torch.Tensor], act: str, fc2w_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
-                sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int) -> None:
+                sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
+                fc2_scale: Optional[torch.Tensor] = None) -> None:
     """``run_e2e`` for a gated feed-forward ``fc2(act(x Wg^T + bg) * (x Wu^T + bu))``: only GEMM1 differs, GEMM2 and the scatter-add see
-    the same packed deltas.  Shapes, pitched cache and batches as for ``run_e2e``."""
+    the same packed deltas.  Shapes, pitched cache, batches and an e4m3 ``fc2w_T`` with ``fc2_scale`` as for ``run_e2e``."""
     assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
     if x.ndim == 3:
         B = x.shape[0]
@@ -181,9 +205,12 @@ def run_e2e_glu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b_gat
     if amd_key("mlp", "fused_scatter"):
         # GEMM1 applies the scatter-add of its own deltas (same bits as the two-kernel form), GEMM2 runs alone
         mm1_glu(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, update_cache=True)
-        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out)
+        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
         return
     mm1_glu(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, update_cache=False)
+    if fc2w_T.dtype == torch.float8_e4m3fn:
+        _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
+        return
     if USE_FUSED_MLP_MATMUL_2:
         mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out, num_sms_scatter_add)
     else:
@@ -212,9 +239,9 @@ def mm1_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, spars
 def run_e2e_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b_gate: Optional[torch.Tensor],
                     b_up: Optional[torch.Tensor], act: str, fc2w_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
                     sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int, scale_a: torch.Tensor,
-                    scale_b_gate: torch.Tensor, scale_b_up: torch.Tensor) -> None:
-    """``run_e2e_glu`` with the gated fp8 GEMM1 (``x`` already quantised to e4m3): the packed deltas are bf16, so GEMM2 (bf16 ``fc2w_T``) and
-    the scatter-add are the operators of the bf16 route."""
+                    scale_b_gate: torch.Tensor, scale_b_up: torch.Tensor, fc2_scale: Optional[torch.Tensor] = None) -> None:
+    """``run_e2e_glu`` with the gated fp8 GEMM1 (``x`` already quantised to e4m3): the packed deltas are bf16, so GEMM2 (``fc2w_T`` bf16, or
+    e4m3 with ``fc2_scale``) and the scatter-add are the operators of the bf16 route."""
     assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
     if x.ndim == 3:
         B = x.shape[0]
@@ -230,9 +257,12 @@ def run_e2e_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b
     sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)   # bf16: x is fp8
     if amd_key("mlp", "fused_scatter"):
         mm1_glu_fp8(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, *scales, update_cache=True)
-        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out)
+        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
         return
     mm1_glu_fp8(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, *scales, update_cache=False)
+    if fc2w_T.dtype == torch.float8_e4m3fn:
+        _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
+        return
     if USE_FUSED_MLP_MATMUL_2:
         mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out, num_sms_scatter_add)
     else:

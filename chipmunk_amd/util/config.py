@@ -118,6 +118,10 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # (ops.mask_to_ragged_indices), in the mask step and in every sparse step whose rows were not kept; the padded [B, H, G, pad192(N)]
     # int32 tensor (7.1 GB per HunyuanVideo layer, 137 GB at 524 288 keys) and its compaction are not made.  Same bits.
     "attn.ragged_mask_to_indices": True,
+    # fp8 fc2 in the sparse MLP: recursive_swap_linears also swaps fc2 of a sparse image MLP and SparseDiffMlp / SparseDiffGatedMlp accept an
+    # F8Linear fc2 with e4m3 weights -- the sparse steps' GEMM2 then gathers e4m3 rows of fc2.weight^T (csp_mlp_mm2_w8: 1 byte per weight
+    # in HBM and through the gather instead of 2 + 2).  Off by default: fc2 stays bf16, as in the reference.
+    "mlp.fp8_fc2": False,
 }
 BASE_CONFIG["offloading"]["keep_resident_if_fits"] = AMD_EXTRA_KEYS["offloading.keep_resident_if_fits"]
 BASE_CONFIG["offloading"]["hbm_budget_gb"] = AMD_EXTRA_KEYS["offloading.hbm_budget_gb"]
@@ -134,6 +138,7 @@ BASE_CONFIG["attn"]["keep_unpacked_indices"] = AMD_EXTRA_KEYS["attn.keep_unpacke
 BASE_CONFIG["attn"]["keep_unpacked_indices_offloaded"] = AMD_EXTRA_KEYS["attn.keep_unpacked_indices_offloaded"]
 BASE_CONFIG["attn"]["kept_indices_offloaded_budget_gb"] = AMD_EXTRA_KEYS["attn.kept_indices_offloaded_budget_gb"]
 BASE_CONFIG["attn"]["ragged_mask_to_indices"] = AMD_EXTRA_KEYS["attn.ragged_mask_to_indices"]
+BASE_CONFIG["mlp"]["fp8_fc2"] = AMD_EXTRA_KEYS["mlp.fp8_fc2"]
 
 GLOBAL_CONFIG: Dict[str, Any] = copy.deepcopy(BASE_CONFIG)
 

@@ -270,6 +270,18 @@ int chipmunk_csp_mlp_mm1_glu_fp8_batched(const void *a, const void *b_gate, cons
                                          int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
                                          void *stream);
 
+/* fp8 fc2: GEMM (ii) over e4m3 rows of fc2^T (weight-only fp8).  mma_a [M,F] bf16 packed deltas, mma_b [F,N2] OCP e4m3 bytes
+ * (float8_e4m3fn), plain row-major, scale_b one device float -- the weight's RECIPROCAL quantisation scale --, mma_c [M,N2] bf16:
+ *   mma_c[m,:] = bf16( bf16( (sum_{c < counts[g]} mma_a[m,c] * f(mma_b[indices[g,c],:])) * scale_b[0] ) + mma_c[m,:] )
+ * f widens e4m3 to bf16 (exact); the sum is chipmunk_csp_mlp_mm2's, in fp32, on the widened weights, so with scale_b a power of two the
+ * result has the bits of chipmunk_csp_mlp_mm2 on bf16(f(mma_b) * scale_b).  Any M > 0 (the *_ragged contract), indices / counts / groups
+ * as for chipmunk_csp_mlp_mm2[_ragged|_batched]; N2 a positive multiple of 16 (one 16-byte chunk of a row is 16 columns); M*F, F*N2 and
+ * M*N2 below 2^31 per sequence; *_batched: B sequences, B * ceil(M/128) <= 65535. */
+int chipmunk_csp_mlp_mm2_w8(const void *mma_a, const void *mma_b, const float *scale_b, void *mma_c, const int32_t *indices,
+                            const int32_t *counts, int M, int F, int N2, void *stream);
+int chipmunk_csp_mlp_mm2_w8_batched(const void *mma_a, const void *mma_b, const float *scale_b, void *mma_c, const int32_t *indices,
+                                    const int32_t *counts, int M, int F, int N2, int B, void *stream);
+
 /* ---------------------------------------------------------------- indexed IO
  * Replaces chipmunk::topk_indices (reference csrc/indexed_io/topk_indices.cu:145-218; schema chipmunk.cpp:58).
  * activation [B*R, C] of `dtype`; indices [B*R, C] int32; counts [B*R] int32.  Threshold = element

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_glu mm1_glu_fp8 mm2 scatter fp8_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -226,6 +226,49 @@ def bench_mm1_glu_fp8(M=32768, K=1536, F=8960, keep=2816, act="silu"):
     print(f"mm1_glu_fp8 / mm1_fp8: {med['glu'] / med['mm1']:7.3f}")
 
 
+def bench_mm2_w8(M=4352, F=12288, N2=3072, keep=3840):
+    """The weight-only fp8 GEMM2 (csp_mlp_mm2_w8: e4m3 rows of fc2^T) against the bf16 csp_mlp_mm2 on the same packed deltas, index lists
+    and shape.  Same process, the two alternating (KB_ROUNDS pairs, default 5); per launch the median bracket of `timeit` (20 launches,
+    clocks warmed), then the median and the range over the rounds.  KB_LAYERS=n rotates n sets of weights / deltas / outputs (n = 8: the
+    weight rows come from HBM, not from the Infinity Cache)."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    sets = []
+    for _ in range(L):
+        w = torch.randn(F, N2, device=dev, generator=g) * 0.02
+        w8 = (w * 512).clamp(-448, 448).to(torch.float8_e4m3fn)
+        packed = torch.randn(M, F, device=dev, dtype=torch.bfloat16, generator=g) * 0.1
+        sets.append((w.to(torch.bfloat16), w8, packed, torch.zeros(M, N2, device=dev, dtype=torch.bfloat16)))
+    sb = torch.tensor([1 / 512.0], device=dev)
+    G = (M + 127) // 128
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_w8():
+        _, w8, packed, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm2_w8(packed, w8, sb, inds, counts, out)
+
+    def run_bf16():
+        w16, _, packed, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm2(packed, w16, inds, counts, out)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {"w8": [], "bf16": []}
+    for _ in range(rounds):
+        t["w8"].append(timeit(run_w8) * 1e3)
+        t["bf16"].append(timeit(run_bf16) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * N2 * keep
+    tag = f"(M={M} F={F} N2={N2} keep={keep} layers={L}, {rounds} alternating rounds)"
+    print(f"mm2_w8  e4m3 rows: {med['w8']:8.1f} us  [{min(t['w8']):.1f} .. {max(t['w8']):.1f}]  {flops/med['w8']/1e6:7.1f} TFLOP/s   {tag}")
+    print(f"mm2     bf16 rows: {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]  {flops/med['bf16']/1e6:7.1f} TFLOP/s")
+    print(f"mm2_w8 / mm2     : {med['w8'] / med['bf16']:8.3f}")
+
+
 def bench_fp8_wan(M=32768, ldc=None):
     """BASELINE config C5 (Wan2.1-1.3B, 832x480x81 -> 32 760 tokens padded to 32 768): fp8 e4m3 GEMM1, M = 32768, K = 1536,
     F = 8960, keep 0.3 (2688 columns); bf16 GEMM1 at the same shape beside it.  M = 32760: the ragged launch on the tokens as they are
@@ -375,6 +418,10 @@ def main():
             bench_mm1_glu(act=os.environ.get("KB_GLU_ACT", "silu"))
         elif w == "mm1_glu_fp8":      # gated fp8 GEMM1 at the Wan fp8 shape against the ungated fp8 launch of equal work (KB_GLU_ACT as mm1_glu)
             bench_mm1_glu_fp8(act=os.environ.get("KB_GLU_ACT", "silu"))
+        elif w == "mm2_w8":           # weight-only fp8 GEMM2 against the bf16 GEMM2 at the FLUX shape, 30 % of 12 288 columns kept
+            bench_mm2_w8()
+        elif w == "mm2_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), N2 = 1 536, F = 8 960, 2 816 kept
+            bench_mm2_w8(M=32760, F=8960, N2=1536, keep=2816)
         elif w == "fp8_wan":
             bench_fp8_wan()
         elif w == "mm2_wan":          # GEMM2 at the Wan2.1 1.3B shape (configs[4]): M = 32 768 rows, N2 = 1 536, F = 8 960, 30 % kept
