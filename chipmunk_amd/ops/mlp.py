@@ -89,7 +89,11 @@ def csp_mlp_mm2(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, indices: t
                 cached_out: torch.Tensor, num_sms: int = 0, fc2_scale: Optional[torch.Tensor] = None) -> None:
     """Native counterpart of the reference's Triton ``csp_mlp_mm2`` (triton/csp_mlp_mm2.py:104-129).  An e4m3 ``fc2wT`` (``[F, N]``
     ``float8_e4m3fn``, plain row-major) takes the weight-only fp8 GEMM2 and needs ``fc2_scale``, the weight's RECIPROCAL quantisation scale
-    (``F8Linear.scale_reciprocal``), which multiplies the fp32 sums before they are rounded to bf16."""
+    (``F8Linear.scale_reciprocal``), which multiplies the fp32 sums before they are rounded to bf16.
+
+    ``counts`` must be multiples of 8: both GEMM2 kernels mask the packed columns past a count in whole 16-byte pieces (the reference's
+    Triton kernel reads whole k blocks), so a count of 154 would take columns 154 .. 159 of ``sparse_act_packed`` into the sum.
+    ``topk_indices`` emits multiples of ``counts_multiple_of`` (256 / 128 as shipped).  GEMM1 and the scatter-add take any count."""
     if fc2wT.dtype == torch.float8_e4m3fn:
         if fc2_scale is None:
             raise ValueError("csp_mlp_mm2: an e4m3 fc2wT needs fc2_scale, the weight's reciprocal quantisation scale (F8Linear.scale_reciprocal)")

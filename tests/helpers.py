@@ -327,3 +327,275 @@ def straddle_inputs(align, pattern, threshold, mult, period, nq, nk, seed, plant
     bound = mult * q.double().norm(dim=-1) * kmax[..., None] * SCALE_LOG2E / threshold
     assert ((bound - f).abs() < 2e-3).all()
     return q, k, v.to(torch.bfloat16), bound
+
+
+# --------------------------------------------------------------------------- sparse-MLP kernels: exact references + segment metric
+# The GEMM1 operators write packed deltas act(h) - cache, the GEMM2 operators add packed x fc2^T[kept] to a base.  Both shrink
+# with the regime (a cache that holds the previous step's activations leaves deltas a tenth of the activations), so an
+# absolute tolerance sees no 1 % defect there.  The error is taken per row and per SEGMENT of W columns against plain fp64:
+# docs/TEST_SENSITIVITY.md, "Sparse MLP kernels".
+#
+# ORACLE_MLP_SEG_ERR: the largest segment error of the CPU references (the oracle where it has the operator, the plain-torch
+# mirrors elsewhere) against the exact references below over the case list of tests/test_mlp_metric_cpu.py, derived terms
+# taken off, rounded up to two digits; that file pins it.
+# MLP_SEG_MARGIN: what a correct kernel may do differently (summation order, MFMA accumulation, hardware exp / tanh).
+# tests/test_mlp_metric_cpu.py caps margin * floor at half the weakest counted mutant's error.
+MLP_BM = 128                  # token rows that share one index list
+MLP_SEG_W1 = 64               # GEMM1's packed deltas and cache columns: the kernel's column sub-tile
+MLP_SEG_W2 = 256              # GEMM2's output: GEMM2_BN
+ORACLE_MLP_SEG_ERR = 0.0035
+MLP_SEG_MARGIN = 2.0
+MLP_SEG_BOUND = MLP_SEG_MARGIN * ORACLE_MLP_SEG_ERR
+MLP_ACTS = ("gelu_tanh", "silu", "gelu")
+MLP_COUNTS = {333: [512, 208, 40], 1000: [512, 0, 208, 16, 40, 512, 64, 272]}      # M -> kept columns per 128-row group
+F8 = torch.float8_e4m3fn
+
+
+def _segments(t, width):
+    pad = (-t.shape[-1]) % width
+    return torch.nn.functional.pad(t, (0, pad)).unflatten(-1, (-1, width))
+
+
+def seg_rel_err(got, exact, width, cols=None):
+    """Per row i and segment s of `width` columns ``||got[i, seg] - exact[i, seg]||_2 / ||exact[i, seg]||_2`` in fp64:
+    ``[..., rows, n] -> [..., rows, ceil(n / width)]``, the last segment short.  cols ``[..., rows]``: the row's live column
+    count (its group's kept columns); the columns at or past it are no part of the result and of no segment.  As `row_rel_err`:
+    a NaN / Inf in a live ``got`` element is an infinite error, a segment whose exact value is 0 (a group without kept
+    columns, a segment past the count) has error 0 if reproduced exactly, else infinite."""
+    exact = exact.double()
+    got = got.to(exact.device).double()
+    if cols is not None:
+        live = torch.arange(exact.shape[-1], device=exact.device) < cols.to(exact.device)[..., None]
+        got, exact = torch.where(live, got, torch.zeros_like(got)), torch.where(live, exact, torch.zeros_like(exact))
+    g, x = _segments(got, width), _segments(exact, width)
+    num, den = (g - x).norm(dim=-1), x.norm(dim=-1)
+    err = num / den
+    err = torch.where(den == 0, torch.where(num == 0, torch.zeros_like(num), torch.full_like(num, float("inf"))), err)
+    return torch.where(torch.isfinite(g).all(dim=-1) & ~torch.isnan(err), err, torch.full_like(err, float("inf")))
+
+
+def seg_term(result, exact, width, cols=None):
+    """``2^-8 ||result[i, seg]|| / ||exact[i, seg]||``, the shape of `seg_rel_err`: what one more bf16 rounding of a stored
+    ``result`` (8 significant bits: element e moves by at most 2^-8 |result_e|) can add to the segment error against
+    ``exact``; 0 where the segment's exact value is 0."""
+    exact = exact.double()
+    result = torch.nan_to_num(result.to(exact.device).double(), nan=0.0, posinf=0.0, neginf=0.0)
+    if cols is not None:
+        live = torch.arange(exact.shape[-1], device=exact.device) < cols.to(exact.device)[..., None]
+        result, exact = torch.where(live, result, torch.zeros_like(result)), torch.where(live, exact, torch.zeros_like(exact))
+    num, den = _segments(result, width).norm(dim=-1), _segments(exact, width).norm(dim=-1)
+    return torch.where(den > 0, BF16_EPS * num / den, torch.zeros_like(den))
+
+
+def refreshed_cache_term(result, fresh, delta, bound, width, cols=None, act_rounded=False):
+    """The per-segment allowance, beyond `bound`, of a cache column refreshed as ``bf16(cache + delta^)`` and held against the
+    fresh fp64 activation: the packed delta is within ``bound ||delta_seg||`` of exact (asserted on its own), the stored sum is
+    rounded once more (2^-8 ||result_seg||, `assert_delta_rows_close`'s term), and a route that rounds the activation to bf16
+    before it subtracts (ungated fp8, `act_rounded`) adds 2^-8 ||fresh_seg||.  Relative to ||fresh_seg||:
+    ``error <= bound rho + 2^-8 ||result_seg|| / ||fresh_seg|| (+ 2^-8)`` with ``rho = ||delta_seg|| / ||fresh_seg||``; returned is that
+    minus `bound`.  With the previous step's activations in the cache rho is 0.1 - 0.2 and the allowance is the one rounding of
+    the stored sum: a refreshed column is one rounding from fresh.  With a random cache rho is 1.4 - 4."""
+    rho = seg_term(delta, fresh, width, cols) / BF16_EPS
+    term = bound * (rho - 1.0) + seg_term(result, fresh, width, cols) + (BF16_EPS if act_rounded else 0.0)
+    return torch.where(rho > 0, term, torch.zeros_like(term))          # (no allowance where nothing is refreshed: those segments are exact)
+
+
+def assert_segs_close(got, exact, bound, what, extra=None, width=MLP_SEG_W1, cols=None):
+    """Every segment of every row of ``got`` ``[rows, n]`` (or ``[B, rows, n]``) within `bound` of ``exact`` (see `seg_rel_err`;
+    rows in groups of 128); ``extra``, the shape of the error, widens the bound per segment by a derived term.  Returns the
+    worst ``error - extra``."""
+    assert got.shape == exact.shape, (got.shape, exact.shape)
+    err = seg_rel_err(got, exact, width, cols)
+    if extra is not None:
+        err = err - extra.to(err.device)
+    worst = float(err.max()) if err.numel() else 0.0
+    bad = ~(err <= bound)
+    shown = err[(err != 0) | bad]          # (the record: segments with a result; those of empty groups and past the counts are exact or bad)
+    _record_row_err(what, float(shown.max()) if shown.numel() else worst, bound)
+    if bad.any():
+        flat = int(torch.nan_to_num(err, nan=float("inf")).argmax())
+        R, S = err.shape[-2], err.shape[-1]
+        b, r, s = flat // (R * S), (flat // S) % R, flat % S
+        live = got.to(exact.device) if cols is None else got.to(exact.device)[torch.arange(exact.shape[-1], device=exact.device) < cols.to(exact.device)[..., None]]
+        raise AssertionError(
+            f"{what}: segment error {worst:.4g} > {bound:.4g} at batch {b} group {r // MLP_BM} row {r} (row {r % MLP_BM} of its "
+            f"group) segment {s} (columns {s * width} to {min(exact.shape[-1], (s + 1) * width) - 1}); {int(bad.sum())} / "
+            f"{bad.numel()} segments over the bound, {int((~torch.isfinite(live.float())).sum())} non-finite elements")
+    return worst
+
+
+def mlp_act64(act, x):
+    """the activations of DESIGN "Gated MLPs" in the precision of ``x``"""
+    if act == "gelu_tanh":
+        return 0.5 * x * (1.0 + torch.tanh(0.7978845608028654 * (x + 0.044715 * x * x * x)))
+    if act == "silu":
+        return x * torch.sigmoid(x)
+    assert act == "gelu", act
+    return 0.5 * x * (1.0 + torch.erf(x / 2.0 ** 0.5))
+
+
+def mlp_group_cols(counts, M):
+    """[M] long: the kept-column count of every token row's 128-row group"""
+    return counts.long().repeat_interleave(MLP_BM)[:M]
+
+
+def mm1_exact(a, w, bias, cache, inds, counts, act="gelu_tanh", w_up=None, bias_up=None, scales=None, pre_mul=1.0):
+    """GEMM1 by its definition (ops/mlp.py, DESIGN "Gated MLPs"), fp64, plain torch on the inputs' device: per 128-row group g
+    and packed column j < counts[g], with col = inds[g, j],
+    ``fresh[m, j] = act(a[m] . w[col] * s + bias[col]) (* (a[m] . w_up[col] * s_up + bias_up[col]))`` and
+    ``delta[m, j] = fresh[m, j] - cache[col, m]``.  a ``[M, K]``, w / w_up ``[F, K]``, bias / bias_up ``[F]`` or None, cache
+    ``[F, M]``.  e4m3 operands are widened exactly; scales = (scale_a, scale_b[, scale_b_up]), the RECIPROCAL quantisation
+    scales as the fp32 numbers the operator receives.  pre_mul multiplies the (gate's) pre-activation: a defect of
+    tests/test_mlp_metric_cpu.py.  Returns (delta, fresh) ``[M, F]`` in the packed layout, 0 at and past the counts."""
+    M, F = a.shape[0], w.shape[0]
+    s = [1.0, 1.0]
+    if scales is not None:
+        ra = float(scales[0].double())
+        s = [ra * float(scales[1].double()), ra * float(scales[2 if len(scales) > 2 else 1].double())]
+    delta = torch.zeros(M, F, dtype=torch.float64, device=a.device)
+    fresh = torch.zeros_like(delta)
+    ad, wd, ud = a.double(), w.double(), None if w_up is None else w_up.double()      # (e4m3 -> fp64 is exact)
+    for g in range(inds.shape[0]):
+        rows, n = slice(g * MLP_BM, min(M, (g + 1) * MLP_BM)), int(counts[g])
+        if n == 0:
+            continue
+        col = inds[g, :n].long()
+        h = (ad[rows] @ wd[col].T) * s[0]
+        if bias is not None:
+            h = h + bias[col].double()
+        f = mlp_act64(act, h * pre_mul)
+        if w_up is not None:
+            u = (ad[rows] @ ud[col].T) * s[1]
+            f = f * (u if bias_up is None else u + bias_up[col].double())
+        fresh[rows, :n] = f
+        delta[rows, :n] = f - cache[col][:, rows].double().T
+    return delta, fresh
+
+
+def mm2_exact(packed, w2T, inds, counts, scale=None):
+    """GEMM2's product by its definition, fp64: ``prod[m] = sum_{j < counts[g]} packed[m, j] * w2T[inds[g, j]]`` (``* scale``, the
+    reciprocal quantisation scale of an e4m3 ``w2T`` as the fp32 number the operator receives); the packed columns at and past
+    the counts are not read.  ``[M, N2]``, 0 for the rows of a group without kept columns."""
+    M = packed.shape[0]
+    out = torch.zeros(M, w2T.shape[1], dtype=torch.float64, device=packed.device)
+    wd = w2T.double()                                                                 # (e4m3 -> fp64 is exact)
+    for g in range(inds.shape[0]):
+        rows, n = slice(g * MLP_BM, min(M, (g + 1) * MLP_BM)), int(counts[g])
+        if n:
+            out[rows] = packed[rows, :n].double() @ wd[inds[g, :n].long()]
+    return out if scale is None else out * float(scale.double())
+
+
+def gathered_cache(cache, inds, counts):
+    """the cache ``[F, M]`` in the packed layout of the deltas: ``[M, F]`` with ``[m, j] = cache[inds[g, j], m]``, 0 at and past the counts"""
+    F, M = cache.shape
+    out = torch.zeros(M, F, dtype=cache.dtype, device=cache.device)
+    for g in range(inds.shape[0]):
+        rows, n = slice(g * MLP_BM, min(M, (g + 1) * MLP_BM)), int(counts[g])
+        out[rows, :n] = cache[inds[g, :n].long()][:, rows].T
+    return out
+
+
+def quantize_e4m3(t):
+    """(e4m3 tensor, reciprocal scale [1] fp32) with scale = 448 / amax: no power of two on random data"""
+    s = 448.0 / t.abs().max()
+    return (t * s).clamp(-448.0, 448.0).to(F8), (1.0 / s).reshape(1).float()
+
+
+# --------------------------------------------------------------------------- inputs shared by test_gpu_mlp_accuracy.py and the CPU
+# test that measures the references on them (tests/test_mlp_metric_cpu.py); all CPU tensors, at the data scales of the
+# existing MLP tests: a 0.5, weights 0.06, biases 0.1
+
+
+def mlp_problem(M, K, F, seed, regime="random", act="gelu_tanh", fp8=False, gated=False, biases=True, counts=None):
+    """One GEMM1 problem.  regime "random": the cache is 0.3 randn.  "previous step": the cache holds bf16 of the activations
+    of x0 and the operator sees x = x0 + 0.05 randn, the regime the method runs in (deltas small against the activations).
+    fp8: a / w / wu are e4m3 with reciprocal scales ra / rb / rbu (the up weight is twice the gate's size, so the two weight
+    scales differ by about 2 x); x0 is quantised with x's scale."""
+    counts = MLP_COUNTS[M] if counts is None else counts
+    G = (M + MLP_BM - 1) // MLP_BM
+    assert len(counts) == G
+    g = torch.Generator().manual_seed(seed)
+    rnd = lambda *shape, scale: torch.randn(*shape, generator=g) * scale      # noqa: E731
+    x0, w, wu = rnd(M, K, scale=0.5), rnd(F, K, scale=0.06), rnd(F, K, scale=0.12 if fp8 else 0.06)
+    bias, bu = rnd(F, scale=0.1).to(torch.bfloat16), rnd(F, scale=0.1).to(torch.bfloat16)
+    cache = rnd(F, M, scale=0.3).to(torch.bfloat16)
+    inds = torch.stack([torch.randperm(F, generator=g) for _ in range(G)]).to(torch.int32)
+    step = rnd(M, K, scale=0.05)
+    p = dict(M=M, K=K, F=F, G=G, counts=list(counts), regime=regime, act=act, fp8=fp8, gated=gated, inds=inds,
+             cnt=torch.tensor(counts, dtype=torch.int32), bias=bias if biases else None, bu=bu if biases and gated else None)
+    x = x0 if regime == "random" else x0.to(torch.bfloat16).float() + step
+    if fp8:
+        p["a"], p["ra"] = quantize_e4m3(x)
+        a0 = (x0 / p["ra"]).clamp(-448.0, 448.0).to(F8)
+        p["w"], p["rb"] = quantize_e4m3(w)
+        p["wu"], p["rbu"] = quantize_e4m3(wu)
+        if not gated:
+            del p["wu"], p["rbu"]
+    else:
+        p["a"], a0, p["w"] = x.to(torch.bfloat16), x0.to(torch.bfloat16), w.to(torch.bfloat16)
+        if gated:
+            p["wu"] = wu.to(torch.bfloat16)
+    if regime != "random":
+        assert regime == "previous step", regime
+        every = torch.arange(F, dtype=torch.int32).expand(G, F)
+        fresh0 = mm1_exact(a0, p["w"], p["bias"], torch.zeros(F, M), every, [F] * G, **mlp_exact_args(p))[1]
+        cache = fresh0.T.to(torch.bfloat16).contiguous()
+    p["cache0"] = cache
+    return p
+
+
+def mlp_exact_args(p):
+    """the keyword arguments of `mm1_exact` that state the operator of problem `p`"""
+    kw = dict(act=p["act"])
+    if p["gated"]:
+        kw.update(w_up=p["wu"], bias_up=p["bu"])
+    if p["fp8"]:
+        kw["scales"] = (p["ra"], p["rb"], p["rbu"]) if p["gated"] else (p["ra"], p["rb"])
+    return kw
+
+
+def mlp2_problem(M, F, N2, seed, counts=None):
+    """One GEMM2 problem: packed ``[M, F]`` 0.2 randn with NaN at and past each group's count, w2T ``[F, N2]`` 0.05 randn (bf16,
+    and as e4m3 `w8` with its reciprocal scale `r8`), one index permutation per group."""
+    counts = MLP_COUNTS[M] if counts is None else counts
+    G = (M + MLP_BM - 1) // MLP_BM
+    g = torch.Generator().manual_seed(seed)
+    packed = (torch.randn(M, F, generator=g) * 0.2).to(torch.bfloat16)
+    w = torch.randn(F, N2, generator=g) * 0.05
+    inds = torch.stack([torch.randperm(F, generator=g) for _ in range(G)]).to(torch.int32)
+    for gi, n in enumerate(counts):
+        packed[gi * MLP_BM:(gi + 1) * MLP_BM, n:] = float("nan")
+    w8, r8 = quantize_e4m3(w)
+    return dict(M=M, F=F, N2=N2, G=G, counts=list(counts), packed=packed, w2T=w.to(torch.bfloat16), w8=w8, r8=r8, inds=inds,
+                cnt=torch.tensor(counts, dtype=torch.int32), seed=seed)
+
+
+def mlp1_cases():
+    """name -> `mlp_problem` arguments: the GEMM1 case list of both MLP accuracy files.  M = 333 (three groups, the last of 77 rows)
+    and 1000 (eight groups, one empty); K = 320 / 256 for bf16 operands (five / four 64-wide k steps), 384 for e4m3 (three 128-wide
+    steps); every operator in both cache regimes; the gated operators with the three activations and, at M = 333, without biases."""
+    out = {}
+    for M in (333, 1000):
+        for regime in ("random", "previous step"):
+            for kind in ("bf16", "fp8", "glu", "glu fp8"):
+                fp8, gated = "fp8" in kind, "glu" in kind
+                K = 384 if fp8 else 320 if M == 333 else 256
+                for act in (MLP_ACTS if gated else ("gelu_tanh",)):
+                    for biases in ((True, False) if gated and M == 333 else (True,)):
+                        name = f"{kind} {act}{'' if biases else ' no bias'} M{M} K{K}, {regime} cache"
+                        out[name] = dict(M=M, K=K, F=512, seed=100 + len(out), regime=regime, act=act, fp8=fp8, gated=gated, biases=biases)
+    return out
+
+
+def mlp2_cases():
+    """name -> `mlp2_problem` arguments: N2 = 384 (one full and one half 256-column tile) and 512 (two full tiles)"""
+    return {f"M{M} N{N2}": dict(M=M, F=512, N2=N2, seed=300 + M + N2) for M in (333, 1000) for N2 in (384, 512)}
+
+
+def mlp2_base(p, kind, exact):
+    """the tensor GEMM2 accumulates into: "zero", "product" (randn of the exact product's rms: the accumulate term stays below
+    the bound) or "unit" (randn: shows that the base survives and the product is added once, and little else)"""
+    g = torch.Generator().manual_seed(p["seed"] + 7)
+    scale = {"zero": 0.0, "product": float(exact.pow(2).mean().sqrt()), "unit": 1.0}[kind]
+    return (torch.randn(p["M"], p["N2"], generator=g) * scale).to(torch.bfloat16)

@@ -87,9 +87,14 @@ def test_from_fused_with_the_up_half_first_gives_the_bits_of_two_projections(dev
         lc.singleton.__init__(0, 0)
         chk = run(dev, cfgmod.GLOBAL_CONFIG, "gelu_tanh_bias", fused=fused)
         st = chk.modules[1].storage
-        outs.append([t.clone() for t in (st.get_out_cache(), st.get_sparse_act_T(), st.get_indices(), st.get_blockmean_mid_cache())])
+        # the index rows are torch.empty past their counts (topk_indices writes the kept columns only): what lies there is whatever the
+        # allocator handed out, so the lists are compared up to the counts, and the counts themselves
+        inds, counts = st.get_indices(), st.get_counts()
+        kept = torch.where(torch.arange(inds.shape[-1], device=inds.device) < counts[..., None], inds, torch.full_like(inds, -1))
+        outs.append([t.clone() for t in (st.get_out_cache(), st.get_sparse_act_T(), kept, counts, st.get_blockmean_mid_cache())])
     fc1 = chk.modules[0].projs[0]      # (of the second run: one projection, its second half the gate, used in place)
     assert fc1.weight.shape[0] == 2 * gm.F and chk.modules[0].gate[0].data_ptr() == fc1.weight.data[gm.F:].data_ptr()
+    assert int(outs[0][3].min()) > 0
     for a, b in zip(*outs):
         assert torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16 else a, b.view(torch.int16) if b.dtype == torch.bfloat16 else b)
 
