@@ -1456,11 +1456,12 @@ extern "C" int chipmunk_dense_colsum_attn(const void *q, const void *k, const vo
 // modules/attn.py:76-84) is never materialised.  Same bits as chipmunk_dense_colsum_attn followed by chipmunk_topk_mask.
 // Returns CHIPMUNK_ERR_UNSUPPORTED (nothing launched) when the launch does not take the one-pass route in one piece; the
 // caller then runs the two operators.
-extern "C" int chipmunk_dense_colsum_topk_mask_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
-                                               const int64_t k_strides[3], const int64_t v_strides[3], const float *pin, void *o,
-                                               const int64_t *o_strides, float *l, int B, int H, int Nq, int Nk, const void *static_mask,
-                                               int64_t static_stride, int static_rows, const void *group_flags, void *mask,
-                                               int topk, double random_amount, void *stream) {
+// (mass: the selection of chipmunk_topk_mask_p, topk is then the cap)
+static int dense_colsum_topk_mask_impl(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                       const int64_t k_strides[3], const int64_t v_strides[3], const float *pin, void *o,
+                                       const int64_t *o_strides, float *l, int B, int H, int Nq, int Nk, const void *static_mask,
+                                       int64_t static_stride, int static_rows, const void *group_flags, void *mask,
+                                       int topk, double random_amount, bool mass, double top_p, int k_min, void *stream) {
     if (int e = check_common(q, k, v, o, B, H, Nq, Nk)) return e;
     CM_CHECK(l && pin && mask, "dense_colsum_topk_mask: p / l / mask missing");
     if (int e = check_strides(q_strides, "q")) return e;
@@ -1482,8 +1483,31 @@ extern "C" int chipmunk_dense_colsum_topk_mask_strided(const void *q, const void
     if (!part) return CHIPMUNK_ERR_UNSUPPORTED;
     if (int e = chipmunk_dense64_colsum_launch(p, part, st)) return e;
     const int nrb = ((Nq + 255) / 256) * 2;
+    if (mass)
+        return chipmunk_topk_mask_p_parts(part, chipmunk_colsum_part_stride(Nk), nrb, p.G, Nq, static_mask, static_stride, static_rows, group_flags, mask,
+                                          B * H * p.G, Nk, topk, top_p, k_min, random_amount, st);
     return chipmunk_topk_mask_parts(part, chipmunk_colsum_part_stride(Nk), nrb, p.G, Nq, static_mask, static_stride, static_rows, group_flags, mask, B * H * p.G, Nk,
                                     topk, random_amount, st);
+}
+
+extern "C" int chipmunk_dense_colsum_topk_mask_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                               const int64_t k_strides[3], const int64_t v_strides[3], const float *pin, void *o,
+                                               const int64_t *o_strides, float *l, int B, int H, int Nq, int Nk, const void *static_mask,
+                                               int64_t static_stride, int static_rows, const void *group_flags, void *mask,
+                                               int topk, double random_amount, void *stream) {
+    return dense_colsum_topk_mask_impl(q, k, v, q_strides, k_strides, v_strides, pin, o, o_strides, l, B, H, Nq, Nk, static_mask, static_stride,
+                                       static_rows, group_flags, mask, topk, random_amount, false, 0.0, 0, stream);
+}
+
+extern "C" int chipmunk_dense_colsum_topk_mask_p_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                                 const int64_t k_strides[3], const int64_t v_strides[3], const float *pin, void *o,
+                                                 const int64_t *o_strides, float *l, int B, int H, int Nq, int Nk, const void *static_mask,
+                                                 int64_t static_stride, int static_rows, const void *group_flags, void *mask,
+                                                 int topk, double random_amount, double top_p, int k_min, void *stream) {
+    CM_CHECK(top_p > 0.0 && top_p <= 1.0, "dense_colsum_topk_mask_p: top_p must be in (0, 1] (got %g)", top_p);
+    CM_CHECK(k_min >= 0, "dense_colsum_topk_mask_p: k_min must be >= 0 (got %d)", k_min);
+    return dense_colsum_topk_mask_impl(q, k, v, q_strides, k_strides, v_strides, pin, o, o_strides, l, B, H, Nq, Nk, static_mask, static_stride,
+                                       static_rows, group_flags, mask, topk, random_amount, true, top_p, k_min, stream);
 }
 
 extern "C" int chipmunk_dense_colsum_topk_mask(const void *q, const void *k, const void *v, const int64_t q_strides[3],

@@ -53,6 +53,10 @@ int chipmunk_dense64_colsum_launch(const AttnParams &p, uint16_t *part, hipStrea
 int chipmunk_topk_mask_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
                              int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double random_amount,
                              hipStream_t stream);
+// ... with the top-p count of chipmunk_topk_mask_p in front of the selection (k is the cap)
+int chipmunk_topk_mask_p_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
+                               int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double top_p, int k_min,
+                               double random_amount, hipStream_t stream);
 size_t chipmunk_colsum_part_bytes(int B, int H, int Nq, int Nk);
 // elements between two partial rows: Nk rounded up to whole 128-byte lines, so that a wave's 64 sums of a key tile are ONE
 // aligned line (a row of 119 056 keys is 1 860.25 lines: at stride Nk every store straddled two)

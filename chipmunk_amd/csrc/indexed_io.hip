@@ -646,14 +646,52 @@ struct TopkMaskParams {
     const uint16_t *parts;
     int64_t pstride;         // elements between two partial rows
     int nrb, ngroups, nq;    // partial rows per (batch*head); 192-row groups per (batch*head); query rows
+    // MASS form: k is the cap; a row keeps the smallest top set that carries top_p of its column-sum mass, at least k_min columns
+    float top_p;
+    int k_min;
 };
+
+// ---- MASS (chipmunk_topk_mask_p): a per-row count in front of the selection.  The mass of a column is its bf16 value
+// where that is positive (keys 0x8000 .. 0xff80), 0 otherwise (negative, NaN; also the padding past n, key 0).
+//   total  = mass of the row,  target = float(top_p) * total                                                   (1 pass)
+//   T      = the largest key with mass{key >= T} >= target: bits 14..0 below the fixed top bit, since all mass has key >= 0x8000
+//            (15 passes; sums of a subset of non-negative terms in ONE fixed order are monotone in the subset, so this is a bisection)
+//   k_p    = #{key > T} + min(#{key == T}, max(1, ceil((target - mass{key > T}) / value(T))))                   (1 pass)
+//   k      = min(k, max(k_p, k_min)); k_p = 0 where total = 0.  The selection below then runs unchanged with this k.
+// Every sum is fp32 in one fixed order: inside a thread its columns ascending, the 64 lanes of a wave by the xor tree
+// (32, 16, .., 1: every lane ends with the same bits), then the 16 wave totals ascending.  Same launch, same bits.
+// The value of a key >= 0x8000 is float((key ^ 0x8000) << 16); under that map a key below 0x8000 (a negative value) gives a negative number
+// or a NaN, key 0 (the padding) gives -0.0, and a key above 0xff80 a NaN.  So "the key lies in [lo, 0xff80]" is ONE float compare,
+// value >= value(lo): false for every NaN and every negative number, and the -0.0 it lets through at lo = 0x8000 adds nothing.
+// A threshold above 0xff80 is a NaN itself: nothing passes, the mass is 0.
+__device__ __forceinline__ float key_value(uint32_t key) { return __uint_as_float((key ^ 0x8000u) << 16); }
+// both keys of a packed word, low column first, added to m
+__device__ __forceinline__ void add_mass2(float &m, uint32_t kw, float flo) {
+    const uint32_t kx = kw ^ 0x80008000u;
+    const float a = __uint_as_float(kx << 16), b = __uint_as_float(kx & 0xffff0000u);
+    m += a >= flo ? a : 0.f;
+    m += b >= flo ? b : 0.f;
+}
+
+__device__ __forceinline__ int topp_count(float total, float target, float above, int gt, int eq, uint32_t thr, int k, int k_min) {
+    int kp = 0;
+    if (total > 0.f && target > 0.f) {
+        const float v = key_value(thr);     // > 0: the keys equal to T carry the mass that reaches the target
+        float t = __builtin_ceilf((target - above) / v);
+        t = t >= 1.f ? t : 1.f;
+        kp = gt + (t < (float)eq ? (int)t : eq);
+    }
+    const int s = kp > k_min ? kp : k_min;
+    return s < k ? s : k;
+}
 
 __device__ __forceinline__ uint32_t bf16_key(uint32_t u) {  // monotone bf16 bits -> u16 (larger value = larger key)
     return (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);
 }
 
-template <int KPT, bool ALIGNED, bool PARTS = false>  // keys per thread (multiple of 4); the row must have n <= 1024 * KPT columns.
+template <int KPT, bool ALIGNED, bool PARTS = false, bool MASS = false>  // keys per thread (multiple of 4); the row must have n <= 1024 * KPT columns.
 // PARTS (ALIGNED only): the row's column sums are not in memory; they are the sum of up to three bf16 partial rows (see above)
+// MASS: the top-p count in front of the selection (see above); the values come back out of the key registers.
 // ALIGNED: n % 4 == 0 and every row of cs / static mask / mask starts on an 8 / 4 / 4-byte boundary, so each thread
 // step is one 8-byte load, one 4-byte load and one 4-byte store; the generic form goes element by element.
 __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p) {
@@ -734,7 +772,78 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
         return t;
     };
     const bool active = p.groups == nullptr || p.groups[row] != 0;
-    const int k = p.k < n ? p.k : n;
+    int k = p.k < n ? p.k : n;
+    if constexpr (MASS) {
+        if (active && k > 0) {   // (uniform over the workgroup)
+            // mass of the keys in [lo, 0xff80]: this thread's columns ascending, the wave's xor tree, the 16 wave totals ascending
+            auto block_mass = [&](uint32_t lo) {
+                const float flo = key_value(lo);
+                float m = 0.f;
+#pragma unroll
+                for (int j = 0; j < NV; ++j)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        // add_mass2 spelled out: two temporaries per word and nothing hoisted out of the rounds (the KPT = 120 forms have
+                        // 60 key registers of the 128 a 1024-thread workgroup gets; the compiler's own schedule of this loop spilled)
+                        uint32_t t, a;
+                        asm volatile("v_xor_b32 %1, 0x80008000, %3\n\t"
+                                     "v_lshlrev_b32 %2, 16, %1\n\t"
+                                     "v_and_b32 %1, 0xffff0000, %1\n\t"
+                                     "v_cmp_ge_f32 vcc, %2, %4\n\t"
+                                     "v_cndmask_b32 %2, 0, %2, vcc\n\t"
+                                     "v_add_f32 %0, %0, %2\n\t"
+                                     "v_cmp_ge_f32 vcc, %1, %4\n\t"
+                                     "v_cndmask_b32 %1, 0, %1, vcc\n\t"
+                                     "v_add_f32 %0, %0, %1"
+                                     : "+v"(m), "=&v"(t), "=&v"(a)
+                                     : "v"(key[j][h]), "s"(flo)
+                                     : "vcc");
+                    }
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) m += __shfl_xor(m, d);
+                if (lane == 0) wave_cnt[w] = __float_as_int(m);
+                __syncthreads();
+                float t = 0.f;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) t += __int_as_float(wave_cnt[i]);
+                __syncthreads();
+                return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t)));   // (the same bits in every lane: scalar registers)
+            };
+            // ONE rolled loop around the unrolled pass (three copies of it cost registers): round 0 the total, rounds 1..15 the bisection
+            // (a candidate above 0xff80 has mass 0 and is rejected), round 16 the mass above the threshold
+            float total = 0.f, target = 0.f, above = 0.f;
+            uint32_t res = 0x8000u;
+#pragma nounroll
+            for (int it = 0; it < 17; ++it) {
+                const uint32_t lo = it == 0 ? 0x8000u : (it < 16 ? (res | (0x8000u >> it)) : res + 1u);
+                const float m = block_mass(lo);
+                if (it == 0) {
+                    total = m, target = p.top_p * m;
+                    if (!(total > 0.f && target > 0.f)) break;   // (uniform: every thread holds the same bits)
+                } else if (it < 16) {
+                    if (m >= target) res = lo;
+                } else {
+                    above = m;
+                }
+            }
+            // #{key >= c} with the packed u16 counters of the selection's rounds below (three operations per two keys, nothing hoisted)
+            auto count_ge = [&](uint32_t c) {
+                const uint32_t cm1 = (c - 1u) | ((c - 1u) << 16), one2 = 0x00010001u;
+                uint32_t cnt2 = 0;
+#pragma unroll
+                for (int j = 0; j < NV; ++j)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        uint32_t d;
+                        asm volatile("v_pk_sub_u16 %0, %1, %2 clamp\n\tv_pk_min_u16 %0, %0, %3" : "=&v"(d) : "v"(key[j][h]), "v"(cm1), "v"(one2));
+                        asm volatile("v_pk_add_u16 %0, %0, %1" : "+v"(cnt2) : "v"(d));
+                    }
+                return __builtin_amdgcn_readfirstlane(block_count((int)(cnt2 & 0xffffu) + (int)(cnt2 >> 16)));
+            };
+            const int gt = count_ge(res + 1u), eq = count_ge(res) - gt;     // (res <= 0xff80)
+            k = topp_count(total, target, above, gt, eq, res, k, p.k_min);
+        }
+    }
     uint32_t thr = 0x10000u;  // keep nothing
     int ties_to_take = 0;
     if (active && k > 0) {
@@ -914,7 +1023,9 @@ __device__ __forceinline__ uint32_t bf16_key2(uint32_t u) {   // bf16_key on bot
     return u ^ (s | 0x80008000u);
 }
 
-template <bool ALIGNED, bool PARTS>
+// MASS: the top-p count (see key_value above) streams the row as well: 1 pass for the total, 15 bisection passes, 1 pass for the mass and
+// count above the threshold and the count at it -- 17 more reads of the row's 2n bytes from L2 in front of the 18 of the selection.
+template <bool ALIGNED, bool PARTS, bool MASS = false>
 __global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskParams p) {
     __shared__ int wave_cnt[16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -935,8 +1046,8 @@ __global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskPa
     const uint32_t lane_off8 = 8u * (uint32_t)tid;
     const int nsteps = (n + 4095) / 4096;
     const bool active = p.groups == nullptr || p.groups[row] != 0;
-    const int k = p.k < n ? p.k : n;
-    const bool select = active && k > 0;
+    int k = p.k < n ? p.k : n;
+    bool select = active && k > 0;
     const bool rnd = active && p.random_amount > 0.f;
 
     // (PARTS: the combined bf16 values of columns c0..c0+3, the additions in the order of the register form)
@@ -1018,6 +1129,60 @@ __global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskPa
         return t;
     };
     constexpr int U = ALIGNED ? 8 : 2;   // row loads in flight per thread
+    if constexpr (MASS) {
+        if (select) {   // (uniform over the workgroup)
+            // one pass: mass of the keys in [lo, 0xff80] (this thread's columns ascending, the wave's xor tree, the 16 wave totals
+            // ascending) and, for the last pass, the keys above / at `lo - 1`
+            auto block_mass = [&](uint32_t lo, int *gt, int *eq) {
+                const float flo = key_value(lo);
+                float m = 0.f;
+                int g = 0, q = 0;
+                for (int j0 = 0; j0 < nsteps; j0 += U) {
+                    uint32_t kw[U][2];
+#pragma unroll
+                    for (int jj = 0; jj < U; ++jj) load_raw(j0 + jj, kw[jj][0], kw[jj][1]);
+#pragma unroll
+                    for (int jj = 0; jj < U; ++jj) {
+                        to_keys(kw[jj][0], kw[jj][1]);
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const uint32_t lo16 = kw[jj][h] & 0xffffu, hi16 = kw[jj][h] >> 16;
+                            add_mass2(m, kw[jj][h], flo);
+                            if (gt) {
+                                g += (lo16 >= lo ? 1 : 0) + (hi16 >= lo ? 1 : 0);
+                                q += (lo16 == lo - 1u ? 1 : 0) + (hi16 == lo - 1u ? 1 : 0);
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) m += __shfl_xor(m, d);
+                if (lane == 0) wave_cnt[w] = __float_as_int(m);
+                __syncthreads();
+                float t = 0.f;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) t += __int_as_float(wave_cnt[i]);
+                __syncthreads();
+                if (gt) *gt = block_count(g), *eq = block_count(q);
+                return t;
+            };
+            const float total = block_mass(0x8000u, nullptr, nullptr);
+            const float target = p.top_p * total;
+            uint32_t res = 0x8000u;
+            if (total > 0.f && target > 0.f) {
+                for (int bit = 14; bit >= 0; --bit) {
+                    const uint32_t cand = res | (1u << bit);
+                    if (cand > 0xff80u) continue;            // no mass up there (NaN keys)
+                    if (block_mass(cand, nullptr, nullptr) >= target) res = cand;
+                }
+            }
+            int gt = 0, eq = 0;
+            // (res = 0xff80 = +inf outside the contract: the pass then sums keys in [0xff81, 0xff80], nothing, and counts the NaN keys)
+            const float above = block_mass(res + 1u, &gt, &eq);
+            k = topp_count(total, target, above, gt, eq, res, k, p.k_min);
+            select = k > 0;
+        }
+    }
     uint32_t thr = 0x10000u;  // keep nothing
     int ties_to_take = 0, my_ties = 0;
     if (select) {
@@ -1315,9 +1480,10 @@ extern "C" int chipmunk_gather_rows(const void *src, void *dst, const int32_t *m
     return CHIPMUNK_OK;
 }
 
-int chipmunk_topk_mask_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
-                             int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double random_amount,
-                             hipStream_t s) {
+template <bool MASS>
+static int topk_mask_parts_impl(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
+                                int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double random_amount,
+                                double top_p, int k_min, hipStream_t s) {
     CM_CHECK(part && mask && rows >= 0 && n > 0 && (n & 3) == 0 && n <= CHIPMUNK_TOPK_MASK_MAX_N && k >= 0 && part_stride >= n && (part_stride & 3) == 0, "topk_mask_parts: bad arguments");
     CM_CHECK(!static_mask || (static_rows > 0 && static_stride >= n && (static_stride & 3) == 0 && ((uintptr_t)static_mask & 3) == 0),
              "topk_mask_parts: bad static mask geometry");
@@ -1327,13 +1493,30 @@ int chipmunk_topk_mask_parts(const uint16_t *part, int part_stride, int nrb, int
                         rows, n, k, static_mask ? static_rows : 1, (float)random_amount,
                         random_amount > 0.0 ? chipmunk_next_random_salt() : 0u};
     p.parts = part, p.pstride = part_stride, p.nrb = nrb, p.ngroups = groups_per_bh, p.nq = Nq;
+    p.top_p = (float)top_p, p.k_min = k_min;
     // rows past the register form's 122 880 columns (or option topk_mask_stream = 1: every row) take the streaming form
-    if (n > 1024 * 120 || chipmunk_get_option("topk_mask_stream") == 1) hipLaunchKernelGGL((topk_mask_stream_kernel<true, true>), dim3(rows), dim3(1024), 0, s, p);
-    else if (n <= 1024 * 16) hipLaunchKernelGGL((topk_mask_kernel<16, true, true>), dim3(rows), dim3(1024), 0, s, p);
-    else if (n <= 1024 * 48) hipLaunchKernelGGL((topk_mask_kernel<48, true, true>), dim3(rows), dim3(1024), 0, s, p);
-    else hipLaunchKernelGGL((topk_mask_kernel<120, true, true>), dim3(rows), dim3(1024), 0, s, p);
+    if (n > 1024 * 120 || chipmunk_get_option("topk_mask_stream") == 1) hipLaunchKernelGGL((topk_mask_stream_kernel<true, true, MASS>), dim3(rows), dim3(1024), 0, s, p);
+    else if (n <= 1024 * 16) hipLaunchKernelGGL((topk_mask_kernel<16, true, true, MASS>), dim3(rows), dim3(1024), 0, s, p);
+    else if (n <= 1024 * 48) hipLaunchKernelGGL((topk_mask_kernel<48, true, true, MASS>), dim3(rows), dim3(1024), 0, s, p);
+    else hipLaunchKernelGGL((topk_mask_kernel<120, true, true, MASS>), dim3(rows), dim3(1024), 0, s, p);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
+}
+
+int chipmunk_topk_mask_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
+                             int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double random_amount,
+                             hipStream_t s) {
+    return topk_mask_parts_impl<false>(part, part_stride, nrb, groups_per_bh, Nq, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k,
+                                       random_amount, 0.0, 0, s);
+}
+
+// the same with the top-p count in front (chipmunk_topk_mask_p): k is the cap
+int chipmunk_topk_mask_p_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
+                               int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double top_p, int k_min,
+                               double random_amount, hipStream_t s) {
+    CM_CHECK(top_p > 0.0 && top_p <= 1.0 && k_min >= 0, "topk_mask_p_parts: top_p must be in (0, 1] and k_min >= 0 (got %g, %d)", top_p, k_min);
+    return topk_mask_parts_impl<true>(part, part_stride, nrb, groups_per_bh, Nq, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k,
+                                      random_amount, top_p, k_min, s);
 }
 
 // ---- QKV projection output -> attention operands: split + q/k RMSNorm + head-major layout in ONE pass.
@@ -1410,9 +1593,10 @@ extern "C" int chipmunk_qkv_split_norm(const void *qkv, int64_t row_stride, cons
     return CHIPMUNK_OK;
 }
 
-extern "C" int chipmunk_topk_mask(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
-                                  int static_rows, const void *group_flags, void *mask, int rows, int n, int k,
-                                  double random_amount, void *stream) {
+template <bool MASS>
+static int topk_mask_impl(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
+                          int static_rows, const void *group_flags, void *mask, int rows, int n, int k,
+                          double random_amount, double top_p, int k_min, void *stream) {
     CM_CHECK(cs && mask, "topk_mask: null pointer");
     CM_CHECK(rows >= 0 && n > 0 && k >= 0, "topk_mask: bad sizes (rows=%d n=%d k=%d)", rows, n, k);
     CM_CHECK(cs_stride >= n, "topk_mask: cs row stride %lld < n %d", (long long)cs_stride, n);
@@ -1423,24 +1607,39 @@ extern "C" int chipmunk_topk_mask(const void *cs, int64_t cs_stride, const void 
     TopkMaskParams p = {(const uint16_t *)cs, (const uint8_t *)static_mask, (const uint8_t *)group_flags, (uint8_t *)mask,
                         cs_stride, static_stride, rows, n, k, static_mask ? static_rows : 1, (float)random_amount,
                         random_amount > 0.0 ? chipmunk_next_random_salt() : 0u};
+    p.top_p = (float)top_p, p.k_min = k_min;
     hipStream_t s = (hipStream_t)stream;
     const bool aligned = n % 4 == 0 && (((uintptr_t)cs) & 7) == 0 && (cs_stride * 2) % 8 == 0 && (((uintptr_t)mask) & 3) == 0 &&
                          (!static_mask || ((((uintptr_t)static_mask) & 3) == 0 && static_stride % 4 == 0));
 #define LAUNCH_TM(KPT)                                                                                       \
     do {                                                                                                     \
-        if (aligned) hipLaunchKernelGGL((topk_mask_kernel<KPT, true>), dim3(rows), dim3(1024), 0, s, p);     \
-        else hipLaunchKernelGGL((topk_mask_kernel<KPT, false>), dim3(rows), dim3(1024), 0, s, p);            \
+        if (aligned) hipLaunchKernelGGL((topk_mask_kernel<KPT, true, false, MASS>), dim3(rows), dim3(1024), 0, s, p);     \
+        else hipLaunchKernelGGL((topk_mask_kernel<KPT, false, false, MASS>), dim3(rows), dim3(1024), 0, s, p);            \
     } while (0)
     // rows past the register form's 122 880 columns (or option topk_mask_stream = 1: every row) take the streaming form
     if (n > 1024 * 120 || chipmunk_get_option("topk_mask_stream") == 1) {
-        if (aligned) hipLaunchKernelGGL((topk_mask_stream_kernel<true, false>), dim3(rows), dim3(1024), 0, s, p);
-        else hipLaunchKernelGGL((topk_mask_stream_kernel<false, false>), dim3(rows), dim3(1024), 0, s, p);
+        if (aligned) hipLaunchKernelGGL((topk_mask_stream_kernel<true, false, MASS>), dim3(rows), dim3(1024), 0, s, p);
+        else hipLaunchKernelGGL((topk_mask_stream_kernel<false, false, MASS>), dim3(rows), dim3(1024), 0, s, p);
     } else if (n <= 1024 * 16) LAUNCH_TM(16);
     else if (n <= 1024 * 48) LAUNCH_TM(48);
     else LAUNCH_TM(120);
 #undef LAUNCH_TM
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
+}
+
+extern "C" int chipmunk_topk_mask(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
+                                  int static_rows, const void *group_flags, void *mask, int rows, int n, int k,
+                                  double random_amount, void *stream) {
+    return topk_mask_impl<false>(cs, cs_stride, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k, random_amount, 0.0, 0, stream);
+}
+
+extern "C" int chipmunk_topk_mask_p(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
+                                    int static_rows, const void *group_flags, void *mask, int rows, int n, int k,
+                                    double random_amount, double top_p, int k_min, void *stream) {
+    CM_CHECK(top_p > 0.0 && top_p <= 1.0, "topk_mask_p: top_p must be in (0, 1] (got %g)", top_p);
+    CM_CHECK(k_min >= 0, "topk_mask_p: k_min must be >= 0 (got %d)", k_min);
+    return topk_mask_impl<true>(cs, cs_stride, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k, random_amount, top_p, k_min, stream);
 }
 
 extern "C" int chipmunk_compact_indices(const int32_t *indices, int64_t idx_stride, const int32_t *counts, const int64_t *offsets,

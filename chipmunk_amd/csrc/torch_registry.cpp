@@ -895,11 +895,13 @@ std::vector<at::Tensor> mask_to_ragged_indices(at::Tensor mask, at::IntArrayRef 
 // dense_colsum_attn + topk_mask without the cs tensor between them (see chipmunk_dense_colsum_topk_mask); falls back to the two
 // operators when the fused entry does not apply to the launch
 std::vector<at::Tensor> dense_colsum_attn_layout(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, bool token_major_o);
-at::Tensor topk_mask(at::Tensor cs, int64_t k, double random_amount, const c10::optional<at::Tensor> &groups,
-                     const c10::optional<at::Tensor> &static_mask);
-std::vector<at::Tensor> dense_colsum_topk_mask(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, int64_t k_top, double random_amount,
-                                               const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask,
-                                               bool token_major_o) {
+// (the `_p` operators: `mass` set, `top_p` / `k_min` the per-row count of chipmunk_topk_mask_p with k as the cap)
+static at::Tensor topk_mask_impl(at::Tensor cs, int64_t k, bool mass, double top_p, int64_t k_min, double random_amount,
+                                 const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask);
+static std::vector<at::Tensor> dense_colsum_topk_mask_impl(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, int64_t k_top, bool mass, double top_p,
+                                                           int64_t k_min, double random_amount, const c10::optional<at::Tensor> &groups,
+                                                           const c10::optional<at::Tensor> &static_mask, bool token_major_o) {
+    if (mass) TORCH_CHECK(top_p > 0.0 && top_p <= 1.0 && k_min >= 0, "top_p must be in (0, 1] and k_min >= 0 (got ", top_p, ", ", k_min, ")");
     CHECK_DEV(q); CHECK_DEV(k); CHECK_DEV(v); CHECK_DEV(p);
     CHECK_BF16(q); CHECK_BF16(k); CHECK_BF16(v);
     const bool shapes_ok = q.dim() == 4 && k.dim() == 4 && v.dim() == 4 && q.size(3) == 128 && q.stride(3) == 1 && k.stride(3) == 1 &&
@@ -934,7 +936,10 @@ std::vector<at::Tensor> dense_colsum_topk_mask(at::Tensor q, at::Tensor k, at::T
             at::Tensor mask = at::empty({B, H, G, Nk}, q.options().dtype(at::kBool));
             const int64_t qs[3] = {q.stride(0), q.stride(1), q.stride(2)}, ks[3] = {k.stride(0), k.stride(1), k.stride(2)},
                           vs[3] = {v.stride(0), v.stride(1), v.stride(2)};
-            const int rc = chipmunk_dense_colsum_topk_mask_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs, ks, vs, p.data_ptr<float>(), o.data_ptr(),
+            const int rc = mass ? chipmunk_dense_colsum_topk_mask_p_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs, ks, vs, p.data_ptr<float>(), o.data_ptr(),
+                                                                            os, l.data_ptr<float>(), (int)B, (int)H, (int)Nq, (int)Nk, st, st_stride, (int)st_rows, gf,
+                                                                            mask.data_ptr(), (int)k_top, random_amount, top_p, (int)(k_min > Nk ? Nk : k_min), cur_stream(q))
+                                : chipmunk_dense_colsum_topk_mask_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs, ks, vs, p.data_ptr<float>(), o.data_ptr(),
                                                            os, l.data_ptr<float>(), (int)B, (int)H, (int)Nq, (int)Nk, st, st_stride, (int)st_rows, gf,
                                                            mask.data_ptr(), (int)k_top, random_amount, cur_stream(q));
             if (rc == CHIPMUNK_OK) return {o, mask, l};
@@ -945,11 +950,23 @@ std::vector<at::Tensor> dense_colsum_topk_mask(at::Tensor q, at::Tensor k, at::T
     at::Tensor cs = ocl[1];
     const int64_t Nk = k.size(2), G = (q.size(2) + 191) / 192;
     if (cs.size(-1) != Nk || cs.size(-2) != G) cs = cs.slice(-2, 0, G).slice(-1, 0, Nk);
-    return {ocl[0], topk_mask(cs, k_top, random_amount, groups, static_mask), ocl[2]};
+    return {ocl[0], topk_mask_impl(cs, k_top, mass, top_p, k_min, random_amount, groups, static_mask), ocl[2]};
 }
 
-at::Tensor topk_mask(at::Tensor cs, int64_t k, double random_amount, const c10::optional<at::Tensor> &groups,
-                     const c10::optional<at::Tensor> &static_mask) {
+std::vector<at::Tensor> dense_colsum_topk_mask(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, int64_t k_top, double random_amount,
+                                               const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask,
+                                               bool token_major_o) {
+    return dense_colsum_topk_mask_impl(q, k, v, p, k_top, false, 0.0, 0, random_amount, groups, static_mask, token_major_o);
+}
+
+std::vector<at::Tensor> dense_colsum_topk_mask_p(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, int64_t k_top, double top_p, int64_t k_min,
+                                                 double random_amount, const c10::optional<at::Tensor> &groups,
+                                                 const c10::optional<at::Tensor> &static_mask, bool token_major_o) {
+    return dense_colsum_topk_mask_impl(q, k, v, p, k_top, true, top_p, k_min, random_amount, groups, static_mask, token_major_o);
+}
+
+static at::Tensor topk_mask_impl(at::Tensor cs, int64_t k, bool mass, double top_p, int64_t k_min, double random_amount,
+                                 const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask) {
     CHECK_DEV(cs); CHECK_BF16(cs);
     TORCH_CHECK(cs.dim() == 4 && cs.stride(3) == 1, "cs must be [B, H, G, N] with a contiguous last dim");
     const int64_t B = cs.size(0), H = cs.size(1), G = cs.size(2), N = cs.size(3);
@@ -978,10 +995,25 @@ at::Tensor topk_mask(at::Tensor cs, int64_t k, double random_amount, const c10::
         gfc = gfc.expand({B, H, G, 1}).contiguous();
         gf = gfc.data_ptr();
     }
-    check(chipmunk_topk_mask(cs.data_ptr(), cs.stride(2), st, st_stride, (int)st_rows, gf, mask.data_ptr(), (int)rows, (int)N,
-                             (int)k, random_amount, cur_stream(cs)),
-          "topk_mask");
+    if (mass)
+        check(chipmunk_topk_mask_p(cs.data_ptr(), cs.stride(2), st, st_stride, (int)st_rows, gf, mask.data_ptr(), (int)rows, (int)N,
+                                   (int)k, random_amount, top_p, (int)(k_min > N ? N : k_min), cur_stream(cs)),
+              "topk_mask_p");
+    else
+        check(chipmunk_topk_mask(cs.data_ptr(), cs.stride(2), st, st_stride, (int)st_rows, gf, mask.data_ptr(), (int)rows, (int)N,
+                                 (int)k, random_amount, cur_stream(cs)),
+              "topk_mask");
     return mask;
+}
+
+at::Tensor topk_mask(at::Tensor cs, int64_t k, double random_amount, const c10::optional<at::Tensor> &groups,
+                     const c10::optional<at::Tensor> &static_mask) {
+    return topk_mask_impl(cs, k, false, 0.0, 0, random_amount, groups, static_mask);
+}
+
+at::Tensor topk_mask_p(at::Tensor cs, int64_t k, double top_p, int64_t k_min, double random_amount, const c10::optional<at::Tensor> &groups,
+                       const c10::optional<at::Tensor> &static_mask) {
+    return topk_mask_impl(cs, k, true, top_p, k_min, random_amount, groups, static_mask);
 }
 
 // reference src/chipmunk/ops/bitpack.py:4-69 as single kernels
@@ -1140,6 +1172,8 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("mask_to_sorted_indices(Tensor mask, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
     m.def("topk_mask(Tensor cs, int k, float random_amount, Tensor? groups, Tensor? static_mask) -> Tensor");
     m.def("dense_colsum_topk_mask(Tensor q, Tensor k, Tensor v, Tensor p, int k_top, float random_amount, Tensor? groups, Tensor? static_mask, bool token_major_o=False) -> Tensor[]");
+    m.def("topk_mask_p(Tensor cs, int k, float top_p, int k_min, float random_amount, Tensor? groups, Tensor? static_mask) -> Tensor");
+    m.def("dense_colsum_topk_mask_p(Tensor q, Tensor k, Tensor v, Tensor p, int k_top, float top_p, int k_min, float random_amount, Tensor? groups, Tensor? static_mask, bool token_major_o=False) -> Tensor[]");
     // the two dense operators with a choice of output layout (the reference's schemas above stay as they are)
     m.def("dense_attn_layout(Tensor q, Tensor k, Tensor v, bool token_major_o) -> Tensor[]");
     m.def("dense_colsum_attn_layout(Tensor q, Tensor k, Tensor v, Tensor p, bool token_major_o) -> Tensor[]");
@@ -1163,6 +1197,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("split_heads_rownorm", &split_heads_rownorm);
     m.impl("csp_mlp_mm1_fp8_scatter", &csp_mlp_mm1_fp8_scatter);
     m.impl("dense_colsum_topk_mask", &dense_colsum_topk_mask);
+    m.impl("dense_colsum_topk_mask_p", &dense_colsum_topk_mask_p);
     m.impl("csp_mlp_mm1", &csp_mlp_mm1);
     m.impl("csp_mlp_mm2_and_scatter_add", &csp_mlp_mm2_and_scatter_add);
     m.impl("copy_indices", &copy_indices);
@@ -1190,6 +1225,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("mask_to_sorted_indices", &mask_to_sorted_indices);
     m.impl("mask_to_ragged_indices", &mask_to_ragged_indices);
     m.impl("topk_mask", &topk_mask);
+    m.impl("topk_mask_p", &topk_mask_p);
     m.impl("transpose_last2", &transpose_last2);
     m.impl("transpose_last2_pitched", &transpose_last2_pitched);
     m.impl("block_mean", &block_mean);

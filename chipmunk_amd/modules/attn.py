@@ -90,11 +90,30 @@ class SparseDiffAttn(nn.Module):
         h = min(heads, singleton_static_mask.shape[1])      # (one plane broadcasts over the heads)
         return (singleton_static_mask[:, :h, g0:g0 + qg, :n], singleton_video_query_groups[:, :h, g0:g0 + qg, :])
 
-    def random_and_topk(self, cs: Tensor, topk: int) -> Tensor:
-        """1% random keys + top-k column sums, limited to the groups that are sparse at all, plus the static mask."""
+    @staticmethod
+    def _top_p(n_keys: int, multiple_of: int):
+        """(``attn.top_p``, minimum key count) of the mask step, ``top_p`` 0.0 when the per-group count is off.  The minimum is
+        ``attn.top_p_min_keys`` of the keys, rounded like ``top_keys``."""
+        top_p = float(amd_key("attn", "top_p"))
+        if top_p == 0.0:
+            return 0.0, 0
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"attn.top_p must be in [0, 1] (got {top_p})")
+        if not GLOBAL_CONFIG["attn"]["should_compress_indices"]:
+            raise ValueError("attn.top_p needs attn.should_compress_indices: without it the layer stores fixed-width torch.topk indices, "
+                             "which cannot hold a key count per query group")
+        return top_p, int(multiple_of * round((float(amd_key("attn", "top_p_min_keys")) * n_keys) / multiple_of))
+
+    def random_and_topk(self, cs: Tensor, topk: int, top_p: float = 0.0, k_min: int = 0) -> Tensor:
+        """1% random keys + top-k column sums, limited to the groups that are sparse at all, plus the static mask.
+        ``top_p`` > 0 (``attn.top_p``): ``topk`` is the cap of the per-group count of ``ops.topk_mask_p``."""
         cfg = GLOBAL_CONFIG["attn"]
         qg, n = cs.shape[-2], cs.shape[-1]
         static, groups = self._static(cs.shape[1], qg, n)
+        if top_p > 0.0:
+            if cs.dtype != torch.bfloat16:
+                raise ValueError(f"attn.top_p: the selection takes bfloat16 column sums (got {cs.dtype})")
+            return ops.topk_mask_p(cs, topk, top_p, k_min, 0.01, groups, static)      # (a row past the kernels' ceiling is refused there)
         if cs.is_cuda and amd_key("attn", "fused_topk_mask") and cs.dtype == torch.bfloat16 and n <= ops.TOPK_MASK_MAX_N:
             # one kernel for the whole chain below (the random 1 % comes from a counter-based hash, not torch's RNG)
             return ops.topk_mask(cs, topk, 0.01, groups, static)
@@ -226,12 +245,16 @@ class SparseDiffAttn(nn.Module):
             if inference_step == 1 or cfg["recompute_mask"]:
                 prev_lse = self.storage.get_lse_constants()
                 tk = int(multiple_of * round((cfg["top_keys"] * k.shape[-2]) / multiple_of))
+                top_p, k_min = self._top_p(k.shape[-2], multiple_of)     # (0.0, 0) unless attn.top_p is set: tk is then only the cap
                 mask = bs = None
                 if (q.is_cuda and cfg["should_compress_indices"] and tk > 0 and amd_key("attn", "fused_colsum_topk")
                         and amd_key("attn", "fused_topk_mask") and k.shape[-2] <= ops.TOPK_MASK_MAX_N):
                     # dense attention -> column sums -> mask without the column-sum tensor in between (same bits as the two steps)
                     static, groups = self._static(q.shape[1], _cdiv(q.shape[-2], bm), k.shape[-2])
-                    o, mask, lse = ops.dense_colsum_topk_mask(q, k, v, prev_lse, tk, 0.01, groups, static, tm)
+                    if top_p > 0.0:
+                        o, mask, lse = ops.dense_colsum_topk_mask_p(q, k, v, prev_lse, tk, top_p, k_min, 0.01, groups, static, tm)
+                    else:
+                        o, mask, lse = ops.dense_colsum_topk_mask(q, k, v, prev_lse, tk, 0.01, groups, static, tm)
                 elif do_padding:
                     o, bs, lse = ops.dense_colsum_attn(q, k, v, prev_lse, tm)
                 else:
@@ -243,7 +266,7 @@ class SparseDiffAttn(nn.Module):
                     if mask is not None:
                         pass
                     elif tk > 0:
-                        mask = self.random_and_topk(bs, tk)
+                        mask = self.random_and_topk(bs, tk, top_p, k_min)
                     else:
                         mask = self._static(bs.shape[1], bs.shape[-2], bs.shape[-1])[0]
                     packed, mask_shape = ops.bitpack(mask)

@@ -104,6 +104,17 @@ def _register():
         return [_o_like(q, token_major_o), q.new_empty((B, H, G, k.shape[2]), dtype=torch.bool),
                 q.new_empty((B, H, Nq, 1), dtype=torch.float32)]
 
+    @lib.register_fake("chipmunk::topk_mask_p")
+    def _(cs, k, top_p, k_min, random_amount, groups, static_mask):
+        return cs.new_empty(cs.shape, dtype=torch.bool)
+
+    @lib.register_fake("chipmunk::dense_colsum_topk_mask_p")
+    def _(q, k, v, p, k_top, top_p, k_min, random_amount, groups, static_mask, token_major_o=False):
+        B, H, Nq, D = q.shape
+        G = (Nq + 191) // 192
+        return [_o_like(q, token_major_o), q.new_empty((B, H, G, k.shape[2]), dtype=torch.bool),
+                q.new_empty((B, H, Nq, 1), dtype=torch.float32)]
+
     @lib.register_fake("chipmunk::qkv_split_norm")
     def _(qkv, q_weight, k_weight, heads, eps, freqs_cos=None, freqs_sin=None):
         out = qkv.new_empty((3, 1, heads, qkv.shape[0], 128))

@@ -76,6 +76,26 @@ def dense_colsum_topk_mask(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p:
     return o, mask, l
 
 
+def dense_colsum_topk_mask_p(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, p: torch.Tensor, k_top: int, top_p: float, k_min: int,
+                             random_amount: float, groups, static_mask, token_major_o: bool = False
+                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``dense_colsum_attn`` followed by ``topk_mask_p`` on its column sums (``k_top`` is the cap), as ``dense_colsum_topk_mask`` is for
+    ``topk_mask``: the same ``o``, ``l`` and mask bits as the two calls.  CPU tensors run exactly those two calls."""
+    if not q.is_cuda:
+        from .indexed_io import topk_mask_p
+        o, cs, l = dense_colsum_attn(q, k, v, p, token_major_o)
+        return o, topk_mask_p(cs, k_top, top_p, k_min, random_amount, groups, static_mask), l
+    n = q.shape[-2]
+    padded = _pad_len(n)
+    assert p.shape[-2] in (n, padded), "p must be the l vector of the previous full step"
+    o, mask, l = torch.ops.chipmunk.dense_colsum_topk_mask_p(_last_dim_contiguous(q), _last_dim_contiguous(k), _last_dim_contiguous(v),
+                                                             p[..., :n, :].contiguous(), k_top, top_p, k_min, random_amount, groups,
+                                                             static_mask, token_major_o)
+    if padded != n:
+        l = F.pad(l, (0, 0, 0, padded - n))
+    return o, mask, l
+
+
 def csp_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, indices: torch.Tensor,
              indices_counts: torch.Tensor) -> torch.Tensor:
     """Out-of-place column-sparse attention (reference ``ops/attn.py:134-169`` -> ``csp_128_attn``)."""
@@ -111,4 +131,4 @@ def csp_attn_out_ragged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o_in:
 
 
 __all__ = ["csp_attn", "csp_attn_inplace", "csp_attn_out", "csp_attn_out_ragged", "compact_indices", "dense_attn", "dense_colsum_attn",
-           "dense_colsum_topk_mask"]
+           "dense_colsum_topk_mask", "dense_colsum_topk_mask_p"]

@@ -88,6 +88,55 @@ def topk_mask(cs: torch.Tensor, k: int, random_amount: float = 0.0, groups: Opti
     return torch.ops.chipmunk.topk_mask(cs, k, random_amount, groups, static_mask)
 
 
+def _bf16_keys(cs: torch.Tensor) -> torch.Tensor:
+    """The order-preserving 16-bit image of bf16 bits as int64 (larger value = larger key; -0.0 below +0.0)."""
+    bits = cs.contiguous().view(torch.int16).to(torch.int64) & 0xFFFF
+    return torch.where((bits & 0x8000) != 0, ~bits & 0xFFFF, bits | 0x8000)
+
+
+def _topk_mask_p_cpu(cs: torch.Tensor, k: int, top_p: float, k_min: int, random_amount: float,
+                     groups: Optional[torch.Tensor], static_mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """The rule of ``topk_mask_p`` in plain torch: one sort per row in the kernels' total order, fp64 prefix sums."""
+    if not (0.0 < top_p <= 1.0) or k_min < 0 or k < 0:
+        raise ValueError(f"topk_mask_p: top_p must be in (0, 1], k and k_min >= 0 (got {top_p}, {k}, {k_min})")
+    B, H, G, n = cs.shape
+    k = min(int(k), n)
+    cols = torch.arange(n, dtype=torch.int64)
+    # one sortable integer per column: key descending, then ((c % 4096) // 4, c) ascending (n <= 2^19, tie rank < 2^30)
+    rank = (0xFFFF - _bf16_keys(cs).view(-1, n)) * (1 << 30) + ((cols % 4096) // 4) * (1 << 20) + cols
+    order = torch.argsort(rank, dim=-1)
+    val = cs.reshape(-1, n).double()
+    mass = torch.where(val > 0, val, torch.zeros_like(val)).gather(-1, order)      # negative and NaN entries carry no mass
+    prefix = mass.cumsum(-1)
+    total = prefix[:, -1:]
+    k_p = (prefix < top_p * total).sum(-1) + 1                                     # the smallest count with prefix mass >= target
+    k_p = torch.where(total[:, 0] > 0, k_p, torch.zeros_like(k_p))
+    s = k_p.clamp(min=int(k_min)).clamp(max=k)
+    keep = torch.zeros(cs.numel() // n, n, dtype=torch.bool)
+    keep.scatter_(-1, order, cols[None, :] < s[:, None])
+    keep = keep.view(B, H, G, n)
+    if random_amount > 0:
+        keep |= torch.rand(keep.shape) < random_amount
+    if groups is not None:
+        keep &= groups
+    if static_mask is not None:
+        keep = keep | static_mask
+    return keep
+
+
+def topk_mask_p(cs: torch.Tensor, k: int, top_p: float, k_min: int = 0, random_amount: float = 0.0,
+                groups: Optional[torch.Tensor] = None, static_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``topk_mask`` with a count per row (not in the reference): an active row keeps the smallest top set of its columns that
+    carries a share ``top_p`` of the row's column-sum mass -- at least ``k_min``, never more than ``k`` columns.  Order: value
+    descending, ties by ``((c % 4096) // 4, c)``; mass of a column: its value where positive (negative and NaN entries carry none);
+    ``s = min(k, max(k_p, k_min))`` with ``k_p`` the smallest prefix whose mass reaches ``top_p`` times the row's, 0 for an all-zero
+    row.  The random, group and static parts are those of ``topk_mask``.  The kernel sums in fp32 in a fixed order (same launch,
+    same bits); CPU tensors take a sort with fp64 sums."""
+    if not cs.is_cuda:
+        return _topk_mask_p_cpu(cs, k, top_p, k_min, random_amount, groups, static_mask)
+    return torch.ops.chipmunk.topk_mask_p(cs, k, top_p, k_min, random_amount, groups, static_mask)
+
+
 def manual_seed(seed: int) -> None:
     """Seed of the random-key hash used when ``random_amount`` / ``rk`` > 0 (see ``include/chipmunk_hip.h``:
     ``chipmunk_set_random_seed``).  Every launch draws a different set; the same seed and launch order reproduce a run."""

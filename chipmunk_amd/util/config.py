@@ -122,6 +122,12 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # F8Linear fc2 with e4m3 weights -- the sparse steps' GEMM2 then gathers e4m3 rows of fc2.weight^T (csp_mlp_mm2_w8: 1 byte per weight
     # in HBM and through the gather instead of 2 + 2).  Off by default: fc2 stays bf16, as in the reference.
     "mlp.fp8_fc2": False,
+    # mask step with a key count per (batch, head, 192-query group) (not in the reference; should_compress_indices only): a sparse group keeps
+    # the smallest top set of keys that carries this share of its column-sum mass (the group's summed softmax probabilities), never more
+    # than the top_keys count -- a head whose mass sits on few keys stores and gathers fewer.  0.0 = off: exactly top_keys keys per group.
+    "attn.top_p": 0.0,
+    # ... and never fewer than this fraction of the keys (rounded like top_keys)
+    "attn.top_p_min_keys": 0.0,
 }
 BASE_CONFIG["offloading"]["keep_resident_if_fits"] = AMD_EXTRA_KEYS["offloading.keep_resident_if_fits"]
 BASE_CONFIG["offloading"]["hbm_budget_gb"] = AMD_EXTRA_KEYS["offloading.hbm_budget_gb"]
@@ -139,6 +145,8 @@ BASE_CONFIG["attn"]["keep_unpacked_indices_offloaded"] = AMD_EXTRA_KEYS["attn.ke
 BASE_CONFIG["attn"]["kept_indices_offloaded_budget_gb"] = AMD_EXTRA_KEYS["attn.kept_indices_offloaded_budget_gb"]
 BASE_CONFIG["attn"]["ragged_mask_to_indices"] = AMD_EXTRA_KEYS["attn.ragged_mask_to_indices"]
 BASE_CONFIG["mlp"]["fp8_fc2"] = AMD_EXTRA_KEYS["mlp.fp8_fc2"]
+BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
+BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
 
 GLOBAL_CONFIG: Dict[str, Any] = copy.deepcopy(BASE_CONFIG)
 

@@ -324,6 +324,29 @@ int chipmunk_topk_mask(const void *cs, int64_t cs_stride, const void *static_mas
                        int static_rows, const void *group_flags, void *mask, int rows, int n, int k,
                        double random_amount, void *stream);
 
+/* chipmunk_topk_mask with a per-row count (not in the reference): an active row keeps the smallest top set of its columns that
+ * carries a share top_p of the row's column-sum mass, at least k_min and at most k columns (k clamped to n):
+ *   order   bf16 value descending, ties by ((c mod 4096) div 4, c) ascending -- the order chipmunk_topk_mask selects in
+ *   mass    m_c = cs[c] where that is positive and finite, 0 otherwise (the contract is finite, non-negative cs);
+ *           total = sum of m_c, target = top_p * total
+ *   k_p     the smallest count whose prefix of the order has mass >= target; 0 when total is 0
+ *   s       min(k, max(k_p, k_min)); the row's top-k part is the first s columns of the order, i.e. chipmunk_topk_mask's for k := s
+ * Inactive rows, the random part and the static part are those of chipmunk_topk_mask.  0 < top_p <= 1, k_min >= 0.
+ * The sums are fp32 in one fixed order (a thread's columns ascending, the wave's xor tree, the 16 wave totals ascending): the
+ * same launch gives the same bits, and rows whose sums are exact in fp32 give exactly the rule above. */
+int chipmunk_topk_mask_p(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
+                         int static_rows, const void *group_flags, void *mask, int rows, int n, int k,
+                         double random_amount, double top_p, int k_min, void *stream);
+
+/* chipmunk_dense_colsum_topk_mask_strided with the selection of chipmunk_topk_mask_p (k_top is the cap); o_strides NULL = the
+ * plain [B, H, Nq, 128] layout.  CHIPMUNK_ERR_UNSUPPORTED as there: run chipmunk_dense_colsum_attn and chipmunk_topk_mask_p. */
+int chipmunk_dense_colsum_topk_mask_p_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                              const int64_t k_strides[3], const int64_t v_strides[3], const float *p, void *o,
+                                              const int64_t *o_strides, float *l, int B, int H, int Nq, int Nk,
+                                              const void *static_mask, int64_t static_stride, int static_rows,
+                                              const void *group_flags, void *mask, int k_top, double random_amount,
+                                              double top_p, int k_min, void *stream);
+
 /* Replaces chipmunk::mask_to_indices (reference csrc/indexed_io/mask_to_indices.cu:92-143; schema chipmunk.cpp:60).
  * mask [rows, n] bool bytes; indices [rows, pad_n] int32; counts [rows] int32.  Bit-exact order: True columns of
  * residue class t (mod 32) ascending for t = 0..31, then the first False columns ascending up to multiple_of. */
