@@ -349,8 +349,28 @@ __device__ __forceinline__ int compact_slot(bool keep, int lane, int w, uint32_t
 // DELTA = true fuses the sparse-MLP sequence |bmfc1 - cache| -> topk_indices -> copy_indices (reference
 // modules/mlp.py:70-85 with bm == mbm): the ranked value is |T(b - cache)| computed on the fly and every selected
 // column (padding included, like copy_indices) is copied into the cache by the thread that owns it.
-template <typename T, bool DELTA>
-__global__ __launch_bounds__(1024) void topk_indices_kernel(const TopkParams p) {
+//
+// TOPP = true is the `_p` form (mlp.top_p; not in the reference): a column count per row from the row's mass.  With m_c = v_c where
+// v_c > 0 (a zero, negative or NaN entry carries none), total = sum of m_c over the WHOLE row and target = float(top_p) * total,
+//   thr_p   = the largest t with sum{m_c : v_c >= t} >= target (a class of equal values is taken whole); +inf when total == 0
+//   thr_q   = the threshold above (k_q = int(1024 * sparsity)); -inf for sparsity == 0: no cap
+//   thr_min = the same order statistic at k_min = int(1024 * (1 - min_keys)) (the host keeps k_min >= k_q); +inf for k_min >= 1024
+//   kept    : m_c > 0 and v_c >= min(max(thr_p, thr_q), thr_min)
+// and the random keys, the padding and the order follow as in the plain form.  Same launch shape and first-pass loads: the 16 values a
+// thread already holds become its masses; the row total and every bisection round are one block-wide fp32 sum in a FIXED order (a
+// thread's columns ascending, the wave by row16_sum / sum_across_rows, the 16 wave partials ascending through LDS) -- no floating-point
+// atomics, the same launch gives the same bits, and a fixed-order sum of non-negative terms is monotone in the set summed, so the
+// bisection over the order-preserving key bits is well defined.  thr_p is the key of a column, and every key of a positive bf16 / fp16
+// value has its low 16 / 13 bits zero (the plain form too: only positive values carry mass), so the rounds stop above them: 15 rounds
+// for bf16, 18 for fp16, 31 for fp32.  Columns past 16 384 do not fit the registers: every round reads them again (L2 hits; FLUX,
+// HunyuanVideo and Wan rows are 12 288 - 13 824 columns and have none).  Lanes past the row's end hold zeros: no mass, no load.
+struct TopkPParams : TopkParams {
+    float top_p;
+    int k_min;  // index of thr_min in the sorted sample; >= 1024: no floor
+};
+
+template <typename T, bool DELTA, bool TOPP = false>
+__global__ __launch_bounds__(1024) void topk_indices_kernel(const typename std::conditional<TOPP, TopkPParams, TopkParams>::type p) {
     __shared__ uint32_t wave_tot[16];
     __shared__ float thr_s;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -366,7 +386,7 @@ __global__ __launch_bounds__(1024) void topk_indices_kernel(const TopkParams p) 
     };
 
     const uint32_t salt = p.salt ^ (__float_as_uint(value(0)) * 0x27D4EB2Fu);  // the fused (delta) form sees what the unfused op sees
-    if (p.quantile == 0.f) {  // keep everything (topk_indices.cu:51-59)
+    if (!TOPP && p.quantile == 0.f) {  // keep everything (topk_indices.cu:51-59); the _p form has no cap there and still selects by mass
         if constexpr (DELTA)
             for (int c = tid; c < cols; c += 1024) xc[c] = x[c];
         for (int c = tid; c < cols; c += 1024) out[c] = c;
@@ -392,8 +412,77 @@ __global__ __launch_bounds__(1024) void topk_indices_kernel(const TopkParams p) 
         v_first[j] = c < cols ? value(c) : 0.f;
     }
     sample[tid] = v_first[0];
-    __syncthreads();
-    if (w == 0) {
+    if constexpr (TOPP) {
+        // ---- masses in place of the values (the sample keeps the values as they are), row total, thr_q / thr_min, thr_p
+        __shared__ float part[2][16];
+        __shared__ float thr_qm[2];
+        auto block_sum = [&](float s, int buf) {  // every thread gets the same bits; one barrier (the buffers alternate)
+            s = sum_across_rows(row16_sum(s));
+            if (lane == 0) part[buf][w] = s;
+            __syncthreads();
+            float t = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) t += part[buf][i];
+            return t;
+        };
+        // mass of the columns >= key `cand` (cand >= 1; a column without mass has key 0)
+        auto mass_from = [&](uint32_t cand) {
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) s += __float_as_uint(v_first[j]) >= cand ? v_first[j] : 0.f;
+            for (int c = 16 * 1024 + tid; c < cols; c += 1024) {
+                const float v = value(c);
+                s += (v > 0.f && __float_as_uint(v) >= cand) ? v : 0.f;
+            }
+            return s;
+        };
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v_first[j] = v_first[j] > 0.f ? v_first[j] : 0.f;
+        const float total = block_sum(mass_from(1u), 0);  // (the barrier inside also publishes the sample)
+        if (w == 0) {
+            uint32_t key[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const uint32_t u = __float_as_uint(sample[lane + 64 * j]);
+                key[j] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone float -> unsigned map
+            }
+            // both order statistics in one loop: the two counts (<= 1024 each) ride one wave sum as cnt_q + 2048 * cnt_min, exact in fp32
+            const int kq = (int)(1024 * p.quantile), km = p.k_min;
+            uint32_t rq = 0, rm = 0;
+            // (the one round for the LOWZ low bits of a 16-bit |delta|: see the plain form below)
+            constexpr int LOWZ = !DELTA ? 0 : std::is_same<T, uint16_t>::value ? 16 : std::is_same<T, _Float16>::value ? 13 : 0;
+            constexpr int LAST = LOWZ ? LOWZ - 1 : 0;
+            for (int bit = 31; bit >= LAST; --bit) {
+                const uint32_t add = LOWZ && bit == LAST ? (1u << LOWZ) - 1u : (1u << bit);
+                const uint32_t cq = rq | add, cm = rm | add;
+                int cnt = 0;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) cnt += (key[j] < cq ? 1 : 0) + (key[j] < cm ? 2048 : 0);
+                const int tot = (int)sum_across_rows(row16_sum((float)cnt));
+                if ((tot & 2047) <= kq) rq = cq;
+                if ((tot >> 11) <= km) rm = cm;
+            }
+            if (lane == 0) {
+                const uint32_t uq = (rq & 0x80000000u) ? (rq & 0x7fffffffu) : ~rq, um = (rm & 0x80000000u) ? (rm & 0x7fffffffu) : ~rm;
+                thr_qm[0] = p.quantile == 0.f ? -INFINITY : __uint_as_float(uq);
+                thr_qm[1] = km >= 1024 ? INFINITY : __uint_as_float(um);
+            }
+        }
+        // thr_p: the largest key whose columns carry the target, from the exponent's top bit down (bit 31 of every positive key's
+        // image is set, the sign bit of the float itself clear: the search runs over the float's own bits)
+        constexpr int LOWZ_P = std::is_same<T, uint16_t>::value ? 16 : std::is_same<T, _Float16>::value ? 13 : 0;
+        const float target = p.top_p * total;
+        uint32_t res = 0;
+        for (int bit = 30; bit >= LOWZ_P; --bit) {
+            const uint32_t cand = res | (1u << bit);
+            if (block_sum(mass_from(cand), (bit & 1) ^ 1) >= target) res = cand;
+        }
+        const float thr_p = total > 0.f ? __uint_as_float(res) : INFINITY;
+        if (tid == 0) thr_s = fminf(fmaxf(thr_p, thr_qm[0]), thr_qm[1]);  // (thr_qm: this thread's own stores)
+    } else {
+        __syncthreads();
+    }
+    if (!TOPP && w == 0) {
         uint32_t key[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -442,7 +531,7 @@ __global__ __launch_bounds__(1024) void topk_indices_kernel(const TopkParams p) 
             const int c = pass0 + j * 1024 + tid;
             bool keep = false;
             if (c < cols) {
-                keep = v[j] >= thr;
+                keep = TOPP ? (v[j] > 0.f && v[j] >= thr) : v[j] >= thr;
                 if (!keep && p.random_amount > 0.f) keep = hash_uniform(row, c, salt) < p.random_amount;
                 if (!keep) my_last_invalid = c;  // ascending c per thread => ends as the last rejected column
             }
@@ -1333,6 +1422,44 @@ static int launch_topk(const void *activation, void *cache, int dtype, int32_t *
     return CHIPMUNK_OK;
 }
 
+// the _p forms: `who` names the entry point in the messages
+static int launch_topk_p(const char *who, const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts, int rows,
+                         int cols, double sparsity_amount, double top_p, double min_keys, int multiple_of, double random_amount,
+                         void *stream) {
+    CM_CHECK(activation && indices && counts, "%s: null pointer", who);
+    CM_CHECK(rows >= 0 && cols >= 1024, "%s: rows >= 0 and cols >= 1024 required (the quantiles are taken over the first 1024 columns); got rows=%d cols=%d", who, rows, cols);
+    CM_CHECK(multiple_of > 0, "%s: multiple_of must be positive", who);
+    CM_CHECK(sparsity_amount >= 0.0 && sparsity_amount <= 1.0, "%s: sparsity_amount must be in [0,1]", who);
+    CM_CHECK(top_p > 0.0 && top_p <= 1.0, "%s: top_p must be in (0, 1] (got %g)", who, top_p);
+    // (1e-9: callers pass sparsity_amount = 1 - top_keys, and 1 - (1 - 0.1) is below 0.1 in double)
+    CM_CHECK(min_keys >= 0.0 && min_keys <= 1.0 - sparsity_amount + 1e-9, "%s: min_keys must be in [0, 1 - sparsity_amount] (got %g with sparsity_amount %g)",
+             who, min_keys, sparsity_amount);
+    if (rows == 0) return CHIPMUNK_OK;
+    TopkPParams p;
+    p.act = activation, p.cache = cache, p.indices = indices, p.counts = counts;
+    p.rows = rows, p.cols = cols, p.multiple_of = multiple_of;
+    p.quantile = (float)sparsity_amount, p.random_amount = (float)random_amount;
+    p.salt = random_amount > 0.0 ? chipmunk_next_random_salt() : 0u;
+    p.top_p = (float)top_p;
+    // the floor's index in the sorted sample, never below the cap's (in exact arithmetic it is not): the kept set stays a subset of the cap's
+    p.k_min = min_keys == 0.0 ? 1024 : std::max((int)(1024 * (float)(1.0 - min_keys)), (int)(1024 * p.quantile));
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH_TOPK_P(T)                                                                                         \
+    do {                                                                                                         \
+        if (cache) hipLaunchKernelGGL((topk_indices_kernel<T, true, true>), dim3(rows), dim3(1024), 0, s, p);    \
+        else hipLaunchKernelGGL((topk_indices_kernel<T, false, true>), dim3(rows), dim3(1024), 0, s, p);         \
+    } while (0)
+    switch (dtype) {
+        case CHIPMUNK_DTYPE_BF16: LAUNCH_TOPK_P(uint16_t); break;
+        case CHIPMUNK_DTYPE_FP16: LAUNCH_TOPK_P(_Float16); break;
+        case CHIPMUNK_DTYPE_FP32: LAUNCH_TOPK_P(float); break;
+        default: CM_CHECK(false, "%s: unsupported dtype code %d", who, dtype);
+    }
+#undef LAUNCH_TOPK_P
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+
 extern "C" int chipmunk_mask_to_sorted_indices(const void *mask, int packed, int32_t *indices, int32_t *counts,
                                                int64_t rows, int n, int pad_n, int multiple_of, void *stream) {
     return packed ? launch_m2i<true, true>(mask, indices, counts, rows, n, pad_n, multiple_of, stream)
@@ -1379,6 +1506,21 @@ extern "C" int chipmunk_topk_delta_indices(const void *activation, void *cache, 
     CM_CHECK(cache != nullptr, "topk_delta_indices: cache missing");
     return launch_topk(activation, cache, dtype, indices, counts, rows, cols, sparsity_amount, multiple_of,
                        random_amount, stream);
+}
+
+extern "C" int chipmunk_topk_indices_p(const void *activation, int dtype, int32_t *indices, int32_t *counts, int rows, int cols,
+                                       double sparsity_amount, double top_p, double min_keys, int multiple_of,
+                                       double random_amount, void *stream) {
+    return launch_topk_p("topk_indices_p", activation, nullptr, dtype, indices, counts, rows, cols, sparsity_amount, top_p, min_keys,
+                         multiple_of, random_amount, stream);
+}
+
+extern "C" int chipmunk_topk_delta_indices_p(const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts,
+                                             int rows, int cols, double sparsity_amount, double top_p, double min_keys,
+                                             int multiple_of, double random_amount, void *stream) {
+    CM_CHECK(cache != nullptr, "topk_delta_indices_p: cache missing");
+    return launch_topk_p("topk_delta_indices_p", activation, cache, dtype, indices, counts, rows, cols, sparsity_amount, top_p,
+                         min_keys, multiple_of, random_amount, stream);
 }
 
 extern "C" int chipmunk_copy_indices(const void *src, void *dst, const int32_t *inds, const int32_t *counts, int B,

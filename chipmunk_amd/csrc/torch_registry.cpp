@@ -738,6 +738,49 @@ void topk_delta_indices(at::Tensor activation, at::Tensor cache, at::Tensor indi
           "topk_delta_indices");
 }
 
+// topk_indices / topk_delta_indices with a column count per row from the row's mass (mlp.top_p; not in the reference)
+static void topk_p_common(const char *who, const at::Tensor &activation, const at::Tensor *cache, const at::Tensor &indices,
+                          const at::Tensor &counts, double sparsity_amount, double top_p, double min_keys, int64_t multiple_of,
+                          double random_amount) {
+    CHECK_DEV(activation); CHECK_DEV(indices); CHECK_DEV(counts);
+    CHECK_CONTIG(activation); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
+    TORCH_CHECK(activation.dim() == 3, who, ": activation must be [batch, rows, cols]");
+    if (cache) {
+        TORCH_CHECK(cache->is_cuda() && cache->is_contiguous(), who, ": cache must be a contiguous GPU tensor");
+        TORCH_CHECK(cache->sizes() == activation.sizes() && cache->scalar_type() == activation.scalar_type(), who,
+                    ": cache must have the shape and dtype of activation");
+    }
+    CHECK_I32(indices); CHECK_I32(counts);
+    TORCH_CHECK(indices.sizes() == activation.sizes(), who, ": indices must have the shape of activation");
+    TORCH_CHECK(counts.numel() == activation.size(0) * activation.size(1), who, ": counts must be [batch, rows]");
+    int dtype;
+    switch (activation.scalar_type()) {
+        case at::kBFloat16: dtype = CHIPMUNK_DTYPE_BF16; break;
+        case at::kHalf: dtype = CHIPMUNK_DTYPE_FP16; break;
+        case at::kFloat: dtype = CHIPMUNK_DTYPE_FP32; break;
+        default: TORCH_CHECK(false, "Unsupported dtype for ", who);
+    }
+    c10::DeviceGuard guard(activation.device());
+    const int rows = (int)(activation.size(0) * activation.size(1)), cols = (int)activation.size(2);
+    if (cache)
+        check(chipmunk_topk_delta_indices_p(activation.data_ptr(), cache->data_ptr(), dtype, indices.data_ptr<int>(), counts.data_ptr<int>(),
+                                            rows, cols, sparsity_amount, top_p, min_keys, (int)multiple_of, random_amount,
+                                            cur_stream(activation)), who);
+    else
+        check(chipmunk_topk_indices_p(activation.data_ptr(), dtype, indices.data_ptr<int>(), counts.data_ptr<int>(), rows, cols,
+                                      sparsity_amount, top_p, min_keys, (int)multiple_of, random_amount, cur_stream(activation)), who);
+}
+
+void topk_indices_p(at::Tensor activation, at::Tensor indices, at::Tensor counts, double sparsity_amount, double top_p,
+                    double min_keys, int64_t multiple_of, double random_amount) {
+    topk_p_common("topk_indices_p", activation, nullptr, indices, counts, sparsity_amount, top_p, min_keys, multiple_of, random_amount);
+}
+
+void topk_delta_indices_p(at::Tensor activation, at::Tensor cache, at::Tensor indices, at::Tensor counts, double sparsity_amount,
+                          double top_p, double min_keys, int64_t multiple_of, double random_amount) {
+    topk_p_common("topk_delta_indices_p", activation, &cache, indices, counts, sparsity_amount, top_p, min_keys, multiple_of, random_amount);
+}
+
 // reference csrc/indexed_io/mask_to_indices.cu:92-143
 std::vector<at::Tensor> mask_to_indices(at::Tensor mask, int64_t multiple_of, int64_t pad_to_multiple_of) {
     TORCH_CHECK(mask.dim() == 4, "mask must be 4-dimensional [b, h, m, n]");
@@ -1168,6 +1211,8 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_glu(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_fp8(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b_gate, Tensor scale_b_up, str act, bool update_cache) -> ()");
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
+    m.def("topk_indices_p(Tensor activation, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
+    m.def("topk_delta_indices_p(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
     m.def("packed_mask_to_indices(Tensor packed, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
     m.def("mask_to_sorted_indices(Tensor mask, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
     m.def("topk_mask(Tensor cs, int k, float random_amount, Tensor? groups, Tensor? static_mask) -> Tensor");
@@ -1221,6 +1266,8 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_glu", &csp_mlp_mm1_glu);
     m.impl("csp_mlp_mm1_glu_fp8", &csp_mlp_mm1_glu_fp8);
     m.impl("topk_delta_indices", &topk_delta_indices);
+    m.impl("topk_indices_p", &topk_indices_p);
+    m.impl("topk_delta_indices_p", &topk_delta_indices_p);
     m.impl("packed_mask_to_indices", &packed_mask_to_indices);
     m.impl("mask_to_sorted_indices", &mask_to_sorted_indices);
     m.impl("mask_to_ragged_indices", &mask_to_ragged_indices);

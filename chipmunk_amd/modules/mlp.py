@@ -77,6 +77,21 @@ def fc2_scale_of(fc2: torch.nn.Module):
     return fc2.scale_reciprocal if fc2.weight.dtype == torch.float8_e4m3fn else None
 
 
+def top_p_of(who: str, cfg) -> tuple:
+    """(``mlp.top_p``, ``mlp.top_p_min_keys``) of a step that makes a selection; ``top_p`` 0.0 when the per-group count is off (the
+    ``top_keys`` selection, untouched).  On: a 128-row group keeps the columns that carry the share ``top_p`` of its |block-mean delta|
+    mass, a subset of what ``top_keys`` keeps, and at least the sampled ``top_p_min_keys`` quantile (``ops.topk_indices_p``)."""
+    top_p = float(amd_key("mlp", "top_p"))
+    if top_p == 0.0:
+        return 0.0, 0.0
+    min_keys = float(amd_key("mlp", "top_p_min_keys"))
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"{who}: mlp.top_p must be in [0, 1] (got {top_p})")
+    if not 0.0 <= min_keys <= cfg["top_keys"]:
+        raise ValueError(f"{who}: mlp.top_p_min_keys must be in [0, mlp.top_keys] (got {min_keys} with top_keys {cfg['top_keys']})")
+    return top_p, min_keys
+
+
 class SparseDiffMlp:
     def __init__(self, layer_num: int, layer_counter: LayerCounter, fc1: torch.nn.Linear,
                  activation: torch.nn.Module, fc2: torch.nn.Linear, heuristic_sms_scatter_add: int = 6):
@@ -96,6 +111,7 @@ class SparseDiffMlp:
         if not cfg["is_enabled"]:
             return fc2(self.activation(fc1(x)))
 
+        top_p, min_keys = top_p_of("SparseDiffMlp", cfg)     # (0.0, 0.0) unless mlp.top_p is set: top_keys is then only the cap
         do_full = self.layer_counter.should_do_full_mlp_step()
         inference_step, layer, _submodule = self.layer_counter.increment()
         assert x.ndim == 3 and x.shape[0] >= 1, "x must be (B, N, C)"
@@ -135,8 +151,12 @@ class SparseDiffMlp:
                 # one kernel for |bmfc1 - cache| -> top-k indices -> copy of the selected columns into the cache
                 inds = torch.empty_like(bmfc1, dtype=torch.int32)
                 counts = torch.empty((bmfc1.size(0), bmfc1.size(1)), dtype=torch.int32, device=x.device)
-                torch.ops.chipmunk.topk_delta_indices(bmfc1, cache, inds, counts, 1 - cfg["top_keys"],
-                                                      cfg["counts_multiple_of"], cfg["random_keys"])
+                if top_p > 0.0:
+                    ops.topk_delta_indices_p(bmfc1, cache, inds, counts, 1 - cfg["top_keys"], top_p, min_keys,
+                                             cfg["counts_multiple_of"], cfg["random_keys"])
+                else:
+                    torch.ops.chipmunk.topk_delta_indices(bmfc1, cache, inds, counts, 1 - cfg["top_keys"],
+                                                          cfg["counts_multiple_of"], cfg["random_keys"])
             else:
                 mdiff = (bmfc1 - cache).abs()
                 b, rows, f = mdiff.shape
@@ -145,8 +165,12 @@ class SparseDiffMlp:
                 mdiff = mdiff.reshape(b, -1, r, f).sum(dim=2)
                 inds = torch.empty_like(mdiff, dtype=torch.int32, device=x.device)
                 counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=x.device)
-                ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
-                                 cfg["random_keys"])
+                if top_p > 0.0:
+                    ops.topk_indices_p(mdiff, inds, counts, 1 - cfg["top_keys"], top_p, min_keys, cfg["counts_multiple_of"],
+                                       cfg["random_keys"])
+                else:
+                    ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
+                                     cfg["random_keys"])
                 ops.copy_indices(bmfc1, cache, inds, counts)
             # the selected columns of the block means were refreshed in the LOADED tensor; a host copy has to follow (as for the activation
             # cache below), or the next selection is made against the block means of the last full step

@@ -24,7 +24,7 @@ from .. import ops
 from ..util.config import GLOBAL_CONFIG
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
-from .mlp import _ceil8, _transposed, _transposed_pitched, block_mean, check_fc2, fc2_scale_of
+from .mlp import _ceil8, _transposed, _transposed_pitched, block_mean, check_fc2, fc2_scale_of, top_p_of
 
 _F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
@@ -148,6 +148,7 @@ class SparseDiffGatedMlp:
         if not cfg["is_enabled"]:
             return self._dense(x)
 
+        top_p, min_keys = top_p_of("SparseDiffGatedMlp", cfg)     # (0.0, 0.0) unless mlp.top_p is set: top_keys is then only the cap
         do_full = self.layer_counter.should_do_full_mlp_step()
         inference_step, layer, _submodule = self.layer_counter.increment()
         assert x.ndim == 3 and x.shape[0] >= 1, "x must be (B, N, C)"
@@ -189,7 +190,10 @@ class SparseDiffGatedMlp:
             mdiff = mdiff.reshape(b, -1, 2 * r, f).sum(dim=2)
             inds = torch.empty_like(mdiff, dtype=torch.int32, device=x.device)
             counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=x.device)
-            ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"], cfg["random_keys"])
+            if top_p > 0.0:
+                ops.topk_indices_p(mdiff, inds, counts, 1 - cfg["top_keys"], top_p, min_keys, cfg["counts_multiple_of"], cfg["random_keys"])
+            else:
+                ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"], cfg["random_keys"])
             ops.copy_indices(bmpre, cache, inds, counts)     # rows [2 r g, 2 r (g + 1)) take group g's list
             # the selected columns of the block means were refreshed in the LOADED tensor; a host copy has to follow
             holder = self.storage.blockmean_mid_cache

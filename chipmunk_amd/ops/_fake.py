@@ -115,6 +115,23 @@ def _register():
         return [_o_like(q, token_major_o), q.new_empty((B, H, G, k.shape[2]), dtype=torch.bool),
                 q.new_empty((B, H, Nq, 1), dtype=torch.float32)]
 
+    @lib.register_fake("chipmunk::topk_indices_p")
+    def _(activation, indices, counts, sparsity_amount, top_p, min_keys, multiple_of, random_amount):
+        # writes indices and counts in place and returns nothing: the shapes are checked, so that a trace fails where the operator would
+        torch._check(activation.ndim == 3 and activation.shape[-1] >= 1024, lambda: "activation must be [batch, rows, cols] with cols >= 1024")
+        torch._check(indices.shape == activation.shape and counts.numel() == activation.shape[0] * activation.shape[1],
+                     lambda: "indices must have the shape of activation, counts must be [batch, rows]")
+        return None
+
+    @lib.register_fake("chipmunk::topk_delta_indices_p")
+    def _(activation, cache, indices, counts, sparsity_amount, top_p, min_keys, multiple_of, random_amount):
+        # as topk_indices_p; also copies the listed columns into cache in place
+        torch._check(activation.ndim == 3 and activation.shape[-1] >= 1024, lambda: "activation must be [batch, rows, cols] with cols >= 1024")
+        torch._check(cache.shape == activation.shape and cache.dtype == activation.dtype, lambda: "cache must have the shape and dtype of activation")
+        torch._check(indices.shape == activation.shape and counts.numel() == activation.shape[0] * activation.shape[1],
+                     lambda: "indices must have the shape of activation, counts must be [batch, rows]")
+        return None
+
     @lib.register_fake("chipmunk::qkv_split_norm")
     def _(qkv, q_weight, k_weight, heads, eps, freqs_cos=None, freqs_sin=None):
         out = qkv.new_empty((3, 1, heads, qkv.shape[0], 128))

@@ -19,6 +19,79 @@ def topk_indices(activations: torch.Tensor, indices_out: torch.Tensor, counts_ou
     torch.ops.chipmunk.topk_indices(activations, indices_out, counts_out, sparsity_amount, multiple_of, rk)
 
 
+def _check_top_p(who: str, sparsity_amount: float, top_p: float, min_keys: float) -> None:
+    if not (0.0 < top_p <= 1.0) or not (0.0 <= sparsity_amount <= 1.0) or not (0.0 <= min_keys <= 1.0 - sparsity_amount + 1e-9):
+        raise ValueError(f"{who}: top_p must be in (0, 1], sparsity_amount in [0, 1] and min_keys in [0, 1 - sparsity_amount] "
+                         f"(got top_p {top_p}, sparsity_amount {sparsity_amount}, min_keys {min_keys})")
+
+
+def _f32(x: float) -> float:
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def _topk_indices_p_cpu(activations: torch.Tensor, indices_out: torch.Tensor, counts_out: torch.Tensor, sparsity_amount: float,
+                        top_p: float, min_keys: float, multiple_of: int, rk: float) -> None:
+    """The rule of ``topk_indices_p`` in plain torch: one sort per row, fp64 sums; output order and padding as the kernel's."""
+    f = activations.shape[-1]
+    if f < 1024:
+        raise ValueError(f"topk_indices_p: rows of 1024 columns or more (the quantiles are taken over the first 1024); got {f}")
+    rows = activations.reshape(-1, f).double()
+    inds, counts = indices_out.view(-1, f), counts_out.view(-1)
+    if _f32(sparsity_amount) == 1.0:       # keep nothing, as topk_indices
+        inds.fill_(-1)
+        counts.zero_()
+        return
+    mass = torch.where(rows > 0, rows, torch.zeros_like(rows))          # a zero, negative or NaN entry carries no mass
+    desc, _ = mass.sort(dim=-1, descending=True)
+    csum = desc.cumsum(-1)
+    total = csum[:, -1:]
+    first = (csum < top_p * total).sum(-1, keepdim=True).clamp(max=f - 1)       # the first prefix whose mass reaches the target
+    inf = torch.full_like(total, float("inf"))
+    thr_p = torch.where(total > 0, desc.gather(-1, first), inf)                 # its value: a class of equal values is taken whole
+    sample = rows[:, :1024].sort(dim=-1).values
+    iq = int(1024 * _f32(sparsity_amount))
+    thr_q = -inf if sparsity_amount == 0 else sample[:, iq:iq + 1]
+    im = 1024 if min_keys == 0 else max(int(1024 * _f32(1.0 - min_keys)), iq)
+    thr_min = inf if im >= 1024 else sample[:, im:im + 1]
+    thr = torch.minimum(torch.maximum(thr_p, thr_q), thr_min)
+    keep = (rows > 0) & (rows >= thr)
+    listed = keep | (~keep & (torch.rand(keep.shape) < rk)) if rk > 0 else keep
+    cols = torch.arange(f, dtype=torch.int64)
+    for r in range(rows.shape[0]):
+        on = cols[listed[r]]
+        off = cols[~listed[r]]
+        last = torch.full((1024,), -1, dtype=torch.int64).scatter_reduce(0, off % 1024, off, "amax")     # last rejected column per residue
+        pad = (-on.numel()) % multiple_of
+        row = torch.cat([on, last[last >= 0][:pad]])
+        inds[r, : row.numel()] = row.to(torch.int32)
+        counts[r] = on.numel() + pad
+
+
+def topk_indices_p(activations: torch.Tensor, indices_out: torch.Tensor, counts_out: torch.Tensor, sparsity_amount: float,
+                   top_p: float, min_keys: float, multiple_of: int, rk: float) -> None:
+    """``topk_indices`` with a column count per row (not in the reference; ``mlp.top_p``).  Per row of values ``v``: mass ``m_c = v_c``
+    where positive (a zero, negative or NaN entry carries none), ``total`` over the whole row; ``thr_p`` the largest ``t`` whose columns
+    ``v_c >= t`` carry ``top_p * total`` (a class of equal values is taken whole; +inf for an all-zero row); ``thr_q`` the threshold of
+    ``topk_indices`` (element ``int(1024 * sparsity_amount)`` of the sorted first 1024 values; -inf for ``sparsity_amount == 0``);
+    ``thr_min`` the same order statistic at ``1 - min_keys`` (+inf for ``min_keys == 0``); kept: ``m_c > 0 and v_c >= min(max(thr_p,
+    thr_q), thr_min)``.  Random keys, padding, order and ``counts`` as ``topk_indices``.  The kept set is a subset of what
+    ``topk_indices`` keeps (the cap is a threshold: no tie-break); an all-zero row keeps nothing (``topk_indices`` keeps all of it);
+    ``sparsity_amount == 1`` keeps nothing; the floor is a sampled quantile like the cap, blind to columns past the first 1024.  The
+    kernel sums in fp32 in a fixed order (same launch, same bits); CPU tensors take a sort with fp64 sums."""
+    _check_top_p("topk_indices_p", sparsity_amount, top_p, min_keys)
+    if not activations.is_cuda:
+        return _topk_indices_p_cpu(activations, indices_out, counts_out, sparsity_amount, top_p, min_keys, multiple_of, rk)
+    torch.ops.chipmunk.topk_indices_p(activations, indices_out, counts_out, sparsity_amount, top_p, min_keys, multiple_of, rk)
+
+
+def topk_delta_indices_p(activations: torch.Tensor, cache: torch.Tensor, indices_out: torch.Tensor, counts_out: torch.Tensor,
+                         sparsity_amount: float, top_p: float, min_keys: float, multiple_of: int, rk: float) -> None:
+    """``|activations - cache|`` (rounded to the element type) -> ``topk_indices_p`` -> copy of every listed column of ``activations``
+    into ``cache``, as one kernel: ``topk_delta_indices`` with the selection of ``topk_indices_p``.  GPU tensors only."""
+    _check_top_p("topk_delta_indices_p", sparsity_amount, top_p, min_keys)
+    torch.ops.chipmunk.topk_delta_indices_p(activations, cache, indices_out, counts_out, sparsity_amount, top_p, min_keys, multiple_of, rk)
+
+
 def scatter_add(packed: torch.Tensor, unpacked: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
                 num_sms: int) -> None:
     if packed.ndim == 3:   # a batch [B, M, F] with unpacked [B, F, M], indices [B, G, F], counts [B, G]: one launch

@@ -128,6 +128,12 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     "attn.top_p": 0.0,
     # ... and never fewer than this fraction of the keys (rounded like top_keys)
     "attn.top_p_min_keys": 0.0,
+    # sparse MLP step with a column count per 128-row group (not in the reference): a group recomputes the fc1 columns that carry this share
+    # of its |block-mean delta| mass (the largest first, a class of equal deltas taken whole), never more than the top_keys rule keeps -- a
+    # group whose input hardly moved, or moved in few columns, runs shorter GEMMs.  0.0 = off: the top_keys selection, as in the reference.
+    "mlp.top_p": 0.0,
+    # ... and never fewer than this fraction of the columns (a sampled quantile like top_keys'; at most top_keys)
+    "mlp.top_p_min_keys": 0.0,
 }
 BASE_CONFIG["offloading"]["keep_resident_if_fits"] = AMD_EXTRA_KEYS["offloading.keep_resident_if_fits"]
 BASE_CONFIG["offloading"]["hbm_budget_gb"] = AMD_EXTRA_KEYS["offloading.hbm_budget_gb"]
@@ -147,6 +153,8 @@ BASE_CONFIG["attn"]["ragged_mask_to_indices"] = AMD_EXTRA_KEYS["attn.ragged_mask
 BASE_CONFIG["mlp"]["fp8_fc2"] = AMD_EXTRA_KEYS["mlp.fp8_fc2"]
 BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
+BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]
+BASE_CONFIG["mlp"]["top_p_min_keys"] = AMD_EXTRA_KEYS["mlp.top_p_min_keys"]
 
 GLOBAL_CONFIG: Dict[str, Any] = copy.deepcopy(BASE_CONFIG)
 

@@ -300,6 +300,32 @@ int chipmunk_topk_delta_indices(const void *activation, void *cache, int dtype, 
                                 int rows, int cols, double sparsity_amount, int multiple_of, double random_amount,
                                 void *stream);
 
+/* chipmunk_topk_indices with a column count per row from the row's mass (not in the reference; config mlp.top_p).
+ * For a row of values v_c (the activations as given):
+ *   mass     m_c = v_c where v_c > 0; a zero, negative or NaN entry carries none
+ *   total    sum of m_c over the whole row (not over the sample); target = float(top_p) * total
+ *   thr_p    the largest t with sum{m_c : v_c >= t} >= target, so a class of equal values is taken whole; +inf when total == 0
+ *   thr_q    chipmunk_topk_indices' threshold: element int(1024 * sparsity_amount) of the ascending-sorted first 1024 values;
+ *            -inf for sparsity_amount == 0 (no cap)
+ *   thr_min  the same order statistic at 1 - min_keys (its index never below thr_q's); +inf for min_keys == 0
+ *   kept     m_c > 0 and v_c >= min(max(thr_p, thr_q), thr_min)
+ * Random keys (a hash draw below random_amount on a column not kept), padding up to multiple_of with rejected columns, the order
+ * (kept columns ascending first) and counts (kept + padding) are chipmunk_topk_indices'.  The kept set is a subset of what
+ * chipmunk_topk_indices keeps (the cap is a threshold: no tie-break).  An all-zero row keeps nothing (count 0 with random_amount
+ * 0; chipmunk_topk_indices keeps the whole row).  sparsity_amount == 1 keeps nothing.  The floor is a sampled quantile like the cap:
+ * blind to columns past the first 1024.  0 < top_p <= 1, 0 <= min_keys <= 1 - sparsity_amount, cols >= 1024.
+ * The sums are fp32 in one fixed order (a thread's columns ascending, the wave's DPP tree, the 16 wave partials ascending), no
+ * floating-point atomics: the same launch gives the same bits, and rows whose sums are exact in fp32 give exactly the rule above. */
+int chipmunk_topk_indices_p(const void *activation, int dtype, int32_t *indices, int32_t *counts, int rows, int cols,
+                            double sparsity_amount, double top_p, double min_keys, int multiple_of, double random_amount,
+                            void *stream);
+
+/* chipmunk_topk_delta_indices with the selection of chipmunk_topk_indices_p: v_c = |T(activation_c - cache_c)| rounded to the element
+ * type T; every listed column (padding included) of `activation` is copied into `cache`. */
+int chipmunk_topk_delta_indices_p(const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts, int rows,
+                                  int cols, double sparsity_amount, double top_p, double min_keys, int multiple_of,
+                                  double random_amount, void *stream);
+
 /* chipmunk_dense_colsum_attn + chipmunk_topk_mask without the cs tensor between them (reference modules/attn.py:131-141 calls
  * dense_colsum_attn, then random_and_topk on its 3.55 GB result at HunyuanVideo size): o, l as chipmunk_dense_colsum_attn,
  * mask [B*H*ceil(Nq/192), Nk] bool bytes as chipmunk_topk_mask would produce from that call's cs -- bit for bit.
