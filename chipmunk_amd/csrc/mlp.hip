@@ -83,6 +83,15 @@ __device__ __forceinline__ f32x2 glu_act2(f32x2 x) {
     }
 }
 
+// (scalar twin, for the direct epilogue of the ungated GEMM1: the same operation sequence per element)
+template <int ACT>
+__device__ __forceinline__ float glu_act(float x) {
+    static_assert(ACT >= 0 && ACT <= 2, "unknown activation");
+    if constexpr (ACT == 0) return gelu_tanh(x);
+    else if constexpr (ACT == 1) return x * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x * -1.44269504089f) + 1.0f);
+    else return (x * 0.5f) * (erff(x * 0.70710678118654752f) + 1.0f);
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     static_assert(N >= 0 && N < 64, "vmcnt immediate out of range");
@@ -213,7 +222,9 @@ struct Mm1GluF8Params : Mm1Params {
 // (and with it the weight the rows are gathered from) is uniform per instruction.  Cache block and output image are TN/2 columns wide.
 // FP8 && GLU (P = Mm1GluF8Params): the k loop of the fp8 form (e4m3 fragments, 32x32x64 MFMA, accumulators from zero) under the B-row gather
 // and the epilogue of the gated form; each branch's sum is scaled by scale_x and its own weight scale, then biased, in the fp8 form's order.
-template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params>
+// Ungated forms with ACT != 0 or NULLB (mm1_act_kernel): c = bf16(act(x W + b) - cache) with act one of CHIPMUNK_ACT_*, and a null bias vector
+// read as zero -- bf16 seeds its accumulators with 0, fp8 adds 0 behind the scales.  ACT = 0 without NULLB is the code mm1_kernel always had.
+template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params, bool NULLB = false>
 __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
     using KT = KTile<BK>;
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
@@ -315,6 +326,8 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         if constexpr (GLU) {   // n4 = 0: the gate's bias, 1: the up projection's; a null vector is zero
             const uint16_t *bp = n4 ? p.bias_up : p.bias;
             bias_v[n4] = bp ? bf16_bits_to_f32(bp[idxg[j < cnt ? j : n0]]) : 0.f;
+        } else if constexpr (NULLB) {
+            bias_v[n4] = p.bias ? bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]) : 0.f;
         } else {
             bias_v[n4] = bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]);
         }
@@ -466,8 +479,8 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                         } else if constexpr (FP8) {
                             // (acc * scale_a) * scale_b + bias in the reference's order -> gelu -> bf16, then a bf16 subtract (csp_mlp_mm1.py:121-133)
                             const f32x2 sav = {sa, sa}, sbv = {sb, sb}, bv = {bia, bia};
-                            const uint32_t t01 = pack_bf16x2_v(gelu_tanh2((a01 * sav) * sbv + bv));
-                            const uint32_t t23 = pack_bf16x2_v(gelu_tanh2((a23 * sav) * sbv + bv));
+                            const uint32_t t01 = pack_bf16x2_v(glu_act2<ACT>((a01 * sav) * sbv + bv));
+                            const uint32_t t23 = pack_bf16x2_v(glu_act2<ACT>((a23 * sav) * sbv + bv));
                             d01 = pack_bf16x2_v(unpack_bf16x2(t01) - c01), d23 = pack_bf16x2_v(unpack_bf16x2(t23) - c23);
                             if constexpr (UPD == 2) n01 = t01, n23 = t23;   // 2: cache = new activation, what the reference's Triton kernel does (csp_mlp_mm1.py:140)
                         } else if constexpr (GLU) {
@@ -477,7 +490,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                             d23 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>(a23), u23, -c23));
                         } else {
                             // the bias is already in the sum (SEED_BIAS)
-                            d01 = pack_bf16x2_v(gelu_tanh2(a01) - c01), d23 = pack_bf16x2_v(gelu_tanh2(a23) - c23);
+                            d01 = pack_bf16x2_v(glu_act2<ACT>(a01) - c01), d23 = pack_bf16x2_v(glu_act2<ACT>(a23) - c23);
                         }
                         uint16_t *op = (uint16_t *)(ot_row(ml) + jl * 2);   // (rows ml .. ml+3: on one side of the split, a multiple of 4)
                         op[0] = (uint16_t)d01, op[PW] = (uint16_t)(d01 >> 16), op[2 * PW] = (uint16_t)d23, op[3 * PW] = (uint16_t)(d23 >> 16);
@@ -545,10 +558,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                     const u32x2 cv = *(const u32x2 *)(crow + m);
                     const float c0 = __uint_as_float(cv[0] << 16), c1 = __uint_as_float(cv[0] & 0xffff0000u);
                     const float c2 = __uint_as_float(cv[1] << 16), c3 = __uint_as_float(cv[1] & 0xffff0000u);
-                    const float x0 = gelu_tanh(acc[mt][n4][q4 * 4 + 0]) - c0;   // (bias already in the sum)
-                    const float x1 = gelu_tanh(acc[mt][n4][q4 * 4 + 1]) - c1;
-                    const float x2 = gelu_tanh(acc[mt][n4][q4 * 4 + 2]) - c2;
-                    const float x3 = gelu_tanh(acc[mt][n4][q4 * 4 + 3]) - c3;
+                    const float x0 = glu_act<ACT>(acc[mt][n4][q4 * 4 + 0]) - c0;   // (bias already in the sum)
+                    const float x1 = glu_act<ACT>(acc[mt][n4][q4 * 4 + 1]) - c1;
+                    const float x2 = glu_act<ACT>(acc[mt][n4][q4 * 4 + 2]) - c2;
+                    const float x3 = glu_act<ACT>(acc[mt][n4][q4 * 4 + 3]) - c3;
                     if (live) {
                         uint16_t *cp = p.c + (int64_t)m * p.F + j;
                         cp[0] = f32_to_bf16_bits(x0);
@@ -637,6 +650,48 @@ __global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const typename std::c
             }
             __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
         }
+    }
+}
+
+// The ungated GEMM1 with the activation as a template parameter (CHIPMUNK_ACT_*) and a bias that may be null (= zero): a kernel of its
+// own, so that mm1_kernel's instantiations keep their names and their code (a walk shared through a device function moved mm1_kernel's
+// scalar register allocation).  mm1_kernel's 4-wave form line for line -- the persistent walk, tail split, ragged last group, batch pointer
+// advance -- with mm1_tile's ACT and NULLB set.
+template <int BN, int BK, int NST, int WPS, bool FP8, int ACT, bool BATCHED = false>
+__global__ __launch_bounds__(256, WPS) void mm1_act_kernel(const typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int NSUB = 2 * (BN / 64);  // 64 x 64 sub-tiles per tile
+    constexpr int SUB_NST = (NST * (BM + BN)) / 128 > 4 ? 4 : (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
+    const TilePlan pl = plan_tiles<BN>(p.counts, G, p.NT, p.NR, p.slots_per_xcd, NSUB);
+    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+        const TileMap tm = tile_at(pl, slot);
+        if (!tm.live) continue;
+        const int cnt = p.counts[tm.g];
+        int g = tm.g;
+        Mm1Params q = p;                              // the tile sees its sequence's operands
+        if constexpr (BATCHED) {
+            const int b = tm.g / Gs;
+            g = tm.g - b * Gs;                        // group inside sequence b
+            q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)b * p.M * p.K * (FP8 ? 1 : 2));
+            q.c = p.c + (int64_t)b * p.M * p.F;
+            q.cache = p.cache + (int64_t)b * p.cache_bs;
+            q.indices = p.indices + (int64_t)b * Gs * p.F;
+        }
+        if (tm.sub < 0) {
+            const int n0 = tm.nt * BN;
+            if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
+            mm1_tile<BM, BN, BK, NST, FP8, 4, false, ACT, Mm1Params, true>(q, smem, g, 0, n0, cnt);
+        } else {
+            const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
+            if (n0 >= cnt) continue;
+            if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
+            mm1_tile<64, 64, BK, SUB_NST, FP8, 4, false, ACT, Mm1Params, true>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
+        }
+        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
     }
 }
 
@@ -1556,7 +1611,9 @@ int launch_mm2_w8(const void *, const void *, const float *, void *, const int32
 template <class P> struct Mm1BatchOf { using type = Mm1Batch; };
 template <> struct Mm1BatchOf<Mm1GluF8Params> { using type = Mm1GluF8Batch; };
 
-template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false, bool GLU = false, int ACT = 0, class P = Mm1Params>
+// ACTK: the ungated form through mm1_act_kernel (activation ACT, nullable bias) instead of mm1_kernel
+template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false, bool GLU = false, int ACT = 0, class P = Mm1Params,
+          bool ACTK = false>
 int launch_mm1_variant(const P &p0, hipStream_t s, bool *cache_updated = nullptr, int B = 1, int64_t cache_bs = 0) {
     constexpr int PBN = GLU ? BN / 2 : BN;   // packed columns per whole tile (gated form: the B tile's rows are {gate, up} pairs)
     constexpr int STAGE = BM * BK * 2 + BN * BK * 2, LDS = NST * STAGE, EPI = BM * PBN * 2;
@@ -1565,9 +1622,12 @@ int launch_mm1_variant(const P &p0, hipStream_t s, bool *cache_updated = nullptr
     auto kern = [] {
         if constexpr (GLU && FP8) return mm1_glu_fp8_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
         else if constexpr (GLU) return mm1_glu_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+        else if constexpr (ACTK) return mm1_act_kernel<BN, BK, NST, WPS, FP8, ACT, BATCHED>;
         else return mm1_kernel<BN, BK, NST, WPS, FP8, NW, BATCHED>;
     }();
     static_assert(!GLU || NW == 4, "the gated GEMM1 has 4 waves");
+    static_assert(!ACTK || (NW == 4 && !GLU), "mm1_act_kernel is the ungated 4-wave form");
+    static_assert(ACTK || GLU || ACT == 0, "mm1_kernel computes tanh-GeLU only");
     static_assert(std::is_same<P, Mm1GluF8Params>::value == (GLU && FP8), "the gated fp8 form, and only it, takes Mm1GluF8Params");
     static uint64_t lds_set = 0;
     ensure_dynamic_lds((const void *)kern, LDS, lds_set);
@@ -1684,6 +1744,55 @@ int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void 
     return launch_mm1_variant<128, 64, 2, 2, true>(p, stream);
 }
 
+// Ungated GEMM1 with an activation code and a nullable bias (mm1_act_kernel): the *_ragged / *_batched contract, the shipped tile shape only
+// (option mm1_variant is ignored; the probe-forms library does not carry these kernels)
+#ifndef CHIPMUNK_MM1_PROBES
+template <bool FP8, bool BATCHED>
+int launch_mm1_act(const Mm1Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
+    switch (act) {
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 0, Mm1Params, true>(p, stream, nullptr, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 1, Mm1Params, true>(p, stream, nullptr, B, cache_bs);
+        default: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 2, Mm1Params, true>(p, stream, nullptr, B, cache_bs);
+    }
+}
+#else
+template <bool FP8, bool BATCHED>
+int launch_mm1_act(const Mm1Params &, int, hipStream_t, int, int64_t) {
+    CM_CHECK(false, "csp_mlp_mm1_act: not part of the probe-forms library");
+    return CHIPMUNK_OK;
+}
+#endif
+// scale_a / scale_b null: the bf16 form (update_cache 0 / 1); both given: the e4m3 form (update_cache 0 / 1 / 2 as chipmunk_csp_mlp_mm1_fp8)
+int mm1_act_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices, const int32_t *counts,
+                  const float *scale_a, const float *scale_b, bool fp8, int M, int K, int F, int ldc, int act, int update_cache,
+                  hipStream_t stream, int B = 0, int64_t cache_bs = 0) {   // B > 0: the *_batched entries
+    if (fp8) CM_CHECK(a && b && c && pa_cache && scale_a && scale_b, "csp_mlp_mm1_fp8_act: null tensor or scale pointer");
+    else CM_CHECK(a && b && c && pa_cache, "csp_mlp_mm1_act: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_cache_pitch(M, F, ldc)) return e;
+    if (B > 0) {
+        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
+    }
+    const char *who = fp8 ? "csp_mlp_mm1_fp8_act" : "csp_mlp_mm1_act";
+    CM_CHECK(act == CHIPMUNK_ACT_GELU_TANH || act == CHIPMUNK_ACT_SILU || act == CHIPMUNK_ACT_GELU_ERF,
+             "%s: unknown activation %d (0 = gelu_tanh, 1 = silu, 2 = gelu)", who, act);
+    if (fp8) {
+        CM_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8_act: update_cache must be 0, 1 or 2 (got %d)", update_cache);
+        CM_CHECK(K > 0 && K % 128 == 0, "csp_mlp_mm1_fp8_act: K must be a positive multiple of 128 (got %d)", K);
+    } else {
+        CM_CHECK(update_cache == 0 || update_cache == 1, "csp_mlp_mm1_act: update_cache must be 0 or 1 (got %d)", update_cache);
+        CM_CHECK(K > 0 && K % 64 == 0, "csp_mlp_mm1_act: K must be a positive multiple of 64 (got %d)", K);
+    }
+    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
+             "%s: operand too large for 32-bit offsets", who);
+    // the kernel's update_cache: 1 = scatter-add of the deltas, 2 (fp8) = store the new activation -- the fp8 entries' 2 and 1
+    const int upd = fp8 ? (update_cache == 1 ? 2 : update_cache == 2 ? 1 : 0) : update_cache;
+    Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
+                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, upd, scale_a, scale_b, ldc};
+    if (fp8) return B > 0 ? launch_mm1_act<true, true>(p, act, stream, B, cache_bs) : launch_mm1_act<true, false>(p, act, stream, 1, 0);
+    return B > 0 ? launch_mm1_act<false, true>(p, act, stream, B, cache_bs) : launch_mm1_act<false, false>(p, act, stream, 1, 0);
+}
+
 // Gated GEMM1 (SwiGLU / GEGLU): the *_ragged / *_batched contract, bf16 (the e4m3 form is mm1_glu_fp8_entry below), the shipped tile shape only
 template <bool BATCHED>
 int launch_mm1_glu(const Mm1Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
@@ -1777,6 +1886,32 @@ extern "C" int chipmunk_csp_mlp_mm1_glu_batched(const void *a, const void *b_gat
     if (int e = check_mlp_batch(B, M)) return e;
     return mm1_glu_entry(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache, indices, counts, M, K, F, ldc, act, update_cache,
                          (hipStream_t)stream, B, cache_batch_stride);
+}
+
+// ---- ungated GEMM1 with an activation code and a nullable bias (include/chipmunk_hip.h, "Ungated activations")
+extern "C" int chipmunk_csp_mlp_mm1_act(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                        const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, void *stream) {
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, nullptr, nullptr, false, M, K, F, ldc, act, update_cache, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_act_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                                const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
+                                                int update_cache, int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, nullptr, nullptr, false, M, K, F, ldc, act, update_cache, (hipStream_t)stream,
+                         B, cache_batch_stride);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_act(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                            const int32_t *counts, const float *scale_a, const float *scale_b, int M, int K, int F, int ldc,
+                                            int act, int update_cache, void *stream) {
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, true, M, K, F, ldc, act, update_cache, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_act_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                                    const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                                    int M, int K, int F, int ldc, int act, int update_cache, int B,
+                                                    int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, true, M, K, F, ldc, act, update_cache, (hipStream_t)stream,
+                         B, cache_batch_stride);
 }
 
 extern "C" int chipmunk_csp_mlp_mm1(const void *a, const void *b, void *c, const void *bias, const void *pa_cache,

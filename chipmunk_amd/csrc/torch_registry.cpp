@@ -515,6 +515,70 @@ void csp_mlp_mm1_fp8_scatter(at::Tensor a, at::Tensor b, at::Tensor c, at::Tenso
     mm1_fp8_impl(a, b, c, bias, pa_cache_colmajor, indices, indices_counts, scale_a, scale_b, 2);
 }
 
+// addition: the ungated GEMM1 with the activation by name and an optional bias, c = bf16(act(a b^T + bias) - cache); bf16 operands, or
+// (scale_a / scale_b given) e4m3 a / b in the arithmetic of csp_mlp_mm1_fp8.  2-D operands or the 3-D batch, always the ragged contract.
+// update_cache: the C entries' (bf16 0 / 1; fp8 0 / 1 / 2).
+static void mm1_act_impl(const char *who, at::Tensor a, at::Tensor b, at::Tensor c, const c10::optional<at::Tensor> &bias,
+                         at::Tensor pa_cache_colmajor, at::Tensor indices, at::Tensor indices_counts, const at::Tensor *scale_a,
+                         const at::Tensor *scale_b, const std::string &act, int update_cache) {
+    const bool fp8 = scale_a != nullptr;
+    CHECK_DEV(a); CHECK_DEV(b); CHECK_DEV(c); CHECK_DEV(pa_cache_colmajor);
+    CHECK_DEV(indices); CHECK_DEV(indices_counts);
+    if (fp8) {
+        TORCH_CHECK(a.scalar_type() == at::kFloat8_e4m3fn && b.scalar_type() == at::kFloat8_e4m3fn,
+                    who, ": a and b must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+        for (const at::Tensor *s : {scale_a, scale_b})
+            TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->numel() == 1,
+                        who, ": scale_a and scale_b must be one-element float32 tensors on the GPU");
+    } else {
+        CHECK_BF16(a); CHECK_BF16(b);
+    }
+    CHECK_BF16(c); CHECK_BF16(pa_cache_colmajor);
+    CHECK_I32(indices); CHECK_I32(indices_counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(b); CHECK_CONTIG(c);
+    CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
+    const Mm1Shape sh = mm1_shape(a, b, c, nullptr, pa_cache_colmajor, indices, indices_counts);
+    const void *bp = nullptr;
+    if (bias.has_value()) {
+        const at::Tensor &t = *bias;
+        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
+        TORCH_CHECK(t.numel() == sh.F, "bias must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
+        bp = t.data_ptr();
+    }
+    int code = -1;
+    if (act == "gelu_tanh") code = CHIPMUNK_ACT_GELU_TANH;
+    else if (act == "silu") code = CHIPMUNK_ACT_SILU;
+    else if (act == "gelu") code = CHIPMUNK_ACT_GELU_ERF;
+    TORCH_CHECK(code >= 0, who, ": unknown activation '", act, "' (one of gelu_tanh, silu, gelu)");
+    c10::DeviceGuard guard(a.device());
+    int *ip = indices.data_ptr<int>(), *cp = indices_counts.data_ptr<int>();
+    const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc;
+    if (fp8 && sh.batched())
+        check(chipmunk_csp_mlp_mm1_fp8_act_batched(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp,
+                                                   scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), M, K, F, ldc, code,
+                                                   update_cache, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (fp8)
+        check(chipmunk_csp_mlp_mm1_fp8_act(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp,
+                                           scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), M, K, F, ldc, code, update_cache,
+                                           cur_stream(a)), who);
+    else if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_act_batched(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp, M, K, F,
+                                               ldc, code, update_cache, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else
+        check(chipmunk_csp_mlp_mm1_act(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp, M, K, F, ldc,
+                                       code, update_cache, cur_stream(a)), who);
+}
+void csp_mlp_mm1_act(at::Tensor a, at::Tensor b, at::Tensor c, const c10::optional<at::Tensor> &bias, at::Tensor pa_cache,
+                     at::Tensor indices, at::Tensor counts, std::string act, bool update_cache) {
+    mm1_act_impl("csp_mlp_mm1_act", a, b, c, bias, pa_cache, indices, counts, nullptr, nullptr, act, update_cache ? 1 : 0);
+}
+void csp_mlp_mm1_fp8_act(at::Tensor a, at::Tensor b, at::Tensor c, const c10::optional<at::Tensor> &bias, at::Tensor pa_cache,
+                         at::Tensor indices, at::Tensor counts, at::Tensor scale_a, at::Tensor scale_b, std::string act,
+                         int64_t update_cache) {
+    TORCH_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8_act: update_cache must be 0, 1 or 2 (got ", update_cache, ")");
+    mm1_act_impl("csp_mlp_mm1_fp8_act", a, b, c, bias, pa_cache, indices, counts, &scale_a, &scale_b, act, (int)update_cache);
+}
+
 int64_t check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, const at::Tensor &inds,
                            const at::Tensor &counts, int64_t *cache_bs) {   // returns the cache pitch; *cache_bs: the cache's batch stride
     // reference csrc/indexed_io/scatter_add.cu:111-142 (B is hard-wired to 1, :58-59,138)
@@ -1210,6 +1274,8 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_fp8_scatter(Tensor a, Tensor b, Tensor(c!) c, Tensor bias, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b) -> ()");
     m.def("csp_mlp_mm1_glu(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_fp8(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b_gate, Tensor scale_b_up, str act, bool update_cache) -> ()");
+    m.def("csp_mlp_mm1_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
+    m.def("csp_mlp_mm1_fp8_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, Tensor scale_a, Tensor scale_b, str act, int update_cache) -> ()");
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
     m.def("topk_indices_p(Tensor activation, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
     m.def("topk_delta_indices_p(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
@@ -1265,6 +1331,8 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_fp8", &csp_mlp_mm1_fp8);
     m.impl("csp_mlp_mm1_glu", &csp_mlp_mm1_glu);
     m.impl("csp_mlp_mm1_glu_fp8", &csp_mlp_mm1_glu_fp8);
+    m.impl("csp_mlp_mm1_act", &csp_mlp_mm1_act);
+    m.impl("csp_mlp_mm1_fp8_act", &csp_mlp_mm1_fp8_act);
     m.impl("topk_delta_indices", &topk_delta_indices);
     m.impl("topk_indices_p", &topk_indices_p);
     m.impl("topk_delta_indices_p", &topk_delta_indices_p);

@@ -11,6 +11,8 @@ scatter the activation deltas into the cache and add ``delta @ fc2^T`` onto the 
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
 from .. import ops
@@ -92,11 +94,36 @@ def top_p_of(who: str, cfg) -> tuple:
     return top_p, min_keys
 
 
+def activation_code(activation: torch.nn.Module, who: str = "SparseDiffGatedMlp", what: str = "the gated GEMM1") -> str:
+    """The GEMM1 kernels' name for an activation module (one of ``ops.mlp.GLU_ACTS``); anything the kernels do not compute raises."""
+    if isinstance(activation, torch.nn.SiLU):
+        return "silu"
+    if isinstance(activation, torch.nn.GELU) and activation.approximate in ("tanh", "none"):
+        return "gelu_tanh" if activation.approximate == "tanh" else "gelu"
+    raise ValueError(f"{who}: unsupported activation {activation!r}: {what} computes nn.SiLU(), "
+                     "nn.GELU(approximate='tanh') and nn.GELU() only")
+
+
 class SparseDiffMlp:
+    """``fc2(activation(fc1(x)))``.  The sparse steps recompute ``activation`` inside GEMM1, so it has to be one the kernel knows:
+    ``nn.GELU(approximate="tanh")`` (the reference's), ``nn.GELU()`` (exact, erf) or ``nn.SiLU()``, subclasses included; for any other
+    callable that computes one of the three, ``act`` names it (``"gelu_tanh"``, ``"gelu"``, ``"silu"``).  Everything else raises at
+    construction: its sparse steps would subtract another function from the activation cache than the full steps put there.
+    ``fc1`` may have no bias (``nn.Linear(..., bias=False)``, or an e4m3 ``F8Linear`` without one)."""
+
     def __init__(self, layer_num: int, layer_counter: LayerCounter, fc1: torch.nn.Linear,
-                 activation: torch.nn.Module, fc2: torch.nn.Linear, heuristic_sms_scatter_add: int = 6):
+                 activation: torch.nn.Module, fc2: torch.nn.Linear, heuristic_sms_scatter_add: int = 6, act: Optional[str] = None):
         # lists keep the Linear modules out of any parent nn.Module's parameter registry (reference mlp.py:21-23)
         check_fc2("SparseDiffMlp", fc2)
+        if act is not None:
+            if act not in ops.GLU_ACTS:
+                raise ValueError(f"SparseDiffMlp: unknown act {act!r} (one of {', '.join(ops.GLU_ACTS)})")
+            self.act_code = act
+        else:
+            try:
+                self.act_code = activation_code(activation, "SparseDiffMlp", "GEMM1")
+            except ValueError as e:
+                raise ValueError(f"{e}; for another callable that computes one of them pass act='gelu_tanh', 'gelu' or 'silu'") from None
         self.fc1 = [fc1]
         self.fc2 = [fc2]
         self.fc2w_T = [fc2.weight.data.transpose(0, 1).contiguous()]
@@ -197,9 +224,10 @@ class SparseDiffMlp:
             x = fc1.quantize_input(x)
             scale_a, scale_b = fc1.input_scale_reciprocal, fc1.scale_reciprocal
 
-        ops.mlp(x=x if batched else x[0], fc1w=fc1.weight.data, fc1b=fc1.bias.data, fc2w_T=self.fc2w_T[0], indices=indices,
-                counts=counts, sparse_act_T=sparse_act_T, cached_out=out_cache,
-                num_sms_scatter_add=self.num_sms_scatter_add, mm1_scale_a=scale_a, mm1_scale_b=scale_b, fc2_scale=fc2_scale_of(fc2))
+        ops.mlp(x=x if batched else x[0], fc1w=fc1.weight.data, fc1b=None if fc1.bias is None else fc1.bias.data,
+                fc2w_T=self.fc2w_T[0], indices=indices, counts=counts, sparse_act_T=sparse_act_T, cached_out=out_cache,
+                num_sms_scatter_add=self.num_sms_scatter_add, mm1_scale_a=scale_a, mm1_scale_b=scale_b, fc2_scale=fc2_scale_of(fc2),
+                act=self.act_code)
 
         # the operators updated the LOADED activation cache in place.  When it lives in host memory (offloading on, not kept resident) the
         # host copy has to follow, or the next step's load brings back the cache of the last full step and that step's deltas are taken

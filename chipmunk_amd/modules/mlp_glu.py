@@ -24,19 +24,9 @@ from .. import ops
 from ..util.config import GLOBAL_CONFIG
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
-from .mlp import _ceil8, _transposed, _transposed_pitched, block_mean, check_fc2, fc2_scale_of, top_p_of
+from .mlp import _ceil8, _transposed, _transposed_pitched, activation_code, block_mean, check_fc2, fc2_scale_of, top_p_of
 
 _F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
-
-
-def activation_code(activation: torch.nn.Module) -> str:
-    """The GEMM1 kernel's name for an activation module; anything the kernel does not compute raises."""
-    if isinstance(activation, torch.nn.SiLU):
-        return "silu"
-    if isinstance(activation, torch.nn.GELU) and activation.approximate in ("tanh", "none"):
-        return "gelu_tanh" if activation.approximate == "tanh" else "gelu"
-    raise ValueError(f"SparseDiffGatedMlp: unsupported activation {activation!r}: the gated GEMM1 computes nn.SiLU(), "
-                     "nn.GELU(approximate='tanh') and nn.GELU() only")
 
 
 def _params(lin: torch.nn.Linear, rows: Optional[slice] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:

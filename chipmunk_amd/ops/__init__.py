@@ -1,5 +1,5 @@
 """Operator wrappers with the reference's names (``src/chipmunk/ops/__init__.py:1-7``)."""
-from .mlp import run_e2e as mlp
+from .mlp import run_e2e as mlp, GLU_ACTS
 from .mlp import run_e2e_glu as mlp_glu, run_e2e_glu, mm1_glu
 from .mlp import run_e2e_glu_fp8 as mlp_glu_fp8, run_e2e_glu_fp8, mm1_glu_fp8
 from .indexed_io import (copy_indices, topk_indices, mask_to_indices, scatter_add, packed_mask_to_indices,

@@ -164,6 +164,30 @@ def _register():
         torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_glu_fp8: unknown activation '{act}'")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm1_act")
+    def _(a, b, c, bias, pa_cache, indices, counts, act, update_cache):
+        # writes c (and the cache) in place and returns nothing: the shapes are checked, so that a trace fails where the operator would
+        torch._check(a.shape[-1] == b.shape[1], lambda: "a and b must share the K dimension")
+        torch._check(c.shape == a.shape[:-1] + (b.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        torch._check(bias is None or bias.numel() == b.shape[0], lambda: "bias must have F entries")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_act: unknown activation '{act}'")
+        return None
+
+    @lib.register_fake("chipmunk::csp_mlp_mm1_fp8_act")
+    def _(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, act, update_cache):
+        # as csp_mlp_mm1_act, with e4m3 a / b and two one-element float32 scales; update_cache 0 / 1 / 2
+        f8 = torch.float8_e4m3fn
+        torch._check(a.dtype == f8 and b.dtype == f8, lambda: "a and b must be float8_e4m3fn")
+        torch._check(c.dtype == torch.bfloat16 and pa_cache.dtype == torch.bfloat16, lambda: "c and pa_cache must be bfloat16")
+        torch._check(a.shape[-1] == b.shape[1], lambda: "a and b must share the K dimension")
+        torch._check(c.shape == a.shape[:-1] + (b.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        torch._check(bias is None or bias.numel() == b.shape[0], lambda: "bias must have F entries")
+        for s in (scale_a, scale_b):
+            torch._check(s.dtype == torch.float32 and s.numel() == 1, lambda: "scale_a and scale_b must be one-element float32 tensors")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_fp8_act: unknown activation '{act}'")
+        torch._check(update_cache in (0, 1, 2), lambda: "csp_mlp_mm1_fp8_act: update_cache must be 0, 1 or 2")
+        return None
+
     @lib.register_fake("chipmunk::csp_mlp_mm2_w8")
     def _(mma_a, mma_b, scale_b, indices, counts, mma_c):
         # accumulates into mma_c in place and returns nothing

@@ -18,55 +18,82 @@ USE_FUSED_MLP_MATMUL_2 = True
 csp_mlp_mm2_function_ptr = 0  # placeholder for the reference's Triton kernel pointer (triton/csp_mlp_mm2.py:131-138)
 
 
-def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: torch.Tensor,
+GLU_ACTS = ("gelu_tanh", "silu", "gelu")
+
+
+def _default_form(who: str, act: str, fc1b: Optional[torch.Tensor]) -> bool:
+    """True for tanh-GELU with a bias -- the operators GEMM1 always had, untouched; every other (activation, bias | None) pair takes
+    ``csp_mlp_mm1_act`` / ``csp_mlp_mm1_fp8_act``.  An unknown ``act`` raises."""
+    if act not in GLU_ACTS:
+        raise ValueError(f"{who}: unknown activation {act!r} (one of {', '.join(GLU_ACTS)})")
+    return act == "gelu_tanh" and fc1b is not None
+
+
+def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
         sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
-        scale_a: Optional[torch.Tensor] = None, scale_b: Optional[torch.Tensor] = None) -> None:
+        scale_a: Optional[torch.Tensor] = None, scale_b: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
     # (the reference asserts x is bf16 even on its fp8 branch, one of the reasons that branch cannot run as shipped)
     assert x.dtype == (torch.float8_e4m3fn if fc1w.dtype == torch.float8_e4m3fn else torch.bfloat16)
     assert sparse_act_packed.dtype == torch.bfloat16
     assert sparse_act_T.dtype == torch.bfloat16
+    default = _default_form("mm1", act, fc1b)
     if fc1w.dtype == torch.bfloat16:
-        torch.ops.chipmunk.csp_mlp_mm1(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
+        if default:
+            torch.ops.chipmunk.csp_mlp_mm1(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
+        else:
+            torch.ops.chipmunk.csp_mlp_mm1_act(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, False)
     elif fc1w.dtype == torch.float8_e4m3fn:
         # reference: triton csp_mlp_mm1_fp8(x, fc1w.T, ...) (ops/mlp.py:22-23).  That kernel also stores the new
         # activation into the cache (triton/csp_mlp_mm1.py:140) and the scatter-add then adds the delta again; here
         # the cache is left to the scatter-add like on the bf16 path (set FP8_MM1_UPDATES_CACHE for the literal form).
-        csp_mlp_mm1_fp8(x, fc1w, fc1b, indices, counts, sparse_act_T, sparse_act_packed, scale_a, scale_b)
+        csp_mlp_mm1_fp8(x, fc1w, fc1b, indices, counts, sparse_act_T, sparse_act_packed, scale_a, scale_b, act)
     else:
         raise ValueError(f"Unsupported dtype: {fc1w.dtype}")
 
 
-def mm1_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: torch.Tensor,
-                sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor) -> None:
+def mm1_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
+                sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, act: str = "gelu_tanh") -> None:
     """GEMM1 + ``csp_scatter_add`` of its output into ``sparse_act_T`` in one kernel (bf16 only)."""
     assert x.dtype == torch.bfloat16 and sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
-    torch.ops.chipmunk.csp_mlp_mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
+    if _default_form("mm1_scatter", act, fc1b):
+        torch.ops.chipmunk.csp_mlp_mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
+    else:
+        torch.ops.chipmunk.csp_mlp_mm1_act(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, True)
 
 
-def mm1_fp8_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: torch.Tensor,
+def mm1_fp8_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
                     sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, scale_a: torch.Tensor,
-                    scale_b: torch.Tensor) -> None:
+                    scale_b: torch.Tensor, act: str = "gelu_tanh") -> None:
     """fp8 GEMM1 + ``csp_scatter_add`` of its output into ``sparse_act_T`` in one kernel (the fp8 counterpart of ``mm1_scatter``;
     bit-identical in the packed deltas and in the cache to ``csp_mlp_mm1_fp8`` followed by the scatter-add)."""
     assert x.dtype == torch.float8_e4m3fn and fc1w.dtype == torch.float8_e4m3fn
-    torch.ops.chipmunk.csp_mlp_mm1_fp8_scatter(x, fc1w.contiguous(), sparse_act_packed, fc1b, sparse_act_T, indices, counts,
-                                               scale_a.reshape(1).float(), scale_b.reshape(1).float())
+    if _default_form("mm1_fp8_scatter", act, fc1b):
+        torch.ops.chipmunk.csp_mlp_mm1_fp8_scatter(x, fc1w.contiguous(), sparse_act_packed, fc1b, sparse_act_T, indices, counts,
+                                                   scale_a.reshape(1).float(), scale_b.reshape(1).float())
+    else:   # update_cache 2: the scatter-add of the deltas
+        torch.ops.chipmunk.csp_mlp_mm1_fp8_act(x, fc1w.contiguous(), sparse_act_packed, fc1b, sparse_act_T, indices, counts,
+                                               scale_a.reshape(1).float(), scale_b.reshape(1).float(), act, 2)
 
 
 FP8_MM1_UPDATES_CACHE = False
 
 
-def csp_mlp_mm1_fp8(a: torch.Tensor, b: torch.Tensor, fc1b: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
+def csp_mlp_mm1_fp8(a: torch.Tensor, b: torch.Tensor, fc1b: Optional[torch.Tensor], indices: torch.Tensor, counts: torch.Tensor,
                     sparse_act_unpacked_inout: torch.Tensor, sparse_act_packed_out: torch.Tensor,
-                    scale_a: torch.Tensor, scale_b: torch.Tensor) -> None:
+                    scale_a: torch.Tensor, scale_b: torch.Tensor, act: str = "gelu_tanh") -> None:
     """Native counterpart of the reference's Triton ``csp_mlp_mm1_fp8`` (same argument order,
     triton/csp_mlp_mm1.py:143).  ``a`` fp8 ``[M,K]``; ``b`` fp8 ``[F,K]`` (the reference passes ``fc1w.T``, a view of
     the same storage); scales are the RECIPROCAL quantisation scales (modules/mlp.py:98-99)."""
     if b.shape[0] == a.shape[1] and b.shape[1] != a.shape[1]:
         b = b.T  # accept the reference's fc1w.T view
-    torch.ops.chipmunk.csp_mlp_mm1_fp8(a, b.contiguous(), sparse_act_packed_out, fc1b, sparse_act_unpacked_inout,
-                                       indices, counts, scale_a.reshape(1).float(), scale_b.reshape(1).float(),
-                                       FP8_MM1_UPDATES_CACHE)
+    if _default_form("csp_mlp_mm1_fp8", act, fc1b):
+        torch.ops.chipmunk.csp_mlp_mm1_fp8(a, b.contiguous(), sparse_act_packed_out, fc1b, sparse_act_unpacked_inout,
+                                           indices, counts, scale_a.reshape(1).float(), scale_b.reshape(1).float(),
+                                           FP8_MM1_UPDATES_CACHE)
+    else:   # update_cache 1: the new activation is stored into the cache (FP8_MM1_UPDATES_CACHE), 0: the cache is left alone
+        torch.ops.chipmunk.csp_mlp_mm1_fp8_act(a, b.contiguous(), sparse_act_packed_out, fc1b, sparse_act_unpacked_inout,
+                                               indices, counts, scale_a.reshape(1).float(), scale_b.reshape(1).float(), act,
+                                               1 if FP8_MM1_UPDATES_CACHE else 0)
 
 
 def mm2_fused(packed: torch.Tensor, unpacked_colmajor: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
@@ -121,16 +148,18 @@ def mm2_unfused(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, cached_out
 
 
 @torch.compiler.disable
-def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: torch.Tensor, fc2w_T: torch.Tensor, indices: torch.Tensor,
+def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], fc2w_T: torch.Tensor, indices: torch.Tensor,
             counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
             mm1_scale_a: Optional[torch.Tensor] = None, mm1_scale_b: Optional[torch.Tensor] = None,
-            fc2_scale: Optional[torch.Tensor] = None) -> None:
+            fc2_scale: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
     # M is any positive row count (ceil(M / 128) groups, the last one short); sparse_act_T is [F, M], contiguous or -- required when
     # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers.
     # A batch: x [B, M, K1] with indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] (or the [..., :M] view of [B, F, ldc]) and
     # cached_out [B, M, N] -- one launch per kernel for all B sequences, the bits of B calls on the slices.
     # fc2w_T float8_e4m3fn with fc2_scale (F8Linear.scale_reciprocal): the scatter-add is GEMM1's own (or csp_scatter_add with
     # mlp.fused_scatter off) and GEMM2 gathers e4m3 rows.
+    # act (one of GLU_ACTS) names fc1's activation and fc1b may be None: anything but tanh-GELU with a bias takes csp_mlp_mm1_act /
+    # csp_mlp_mm1_fp8_act in GEMM1's place, everything behind GEMM1 is unchanged.
     assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
     if x.ndim == 3:
         B = x.shape[0]
@@ -147,15 +176,15 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: torch.Tensor, fc2w_T: tor
     if (x.is_cuda and fc1w.dtype == torch.bfloat16
             and amd_key("mlp", "fused_scatter")):
         # GEMM1 applies the scatter-add of its own deltas (same bits as the two-kernel form), GEMM2 runs alone
-        mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
+        mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act)
         csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
         return
     if (x.is_cuda and fc1w.dtype == torch.float8_e4m3fn and x.dtype == torch.float8_e4m3fn and amd_key("mlp", "fused_scatter")
             and not FP8_MM1_UPDATES_CACHE and K1 % 128 == 0):
-        mm1_fp8_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b)
+        mm1_fp8_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b, act)
         csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
         return
-    mm1(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b)
+    mm1(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b, act)
     if fc2w_T.dtype == torch.float8_e4m3fn:
         if fc1w.dtype == torch.float8_e4m3fn and FP8_MM1_UPDATES_CACHE:
             raise ValueError("run_e2e: FP8_MM1_UPDATES_CACHE (GEMM1 stores the activation, the scatter-add adds the delta again) has no e4m3 fc2 form")
@@ -166,9 +195,6 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: torch.Tensor, fc2w_T: tor
                   num_sms_scatter_add)
     else:
         mm2_unfused(sparse_act_packed, fc2w_T, cached_out, sparse_act_T, indices, counts, num_sms_scatter_add)
-
-
-GLU_ACTS = ("gelu_tanh", "silu", "gelu")
 
 
 def mm1_glu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sparse_act_packed: torch.Tensor,

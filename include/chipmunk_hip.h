@@ -270,6 +270,30 @@ int chipmunk_csp_mlp_mm1_glu_fp8_batched(const void *a, const void *b_gate, cons
                                          int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
                                          void *stream);
 
+/* Ungated activations: GEMM1 of fc2(act(x W1 + b1)) for any of the CHIPMUNK_ACT_* codes above, with or without a bias (no reference
+ * counterpart: chipmunk_csp_mlp_mm1 and the reference compute tanh-GeLU with a bias only).  For group g and packed column
+ * j < counts[g], with i = idx[g,j]:
+ *   bf16:  c[m,j] = bf16( act(a[m,:].b[i,:] + bias[i]) - pa_cache[i, m] )              fp32, the bias inside the sum, one rounding
+ *   fp8:   t = bf16( act((a[m,:].b[i,:] * scale_a) * scale_b + bias[i]) );  c[m,j] = bf16( t - pa_cache[i, m] )
+ * bias is bf16 [F] or NULL (= zero).  act = CHIPMUNK_ACT_GELU_TANH with a bias gives the bits of chipmunk_csp_mlp_mm1[_scatter] /
+ * chipmunk_csp_mlp_mm1_fp8.  update_cache, bf16 pair: 0 leaves the cache, 1 also applies the scatter-add of c (the bits of
+ * chipmunk_csp_scatter_add afterwards); fp8 pair: 0 / 1 / 2 as chipmunk_csp_mlp_mm1_fp8 (1 stores t, 2 applies the scatter-add).
+ * Contract of the *_ragged entries (any M >= 1, ldc >= M, ldc % 8 == 0, F % 64 == 0; K % 64 == 0 for bf16, K % 128 == 0 and e4m3 a / b
+ * with two reciprocal scales for fp8) and, for *_batched, of the batch entries above.  An unknown act, an update_cache out of range or
+ * a K off its multiple returns CHIPMUNK_ERR_INVALID with a message, before anything is enqueued. */
+int chipmunk_csp_mlp_mm1_act(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                             const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, void *stream);
+int chipmunk_csp_mlp_mm1_act_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                     const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, int B,
+                                     int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_fp8_act(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                 const int32_t *counts, const float *scale_a, const float *scale_b, int M, int K, int F, int ldc,
+                                 int act, int update_cache, void *stream);
+int chipmunk_csp_mlp_mm1_fp8_act_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                         const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                         int M, int K, int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                         void *stream);
+
 /* fp8 fc2: GEMM (ii) over e4m3 rows of fc2^T (weight-only fp8).  mma_a [M,F] bf16 packed deltas, mma_b [F,N2] OCP e4m3 bytes
  * (float8_e4m3fn), plain row-major, scale_b one device float -- the weight's RECIPROCAL quantisation scale --, mma_c [M,N2] bf16:
  *   mma_c[m,:] = bf16( bf16( (sum_{c < counts[g]} mma_a[m,c] * f(mma_b[indices[g,c],:])) * scale_b[0] ) + mma_c[m,:] )

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -185,6 +185,36 @@ def bench_mm1_glu(M=4352, K=3072, F=12288, keep=3840, act="silu"):
     print(f"mm1_glu {act:9s}: {med['glu']:8.1f} us  [{min(t['glu']):.1f} .. {max(t['glu']):.1f}]  {flops/med['glu']/1e6:7.1f} TFLOP/s   {tag}")
     print(f"mm1 2x keep, 2F : {med['mm1']:8.1f} us  [{min(t['mm1']):.1f} .. {max(t['mm1']):.1f}]  {flops/med['mm1']/1e6:7.1f} TFLOP/s")
     print(f"mm1_glu / mm1   : {med['glu'] / med['mm1']:8.3f}")
+
+
+def bench_mm1_act(M=4352, K=3072, F=12288, keep=3840):
+    """The ungated GEMM1 with the activation as an argument (csp_mlp_mm1_act, scatter form, with a bias and -- tanh-GELU -- without one) at
+    the FLUX MLP shape, 30 % of the columns kept, against csp_mlp_mm1_scatter on the same operands: the same tile code, the epilogue's
+    activation apart.  Same process, all launches alternating (KB_ROUNDS rounds, default 5); per launch the median bracket of `timeit`,
+    then the median and the range over the rounds."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    a = torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g)
+    w = (torch.randn(F, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
+    bias = (torch.randn(F, device=dev, generator=g) * 0.1).to(torch.bfloat16)
+    cache = torch.randn(F, M, device=dev, dtype=torch.bfloat16, generator=g)
+    packed = torch.empty(M, F, device=dev, dtype=torch.bfloat16)
+    G = (M + 127) // 128
+    inds, counts = rand_rows(G, F, keep, g), torch.full((G,), keep, dtype=torch.int32, device=dev)
+    ops = torch.ops.chipmunk
+    runs = {"mm1_scatter (tanh-GELU)": lambda: ops.csp_mlp_mm1_scatter(a, w, packed, bias, cache, inds, counts)}
+    for act in ("gelu_tanh", "silu", "gelu"):
+        runs[f"mm1_act {act}"] = lambda act=act: ops.csp_mlp_mm1_act(a, w, packed, bias, cache, inds, counts, act, True)
+    runs["mm1_act gelu_tanh, no bias"] = lambda: ops.csp_mlp_mm1_act(a, w, packed, None, cache, inds, counts, "gelu_tanh", True)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {k: [] for k in runs}
+    for _ in range(rounds):
+        for k, fn in runs.items():
+            t[k].append(timeit(fn) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * K * keep
+    print(f"(M={M} K={K} F={F} keep={keep} scatter forms, {rounds} alternating rounds)")
+    for k in runs:
+        print(f"{k:28s}: {med[k]:8.1f} us  [{min(t[k]):.1f} .. {max(t[k]):.1f}]  {flops/med[k]/1e6:7.1f} TFLOP/s   x {med[k] / med['mm1_scatter (tanh-GELU)']:.3f}")
 
 
 def bench_mm1_glu_fp8(M=32768, K=1536, F=8960, keep=2816, act="silu"):
@@ -416,6 +446,8 @@ def main():
             bench_mlp(w, variants, keep=int(os.environ.get("KB_KEEP", "4096")))   # KB_KEEP: kept columns per group (FLUX: 0.3 * 12288 -> 3840)
         elif w == "mm1_glu":          # gated GEMM1 at the FLUX MLP shape against the ungated launch of equal work (KB_GLU_ACT: silu, gelu_tanh, gelu)
             bench_mm1_glu(act=os.environ.get("KB_GLU_ACT", "silu"))
+        elif w == "mm1_act":          # ungated GEMM1 with SiLU / exact GELU / tanh-GELU at the FLUX MLP shape against csp_mlp_mm1_scatter
+            bench_mm1_act()
         elif w == "mm1_glu_fp8":      # gated fp8 GEMM1 at the Wan fp8 shape against the ungated fp8 launch of equal work (KB_GLU_ACT as mm1_glu)
             bench_mm1_glu_fp8(act=os.environ.get("KB_GLU_ACT", "silu"))
         elif w == "mm2_w8":           # weight-only fp8 GEMM2 against the bf16 GEMM2 at the FLUX shape, 30 % of 12 288 columns kept
