@@ -272,7 +272,8 @@ __global__ __launch_bounds__(256, CSONLY ? 4 : 2) void attn_kernel(const AttnPar
     // The item's key count is REQUESTED here and first used below the Q loads: count, the first key tiles' indices and the Q rows make
     // one memory round trip together instead of three in a row (tools/attn_prof.py: 7 k + 9 k cycles of a FLUX item's 114 k passed
     // before its first tile).
-    int count_v = GATHER ? p.counts[(int64_t)bh * p.G + g] : p.Nk;
+    // (dense forms with k_lens: the sequence's own key count -- one scalar load; tiles, slices, masking and the column sums follow)
+    int count_v = GATHER ? p.counts[(int64_t)bh * p.G + g] : item_nk(p.klens, __builtin_amdgcn_readfirstlane(b), p.Nk);
     const IndexRow irow = GATHER ? index_row(p, (int64_t)bh * p.G + g) : IndexRow{nullptr, 0};
     const int32_t *idx = irow.ptr;
     const uint16_t *kbase = p.k + b * p.ks[0] + h * p.ks[1];
@@ -482,6 +483,8 @@ __global__ __launch_bounds__(256, CSONLY ? 4 : 2) void attn_kernel(const AttnPar
         }
         __syncthreads();
         if (ntiles > 0) flush((ntiles - 1) & ~1, it - 1);
+        // k_lens: the columns past the sequence's last tile are 0 (inside it the masked sums above are)
+        for (int pos = ntiles * KVT + tid; pos < p.Nk; pos += 256) p.cs[((int64_t)bh * p.G + g) * p.cs_stride + pos] = 0;
         return;
     }
 
@@ -1345,9 +1348,10 @@ static int output_strides(int64_t os[3], const int64_t *o_strides, int H, int Nq
     return check_strides(o_strides, "o");
 }
 
-extern "C" int chipmunk_dense_attn_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
-                                           const int64_t k_strides[3], const int64_t v_strides[3], void *o,
-                                           const int64_t *o_strides, float *l, int B, int H, int Nq, int Nk, void *stream) {
+// klens: per-sequence key counts (int32 [B] on the device) or nullptr; the entry points without it are the nullptr case
+static int dense_attn_impl(const void *q, const void *k, const void *v, const int64_t q_strides[3], const int64_t k_strides[3],
+                           const int64_t v_strides[3], void *o, const int64_t *o_strides, float *l, const int32_t *klens, int B, int H,
+                           int Nq, int Nk, void *stream) {
     if (int e = check_common(q, k, v, o, B, H, Nq, Nk)) return e;
     CM_CHECK(l != nullptr, "dense_attn: l output missing");
     if (int e = check_strides(q_strides, "q")) return e;
@@ -1357,15 +1361,28 @@ extern "C" int chipmunk_dense_attn_strided(const void *q, const void *k, const v
     p.q = (const uint16_t *)q, p.k = (const uint16_t *)k, p.v = (const uint16_t *)v, p.o = (uint16_t *)o;
     for (int i = 0; i < 3; ++i) p.qs[i] = q_strides[i], p.ks[i] = k_strides[i], p.vs[i] = v_strides[i];
     if (int e = output_strides(p.os, o_strides, H, Nq)) return e;
-    p.l_out = l;
+    p.l_out = l, p.klens = klens;
     p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.G = (Nq + QG - 1) / QG;
     p.o_scale = 1.f;
     if (use_dense64(B, H, Nq, Nk)) {
         CM_CHECK((int64_t)Nk * p.ks[2] * 2 < (1ll << 32) && (int64_t)Nk * p.vs[2] * 2 < (1ll << 32),
                  "attention: one head's K or V spans more than 4 GiB (32-bit DMA offsets)");
-        return chipmunk_dense64_launch(q, k, v, o, l, p.qs, p.ks, p.vs, p.os, B, H, Nq, Nk, (hipStream_t)stream);
+        return chipmunk_dense64_launch(q, k, v, o, l, p.qs, p.ks, p.vs, p.os, B, H, Nq, Nk, (hipStream_t)stream, klens);
     }
     return launch_attn<false, false, true>(p, (hipStream_t)stream);
+}
+
+extern "C" int chipmunk_dense_attn_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                           const int64_t k_strides[3], const int64_t v_strides[3], void *o,
+                                           const int64_t *o_strides, float *l, int B, int H, int Nq, int Nk, void *stream) {
+    return dense_attn_impl(q, k, v, q_strides, k_strides, v_strides, o, o_strides, l, nullptr, B, H, Nq, Nk, stream);
+}
+
+extern "C" int chipmunk_dense_attn_varlen(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                          const int64_t k_strides[3], const int64_t v_strides[3], void *o,
+                                          const int64_t *o_strides, float *l, const int32_t *k_lens, int B, int H, int Nq, int Nk,
+                                          void *stream) {
+    return dense_attn_impl(q, k, v, q_strides, k_strides, v_strides, o, o_strides, l, k_lens, B, H, Nq, Nk, stream);
 }
 
 extern "C" int chipmunk_dense_attn(const void *q, const void *k, const void *v, const int64_t q_strides[3],
@@ -1374,10 +1391,9 @@ extern "C" int chipmunk_dense_attn(const void *q, const void *k, const void *v, 
     return chipmunk_dense_attn_strided(q, k, v, q_strides, k_strides, v_strides, o, nullptr, l, B, H, Nq, Nk, stream);
 }
 
-extern "C" int chipmunk_dense_colsum_attn_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
-                                                  const int64_t k_strides[3], const int64_t v_strides[3], const float *pin,
-                                                  void *o, const int64_t *o_strides, void *cs, float *l, int B, int H, int Nq,
-                                                  int Nk, int cs_stride, void *stream) {
+static int dense_colsum_attn_impl(const void *q, const void *k, const void *v, const int64_t q_strides[3], const int64_t k_strides[3],
+                                  const int64_t v_strides[3], const float *pin, void *o, const int64_t *o_strides, void *cs, float *l,
+                                  const int32_t *klens, int B, int H, int Nq, int Nk, int cs_stride, void *stream) {
     if (int e = check_common(q, k, v, o, B, H, Nq, Nk)) return e;
     CM_CHECK(l && cs && pin, "dense_colsum_attn: p / cs / l missing");
     CM_CHECK(cs_stride >= Nk, "dense_colsum_attn: cs row stride %d < Nk %d", cs_stride, Nk);
@@ -1388,7 +1404,7 @@ extern "C" int chipmunk_dense_colsum_attn_strided(const void *q, const void *k, 
     p.q = (const uint16_t *)q, p.k = (const uint16_t *)k, p.v = (const uint16_t *)v, p.o = (uint16_t *)o;
     for (int i = 0; i < 3; ++i) p.qs[i] = q_strides[i], p.ks[i] = k_strides[i], p.vs[i] = v_strides[i];
     if (int e = output_strides(p.os, o_strides, H, Nq)) return e;
-    p.l_out = l, p.p_in = pin, p.cs = (uint16_t *)cs, p.cs_stride = cs_stride;
+    p.l_out = l, p.p_in = pin, p.cs = (uint16_t *)cs, p.cs_stride = cs_stride, p.klens = klens;
     p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.G = (Nq + QG - 1) / QG;
     p.o_scale = 1.f;
     // Two passes: (1) dense attention, (2) a K-only pass that recomputes the scores and reduces the column sums; they
@@ -1427,12 +1443,13 @@ extern "C" int chipmunk_dense_colsum_attn_strided(const void *q, const void *k, 
                         c.o += b * p.os[0] + h0 * p.os[1];
                         c.l_out += bh0 * Nq, c.p_in += bh0 * Nq, c.cs += bh0 * p.G * (int64_t)cs_stride;
                         c.B = 1, c.H = hn;
+                        if (c.klens) c.klens += b;
                         if (int e = chipmunk_dense64_colsum_launch(c, part, st)) return e;
                     }
                 return CHIPMUNK_OK;
             }
         }
-        rc = chipmunk_dense64_launch(q, k, v, o, l, p.qs, p.ks, p.vs, p.os, B, H, Nq, Nk, st);
+        rc = chipmunk_dense64_launch(q, k, v, o, l, p.qs, p.ks, p.vs, p.os, B, H, Nq, Nk, st, klens);
     } else {
         rc = launch_attn<false, false, true>(p, st);
     }
@@ -1440,6 +1457,22 @@ extern "C" int chipmunk_dense_colsum_attn_strided(const void *q, const void *k, 
     // second pass: one wave per 192-row group where that fills the CUs (attn64.hip), the general kernel's K-only pass otherwise
     if (use_colsum64(B, H, Nq, Nk)) return chipmunk_colsum64_launch(p, st);
     return launch_attn<false, false, false, true>(p, st);
+}
+
+extern "C" int chipmunk_dense_colsum_attn_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                                  const int64_t k_strides[3], const int64_t v_strides[3], const float *pin,
+                                                  void *o, const int64_t *o_strides, void *cs, float *l, int B, int H, int Nq,
+                                                  int Nk, int cs_stride, void *stream) {
+    return dense_colsum_attn_impl(q, k, v, q_strides, k_strides, v_strides, pin, o, o_strides, cs, l, nullptr, B, H, Nq, Nk, cs_stride,
+                                  stream);
+}
+
+extern "C" int chipmunk_dense_colsum_attn_varlen(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                                 const int64_t k_strides[3], const int64_t v_strides[3], const float *pin,
+                                                 void *o, const int64_t *o_strides, void *cs, float *l, const int32_t *k_lens, int B,
+                                                 int H, int Nq, int Nk, int cs_stride, void *stream) {
+    return dense_colsum_attn_impl(q, k, v, q_strides, k_strides, v_strides, pin, o, o_strides, cs, l, k_lens, B, H, Nq, Nk, cs_stride,
+                                  stream);
 }
 
 extern "C" int chipmunk_dense_colsum_attn(const void *q, const void *k, const void *v, const int64_t q_strides[3],
@@ -1461,7 +1494,8 @@ static int dense_colsum_topk_mask_impl(const void *q, const void *k, const void 
                                        const int64_t k_strides[3], const int64_t v_strides[3], const float *pin, void *o,
                                        const int64_t *o_strides, float *l, int B, int H, int Nq, int Nk, const void *static_mask,
                                        int64_t static_stride, int static_rows, const void *group_flags, void *mask,
-                                       int topk, double random_amount, bool mass, double top_p, int k_min, void *stream) {
+                                       int topk, double random_amount, bool mass, double top_p, int k_min, void *stream,
+                                       const int32_t *klens = nullptr) {
     if (int e = check_common(q, k, v, o, B, H, Nq, Nk)) return e;
     CM_CHECK(l && pin && mask, "dense_colsum_topk_mask: p / l / mask missing");
     if (int e = check_strides(q_strides, "q")) return e;
@@ -1476,7 +1510,7 @@ static int dense_colsum_topk_mask_impl(const void *q, const void *k, const void 
     CM_CHECK((int64_t)Nk * p.ks[2] * 2 < (1ll << 32) && (int64_t)Nk * p.vs[2] * 2 < (1ll << 32),
              "attention: one head's K or V spans more than 4 GiB (32-bit DMA offsets)");
     if (int e = output_strides(p.os, o_strides, H, Nq)) return e;
-    p.l_out = l, p.p_in = pin, p.cs = nullptr, p.cs_stride = 0;
+    p.l_out = l, p.p_in = pin, p.cs = nullptr, p.cs_stride = 0, p.klens = klens;
     p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.G = (Nq + QG - 1) / QG;
     p.o_scale = 1.f;
     uint16_t *part = (uint16_t *)chipmunk_big_scratch(st, chipmunk_colsum_part_bytes(B, H, Nq, Nk));
@@ -1485,9 +1519,9 @@ static int dense_colsum_topk_mask_impl(const void *q, const void *k, const void 
     const int nrb = ((Nq + 255) / 256) * 2;
     if (mass)
         return chipmunk_topk_mask_p_parts(part, chipmunk_colsum_part_stride(Nk), nrb, p.G, Nq, static_mask, static_stride, static_rows, group_flags, mask,
-                                          B * H * p.G, Nk, topk, top_p, k_min, random_amount, st);
+                                          B * H * p.G, Nk, topk, top_p, k_min, random_amount, st, klens, H * p.G);
     return chipmunk_topk_mask_parts(part, chipmunk_colsum_part_stride(Nk), nrb, p.G, Nq, static_mask, static_stride, static_rows, group_flags, mask, B * H * p.G, Nk,
-                                    topk, random_amount, st);
+                                    topk, random_amount, st, klens, H * p.G);
 }
 
 extern "C" int chipmunk_dense_colsum_topk_mask_strided(const void *q, const void *k, const void *v, const int64_t q_strides[3],
@@ -1518,4 +1552,26 @@ extern "C" int chipmunk_dense_colsum_topk_mask(const void *q, const void *k, con
     return chipmunk_dense_colsum_topk_mask_strided(q, k, v, q_strides, k_strides, v_strides, pin, o, nullptr, l, B, H, Nq, Nk,
                                                    static_mask, static_stride, static_rows, group_flags, mask, topk, random_amount,
                                                    stream);
+}
+
+// the fused mask step over a padded batch (k_lens: int32 [B] on the device, see chipmunk_dense_attn_varlen)
+extern "C" int chipmunk_dense_colsum_topk_mask_varlen(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                                      const int64_t k_strides[3], const int64_t v_strides[3], const float *pin, void *o,
+                                                      const int64_t *o_strides, float *l, const int32_t *k_lens, int B, int H, int Nq,
+                                                      int Nk, const void *static_mask, int64_t static_stride, int static_rows,
+                                                      const void *group_flags, void *mask, int topk, double random_amount, void *stream) {
+    return dense_colsum_topk_mask_impl(q, k, v, q_strides, k_strides, v_strides, pin, o, o_strides, l, B, H, Nq, Nk, static_mask, static_stride,
+                                       static_rows, group_flags, mask, topk, random_amount, false, 0.0, 0, stream, k_lens);
+}
+
+extern "C" int chipmunk_dense_colsum_topk_mask_p_varlen(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                                        const int64_t k_strides[3], const int64_t v_strides[3], const float *pin, void *o,
+                                                        const int64_t *o_strides, float *l, const int32_t *k_lens, int B, int H, int Nq,
+                                                        int Nk, const void *static_mask, int64_t static_stride, int static_rows,
+                                                        const void *group_flags, void *mask, int topk, double random_amount, double top_p,
+                                                        int k_min, void *stream) {
+    CM_CHECK(top_p > 0.0 && top_p <= 1.0, "dense_colsum_topk_mask_p: top_p must be in (0, 1] (got %g)", top_p);
+    CM_CHECK(k_min >= 0, "dense_colsum_topk_mask_p: k_min must be >= 0 (got %d)", k_min);
+    return dense_colsum_topk_mask_impl(q, k, v, q_strides, k_strides, v_strides, pin, o, o_strides, l, B, H, Nq, Nk, static_mask, static_stride,
+                                       static_rows, group_flags, mask, topk, random_amount, true, top_p, k_min, stream, k_lens);
 }

@@ -141,8 +141,9 @@ __device__ __forceinline__ float cs_pair_quad(float a, float b, bool hi) {
 // over the block, one atomicMax on the float's bits (non-negative floats order like unsigned integers; the buffer is
 // zeroed by a memset node before every launch).  730 MB of K at HunyuanVideo size: ~0.2 ms beside a 130 ms launch.
 __global__ __launch_bounds__(256) void knorm_max_kernel(const uint16_t *k, const int64_t ks0, const int64_t ks1, const int64_t ks2, int H, int Nk,
-                                                        float *out) {
+                                                        float *out, const int32_t *klens) {
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
+    Nk = item_nk(klens, b, Nk);   // a padded batch: the valid rows of this sequence only (the padding is never read)
     const uint16_t *kb = k + b * ks0 + h * ks1;
     const int grp = threadIdx.x >> 4, li = threadIdx.x & 15;
     float best = 0.f;
@@ -176,8 +177,12 @@ __global__ __launch_bounds__(256) void knorm_max_kernel(const uint16_t *k, const
 //   the four-wave dense kernel's throughput on dense data (the compute waves' tiles get shorter, the chip clocks higher).
 //   Work items come from the device-built plan of attn.hip (longest-first order, heavy items sliced over their key tiles
 //   and merged by the last arriver).
-template <int MODE>
+// KL: the launch carries per-sequence key lengths (p.klens, dense modes only).  It is a template flag, not a run-time test, so that the
+// instantiation every launch without k_lens takes is the kernel it was, instruction for instruction: this loop is bound by one wave's
+// issue slots and a scalar add per tile shows (docs/EXPERIMENTS_klens.md).
+template <int MODE, bool KL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void attn64_kernel(const AttnParams p) {
+    static_assert(!KL || MODE == 0 || MODE == 3, "key lengths belong to the dense forms");
     constexpr bool GATHER = MODE == 1 || MODE == 2, INPLACE = MODE == 2;
     constexpr bool CSUM = MODE == 3;   // dense + the column sums of dense_colsum_attn in the same pass (see below)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -197,7 +202,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int bh = wid / p.G, g = wid - bh * p.G;
     const int b = bh / p.H, h = bh - b * p.H;
     const int row0 = g * (GATHER ? 192 : WGROWS) + w * WROWS;
-    const int count = GATHER ? p.counts[(int64_t)bh * p.G + g] : p.Nk;
+    // dense forms: the sequence's own key count where the launch carries k_lens (wave-uniform; everything below follows from `valid`)
+    const int count = GATHER ? p.counts[(int64_t)bh * p.G + g] : (KL ? item_nk(p.klens, b, p.Nk) : p.Nk);
     const int valid = count < p.Nk ? count : p.Nk;   // packed positions >= Nk are masked out (csp_128_attn.cu:314)
     const int ntiles_all = (valid + KT - 1) / KT;
     const int tbeg = (int)((int64_t)ntiles_all * sp / nsp), tend = (int)((int64_t)ntiles_all * (sp + 1) / nsp);
@@ -321,29 +327,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         vad[db] = lds0 + VRING + (4 * hf + (l15 >> 2)) * 256 + (((db * 4 + 2 * (lg & 1) + ((l15 & 3) >> 1)) ^ ((l15 >> 2) << 2)) << 4) +
                   (l15 & 1) * 8;
     // DMA: wave w stages pieces w*4 + i (4 rows of 256 B each), i = 0..3, of the K tile and of the V tile
+    // k_lens: a sequence of fewer than 64 keys (`sub`, wave-uniform) has no "last 64 rows" to fetch a ragged tile from.  Its one tile is
+    // fetched from rows 0..63 in REVERSE order -- LDS row r = key 63 - r, for K and V alike -- so that the live keys sit at the END of the
+    // LDS rows exactly as in a ragged last tile, and the loop below masks its 64 - valid leading rows without knowing the difference.
+    // (Rows valid..63 are padding rows that ARE read: they must be finite; their probabilities are 0.)  All of this is lane offsets and
+    // scalars set here -- the KL loop differs from the other by one scalar add per tile (dadj).  K: four lane offsets, the tile's scalar offset times kmul = 0.
+    // V's four pieces share one lane offset and differ by a scalar step: -stride from a base 12 rows up (tile base -12 times -stride;
+    // all sums in 32-bit scalar arithmetic, every offset that reaches the DMA is >= 0).
+    const bool sub = KL && valid < KT;
     uint32_t kofs[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) kofs[i] = (uint32_t)(w * 16 + 4 * i + lg) * kstride_b + ((uint32_t)(l15 ^ (4 * i + lg)) << 4);
-    const uint32_t vofs = (uint32_t)(w * 16 + lg) * vstride_b + ((uint32_t)(l15 ^ (lg << 2)) << 4);
+    for (int i = 0; i < 4; ++i) {
+        const int r = w * 16 + 4 * i + lg;
+        kofs[i] = (uint32_t)(sub ? KT - 1 - r : r) * kstride_b + ((uint32_t)(l15 ^ (4 * i + lg)) << 4);
+    }
+    const uint32_t vofs = (uint32_t)(sub ? KT - 13 - (w * 16 + lg) : w * 16 + lg) * vstride_b + ((uint32_t)(l15 ^ (lg << 2)) << 4);
+    const uint32_t kmul = sub ? 0u : kstride_b, vstep_b = sub ? 0u - vstride_b : vstride_b;   // (!KL: the strides themselves)
 
     // One DMA piece (4 rows) of tile T.  A ragged last tile and the padding tiles are fetched from the last 64 rows of
     // the key range instead (rows [Nk-64, Nk): in bounds, wave-uniform), which shifts the tile's live keys to the END of
     // its LDS rows; the dead rows in front hold keys of the previous tile and are masked in the scores.
-    const int last_base = p.Nk - KT;
+    // (`sub`: every tile has "base" -12, which the multipliers above turn into row 0 of K and row 12 of V; its dead rows are the
+    // 64 - valid in front: dadj tops the 12 up)
+    const int last_base = !KL ? p.Nk - KT : (sub ? -12 : valid - KT);
+    const int dadj = sub ? (KT - valid) - 12 : 0;
     auto tile_base = [&](int T) { return T * KT < last_base ? T * KT : last_base; };
     auto issue_k1 = [&](uint32_t soff, uint32_t ldsw, int slot, int i) {
         blds16(krsrc, kofs[i], soff, smem + ldsw + slot * TB + i * 1024);
     };
     auto issue_v1 = [&](uint32_t soff, uint32_t ldsw, int slot, int i) {
-        blds16(vrsrc, vofs, soff + (uint32_t)(4 * i) * vstride_b, smem + ldsw + VRING + slot * TB + i * 1024);
+        blds16(vrsrc, vofs, soff + (uint32_t)(4 * i) * vstep_b, smem + ldsw + VRING + slot * TB + i * 1024);
     };
     auto issue_k = [&](int T, int slot) {
-        const uint32_t soff = (uint32_t)tile_base(T) * kstride_b;
+        const uint32_t soff = (uint32_t)tile_base(T) * kmul;
 #pragma unroll
         for (int i = 0; i < 4; ++i) issue_k1(soff, w * 4096, slot, i);
     };
     auto issue_v = [&](int T, int slot) {
-        const uint32_t soff = (uint32_t)tile_base(T) * vstride_b;
+        const uint32_t soff = (uint32_t)tile_base(T) * vstep_b;
 #pragma unroll
         for (int i = 0; i < 4; ++i) issue_v1(soff, w * 4096, slot, i);
     };
@@ -393,6 +414,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const int prow = lg * 4 + (l15 >> 2);
         pst_r = pst + prow * 128 + ((uint32_t)(((l15 & 3) >> 1) ^ (prow & 7)) << 4) + (l15 & 1) * 8;
         csoff_mx = 2u * (uint32_t)(16 * lg + 8 * ((l15 >> 2) & 1) + 4 * (l15 >> 3) + (l15 & 3));
+        if (sub) csoff_mx = 2u * (2 * KT - 1) - csoff_mx;   // (LDS row r is key 63 - r; + 64 columns, which prsrc takes back: see there)
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             const int qrow = row0 + qb * 32 + l31;
@@ -402,6 +424,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // the lane that ends up with key row (kb, u, rr, hf) of the tile: kb = bit 0, u = bit 1, rr = bits 4 3 2 (lsb first)
         const int rr = ((lane >> 4) & 1) | (((lane >> 3) & 1) << 1) | (((lane >> 2) & 1) << 2);
         csoff = 2u * (uint32_t)(32 * (lane & 1) + (rr & 3) + 8 * (2 * ((lane >> 1) & 1) + (rr >> 2)) + 4 * hf);
+        if (sub) csoff = 2u * (2 * KT - 1) - csoff;
         // In-workgroup combine (round 6): a 192-row group is three 64-row waves and a workgroup four, so a workgroup's waves belong to
         // TWO groups -- the first nA = 3 - (4g mod 3) waves to one, the rest to the next.  Each wave drops its tile's 64 sums into a 2 KiB
         // exchange area behind the rings (one ds_write_b32 per lane and tile), and one tile later -- behind the tile's barrier -- the first
@@ -412,7 +435,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         cs_extra = w == lead ? members : 0;       // 0: not a set's first wave; else the waves of the set (1..3)
         ex_w = lds0 + LDS_BYTES + (uint32_t)w * 256u + (uint32_t)lane * 4u;
         ex_r = lds0 + LDS_BYTES + (uint32_t)(lead + 1) * 256u + (uint32_t)lane * 4u;
-        prsrc = make_rsrc(p.cs_part + ((int64_t)bh * (p.G * 2) + (g * 2 + (w < nA ? 0 : 1))) * p.cs_pstride);
+        // (`sub`: the stores' test "this lane's row >= the tile's dead rows" sees row + 64 and passes for every lane -- the dead rows' sums
+        // are exact zeros and land in padding columns --, the resource starts 64 columns early, and the scalar offset is the clamped base.
+        // Invariant: every store of such a wave has lane offset csoff >= 128 bytes and scalar offset 0, so no address lies below the
+        // row's first element although the resource's base does -- for row 0 of the buffer 128 bytes in front of the allocation.  The
+        // resource is a raw one over the whole address range (make_rsrc: num_records 0xffffffff, no range check against the base), so
+        // the base is only ever a number that offsets are added to.)
+        prsrc = make_rsrc(p.cs_part + ((int64_t)bh * (p.G * 2) + (g * 2 + (w < nA ? 0 : 1))) * p.cs_pstride - (sub ? KT : 0));
     }
     // "tile -1": the first pass runs steps 20.. of the softmax pipeline on it -- elements 0..19 as if already exponentiated
 #pragma unroll
@@ -574,8 +603,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             // SALU op each instead of values the compiler hoists and then spills)
             if constexpr (!GATHER) {
                 asm volatile("" : "+s"(ldsw));
-                ksoff = (uint32_t)tile_base(t + 4) * kstride_b;
-                vsoff = (uint32_t)tile_base(t + 2) * vstride_b;
+                ksoff = (uint32_t)tile_base(t + 4) * kmul;
+                vsoff = (uint32_t)tile_base(t + 2) * vstep_b;
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -614,7 +643,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         bool moved = false;
         // dense: the first `dead` LDS rows of a ragged / padding tile are not this tile's keys (see tile_base; 0 for a full
         // tile).  gathered: LDS row 4*pc + lg holds packed position lg*16 + pc; positions >= vleft do not exist.
-        const int dead = GATHER ? 0 : (t * KT - tile_base(t) < KT ? t * KT - tile_base(t) : KT);
+        const int dead = GATHER ? 0 : (t * KT - tile_base(t) + dadj < KT ? t * KT - tile_base(t) + dadj : KT);
         const int vleft = !GATHER ? KT : (t < ntiles ? valid - (tbeg + t) * KT : 0);
         auto phase_b_gap = [&](auto gg) __attribute__((always_inline)) {
             constexpr int G = decltype(gg)::value;
@@ -644,8 +673,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         const uint32_t off = UWT ? csoff_mx : csoff;
                         if (dd <= 0 || (int)(off >> 1) >= dd) {
                             const uint16_t val = (uint16_t)(pack_bf16x2((cs_own + x1) + x2, 0.f) & 0xffffu);
-                            if (p.probe & 16) __builtin_amdgcn_raw_buffer_store_b16(val, prsrc, off, (uint32_t)tb2 * 2u, 2);
-                            else __builtin_amdgcn_raw_buffer_store_b16(val, prsrc, off, (uint32_t)tb2 * 2u, 0);
+                            if (p.probe & 16) __builtin_amdgcn_raw_buffer_store_b16(val, prsrc, off, (uint32_t)(KL && tb2 < 0 ? 0 : tb2) * 2u, 2);
+                            else __builtin_amdgcn_raw_buffer_store_b16(val, prsrc, off, (uint32_t)(KL && tb2 < 0 ? 0 : tb2) * 2u, 0);
                         }
                     }
                 }
@@ -837,7 +866,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const int tb1 = tile_base(T4 - 1), dd = (T4 - 1) * KT - tb1;
             const uint32_t off = (unitw && !A64_CSUM_VALU) ? csoff_mx : csoff;
             if (dd < KT && (dd <= 0 || (int)(off >> 1) >= dd))
-                __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(pack_bf16x2((cs_own + x1) + x2, 0.f) & 0xffffu), prsrc, off, (uint32_t)tb1 * 2u, 0);
+                __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(pack_bf16x2((cs_own + x1) + x2, 0.f) & 0xffffu), prsrc, off, (uint32_t)(KL && tb1 < 0 ? 0 : tb1) * 2u, 0);
         }
     }
 
@@ -972,7 +1001,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int bh = __builtin_amdgcn_readfirstlane(wid / G4), g = (wid - bh * G4) * 4 + w;   // this wave's 192-row group (>= p.G: nothing to store)
     const int b = __builtin_amdgcn_readfirstlane(bh / p.H), h = bh - b * p.H;
     const int row0 = g * 192;
-    const int ntiles = (p.Nk + KT - 1) / KT;
+    const int nk = item_nk(p.klens, b, p.Nk);   // this sequence's keys (k_lens), wave-uniform
+    const int ntiles = (nk + KT - 1) / KT;
     const int T4 = (ntiles + 3) & ~3;
     const uint16_t *kbase = p.k + b * p.ks[0] + h * p.ks[1];
     const __amdgpu_buffer_rsrc_t krsrc = make_rsrc(kbase);
@@ -1010,7 +1040,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     uint32_t kofs[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) kofs[i] = (uint32_t)(w * 16 + 4 * i + lg) * kstride_b + ((uint32_t)(l15 ^ (4 * i + lg)) << 4);
-    const int last_base = p.Nk - KT;
+    // (a sequence of fewer than 64 keys: base 0; the sums of its tile's rows nk..63 -- padding rows -- are replaced by 0 after the loop)
+    const int last_base = nk > KT ? nk - KT : 0;
     auto tile_base = [&](int T) { return T * KT < last_base ? T * KT : last_base; };
     auto issue_k1 = [&](uint32_t soff, uint32_t ldsw, int slot, int i) { blds16(krsrc, kofs[i], soff, smem + ldsw + slot * TB + i * 1024); };
     auto issue_k = [&](int T, int slot) {
@@ -1110,11 +1141,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         tile(ic<3>{}, tb + 3);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // k_lens: the columns of the padding are 0.  A sequence shorter than one tile had the sums of rows nk..63 stored by the loop: those
+    // stores have completed (the wait above) before these replace them.
+    if (g < p.G) {
+        const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));   // (the lane id again: nothing kept alive for this)
+        for (int col = nk + ln; col < p.Nk; col += 64) p.cs[((int64_t)bh * p.G + g) * p.cs_stride + col] = 0;
+    }
 }
 
-template <int MODE>
+template <int MODE, bool KL = false>
 int launch64(const AttnParams &p, int64_t grid, hipStream_t stream) {
-    auto kern = attn64_kernel<MODE>;
+    auto kern = attn64_kernel<MODE, KL>;
     static uint64_t lds_set = 0;
     constexpr int LDS = (MODE == 3 && !A64_CSUM_VALU) ? LDS_BYTES_CSUM + CS_EXCH_BYTES : MODE == 3 ? LDS_BYTES + CS_EXCH_BYTES : LDS_BYTES;
     ensure_dynamic_lds((const void *)kern, LDS, lds_set);
@@ -1134,28 +1171,29 @@ extern "C" int chipmunk_attn64_prof_read(unsigned long long *out) {
 // The largest K row norm per (batch, head) for the fixed reference point of attn64 / attn96 (nullptr: not available, the
 // kernels then keep a running maximum).  Lives in the second half of the library scratch's 64 KiB ticket region (the tickets
 // of attn.hip's hand-offs use the first few KiB); option attn_nomax = 2 switches it off (A/B, tests).
-const float *chipmunk_knorm_max(const uint16_t *k, const int64_t ks[3], int B, int H, int Nk, hipStream_t stream) {
+const float *chipmunk_knorm_max(const uint16_t *k, const int64_t ks[3], int B, int H, int Nk, hipStream_t stream, const int32_t *klens) {
     if (chipmunk_get_option("attn_nomax") == 2 || (size_t)B * H * sizeof(float) > (32 << 10)) return nullptr;
     unsigned char *sc = (unsigned char *)chipmunk_scratch(stream, 64 << 10);
     if (!sc) return nullptr;
     float *km = (float *)(sc + (32 << 10));
     if (hipMemsetAsync(km, 0, (size_t)B * H * sizeof(float), stream) != hipSuccess) return nullptr;
-    hipLaunchKernelGGL(knorm_max_kernel, dim3(Nk >= 4096 ? 64 : 8, B * H), dim3(256), 0, stream, k, ks[0], ks[1], ks[2], H, Nk, km);
+    hipLaunchKernelGGL(knorm_max_kernel, dim3(Nk >= 4096 ? 64 : 8, B * H), dim3(256), 0, stream, k, ks[0], ks[1], ks[2], H, Nk, km, klens);
     return km;
 }
 
 // dense attention through the one-wave-per-SIMD kernel (strides in elements, [batch, head, row])
 int chipmunk_dense64_launch(const void *q, const void *k, const void *v, void *o, float *l, const int64_t qs[3],
                             const int64_t ks[3], const int64_t vs[3], const int64_t os[3], int B, int H, int Nq, int Nk,
-                            hipStream_t stream) {
+                            hipStream_t stream, const int32_t *klens) {
     AttnParams p = {};
     p.q = (const uint16_t *)q, p.k = (const uint16_t *)k, p.v = (const uint16_t *)v, p.o = (uint16_t *)o;
     for (int i = 0; i < 3; ++i) p.qs[i] = qs[i], p.ks[i] = ks[i], p.vs[i] = vs[i], p.os[i] = os[i];
     p.l_out = l;
     p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.G = (Nq + WGROWS - 1) / WGROWS;
     p.o_scale = 1.f;
-    p.kmax = chipmunk_knorm_max(p.k, ks, B, H, Nk, stream);
-    return launch64<0>(p, (int64_t)B * H * p.G, stream);
+    p.klens = klens;
+    p.kmax = chipmunk_knorm_max(p.k, ks, B, H, Nk, stream, klens);
+    return klens ? launch64<0, true>(p, (int64_t)B * H * p.G, stream) : launch64<0>(p, (int64_t)B * H * p.G, stream);
 }
 
 // ---- dense_colsum_attn in one pass (MODE 3).  cs[bh][g][j] = sum over the group's rows i of exp2(s_ij c + log2 p_i) =
@@ -1167,8 +1205,11 @@ int chipmunk_dense64_launch(const void *q, const void *k, const void *v, void *o
 // and cs_combine_kernel -- or the top-k mask kernel itself, when the caller only wants the mask -- adds the one or two rows of a group
 // in fp32 (fixed order: the result does not depend on scheduling).
 namespace {
-__global__ __launch_bounds__(256) void cs_combine_kernel(const uint16_t *part, int pstride, uint16_t *cs, int NRB, int G, int Nq, int Nk, int cs_stride) {
+template <bool KL>   // KL: with per-sequence key lengths (the form without is the kernel it was)
+__global__ __launch_bounds__(256) void cs_combine_kernel(const uint16_t *part, int pstride, uint16_t *cs, int NRB, int G, int Nq, int Nk, int cs_stride,
+                                                         const int32_t *klens, int H) {
     const int g = blockIdx.y, bh = blockIdx.z;
+    const int nv = KL ? item_nk(klens, bh / H, Nk) : Nk;   // k_lens: columns nv..Nk-1 are 0; the partial rows hold nothing there and are not read
     int r0, r1;
     const int nrows = colsum_part_rows(g, NRB / 2, r0, r1);
     const uint16_t *src = part + ((int64_t)bh * NRB + r0) * pstride;
@@ -1177,6 +1218,10 @@ __global__ __launch_bounds__(256) void cs_combine_kernel(const uint16_t *part, i
     if (((Nk | cs_stride) & 3) == 0) {
         const int j = (blockIdx.x * 256 + threadIdx.x) * 4;
         if (j >= Nk) return;
+        if (KL && j >= nv) {
+            *(u32x2 *)(dst + j) = (u32x2){0u, 0u};
+            return;
+        }
         float acc[4];
         {
             const u32x2 x = *(const u32x2 *)(src + j);
@@ -1188,11 +1233,17 @@ __global__ __launch_bounds__(256) void cs_combine_kernel(const uint16_t *part, i
             acc[0] += __uint_as_float(x[0] << 16), acc[1] += __uint_as_float(x[0] & 0xffff0000u);
             acc[2] += __uint_as_float(x[1] << 16), acc[3] += __uint_as_float(x[1] & 0xffff0000u);
         }
+        if (KL && j + 4 > nv)   // the 4-column step that straddles the sequence's end
+            for (int e = 0; e < 4; ++e) acc[e] = j + e < nv ? acc[e] : 0.f;
         *(u32x2 *)(dst + j) = (u32x2){pack_bf16x2(acc[0], acc[1]), pack_bf16x2(acc[2], acc[3])};
     } else {
         for (int e = 0; e < 4; ++e) {
             const int j = (blockIdx.x * 256 + threadIdx.x) * 4 + e;
             if (j >= Nk) return;
+            if (KL && j >= nv) {
+                dst[j] = 0;
+                continue;
+            }
             float acc = bf16_bits_to_f32(src[j]);
             if (nrows == 2) acc += bf16_bits_to_f32(src[row1 + j]);
             dst[j] = f32_to_bf16_bits(acc);
@@ -1224,11 +1275,16 @@ int chipmunk_dense64_colsum_launch(const AttnParams &p0, uint16_t *part, hipStre
     p.cs_part = part, p.cs_pstride = chipmunk_colsum_part_stride(p.Nk);
     if (chipmunk_get_option("attn_cs_probe") & 2) p.probe |= 16;   // non-temporal partial-row stores
     if (chipmunk_get_option("attn_fused_colsum") == 3) p.probe |= 4;   // weighted column sums even where unit weights would do
-    p.kmax = chipmunk_knorm_max(p.k, p.ks, p.B, p.H, p.Nk, stream);
-    if (int rc = launch64<3>(p, (int64_t)p.B * p.H * p.G, stream)) return rc;
+    p.kmax = chipmunk_knorm_max(p.k, p.ks, p.B, p.H, p.Nk, stream, p.klens);
+    if (int rc = p.klens ? launch64<3, true>(p, (int64_t)p.B * p.H * p.G, stream) : launch64<3>(p, (int64_t)p.B * p.H * p.G, stream)) return rc;
     if (!p.cs) return CHIPMUNK_OK;   // the caller reads the partial rows itself (chipmunk_topk_mask_parts)
-    hipLaunchKernelGGL(cs_combine_kernel, dim3((unsigned)((p.Nk + 1023) / 1024), (unsigned)G192, (unsigned)(p.B * p.H)), dim3(256), 0, stream,
-                       part, p.cs_pstride, p.cs, p.G * 2, G192, p.Nq, p.Nk, p.cs_stride);
+    const dim3 cgrid((unsigned)((p.Nk + 1023) / 1024), (unsigned)G192, (unsigned)(p.B * p.H));
+    if (p.klens)
+        hipLaunchKernelGGL(cs_combine_kernel<true>, cgrid, dim3(256), 0, stream, part, p.cs_pstride, p.cs, p.G * 2, G192, p.Nq, p.Nk, p.cs_stride,
+                           p.klens, p.H);
+    else
+        hipLaunchKernelGGL(cs_combine_kernel<false>, cgrid, dim3(256), 0, stream, part, p.cs_pstride, p.cs, p.G * 2, G192, p.Nq, p.Nk, p.cs_stride,
+                           p.klens, p.H);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }

@@ -38,7 +38,17 @@ struct AttnParams {
     uint16_t *cs_part;
     int cs_pstride;  // elements between two of those rows (chipmunk_colsum_part_stride)
     int probe;  // timing probes (tools/kbench.py --variants): 1 = no gathers after the prologue, 2 = gathers only
+    // per-sequence key counts of the dense forms (k_lens, int32 [B]) or nullptr: keys j >= klens[b] of sequence b do not exist
+    // (padded batches).  Read through item_nk, which clamps into [1, Nk].
+    const int32_t *klens;
 };
+
+// the key count of sequence b of a dense launch: Nk, or klens[b] clamped into [1, Nk] (memory safety for malformed lengths)
+__device__ __forceinline__ int item_nk(const int32_t *klens, int b, int Nk) {
+    if (!klens) return Nk;
+    const int n = klens[b];
+    return n < 1 ? 1 : (n < Nk ? n : Nk);
+}
 
 
 // attn64.hip: gathered attention over a work plan (p.plan, p.tickets, p.ws set by launch_attn); inplace = 1 for the
@@ -49,14 +59,15 @@ int chipmunk_csp64_launch(const AttnParams &p, int inplace, int grid, hipStream_
 // partial sums into cs; with p.cs == nullptr the partial rows are the result (chipmunk_topk_mask_parts reads them)
 int chipmunk_dense64_colsum_launch(const AttnParams &p, uint16_t *part, hipStream_t stream);
 // indexed_io.hip: the top-k mask straight from the partial rows (row r of the mask = sum of the one or two rows colsum_part_rows names in
-// its (batch*head) block of `nrb` = 2 * workgroups rows, rounded to bf16 -- exactly what the combine would have written)
+// its (batch*head) block of `nrb` = 2 * workgroups rows, rounded to bf16 -- exactly what the combine would have written);
+// klens: per-sequence valid columns (rows / B rows per sequence), see chipmunk_topk_mask_varlen
 int chipmunk_topk_mask_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
                              int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double random_amount,
-                             hipStream_t stream);
+                             hipStream_t stream, const int32_t *klens = nullptr, int seq_rows = 0);
 // ... with the top-p count of chipmunk_topk_mask_p in front of the selection (k is the cap)
 int chipmunk_topk_mask_p_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
                                int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double top_p, int k_min,
-                               double random_amount, hipStream_t stream);
+                               double random_amount, hipStream_t stream, const int32_t *klens = nullptr, int seq_rows = 0);
 size_t chipmunk_colsum_part_bytes(int B, int H, int Nq, int Nk);
 // elements between two partial rows: Nk rounded up to whole 128-byte lines, so that a wave's 64 sums of a key tile are ONE
 // aligned line (a row of 119 056 keys is 1 860.25 lines: at stride Nk every store straddled two)
@@ -66,7 +77,8 @@ int chipmunk_colsum64_launch(const AttnParams &p, hipStream_t stream);
 // attn96.hip: gathered attention, two waves x 96 rows per 192-row group, two workgroups per CU (plan as for csp64)
 int chipmunk_csp96_launch(const AttnParams &p, int inplace, int grid, hipStream_t stream);
 // attn64.hip: max_j |k_j| per (batch, head) into library scratch (nullptr if switched off / unavailable); see AttnParams::kmax
-const float *chipmunk_knorm_max(const uint16_t *k, const int64_t ks[3], int B, int H, int Nk, hipStream_t stream);
+// (klens: the maximum runs over the first klens[b] rows of each sequence)
+const float *chipmunk_knorm_max(const uint16_t *k, const int64_t ks[3], int B, int H, int Nk, hipStream_t stream, const int32_t *klens = nullptr);
 
 // Partial column-sum rows of attn64.hip MODE 3: per (batch*head) 2 rows per 256-row workgroup -- row 2a = the waves of workgroup a that
 // belong to its FIRST 192-row group, row 2a + 1 = the rest (see the kernel).  Group j starts at wave block 3j = workgroup a, wave w0;

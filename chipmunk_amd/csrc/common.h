@@ -170,7 +170,7 @@ void *chipmunk_big_scratch(hipStream_t stream, size_t bytes);   // separate mult
 // attn64.hip: dense attention, one wave per SIMD (see there); strides in elements, [batch, head, row]
 int chipmunk_dense64_launch(const void *q, const void *k, const void *v, void *o, float *l, const int64_t qs[3],
                             const int64_t ks[3], const int64_t vs[3], const int64_t os[3], int B, int H, int Nq, int Nk,
-                            hipStream_t stream);
+                            hipStream_t stream, const int32_t *klens = nullptr);   // klens: per-sequence key counts or nullptr
 #define CM_CHECK(cond, ...)                    \
     do {                                       \
         if (!(cond)) {                         \

@@ -738,7 +738,35 @@ struct TopkMaskParams {
     // MASS form: k is the cap; a row keeps the smallest top set that carries top_p of its column-sum mass, at least k_min columns
     float top_p;
     int k_min;
+    // padded batches (k_lens): rows [b * seq_rows, (b + 1) * seq_rows) belong to sequence b, whose columns >= klens[b] do not
+    // exist -- they are read as the padding past n is (key 0), take part in no count, mass or tie, and their mask bytes are 0 whatever the
+    // random part, the static mask and the group flag say.  nullptr: every row has n columns.
+    const int32_t *klens;
+    int seq_rows;
 };
+
+// valid columns of a row: n, or the row's sequence length clamped into [1, n]
+__device__ __forceinline__ int topk_mask_row_len(const TopkMaskParams &p, int row) {
+    if (!p.klens) return p.n;
+    const int v = p.klens[row / p.seq_rows];
+    return v < 1 ? 1 : (v < p.n ? v : p.n);
+}
+// ALIGNED forms: a row end nv that is no multiple of 4 falls inside ONE 4-column step of the row -- step (nv - 1) >> 12 of thread
+// ((nv - 1) >> 2) & 1023 (thread t owns columns 4t + 4096j ..+3).  That step is loaded whole; these are the halves of its two words that
+// belong to columns < nv (uniform over the workgroup, so the loops pay one compare per step and nothing per column).
+struct RowCut {
+    int tid, step;          // tid = -1: the row ends on a step boundary
+    uint32_t keep0, keep1;
+};
+__device__ __forceinline__ RowCut row_cut(int nv) {
+    const int rem = nv & 3;
+    RowCut c;
+    c.tid = rem ? ((nv - 1) >> 2) & 1023 : -1;
+    c.step = (nv - 1) >> 12;
+    c.keep0 = rem == 1 ? 0xffffu : 0xffffffffu;
+    c.keep1 = rem == 3 ? 0xffffu : (rem ? 0u : 0xffffffffu);
+    return c;
+}
 
 // ---- MASS (chipmunk_topk_mask_p): a per-row count in front of the selection.  The mass of a column is its bf16 value
 // where that is positive (keys 0x8000 .. 0xff80), 0 otherwise (negative, NaN; also the padding past n, key 0).
@@ -789,6 +817,7 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const int n = p.n;
+    const int nv = topk_mask_row_len(p, row);   // the row's valid columns (k_lens), uniform over the workgroup
     const uint16_t *x = nullptr;
     int prow = 1;
     int64_t row1 = 0;      // PARTS: elements from the group's first partial row to its second
@@ -816,7 +845,7 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
             const int c = 4 * tid + 4096 * (j0 + jj);
             uint32_t v0 = 0xffffffffu, v1 = 0xffffffffu;
             if constexpr (ALIGNED) {
-                if (c < n) {
+                if (c < nv) {
                     // wave-uniform base + one shared 32-bit lane offset: the saddr form, no 64-bit address per step
                     const u32x2 v = *(const u32x2 *)((const unsigned char *)(x + 4096 * (j0 + jj)) + lane_off8);
                     v0 = v[0], v1 = v[1];
@@ -831,11 +860,11 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
                         }
                     }
                 }
-            } else if (c < n) {
+            } else if (c < nv) {
                 v0 = v1 = 0;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const uint32_t u = c + e < n ? x[c + e] : 0xffffu;
+                    const uint32_t u = c + e < nv ? x[c + e] : 0xffffu;
                     if (e < 2) v0 |= u << (16 * e);
                     else v1 |= u << (16 * (e - 2));
                 }
@@ -849,6 +878,15 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+    if constexpr (ALIGNED) {
+        // k_lens: the step that straddles the row's end was loaded whole; its columns >= nv get key 0 like the rest of the padding
+        const RowCut rc = row_cut(nv);
+        if (tid == rc.tid) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (j == rc.step) key[j][0] &= rc.keep0, key[j][1] &= rc.keep1;
+        }
+    }
     auto block_count = [&](int mine) {  // sum over the 1024 threads, broadcast
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d);
@@ -861,7 +899,7 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
         return t;
     };
     const bool active = p.groups == nullptr || p.groups[row] != 0;
-    int k = p.k < n ? p.k : n;
+    int k = p.k < nv ? p.k : nv;
     if constexpr (MASS) {
         if (active && k > 0) {   // (uniform over the workgroup)
             // mass of the keys in [lo, 0xff80]: this thread's columns ascending, the wave's xor tree, the 16 wave totals ascending
@@ -1036,11 +1074,12 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
             const uint32_t half = ((e < 2 ? v0 : v1) >> (16 * (e & 1))) & 0xffffu;
             const uint32_t kv = decltype(keyed)::value ? half : bf16_key(half);
             bool keep = kv > thr;                      // thr = 0x10000 when the row is inactive or k = 0
-            const bool tie = kv == thr && tie_budget > 0 && c + e < n;
+            const bool tie = kv == thr && tie_budget > 0 && c + e < nv;
             tie_budget -= tie ? 1 : 0;
             keep = keep || tie;
             if (rnd && !keep) keep = hash_uniform(row, c + e, salt) < p.random_amount;
             keep = keep || ((sb >> (8 * e)) & 0xffu) != 0;
+            keep = keep && c + e < nv;                 // (k_lens: no bit past the sequence's end, whatever set it)
             bytes |= (keep ? 1u : 0u) << (8 * e);
         }
         if constexpr (ALIGNED) {
@@ -1083,7 +1122,7 @@ __global__ __launch_bounds__(1024) void topk_mask_kernel(const TopkMaskParams p)
             uint32_t v0 = 0, v1 = 0, sb = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const uint32_t u = c + e < n ? x[c + e] : 0xffffu;
+                const uint32_t u = c + e < nv ? x[c + e] : 0xffffu;
                 if (e < 2) v0 |= u << (16 * e);
                 else v1 |= u << (16 * (e - 2));
                 if (st && c + e < n) sb |= (uint32_t)st[c + e] << (8 * e);
@@ -1120,6 +1159,7 @@ __global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskPa
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
     const int n = p.n;
+    const int nv = topk_mask_row_len(p, row);   // the row's valid columns (k_lens), uniform over the workgroup
     const uint16_t *x = nullptr;
     int prow = 1;
     int64_t row1 = 0;      // PARTS: elements from the group's first partial row to its second
@@ -1135,7 +1175,9 @@ __global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskPa
     const uint32_t lane_off8 = 8u * (uint32_t)tid;
     const int nsteps = (n + 4095) / 4096;
     const bool active = p.groups == nullptr || p.groups[row] != 0;
-    int k = p.k < n ? p.k : n;
+    int k = p.k < nv ? p.k : nv;
+    const RowCut rc = row_cut(nv);
+    const int cut_step = ALIGNED && tid == rc.tid ? rc.step : -1;   // k_lens: this thread's step that straddles the row's end, or none
     bool select = active && k > 0;
     const bool rnd = active && p.random_amount > 0.f;
 
@@ -1171,11 +1213,12 @@ __global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskPa
             uint16_t *xk = const_cast<uint16_t *>(x);
             for (int j = 0; j < nsteps; ++j) {
                 const int c = 4 * tid + 4096 * j;
-                if (c < n) {
+                if (c < nv) {   // (the partial rows hold nothing past the sequence's end: neither read nor written there)
                     uint32_t v0, v1;
                     combined4(c, v0, v1);
-                    u32x2 kk = {bf16_key2(v0), bf16_key2(v1)};
-                    *(u32x2 *)(xk + c) = kk;
+                    uint32_t k0 = bf16_key2(v0), k1 = bf16_key2(v1);
+                    if (j == cut_step) k0 &= rc.keep0, k1 &= rc.keep1;   // key 0 for the columns >= nv of the straddling step
+                    *(u32x2 *)(xk + c) = (u32x2){k0, k1};
                 }
             }
         }
@@ -1186,17 +1229,19 @@ __global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskPa
         const int c = 4 * tid + 4096 * j;
         if constexpr (ALIGNED) {
             v0 = v1 = PARTS ? 0u : 0xffffffffu;
-            if (c < n) {
+            if (c < nv) {
                 const u32x2 v = *(const u32x2 *)((const unsigned char *)(x + 4096 * j) + lane_off8);
                 v0 = v[0], v1 = v[1];
+                if constexpr (!PARTS)
+                    if (j == cut_step) v0 |= ~rc.keep0, v1 |= ~rc.keep1;   // raw 0xffff = key 0 (PARTS: cut when the keys were written)
             }
         } else {
             v0 = v1 = 0xffffffffu;
-            if (c < n) {
+            if (c < nv) {
                 v0 = v1 = 0;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const uint32_t u = c + e < n ? x[c + e] : 0xffffu;
+                    const uint32_t u = c + e < nv ? x[c + e] : 0xffffu;
                     if (e < 2) v0 |= u << (16 * e);
                     else v1 |= u << (16 * (e - 2));
                 }
@@ -1366,11 +1411,12 @@ __global__ __launch_bounds__(1024) void topk_mask_stream_kernel(const TopkMaskPa
             for (int e = 0; e < 4; ++e) {
                 const uint32_t kv = (kw[jj][e >> 1] >> (16 * (e & 1))) & 0xffffu;
                 bool keep = kv > thr;                      // thr = 0x10000 when the row is inactive or k = 0
-                const bool tie = kv == thr && tie_budget > 0 && c + e < n;
+                const bool tie = kv == thr && tie_budget > 0 && c + e < nv;
                 tie_budget -= tie ? 1 : 0;
                 keep = keep || tie;
                 if (rnd && !keep) keep = hash_uniform(row, c + e, salt) < p.random_amount;
                 keep = keep || ((sbv[jj] >> (8 * e)) & 0xffu) != 0;
+                keep = keep && c + e < nv;                 // (k_lens: no bit past the sequence's end)
                 bytes |= (keep ? 1u : 0u) << (8 * e);
             }
             if constexpr (ALIGNED) {
@@ -1625,7 +1671,8 @@ extern "C" int chipmunk_gather_rows(const void *src, void *dst, const int32_t *m
 template <bool MASS>
 static int topk_mask_parts_impl(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
                                 int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double random_amount,
-                                double top_p, int k_min, hipStream_t s) {
+                                double top_p, int k_min, hipStream_t s, const int32_t *klens, int seq_rows) {
+    CM_CHECK(!klens || seq_rows > 0, "topk_mask_parts: k_lens without the rows per sequence");
     CM_CHECK(part && mask && rows >= 0 && n > 0 && (n & 3) == 0 && n <= CHIPMUNK_TOPK_MASK_MAX_N && k >= 0 && part_stride >= n && (part_stride & 3) == 0, "topk_mask_parts: bad arguments");
     CM_CHECK(!static_mask || (static_rows > 0 && static_stride >= n && (static_stride & 3) == 0 && ((uintptr_t)static_mask & 3) == 0),
              "topk_mask_parts: bad static mask geometry");
@@ -1636,6 +1683,7 @@ static int topk_mask_parts_impl(const uint16_t *part, int part_stride, int nrb, 
                         random_amount > 0.0 ? chipmunk_next_random_salt() : 0u};
     p.parts = part, p.pstride = part_stride, p.nrb = nrb, p.ngroups = groups_per_bh, p.nq = Nq;
     p.top_p = (float)top_p, p.k_min = k_min;
+    p.klens = klens, p.seq_rows = seq_rows;
     // rows past the register form's 122 880 columns (or option topk_mask_stream = 1: every row) take the streaming form
     if (n > 1024 * 120 || chipmunk_get_option("topk_mask_stream") == 1) hipLaunchKernelGGL((topk_mask_stream_kernel<true, true, MASS>), dim3(rows), dim3(1024), 0, s, p);
     else if (n <= 1024 * 16) hipLaunchKernelGGL((topk_mask_kernel<16, true, true, MASS>), dim3(rows), dim3(1024), 0, s, p);
@@ -1647,18 +1695,18 @@ static int topk_mask_parts_impl(const uint16_t *part, int part_stride, int nrb, 
 
 int chipmunk_topk_mask_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
                              int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double random_amount,
-                             hipStream_t s) {
+                             hipStream_t s, const int32_t *klens, int seq_rows) {
     return topk_mask_parts_impl<false>(part, part_stride, nrb, groups_per_bh, Nq, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k,
-                                       random_amount, 0.0, 0, s);
+                                       random_amount, 0.0, 0, s, klens, seq_rows);
 }
 
 // the same with the top-p count in front (chipmunk_topk_mask_p): k is the cap
 int chipmunk_topk_mask_p_parts(const uint16_t *part, int part_stride, int nrb, int groups_per_bh, int Nq, const void *static_mask, int64_t static_stride,
                                int static_rows, const void *group_flags, void *mask, int rows, int n, int k, double top_p, int k_min,
-                               double random_amount, hipStream_t s) {
+                               double random_amount, hipStream_t s, const int32_t *klens, int seq_rows) {
     CM_CHECK(top_p > 0.0 && top_p <= 1.0 && k_min >= 0, "topk_mask_p_parts: top_p must be in (0, 1] and k_min >= 0 (got %g, %d)", top_p, k_min);
     return topk_mask_parts_impl<true>(part, part_stride, nrb, groups_per_bh, Nq, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k,
-                                      random_amount, top_p, k_min, s);
+                                      random_amount, top_p, k_min, s, klens, seq_rows);
 }
 
 // ---- QKV projection output -> attention operands: split + q/k RMSNorm + head-major layout in ONE pass.
@@ -1738,8 +1786,9 @@ extern "C" int chipmunk_qkv_split_norm(const void *qkv, int64_t row_stride, cons
 template <bool MASS>
 static int topk_mask_impl(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
                           int static_rows, const void *group_flags, void *mask, int rows, int n, int k,
-                          double random_amount, double top_p, int k_min, void *stream) {
+                          double random_amount, double top_p, int k_min, void *stream, const int32_t *klens = nullptr, int seq_rows = 0) {
     CM_CHECK(cs && mask, "topk_mask: null pointer");
+    CM_CHECK(!klens || (seq_rows > 0 && rows % seq_rows == 0), "topk_mask: %d rows are no whole sequences of %d rows", rows, seq_rows);
     CM_CHECK(rows >= 0 && n > 0 && k >= 0, "topk_mask: bad sizes (rows=%d n=%d k=%d)", rows, n, k);
     CM_CHECK(cs_stride >= n, "topk_mask: cs row stride %lld < n %d", (long long)cs_stride, n);
     CM_CHECK(n <= CHIPMUNK_TOPK_MASK_MAX_N, "topk_mask: rows of more than %d columns are not supported (got %d)", CHIPMUNK_TOPK_MASK_MAX_N, n);
@@ -1750,6 +1799,7 @@ static int topk_mask_impl(const void *cs, int64_t cs_stride, const void *static_
                         cs_stride, static_stride, rows, n, k, static_mask ? static_rows : 1, (float)random_amount,
                         random_amount > 0.0 ? chipmunk_next_random_salt() : 0u};
     p.top_p = (float)top_p, p.k_min = k_min;
+    p.klens = klens, p.seq_rows = seq_rows;
     hipStream_t s = (hipStream_t)stream;
     const bool aligned = n % 4 == 0 && (((uintptr_t)cs) & 7) == 0 && (cs_stride * 2) % 8 == 0 && (((uintptr_t)mask) & 3) == 0 &&
                          (!static_mask || ((((uintptr_t)static_mask) & 3) == 0 && static_stride % 4 == 0));
@@ -1782,6 +1832,24 @@ extern "C" int chipmunk_topk_mask_p(const void *cs, int64_t cs_stride, const voi
     CM_CHECK(top_p > 0.0 && top_p <= 1.0, "topk_mask_p: top_p must be in (0, 1] (got %g)", top_p);
     CM_CHECK(k_min >= 0, "topk_mask_p: k_min must be >= 0 (got %d)", k_min);
     return topk_mask_impl<true>(cs, cs_stride, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k, random_amount, top_p, k_min, stream);
+}
+
+// The selection over a padded batch: k_lens = int32 [rows / seq_rows] on the device, rows [b * seq_rows, (b + 1) * seq_rows) belong to
+// sequence b.  A row of sequence b selects among its first k_lens[b] columns only (k capped there) and writes 0 past them.
+extern "C" int chipmunk_topk_mask_varlen(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
+                                         int static_rows, const void *group_flags, void *mask, const int32_t *k_lens, int seq_rows, int rows,
+                                         int n, int k, double random_amount, void *stream) {
+    return topk_mask_impl<false>(cs, cs_stride, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k, random_amount, 0.0, 0, stream,
+                                 k_lens, seq_rows);
+}
+
+extern "C" int chipmunk_topk_mask_p_varlen(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
+                                           int static_rows, const void *group_flags, void *mask, const int32_t *k_lens, int seq_rows, int rows,
+                                           int n, int k, double random_amount, double top_p, int k_min, void *stream) {
+    CM_CHECK(top_p > 0.0 && top_p <= 1.0, "topk_mask_p: top_p must be in (0, 1] (got %g)", top_p);
+    CM_CHECK(k_min >= 0, "topk_mask_p: k_min must be >= 0 (got %d)", k_min);
+    return topk_mask_impl<true>(cs, cs_stride, static_mask, static_stride, static_rows, group_flags, mask, rows, n, k, random_amount, top_p, k_min,
+                                stream, k_lens, seq_rows);
 }
 
 extern "C" int chipmunk_compact_indices(const int32_t *indices, int64_t idx_stride, const int32_t *counts, const int64_t *offsets,

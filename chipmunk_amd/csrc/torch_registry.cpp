@@ -209,26 +209,47 @@ static at::Tensor alloc_o(const at::Tensor &q, const at::Tensor &v, bool token_m
     return at::empty({q.size(0), q.size(2), q.size(1), q.size(3)}, v.options()).permute({0, 2, 1, 3});
 }
 
+// per-sequence key lengths of a padded batch (an addition): int32 [B] on the GPU; nullptr when absent
+using OptTensor = c10::optional<at::Tensor>;
+static const int32_t *klens_ptr(const OptTensor &k_lens, const at::Tensor &like, int64_t B) {
+    if (!k_lens.has_value() || !k_lens->defined()) return nullptr;
+    const at::Tensor &t = *k_lens;
+    TORCH_CHECK(t.is_cuda() && t.device() == like.device(), "k_lens must be a GPU tensor on the device of the other operands");
+    TORCH_CHECK(t.scalar_type() == at::kInt, "k_lens must be int32");
+    TORCH_CHECK(t.is_contiguous() && t.numel() == B, "k_lens must be contiguous with one entry per sequence (", B, "), got ", t.numel());
+    return t.data_ptr<int32_t>();
+}
+
 // reference csrc/attn/dense_attn.cu:246-372
-std::vector<at::Tensor> dense_attn_layout(at::Tensor q, at::Tensor k, at::Tensor v, bool token_major_o) {
+static std::vector<at::Tensor> dense_attn_klens(at::Tensor q, at::Tensor k, at::Tensor v, bool token_major_o, const OptTensor &k_lens) {
     check_attn_shapes(q, k, v);
+    const int32_t *kl = klens_ptr(k_lens, q, q.size(0));
     c10::DeviceGuard guard(q.device());
     auto qs = strides_of(q, "Q"), ks = strides_of(k, "K"), vs = strides_of(v, "V");
     at::Tensor o = alloc_o(q, v, token_major_o);
     auto os = strides_of(o, "O");
     at::Tensor l = at::empty({q.size(0), q.size(1), q.size(2), 1}, q.options().dtype(at::kFloat));
-    check(chipmunk_dense_attn_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs.s, ks.s, vs.s, o.data_ptr(), os.s,
-                                      l.data_ptr<float>(), (int)q.size(0), (int)q.size(1), (int)q.size(2), (int)k.size(2),
-                                      cur_stream(q)),
+    check(chipmunk_dense_attn_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs.s, ks.s, vs.s, o.data_ptr(), os.s,
+                                     l.data_ptr<float>(), kl, (int)q.size(0), (int)q.size(1), (int)q.size(2), (int)k.size(2),
+                                     cur_stream(q)),
           "dense_attn");
     return {o, l};
+}
+
+std::vector<at::Tensor> dense_attn_layout(at::Tensor q, at::Tensor k, at::Tensor v, bool token_major_o) {
+    return dense_attn_klens(q, k, v, token_major_o, c10::nullopt);
+}
+std::vector<at::Tensor> dense_attn_varlen(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor k_lens, bool token_major_o) {
+    return dense_attn_klens(q, k, v, token_major_o, k_lens);
 }
 
 std::vector<at::Tensor> dense_attn(at::Tensor q, at::Tensor k, at::Tensor v) { return dense_attn_layout(q, k, v, false); }
 
 // reference csrc/attn/dense_colsum_attn.cu:521-668
-std::vector<at::Tensor> dense_colsum_attn_layout(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, bool token_major_o) {
+static std::vector<at::Tensor> dense_colsum_attn_klens(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, bool token_major_o,
+                                                       const OptTensor &k_lens) {
     check_attn_shapes(q, k, v);
+    const int32_t *kl = klens_ptr(k_lens, q, q.size(0));
     CHECK_DEV(p);
     TORCH_CHECK(p.scalar_type() == at::kFloat, "p must be float32");
     TORCH_CHECK(p.is_contiguous(), "p must be contiguous");
@@ -243,11 +264,18 @@ std::vector<at::Tensor> dense_colsum_attn_layout(at::Tensor q, at::Tensor k, at:
     auto os = strides_of(o, "O");
     at::Tensor cs = at::empty({q.size(0), q.size(1), groups, width}, v.options());
     at::Tensor l = at::empty({q.size(0), q.size(1), q.size(2), 1}, q.options().dtype(at::kFloat));
-    check(chipmunk_dense_colsum_attn_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs.s, ks.s, vs.s, p.data_ptr<float>(),
-                                             o.data_ptr(), os.s, cs.data_ptr(), l.data_ptr<float>(), (int)q.size(0),
-                                             (int)q.size(1), (int)q.size(2), (int)k.size(2), (int)width, cur_stream(q)),
+    check(chipmunk_dense_colsum_attn_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs.s, ks.s, vs.s, p.data_ptr<float>(),
+                                            o.data_ptr(), os.s, cs.data_ptr(), l.data_ptr<float>(), kl, (int)q.size(0),
+                                            (int)q.size(1), (int)q.size(2), (int)k.size(2), (int)width, cur_stream(q)),
           "dense_colsum_attn");
     return {o, cs, l};
+}
+
+std::vector<at::Tensor> dense_colsum_attn_layout(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, bool token_major_o) {
+    return dense_colsum_attn_klens(q, k, v, p, token_major_o, c10::nullopt);
+}
+std::vector<at::Tensor> dense_colsum_attn_varlen(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, at::Tensor k_lens, bool token_major_o) {
+    return dense_colsum_attn_klens(q, k, v, p, token_major_o, k_lens);
 }
 
 std::vector<at::Tensor> dense_colsum_attn(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p) {
@@ -1004,10 +1032,13 @@ std::vector<at::Tensor> mask_to_ragged_indices(at::Tensor mask, at::IntArrayRef 
 std::vector<at::Tensor> dense_colsum_attn_layout(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, bool token_major_o);
 // (the `_p` operators: `mass` set, `top_p` / `k_min` the per-row count of chipmunk_topk_mask_p with k as the cap)
 static at::Tensor topk_mask_impl(at::Tensor cs, int64_t k, bool mass, double top_p, int64_t k_min, double random_amount,
-                                 const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask);
+                                 const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask,
+                                 const OptTensor &k_lens = c10::nullopt);
 static std::vector<at::Tensor> dense_colsum_topk_mask_impl(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, int64_t k_top, bool mass, double top_p,
                                                            int64_t k_min, double random_amount, const c10::optional<at::Tensor> &groups,
-                                                           const c10::optional<at::Tensor> &static_mask, bool token_major_o) {
+                                                           const c10::optional<at::Tensor> &static_mask, bool token_major_o,
+                                                           const OptTensor &k_lens = c10::nullopt) {
+    const int32_t *kl = klens_ptr(k_lens, q, q.dim() == 4 ? q.size(0) : 0);
     if (mass) TORCH_CHECK(top_p > 0.0 && top_p <= 1.0 && k_min >= 0, "top_p must be in (0, 1] and k_min >= 0 (got ", top_p, ", ", k_min, ")");
     CHECK_DEV(q); CHECK_DEV(k); CHECK_DEV(v); CHECK_DEV(p);
     CHECK_BF16(q); CHECK_BF16(k); CHECK_BF16(v);
@@ -1043,21 +1074,33 @@ static std::vector<at::Tensor> dense_colsum_topk_mask_impl(at::Tensor q, at::Ten
             at::Tensor mask = at::empty({B, H, G, Nk}, q.options().dtype(at::kBool));
             const int64_t qs[3] = {q.stride(0), q.stride(1), q.stride(2)}, ks[3] = {k.stride(0), k.stride(1), k.stride(2)},
                           vs[3] = {v.stride(0), v.stride(1), v.stride(2)};
-            const int rc = mass ? chipmunk_dense_colsum_topk_mask_p_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs, ks, vs, p.data_ptr<float>(), o.data_ptr(),
-                                                                            os, l.data_ptr<float>(), (int)B, (int)H, (int)Nq, (int)Nk, st, st_stride, (int)st_rows, gf,
-                                                                            mask.data_ptr(), (int)k_top, random_amount, top_p, (int)(k_min > Nk ? Nk : k_min), cur_stream(q))
-                                : chipmunk_dense_colsum_topk_mask_strided(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs, ks, vs, p.data_ptr<float>(), o.data_ptr(),
-                                                           os, l.data_ptr<float>(), (int)B, (int)H, (int)Nq, (int)Nk, st, st_stride, (int)st_rows, gf,
+            const int rc = mass ? chipmunk_dense_colsum_topk_mask_p_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs, ks, vs, p.data_ptr<float>(), o.data_ptr(),
+                                                                           os, l.data_ptr<float>(), kl, (int)B, (int)H, (int)Nq, (int)Nk, st, st_stride, (int)st_rows, gf,
+                                                                           mask.data_ptr(), (int)k_top, random_amount, top_p, (int)(k_min > Nk ? Nk : k_min), cur_stream(q))
+                                : chipmunk_dense_colsum_topk_mask_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), qs, ks, vs, p.data_ptr<float>(), o.data_ptr(),
+                                                           os, l.data_ptr<float>(), kl, (int)B, (int)H, (int)Nq, (int)Nk, st, st_stride, (int)st_rows, gf,
                                                            mask.data_ptr(), (int)k_top, random_amount, cur_stream(q));
             if (rc == CHIPMUNK_OK) return {o, mask, l};
             if (rc != CHIPMUNK_ERR_UNSUPPORTED) check(rc, "dense_colsum_topk_mask");
         }
     }
-    auto ocl = dense_colsum_attn_layout(q, k, v, p, token_major_o);
+    auto ocl = dense_colsum_attn_klens(q, k, v, p, token_major_o, k_lens);
     at::Tensor cs = ocl[1];
     const int64_t Nk = k.size(2), G = (q.size(2) + 191) / 192;
     if (cs.size(-1) != Nk || cs.size(-2) != G) cs = cs.slice(-2, 0, G).slice(-1, 0, Nk);
-    return {ocl[0], topk_mask_impl(cs, k_top, mass, top_p, k_min, random_amount, groups, static_mask), ocl[2]};
+    return {ocl[0], topk_mask_impl(cs, k_top, mass, top_p, k_min, random_amount, groups, static_mask, k_lens), ocl[2]};
+}
+
+std::vector<at::Tensor> dense_colsum_topk_mask_varlen(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, at::Tensor k_lens, int64_t k_top,
+                                                      double random_amount, const c10::optional<at::Tensor> &groups,
+                                                      const c10::optional<at::Tensor> &static_mask, bool token_major_o) {
+    return dense_colsum_topk_mask_impl(q, k, v, p, k_top, false, 0.0, 0, random_amount, groups, static_mask, token_major_o, k_lens);
+}
+
+std::vector<at::Tensor> dense_colsum_topk_mask_p_varlen(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, at::Tensor k_lens, int64_t k_top,
+                                                        double top_p, int64_t k_min, double random_amount, const c10::optional<at::Tensor> &groups,
+                                                        const c10::optional<at::Tensor> &static_mask, bool token_major_o) {
+    return dense_colsum_topk_mask_impl(q, k, v, p, k_top, true, top_p, k_min, random_amount, groups, static_mask, token_major_o, k_lens);
 }
 
 std::vector<at::Tensor> dense_colsum_topk_mask(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor p, int64_t k_top, double random_amount,
@@ -1073,10 +1116,12 @@ std::vector<at::Tensor> dense_colsum_topk_mask_p(at::Tensor q, at::Tensor k, at:
 }
 
 static at::Tensor topk_mask_impl(at::Tensor cs, int64_t k, bool mass, double top_p, int64_t k_min, double random_amount,
-                                 const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask) {
+                                 const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask,
+                                 const OptTensor &k_lens) {
     CHECK_DEV(cs); CHECK_BF16(cs);
     TORCH_CHECK(cs.dim() == 4 && cs.stride(3) == 1, "cs must be [B, H, G, N] with a contiguous last dim");
     const int64_t B = cs.size(0), H = cs.size(1), G = cs.size(2), N = cs.size(3);
+    const int32_t *kl = klens_ptr(k_lens, cs, B);
     // rows must be addressable with one stride: collapse (B, H, G) or copy
     if (!(cs.stride(1) == G * cs.stride(2) && (B == 1 || cs.stride(0) == H * cs.stride(1)))) cs = cs.contiguous();
     const int64_t rows = B * H * G;
@@ -1103,14 +1148,24 @@ static at::Tensor topk_mask_impl(at::Tensor cs, int64_t k, bool mass, double top
         gf = gfc.data_ptr();
     }
     if (mass)
-        check(chipmunk_topk_mask_p(cs.data_ptr(), cs.stride(2), st, st_stride, (int)st_rows, gf, mask.data_ptr(), (int)rows, (int)N,
-                                   (int)k, random_amount, top_p, (int)(k_min > N ? N : k_min), cur_stream(cs)),
+        check(chipmunk_topk_mask_p_varlen(cs.data_ptr(), cs.stride(2), st, st_stride, (int)st_rows, gf, mask.data_ptr(), kl, (int)(H * G),
+                                          (int)rows, (int)N, (int)k, random_amount, top_p, (int)(k_min > N ? N : k_min), cur_stream(cs)),
               "topk_mask_p");
     else
-        check(chipmunk_topk_mask(cs.data_ptr(), cs.stride(2), st, st_stride, (int)st_rows, gf, mask.data_ptr(), (int)rows, (int)N,
-                                 (int)k, random_amount, cur_stream(cs)),
+        check(chipmunk_topk_mask_varlen(cs.data_ptr(), cs.stride(2), st, st_stride, (int)st_rows, gf, mask.data_ptr(), kl, (int)(H * G),
+                                        (int)rows, (int)N, (int)k, random_amount, cur_stream(cs)),
               "topk_mask");
     return mask;
+}
+
+at::Tensor topk_mask_varlen(at::Tensor cs, at::Tensor k_lens, int64_t k, double random_amount, const c10::optional<at::Tensor> &groups,
+                            const c10::optional<at::Tensor> &static_mask) {
+    return topk_mask_impl(cs, k, false, 0.0, 0, random_amount, groups, static_mask, k_lens);
+}
+
+at::Tensor topk_mask_p_varlen(at::Tensor cs, at::Tensor k_lens, int64_t k, double top_p, int64_t k_min, double random_amount,
+                              const c10::optional<at::Tensor> &groups, const c10::optional<at::Tensor> &static_mask) {
+    return topk_mask_impl(cs, k, true, top_p, k_min, random_amount, groups, static_mask, k_lens);
 }
 
 at::Tensor topk_mask(at::Tensor cs, int64_t k, double random_amount, const c10::optional<at::Tensor> &groups,
@@ -1288,6 +1343,13 @@ TORCH_LIBRARY(chipmunk, m) {
     // the two dense operators with a choice of output layout (the reference's schemas above stay as they are)
     m.def("dense_attn_layout(Tensor q, Tensor k, Tensor v, bool token_major_o) -> Tensor[]");
     m.def("dense_colsum_attn_layout(Tensor q, Tensor k, Tensor v, Tensor p, bool token_major_o) -> Tensor[]");
+    // padded batches: the dense and mask-step operators with per-sequence key lengths, int32 [B] on the GPU
+    m.def("dense_attn_varlen(Tensor q, Tensor k, Tensor v, Tensor k_lens, bool token_major_o=False) -> Tensor[]");
+    m.def("dense_colsum_attn_varlen(Tensor q, Tensor k, Tensor v, Tensor p, Tensor k_lens, bool token_major_o=False) -> Tensor[]");
+    m.def("topk_mask_varlen(Tensor cs, Tensor k_lens, int k, float random_amount, Tensor? groups, Tensor? static_mask) -> Tensor");
+    m.def("topk_mask_p_varlen(Tensor cs, Tensor k_lens, int k, float top_p, int k_min, float random_amount, Tensor? groups, Tensor? static_mask) -> Tensor");
+    m.def("dense_colsum_topk_mask_varlen(Tensor q, Tensor k, Tensor v, Tensor p, Tensor k_lens, int k_top, float random_amount, Tensor? groups, Tensor? static_mask, bool token_major_o=False) -> Tensor[]");
+    m.def("dense_colsum_topk_mask_p_varlen(Tensor q, Tensor k, Tensor v, Tensor p, Tensor k_lens, int k_top, float top_p, int k_min, float random_amount, Tensor? groups, Tensor? static_mask, bool token_major_o=False) -> Tensor[]");
     m.def("compact_indices(Tensor indices, Tensor counts) -> Tensor[]");
     m.def("mask_to_ragged_indices(Tensor mask, int[] shape, int multiple_of, int pad_to_multiple_of, bool sorted) -> Tensor[]");
     m.def("csp_attn_out_ragged(Tensor q, Tensor k, Tensor v, Tensor o_in, Tensor indices, Tensor offsets, Tensor indices_counts, int o_scale) -> Tensor");
@@ -1322,6 +1384,12 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("compact_indices", &compact_indices);
     m.impl("residual_ln_modulate", &residual_ln_modulate);
     m.impl("csp_attn_out_ragged", &csp_attn_out_ragged);
+    m.impl("dense_attn_varlen", &dense_attn_varlen);
+    m.impl("dense_colsum_attn_varlen", &dense_colsum_attn_varlen);
+    m.impl("topk_mask_varlen", &topk_mask_varlen);
+    m.impl("topk_mask_p_varlen", &topk_mask_p_varlen);
+    m.impl("dense_colsum_topk_mask_varlen", &dense_colsum_topk_mask_varlen);
+    m.impl("dense_colsum_topk_mask_p_varlen", &dense_colsum_topk_mask_p_varlen);
     m.impl("dense_attn_layout", &dense_attn_layout);
     m.impl("dense_colsum_attn_layout", &dense_colsum_attn_layout);
     m.impl("csp_attn_out", &csp_attn_out);

@@ -39,9 +39,24 @@ def _cdiv(a: int, b: int) -> int:
     return (a + b - 1) // b
 
 
-def _dense_attn_raw(q: Tensor, k: Tensor, v: Tensor, token_major_o: bool):
+def _dense_attn_raw(q: Tensor, k: Tensor, v: Tensor, token_major_o: bool, k_lens: Optional[Tensor] = None):
     """The operator itself (no padding of l), as the reference's unpadded path calls it (modules/attn.py:126)."""
+    if k_lens is not None:
+        return torch.ops.chipmunk.dense_attn_varlen(q, k, v, k_lens, token_major_o)
     return torch.ops.chipmunk.dense_attn_layout(q, k, v, True) if token_major_o else torch.ops.chipmunk.dense_attn(q, k, v)
+
+
+def _valid_keys(k_lens: Tensor, n: int) -> Tensor:
+    """bool ``[B, 1, 1, n]``: key ``j`` of sequence ``b`` exists (``j < k_lens[b]``)."""
+    return (torch.arange(n, device=k_lens.device)[None, :] < k_lens[:, None])[:, None, None, :]
+
+
+def _cap_counts(counts: Tensor, k_lens: Optional[Tensor]) -> Tensor:
+    """Index rows list a group's kept keys, then -- up to the count rounded to ``counts_multiple_of`` -- the first columns it did NOT
+    keep, ascending.  With ``k_lens`` the kept keys are all valid, so the first ``k_lens[b]`` entries of a row are exactly its valid
+    columns: a count capped there drops the padding keys the rounding would list (a group that keeps every valid key has no other
+    column to round up with) and nothing else."""
+    return counts if k_lens is None else torch.minimum(counts, k_lens.view(-1, 1, 1).to(counts.dtype))
 
 
 class SparseDiffAttn(nn.Module):
@@ -104,25 +119,31 @@ class SparseDiffAttn(nn.Module):
                              "which cannot hold a key count per query group")
         return top_p, int(multiple_of * round((float(amd_key("attn", "top_p_min_keys")) * n_keys) / multiple_of))
 
-    def random_and_topk(self, cs: Tensor, topk: int, top_p: float = 0.0, k_min: int = 0) -> Tensor:
+    def random_and_topk(self, cs: Tensor, topk: int, top_p: float = 0.0, k_min: int = 0, k_lens: Optional[Tensor] = None) -> Tensor:
         """1% random keys + top-k column sums, limited to the groups that are sparse at all, plus the static mask.
-        ``top_p`` > 0 (``attn.top_p``): ``topk`` is the cap of the per-group count of ``ops.topk_mask_p``."""
+        ``top_p`` > 0 (``attn.top_p``): ``topk`` is the cap of the per-group count of ``ops.topk_mask_p``.
+        ``k_lens``: no key at or past a sequence's length is kept (the mask kernels; the torch chain clears those columns last)."""
         cfg = GLOBAL_CONFIG["attn"]
         qg, n = cs.shape[-2], cs.shape[-1]
         static, groups = self._static(cs.shape[1], qg, n)
         if top_p > 0.0:
             if cs.dtype != torch.bfloat16:
                 raise ValueError(f"attn.top_p: the selection takes bfloat16 column sums (got {cs.dtype})")
-            return ops.topk_mask_p(cs, topk, top_p, k_min, 0.01, groups, static)      # (a row past the kernels' ceiling is refused there)
+            return ops.topk_mask_p(cs, topk, top_p, k_min, 0.01, groups, static, k_lens)      # (a row past the kernels' ceiling is refused there)
         if cs.is_cuda and amd_key("attn", "fused_topk_mask") and cs.dtype == torch.bfloat16 and n <= ops.TOPK_MASK_MAX_N:
             # one kernel for the whole chain below (the random 1 % comes from a counter-based hash, not torch's RNG)
-            return ops.topk_mask(cs, topk, 0.01, groups, static)
+            return ops.topk_mask(cs, topk, 0.01, groups, static, k_lens)
         mask = torch.randint(0, 100, cs.shape, device=cs.device, dtype=torch.uint8) == 0
+        valid = _valid_keys(k_lens, n) if k_lens is not None else None
+        if valid is not None:   # the padding must not win a place in the top-k either
+            cs = cs.masked_fill(~valid, torch.finfo(cs.dtype).min)
         mask.scatter_(-1, cs.topk(k=topk, dim=-1).indices, True)
         # (mask * groups) | static of the reference (modules/attn.py:76-82) as in-place logical ops on the fresh mask: same
         # booleans, no bool x bool product kernel and no two 1.8 GB temporaries at HunyuanVideo size (16 -> 3 ms)
         mask.logical_and_(groups)
         mask.logical_or_(static)
+        if valid is not None:
+            mask.logical_and_(valid)
         return mask
 
     # ------------------------------------------------------------------------------------------ helpers
@@ -221,7 +242,8 @@ class SparseDiffAttn(nn.Module):
         return self.storage.get_indices(), self.storage.get_counts()
 
     # ------------------------------------------------------------------------------------------ state machine
-    def _fast_attention(self, q: Tensor, k: Tensor, v: Tensor, inference_step: int, do_full_step: bool) -> Tensor:
+    def _fast_attention(self, q: Tensor, k: Tensor, v: Tensor, inference_step: int, do_full_step: bool,
+                        k_lens: Optional[Tensor] = None) -> Tensor:
         cfg = GLOBAL_CONFIG["attn"]
         bm = cfg["mbm"]
         assert bm == 192, "The kernel was written for BM=192. You may need to change the kernel."
@@ -231,12 +253,14 @@ class SparseDiffAttn(nn.Module):
         tm = bool(q.is_cuda and amd_key("attn", "token_major_output"))     # output layout of the dense calls; the sparse ones follow the cache
         use_ragged = self._ragged_enabled(q)
         if self.layer_num < cfg["first_n_dense_layers"]:
-            o, _ = ops.dense_attn(q, k, v, tm)
+            o, _ = ops.dense_attn(q, k, v, tm, k_lens)
             return o
 
+        # (k_lens reaches every dense pass, and the mask those passes store lists no key past a sequence's end; what is left for the
+        # gathered steps is the rounding of the row counts, see _cap_counts)
         if do_full_step:
             if inference_step == 0:
-                o, lse = ops.dense_attn(q, k, v, tm) if do_padding else _dense_attn_raw(q, k, v, tm)
+                o, lse = ops.dense_attn(q, k, v, tm, k_lens) if do_padding else _dense_attn_raw(q, k, v, tm, k_lens)
                 lse[..., k.shape[-2]:, :] = 0
                 self.storage.set_lse_constants(lse)
                 return o
@@ -252,11 +276,13 @@ class SparseDiffAttn(nn.Module):
                     # dense attention -> column sums -> mask without the column-sum tensor in between (same bits as the two steps)
                     static, groups = self._static(q.shape[1], _cdiv(q.shape[-2], bm), k.shape[-2])
                     if top_p > 0.0:
-                        o, mask, lse = ops.dense_colsum_topk_mask_p(q, k, v, prev_lse, tk, top_p, k_min, 0.01, groups, static, tm)
+                        o, mask, lse = ops.dense_colsum_topk_mask_p(q, k, v, prev_lse, tk, top_p, k_min, 0.01, groups, static, tm, k_lens)
                     else:
-                        o, mask, lse = ops.dense_colsum_topk_mask(q, k, v, prev_lse, tk, 0.01, groups, static, tm)
+                        o, mask, lse = ops.dense_colsum_topk_mask(q, k, v, prev_lse, tk, 0.01, groups, static, tm, k_lens)
                 elif do_padding:
-                    o, bs, lse = ops.dense_colsum_attn(q, k, v, prev_lse, tm)
+                    o, bs, lse = ops.dense_colsum_attn(q, k, v, prev_lse, tm, k_lens)
+                elif k_lens is not None:
+                    o, bs, lse = torch.ops.chipmunk.dense_colsum_attn_varlen(q, k, v, prev_lse, k_lens, tm)
                 else:
                     o, bs, lse = (torch.ops.chipmunk.dense_colsum_attn_layout(q, k, v, prev_lse, True) if tm else
                                   torch.ops.chipmunk.dense_colsum_attn(q, k, v, prev_lse))
@@ -266,24 +292,32 @@ class SparseDiffAttn(nn.Module):
                     if mask is not None:
                         pass
                     elif tk > 0:
-                        mask = self.random_and_topk(bs, tk, top_p, k_min)
+                        mask = self.random_and_topk(bs, tk, top_p, k_min, k_lens)
                     else:
                         mask = self._static(bs.shape[1], bs.shape[-2], bs.shape[-1])[0]
+                        if k_lens is not None:
+                            mask = mask & _valid_keys(k_lens, mask.shape[-1])
                     packed, mask_shape = ops.bitpack(mask)
                     self.mask_shape[self.layer_counter.cur_model_invocation_per_step] = mask_shape
                     self.storage.set_indices(packed)
                     if use_ragged:
                         ragged = self._ragged_indices(packed, mask_shape, multiple_of, bm, mask)
+                        ragged = (ragged[0], ragged[1], _cap_counts(ragged[2], k_lens))
                         self._remember_indices(None, ragged[2], ragged[:2])
                     else:
                         if mask.is_cuda and amd_key("attn", "fused_packed_mask_to_indices") and amd_key("attn", "sorted_indices"):
                             inds, counts = ops.mask_to_sorted_indices(mask, mask.shape, multiple_of, bm)
                         else:
                             inds, counts = ops.mask_to_indices(mask, multiple_of, bm)
+                        counts = _cap_counts(counts, k_lens)
                         self._remember_indices(inds, counts)
                 else:
                     kseq = k.shape[-2]
                     bs = bs[..., :_cdiv(kseq, bm), :kseq]
+                    if k_lens is not None:
+                        # fixed-width index rows: every sequence must have the tk keys (tk <= min(k_lens), the caller's precondition);
+                        # the padding takes the lowest value so that it is never among them
+                        bs = bs.masked_fill(~_valid_keys(k_lens, kseq), torch.finfo(bs.dtype).min)
                     inds = torch.topk(bs, k=tk, dim=-1).indices
                     counts = torch.full((q.shape[0], q.shape[1], _cdiv(q.shape[-2], bm)), tk, device=q.device,
                                         dtype=torch.int32)
@@ -292,16 +326,19 @@ class SparseDiffAttn(nn.Module):
                     self.storage.set_indices(inds)
                     self.storage.set_counts(counts)
             else:
-                o, _ = ops.dense_attn(q, k, v, tm)
+                o, _ = ops.dense_attn(q, k, v, tm, k_lens)
 
             if use_ragged:
                 if ragged is None:      # a full step that reads the stored mask (no recompute_mask)
                     ragged = self._ragged_indices(*self._stored_mask(), multiple_of, bm)
+                    ragged = (ragged[0], ragged[1], _cap_counts(ragged[2], k_lens))
             elif not (inference_step == 1 or cfg["recompute_mask"]):
                 # (a step that made the selection itself holds it in `inds`, `counts`.  The reference reads it back from the storage here,
                 # attn.py:150-160: with `attn.indices` on the host that getter shows the pipeline slot -- empty at step 1, or another
                 # layer's rows -- and not what was stored a moment ago.)
                 inds, counts = self._stored_indices(multiple_of, bm)
+                if cfg["should_compress_indices"]:
+                    counts = _cap_counts(counts, k_lens)
 
             if ragged is not None:
                 o_cache = ops.csp_attn_out_ragged(q, k, v, o, ragged[0], ragged[1], ragged[2], -1)
@@ -324,8 +361,10 @@ class SparseDiffAttn(nn.Module):
             return ops.csp_attn_out_ragged(q, k, v, o, kept[0], kept[1], kept[2], 1)    # cache + delta, index rows as kept
         if use_ragged:
             flat, offsets, counts = self._ragged_indices(*self._stored_mask(), multiple_of, bm)
-            return ops.csp_attn_out_ragged(q, k, v, o, flat, offsets, counts, 1)
+            return ops.csp_attn_out_ragged(q, k, v, o, flat, offsets, _cap_counts(counts, k_lens), 1)
         inds, counts = self._stored_indices(multiple_of, bm)
+        if cfg["should_compress_indices"]:
+            counts = _cap_counts(counts, k_lens)
         if do_padding:
             if o.is_cuda and amd_key("attn", "fused_residual"):
                 return ops.csp_attn_out(q, k, v, o, inds, counts, 1)   # cache + delta in one kernel; the cache is only read
@@ -341,11 +380,23 @@ class SparseDiffAttn(nn.Module):
         ops.csp_attn_inplace(q, k, v, o, inds, counts, 1)
         return o
 
-    def forward(self, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
+    def forward(self, q: Tensor, k: Tensor, v: Tensor, k_lens: Optional[Tensor] = None) -> Tensor:
+        """``k_lens`` (optional, int32 ``[B]`` on the GPU): the key count of every sequence of a padded batch -- keys at or past
+        ``k_lens[b]`` do not exist for sequence ``b`` in any dense pass, in the column sums or in the stored mask.  Pass it on EVERY
+        call of a padded batch, the sparse steps included: index rows are rounded up to ``counts_multiple_of`` with columns the group
+        did not keep, and a step that unpacks the stored mask itself can only keep padding keys out of that rounding when it knows the
+        lengths (the rows kept from the mask step are capped already).  With it on every call no K / V row at or past ``k_lens[b]``
+        is read and the padding may hold anything -- except on launches that take the 64-row kernels, where the first 64 rows of K and
+        V must be finite (``include/chipmunk_hip.h``).  All query rows are computed (rows that are padding themselves attend to the
+        valid keys).  ``top_keys`` stays a share of the padded key count; on the ``torch.topk`` route (``should_compress_indices`` off)
+        it must not exceed ``min(k_lens)``.  ``None``: the layer as it was."""
+        ops.attn.check_k_lens(k_lens, q, "SparseDiffAttn")
         if not GLOBAL_CONFIG["attn"]["is_enabled"]:
+            if k_lens is not None:
+                return F.scaled_dot_product_attention(q, k, v, attn_mask=_valid_keys(k_lens, k.shape[-2]))
             return F.scaled_dot_product_attention(q, k, v)
         do_full_step = self.layer_counter.should_do_full_attn_step()
-        out = self._fast_attention(q, k, v, self.layer_counter.cur_inference_step, do_full_step)
+        out = self._fast_attention(q, k, v, self.layer_counter.cur_inference_step, do_full_step, k_lens)
         self.layer_counter.increment()
         return out
 

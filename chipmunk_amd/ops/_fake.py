@@ -115,6 +115,37 @@ def _register():
         return [_o_like(q, token_major_o), q.new_empty((B, H, G, k.shape[2]), dtype=torch.bool),
                 q.new_empty((B, H, Nq, 1), dtype=torch.float32)]
 
+    # padded batches (k_lens): the shapes and dtypes of the operators without it
+    def _dense_out(q):
+        return q.new_empty((q.shape[0], q.shape[1], q.shape[2], 1), dtype=torch.float32)
+
+    @lib.register_fake("chipmunk::dense_attn_varlen")
+    def _(q, k, v, k_lens, token_major_o=False):
+        return [_o_like(q, token_major_o), _dense_out(q)]
+
+    @lib.register_fake("chipmunk::dense_colsum_attn_varlen")
+    def _(q, k, v, p, k_lens, token_major_o=False):
+        groups = (q.shape[2] + 191) // 192
+        return [_o_like(q, token_major_o), q.new_empty((q.shape[0], q.shape[1], groups, max(q.shape[2], k.shape[2]))), _dense_out(q)]
+
+    @lib.register_fake("chipmunk::topk_mask_varlen")
+    def _(cs, k_lens, k, random_amount, groups, static_mask):
+        return cs.new_empty(cs.shape, dtype=torch.bool)
+
+    @lib.register_fake("chipmunk::topk_mask_p_varlen")
+    def _(cs, k_lens, k, top_p, k_min, random_amount, groups, static_mask):
+        return cs.new_empty(cs.shape, dtype=torch.bool)
+
+    @lib.register_fake("chipmunk::dense_colsum_topk_mask_varlen")
+    def _(q, k, v, p, k_lens, k_top, random_amount, groups, static_mask, token_major_o=False):
+        G = (q.shape[2] + 191) // 192
+        return [_o_like(q, token_major_o), q.new_empty((q.shape[0], q.shape[1], G, k.shape[2]), dtype=torch.bool), _dense_out(q)]
+
+    @lib.register_fake("chipmunk::dense_colsum_topk_mask_p_varlen")
+    def _(q, k, v, p, k_lens, k_top, top_p, k_min, random_amount, groups, static_mask, token_major_o=False):
+        G = (q.shape[2] + 191) // 192
+        return [_o_like(q, token_major_o), q.new_empty((q.shape[0], q.shape[1], G, k.shape[2]), dtype=torch.bool), _dense_out(q)]
+
     @lib.register_fake("chipmunk::topk_indices_p")
     def _(activation, indices, counts, sparsity_amount, top_p, min_keys, multiple_of, random_amount):
         # writes indices and counts in place and returns nothing: the shapes are checked, so that a trace fails where the operator would

@@ -152,12 +152,18 @@ def mask_to_ragged_indices(mask: torch.Tensor, shape: Sequence[int], multiple_of
 
 
 def topk_mask(cs: torch.Tensor, k: int, random_amount: float = 0.0, groups: Optional[torch.Tensor] = None,
-              static_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+              static_mask: Optional[torch.Tensor] = None, k_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``((top-k of cs | random) & groups) | static_mask`` as one kernel: the reference's ``random_and_topk``
     (``modules/attn.py:76-82``: randint + topk + scatter_ + two mask combines).  Exactly ``k`` columns per active row
     come from the top-k part (ties at the k-th value broken deterministically); the random part is a counter-based
     hash, so only ``random_amount = 0`` is comparable bit for bit with the torch chain.  Rows of up to
-    ``TOPK_MASK_MAX_N`` columns; ties at the k-th value go to the columns lowest in ``((c % 4096) // 4, c)`` order."""
+    ``TOPK_MASK_MAX_N`` columns; ties at the k-th value go to the columns lowest in ``((c % 4096) // 4, c)`` order.
+    ``k_lens`` (an addition, int32 ``[B]`` on the GPU; padded batches): the rows of ``cs[b]`` select among their first
+    ``k_lens[b]`` columns only -- ``k`` is capped there -- and are False past them whatever ``random_amount``, ``groups`` and
+    ``static_mask`` say: ``mask[b, ..., :L]`` is the mask of ``cs[b, ..., :L]``."""
+    from .attn import check_k_lens
+    if check_k_lens(k_lens, cs, "topk_mask") is not None:
+        return torch.ops.chipmunk.topk_mask_varlen(cs, k_lens, k, random_amount, groups, static_mask)
     return torch.ops.chipmunk.topk_mask(cs, k, random_amount, groups, static_mask)
 
 
@@ -198,15 +204,20 @@ def _topk_mask_p_cpu(cs: torch.Tensor, k: int, top_p: float, k_min: int, random_
 
 
 def topk_mask_p(cs: torch.Tensor, k: int, top_p: float, k_min: int = 0, random_amount: float = 0.0,
-                groups: Optional[torch.Tensor] = None, static_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                groups: Optional[torch.Tensor] = None, static_mask: Optional[torch.Tensor] = None,
+                k_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``topk_mask`` with a count per row (not in the reference): an active row keeps the smallest top set of its columns that
     carries a share ``top_p`` of the row's column-sum mass -- at least ``k_min``, never more than ``k`` columns.  Order: value
     descending, ties by ``((c % 4096) // 4, c)``; mass of a column: its value where positive (negative and NaN entries carry none);
     ``s = min(k, max(k_p, k_min))`` with ``k_p`` the smallest prefix whose mass reaches ``top_p`` times the row's, 0 for an all-zero
     row.  The random, group and static parts are those of ``topk_mask``.  The kernel sums in fp32 in a fixed order (same launch,
-    same bits); CPU tensors take a sort with fp64 sums."""
+    same bits); CPU tensors take a sort with fp64 sums.  ``k_lens`` as in ``topk_mask`` (the mass is that of the valid columns)."""
+    from .attn import check_k_lens
+    check_k_lens(k_lens, cs, "topk_mask_p")
     if not cs.is_cuda:
         return _topk_mask_p_cpu(cs, k, top_p, k_min, random_amount, groups, static_mask)
+    if k_lens is not None:
+        return torch.ops.chipmunk.topk_mask_p_varlen(cs, k_lens, k, top_p, k_min, random_amount, groups, static_mask)
     return torch.ops.chipmunk.topk_mask_p(cs, k, top_p, k_min, random_amount, groups, static_mask)
 
 

@@ -397,6 +397,45 @@ int chipmunk_dense_colsum_topk_mask_p_strided(const void *q, const void *k, cons
                                               const void *group_flags, void *mask, int k_top, double random_amount,
                                               double top_p, int k_min, void *stream);
 
+/* ---- Padded batches: per-sequence key lengths (not in the reference).
+ * k_lens: int32 [B] in DEVICE memory (a captured graph replays with whatever it holds then; no call reads it on the host),
+ * 1 <= k_lens[b] <= Nk, clamped into that range by the kernels.  For sequence b the keys j >= k_lens[b] do not exist: o, l,
+ * the column sums and the mask are those of the same call on K / V cropped to k_lens[b] rows; cs[b, :, :, j] and mask[b, :, :, j]
+ * are 0 for j >= k_lens[b].  All Nq query rows are computed.  k_lens == NULL is the entry point without the suffix, bit for bit.
+ * No K / V row at or past k_lens[b] is read -- the padding may hold anything, NaN included -- with one exception: launches that
+ * take the 64-row kernels (Nk >= 1024 on a full machine; options attn_dense64 / attn_colsum64) read rows 0..63 of a sequence
+ * with k_lens[b] < 64, so the FIRST 64 ROWS of K and V must be finite.  Routing is decided on Nk, never on the lengths.
+ * Otherwise each entry is its namesake: chipmunk_dense_attn_strided, chipmunk_dense_colsum_attn_strided,
+ * chipmunk_dense_colsum_topk_mask_strided, chipmunk_dense_colsum_topk_mask_p_strided (o_strides NULL = plain layout,
+ * CHIPMUNK_ERR_UNSUPPORTED as there), chipmunk_topk_mask, chipmunk_topk_mask_p.
+ * The mask entries: rows [b * seq_rows, (b + 1) * seq_rows) of cs / mask belong to sequence b (seq_rows = H * groups, rows a
+ * multiple of it); a row selects among its first k_lens[b] columns only -- they alone enter the counts, the top-p mass and the tie
+ * order, k is capped at k_lens[b] -- and its bytes past them are 0 whatever the random part, the static mask and the group flag say. */
+int chipmunk_dense_attn_varlen(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                               const int64_t k_strides[3], const int64_t v_strides[3], void *o, const int64_t *o_strides,
+                               float *l, const int32_t *k_lens, int B, int H, int Nq, int Nk, void *stream);
+int chipmunk_dense_colsum_attn_varlen(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                      const int64_t k_strides[3], const int64_t v_strides[3], const float *p, void *o,
+                                      const int64_t *o_strides, void *cs, float *l, const int32_t *k_lens, int B, int H,
+                                      int Nq, int Nk, int cs_stride, void *stream);
+int chipmunk_dense_colsum_topk_mask_varlen(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                           const int64_t k_strides[3], const int64_t v_strides[3], const float *p, void *o,
+                                           const int64_t *o_strides, float *l, const int32_t *k_lens, int B, int H, int Nq,
+                                           int Nk, const void *static_mask, int64_t static_stride, int static_rows,
+                                           const void *group_flags, void *mask, int k_top, double random_amount, void *stream);
+int chipmunk_dense_colsum_topk_mask_p_varlen(const void *q, const void *k, const void *v, const int64_t q_strides[3],
+                                             const int64_t k_strides[3], const int64_t v_strides[3], const float *p, void *o,
+                                             const int64_t *o_strides, float *l, const int32_t *k_lens, int B, int H, int Nq,
+                                             int Nk, const void *static_mask, int64_t static_stride, int static_rows,
+                                             const void *group_flags, void *mask, int k_top, double random_amount,
+                                             double top_p, int k_min, void *stream);
+int chipmunk_topk_mask_varlen(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
+                              int static_rows, const void *group_flags, void *mask, const int32_t *k_lens, int seq_rows,
+                              int rows, int n, int k, double random_amount, void *stream);
+int chipmunk_topk_mask_p_varlen(const void *cs, int64_t cs_stride, const void *static_mask, int64_t static_stride,
+                                int static_rows, const void *group_flags, void *mask, const int32_t *k_lens, int seq_rows,
+                                int rows, int n, int k, double random_amount, double top_p, int k_min, void *stream);
+
 /* Replaces chipmunk::mask_to_indices (reference csrc/indexed_io/mask_to_indices.cu:92-143; schema chipmunk.cpp:60).
  * mask [rows, n] bool bytes; indices [rows, pad_n] int32; counts [rows] int32.  Bit-exact order: True columns of
  * residue class t (mod 32) ascending for t = 0..31, then the first False columns ascending up to multiple_of. */
