@@ -224,8 +224,14 @@ struct Mm1GluF8Params : Mm1Params {
 // and the epilogue of the gated form; each branch's sum is scaled by scale_x and its own weight scale, then biased, in the fp8 form's order.
 // Ungated forms with ACT != 0 or NULLB (mm1_act_kernel): c = bf16(act(x W + b) - cache) with act one of CHIPMUNK_ACT_*, and a null bias vector
 // read as zero -- bf16 seeds its accumulators with 0, fp8 adds 0 behind the scales.  ACT = 0 without NULLB is the code mm1_kernel always had.
-template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params, bool NULLB = false>
+// RS (ungated fp8 only; chipmunk_csp_mlp_mm1_fp8_act_rs): scale_a is a vector over the token rows ([M]), scale_b one over the fc1 columns ([F]).
+// The column's scale is a per-lane scalar like its bias -- gathered through the indices in the prologue --, the row scales of a lane's runs of
+// four rows are fetched behind the k loop, under the wait for the cache block: the loop carries nothing new.  Rows at or past M read a live
+// row's scale (as their A rows do) and are never stored.  (acc * scale_a[m]) * scale_b[i] + bias[i]: the scalar form's order and its bits.
+template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params, bool NULLB = false,
+          bool RS = false>
 __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
+    static_assert(!RS || (FP8 && !GLU && NULLB), "row / column scale vectors: the ungated fp8 form with a nullable bias (mm1_rs_kernel) only");
     using KT = KTile<BK>;
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
     constexpr int A_TILE = TM * BK * 2, B_TILE = TN * BK * 2, STAGE = A_TILE + B_TILE;
@@ -317,8 +323,9 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     constexpr bool SEED_BIAS = !FP8;
     float bias_v[NT4], sa = 1.f, sb = 1.f;   // loaded here for both forms: in front of the epilogue the round trips would be exposed
     float sb_up = 1.f;                       // (gated fp8 form: sb is the gate weight's scale, sb_up the up weight's)
+    float sb_col[RS ? NT4 : 1];              // (RS: the weight scale of the lane's column of every 32-wide tile)
     if constexpr (FP8 && GLU) sa = p.scale_x[0], sb = p.scale_gate[0], sb_up = p.scale_up[0];
-    else if constexpr (FP8) sa = p.scale_a[0], sb = p.scale_b[0];
+    else if constexpr (FP8 && !RS) sa = p.scale_a[0], sb = p.scale_b[0];
     f32x16 acc[MT][NT4];
 #pragma unroll
     for (int n4 = 0; n4 < NT4; ++n4) {
@@ -328,6 +335,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
             bias_v[n4] = bp ? bf16_bits_to_f32(bp[idxg[j < cnt ? j : n0]]) : 0.f;
         } else if constexpr (NULLB) {
             bias_v[n4] = p.bias ? bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]) : 0.f;
+            if constexpr (RS) sb_col[n4] = p.scale_b[idxg[j < cnt ? j : n0]];
         } else {
             bias_v[n4] = bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]);
         }
@@ -434,6 +442,26 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         // output row r of the stage image (FLAT: the rows that do not fit stage 0 continue behind the cache block)
         auto ot_row = [&](int r) { return Ot + r * (PW * 2) + ((FLAT && r >= STAGE / (TN * 2)) ? EPI : 0); };
         constexpr int LPO = PW * 2 / 16;  // 16-byte chunks per output row
+        // RS: the reciprocal scales of the lane's rows, runs of four (ml .. ml + 3 per (mt, q4)), requested here so that they land under the
+        // wait for the cache block.  M % 4 == 0 and a 16-byte aligned vector (wave-uniform): a run is live or dead as a whole and arrives as
+        // one 16-byte read, a dead run re-reads the tile's last live one; otherwise four reads, each row clamped to the last live row.
+        f32x4 sa_row[RS ? MT : 1][RS ? 4 : 1];
+        if constexpr (RS) {
+            const float *sap = p.scale_a + (g * BM + m_off);
+            const bool vec = (p.M & 3) == 0 && ((uintptr_t)p.scale_a & 15) == 0;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const int ml = wm * (TM / 2) + mt * 32 + q4 * 8 + (lane >> 5) * 4;
+                    if (vec) {
+                        sa_row[mt][q4] = *(const f32x4 *)(sap + min(ml, rows - 4));
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) sa_row[mt][q4][e] = sap[min(ml + e, rows - 1)];
+                    }
+                }
+        }
         wait_vmcnt<0>();
         __syncthreads();  // cache block landed; every wave is done reading the last tile
         // The output stage is plain row-major: a ds_write_b16 puts 32 consecutive columns of one row (64 contiguous bytes) per half
@@ -478,9 +506,14 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                             d23 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>((a23 * sav) * sgv + bgv), (u23 * sav) * suv + buv, -c23));
                         } else if constexpr (FP8) {
                             // (acc * scale_a) * scale_b + bias in the reference's order -> gelu -> bf16, then a bf16 subtract (csp_mlp_mm1.py:121-133)
-                            const f32x2 sav = {sa, sa}, sbv = {sb, sb}, bv = {bia, bia};
+                            f32x2 sav = {sa, sa}, sav23 = {sa, sa}, sbv = {sb, sb};
+                            if constexpr (RS) {   // the rows' own scales, the gathered column's
+                                sav = (f32x2){sa_row[mt][q4][0], sa_row[mt][q4][1]}, sav23 = (f32x2){sa_row[mt][q4][2], sa_row[mt][q4][3]};
+                                sbv = (f32x2){sb_col[n4], sb_col[n4]};
+                            }
+                            const f32x2 bv = {bia, bia};
                             const uint32_t t01 = pack_bf16x2_v(glu_act2<ACT>((a01 * sav) * sbv + bv));
-                            const uint32_t t23 = pack_bf16x2_v(glu_act2<ACT>((a23 * sav) * sbv + bv));
+                            const uint32_t t23 = pack_bf16x2_v(glu_act2<ACT>((a23 * sav23) * sbv + bv));
                             d01 = pack_bf16x2_v(unpack_bf16x2(t01) - c01), d23 = pack_bf16x2_v(unpack_bf16x2(t23) - c23);
                             if constexpr (UPD == 2) n01 = t01, n23 = t23;   // 2: cache = new activation, what the reference's Triton kernel does (csp_mlp_mm1.py:140)
                         } else if constexpr (GLU) {
@@ -690,6 +723,48 @@ __global__ __launch_bounds__(256, WPS) void mm1_act_kernel(const typename std::c
             if (n0 >= cnt) continue;
             if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
             mm1_tile<64, 64, BK, SUB_NST, FP8, 4, false, ACT, Mm1Params, true>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
+        }
+        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
+    }
+}
+
+// The ungated fp8 GEMM1 with scale VECTORS (mm1_tile's RS form: scale_a [M] per token row, [B, M] for a batch; scale_b [F] per fc1 column):
+// mm1_act_kernel's fp8 walk line for line with RS set and the sequence's row scales behind the batch pointer advance -- a kernel of its own,
+// so that mm1_act_kernel's instantiations keep their names and their code.
+template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED = false>
+__global__ __launch_bounds__(256, WPS) void mm1_rs_kernel(const typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int NSUB = 2 * (BN / 64);  // 64 x 64 sub-tiles per tile
+    constexpr int SUB_NST = (NST * (BM + BN)) / 128 > 4 ? 4 : (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
+    const TilePlan pl = plan_tiles<BN>(p.counts, G, p.NT, p.NR, p.slots_per_xcd, NSUB);
+    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+        const TileMap tm = tile_at(pl, slot);
+        if (!tm.live) continue;
+        const int cnt = p.counts[tm.g];
+        int g = tm.g;
+        Mm1Params q = p;                              // the tile sees its sequence's operands
+        if constexpr (BATCHED) {
+            const int b = tm.g / Gs;
+            g = tm.g - b * Gs;                        // group inside sequence b
+            q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)b * p.M * p.K);
+            q.c = p.c + (int64_t)b * p.M * p.F;
+            q.cache = p.cache + (int64_t)b * p.cache_bs;
+            q.indices = p.indices + (int64_t)b * Gs * p.F;
+            q.scale_a = p.scale_a + (int64_t)b * p.M;   // [B, M]: the sequence's row scales
+        }
+        if (tm.sub < 0) {
+            const int n0 = tm.nt * BN;
+            if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
+            mm1_tile<BM, BN, BK, NST, true, 4, false, ACT, Mm1Params, true, true>(q, smem, g, 0, n0, cnt);
+        } else {
+            const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
+            if (n0 >= cnt) continue;
+            if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
+            mm1_tile<64, 64, BK, SUB_NST, true, 4, false, ACT, Mm1Params, true, true>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
         }
         __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
     }
@@ -1613,7 +1688,7 @@ template <> struct Mm1BatchOf<Mm1GluF8Params> { using type = Mm1GluF8Batch; };
 
 // ACTK: the ungated form through mm1_act_kernel (activation ACT, nullable bias) instead of mm1_kernel
 template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false, bool GLU = false, int ACT = 0, class P = Mm1Params,
-          bool ACTK = false>
+          bool ACTK = false, bool RS = false>
 int launch_mm1_variant(const P &p0, hipStream_t s, bool *cache_updated = nullptr, int B = 1, int64_t cache_bs = 0) {
     constexpr int PBN = GLU ? BN / 2 : BN;   // packed columns per whole tile (gated form: the B tile's rows are {gate, up} pairs)
     constexpr int STAGE = BM * BK * 2 + BN * BK * 2, LDS = NST * STAGE, EPI = BM * PBN * 2;
@@ -1622,11 +1697,13 @@ int launch_mm1_variant(const P &p0, hipStream_t s, bool *cache_updated = nullptr
     auto kern = [] {
         if constexpr (GLU && FP8) return mm1_glu_fp8_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
         else if constexpr (GLU) return mm1_glu_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+        else if constexpr (ACTK && RS) return mm1_rs_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
         else if constexpr (ACTK) return mm1_act_kernel<BN, BK, NST, WPS, FP8, ACT, BATCHED>;
         else return mm1_kernel<BN, BK, NST, WPS, FP8, NW, BATCHED>;
     }();
     static_assert(!GLU || NW == 4, "the gated GEMM1 has 4 waves");
     static_assert(!ACTK || (NW == 4 && !GLU), "mm1_act_kernel is the ungated 4-wave form");
+    static_assert(!RS || (ACTK && FP8), "scale vectors (mm1_rs_kernel): the ungated fp8 form only");
     static_assert(ACTK || GLU || ACT == 0, "mm1_kernel computes tanh-GeLU only");
     static_assert(std::is_same<P, Mm1GluF8Params>::value == (GLU && FP8), "the gated fp8 form, and only it, takes Mm1GluF8Params");
     static uint64_t lds_set = 0;
@@ -1747,16 +1824,16 @@ int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void 
 // Ungated GEMM1 with an activation code and a nullable bias (mm1_act_kernel): the *_ragged / *_batched contract, the shipped tile shape only
 // (option mm1_variant is ignored; the probe-forms library does not carry these kernels)
 #ifndef CHIPMUNK_MM1_PROBES
-template <bool FP8, bool BATCHED>
+template <bool FP8, bool BATCHED, bool RS = false>   // RS: scale_a [M] / scale_b [F] vectors (fp8 only)
 int launch_mm1_act(const Mm1Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
     switch (act) {
-        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 0, Mm1Params, true>(p, stream, nullptr, B, cache_bs);
-        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 1, Mm1Params, true>(p, stream, nullptr, B, cache_bs);
-        default: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 2, Mm1Params, true>(p, stream, nullptr, B, cache_bs);
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 0, Mm1Params, true, RS>(p, stream, nullptr, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 1, Mm1Params, true, RS>(p, stream, nullptr, B, cache_bs);
+        default: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 2, Mm1Params, true, RS>(p, stream, nullptr, B, cache_bs);
     }
 }
 #else
-template <bool FP8, bool BATCHED>
+template <bool FP8, bool BATCHED, bool RS = false>
 int launch_mm1_act(const Mm1Params &, int, hipStream_t, int, int64_t) {
     CM_CHECK(false, "csp_mlp_mm1_act: not part of the probe-forms library");
     return CHIPMUNK_OK;
@@ -1765,9 +1842,10 @@ int launch_mm1_act(const Mm1Params &, int, hipStream_t, int, int64_t) {
 // scale_a / scale_b null: the bf16 form (update_cache 0 / 1); both given: the e4m3 form (update_cache 0 / 1 / 2 as chipmunk_csp_mlp_mm1_fp8)
 int mm1_act_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices, const int32_t *counts,
                   const float *scale_a, const float *scale_b, bool fp8, int M, int K, int F, int ldc, int act, int update_cache,
-                  hipStream_t stream, int B = 0, int64_t cache_bs = 0) {   // B > 0: the *_batched entries
+                  hipStream_t stream, int B = 0, int64_t cache_bs = 0, bool rs = false) {   // B > 0: the *_batched entries; rs: the *_rs entries
     if (fp8) CM_CHECK(a && b && c && pa_cache && scale_a && scale_b, "csp_mlp_mm1_fp8_act: null tensor or scale pointer");
     else CM_CHECK(a && b && c && pa_cache, "csp_mlp_mm1_act: null tensor pointer");
+    CM_CHECK(!rs || (((uintptr_t)scale_a | (uintptr_t)scale_b) & 3) == 0, "csp_mlp_mm1_fp8_act_rs: scale_a and scale_b must be 4-byte aligned");
     if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
     if (int e = check_cache_pitch(M, F, ldc)) return e;
     if (B > 0) {
@@ -1789,6 +1867,7 @@ int mm1_act_entry(const void *a, const void *b, void *c, const void *bias, void 
     const int upd = fp8 ? (update_cache == 1 ? 2 : update_cache == 2 ? 1 : 0) : update_cache;
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, upd, scale_a, scale_b, ldc};
+    if (rs) return B > 0 ? launch_mm1_act<true, true, true>(p, act, stream, B, cache_bs) : launch_mm1_act<true, false, true>(p, act, stream, 1, 0);
     if (fp8) return B > 0 ? launch_mm1_act<true, true>(p, act, stream, B, cache_bs) : launch_mm1_act<true, false>(p, act, stream, 1, 0);
     return B > 0 ? launch_mm1_act<false, true>(p, act, stream, B, cache_bs) : launch_mm1_act<false, false>(p, act, stream, 1, 0);
 }
@@ -1912,6 +1991,21 @@ extern "C" int chipmunk_csp_mlp_mm1_fp8_act_batched(const void *a, const void *b
     if (int e = check_mlp_batch(B, M)) return e;
     return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, true, M, K, F, ldc, act, update_cache, (hipStream_t)stream,
                          B, cache_batch_stride);
+}
+
+extern "C" int chipmunk_csp_mlp_mm1_fp8_act_rs(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                               const int32_t *counts, const float *scale_a, const float *scale_b, int M, int K, int F, int ldc,
+                                               int act, int update_cache, void *stream) {
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, true, M, K, F, ldc, act, update_cache, (hipStream_t)stream,
+                         0, 0, true);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_act_rs_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                                       const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                                       int M, int K, int F, int ldc, int act, int update_cache, int B,
+                                                       int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, true, M, K, F, ldc, act, update_cache, (hipStream_t)stream,
+                         B, cache_batch_stride, true);
 }
 
 extern "C" int chipmunk_csp_mlp_mm1(const void *a, const void *b, void *c, const void *bias, const void *pa_cache,

@@ -265,6 +265,96 @@ extern "C" int chipmunk_quantize_fp8(const void *x, const float *scale, void *ou
     return CHIPMUNK_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- fp8 input quantisation, one scale per row
+// F8Linear.quantize_input_rowwise: per row r of a bf16 [rows, K] tensor, all in fp32 with IEEE division,
+//     amax = max_k |x[r, k]|;  scale = min(max / max(amax, 1e-12), max);  out[r, k] = e4m3_rne(clamp(float(x[r, k]) * scale, -max, max));
+//     scale_recip[r] = 1 / scale
+// -- torch's `x.float() * scale[:, None]` chain: the product is fp32 and rounded ONCE, into e4m3 (the per-tensor kernel above mirrors
+// torch's bf16 x 0-dim product and rounds to bf16 in between; this one does not).  One wave per row and one pass over HBM: the row stays
+// packed in registers (NV 16-byte vectors per lane, K <= 512 * NV) between the |max| reduction (DPP + lane swaps, no LDS) and the
+// conversion; a wave walks rows with the grid's stride.  HBM-bound: 3 * rows * K + 4 * rows bytes.  Rows with a NaN or Inf are outside the
+// contract (amax, and with it every byte of the row, is then unspecified).
+namespace {
+__device__ __forceinline__ float row16_max(float x) {
+    x = fmaxf(x, dpp_row_ror<8>(x));
+    x = fmaxf(x, dpp_row_ror<4>(x));
+    x = fmaxf(x, dpp_row_ror<2>(x));
+    x = fmaxf(x, dpp_row_ror<1>(x));
+    return x;
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void quantize_fp8_rowwise_kernel(const uint16_t *x, uint8_t *out, float *scale_recip, int64_t rows, int K,
+                                                                   float maxv) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t r = wave; r < rows; r += nwaves) {
+        u32x4 xv[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = (lane + 64 * j) * 8;
+            const u32x4 z = {0u, 0u, 0u, 0u};
+            xv[j] = c < K ? *(const u32x4 *)(x + r * K + c) : z;   // (a vector past the row counts as zero: |0| changes no maximum)
+        }
+        float am = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                am = fmaxf(am, fmaxf(__uint_as_float((xv[j][e] << 16) & 0x7fffffffu), __uint_as_float(xv[j][e] & 0x7fff0000u)));
+        am = max_across_rows(row16_max(am));
+        const float scale = fminf(maxv / fmaxf(am, 1e-12f), maxv);   // amax_to_scale; IEEE division
+        if (lane == 0) scale_recip[r] = 1.0f / scale;
+        // the row stays packed across the reduction (see rownorm_rows: left alone the compiler keeps the unpacked floats, 8 per vector)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) asm volatile("" : "+v"(xv[j]));
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = (lane + 64 * j) * 8;
+            float f[8];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                f[2 * e] = fminf(fmaxf(__uint_as_float(xv[j][e] << 16) * scale, -maxv), maxv);
+                f[2 * e + 1] = fminf(fmaxf(__uint_as_float(xv[j][e] & 0xffff0000u) * scale, -maxv), maxv);
+            }
+            int w0 = 0, w1 = 0;
+            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
+            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
+            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
+            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
+            if (c < K) *(u32x2 *)(out + r * K + c) = (u32x2){(uint32_t)w0, (uint32_t)w1};
+        }
+    }
+}
+
+template <int NV>
+void launch_quantize_rowwise(const void *x, void *out, float *scale_recip, int64_t rows, int K, float maxv, hipStream_t s) {
+    // 4 rows per workgroup at a time; enough workgroups for 8 per CU, the rest of the rows by stride
+    const int64_t want = (rows + 3) / 4;
+    const unsigned grid = (unsigned)(want < 256 * 8 ? want : 256 * 8);
+    hipLaunchKernelGGL((quantize_fp8_rowwise_kernel<NV>), dim3(grid), dim3(256), 0, s, (const uint16_t *)x, (uint8_t *)out, scale_recip, rows, K,
+                       maxv);
+}
+}  // namespace
+
+extern "C" int chipmunk_quantize_fp8_rowwise(const void *x, void *out, float *scale_recip, int64_t rows, int K, float max_value, void *stream) {
+    CM_CHECK(x && out && scale_recip, "quantize_fp8_rowwise: null pointer");
+    CM_CHECK(rows >= 0 && K > 0 && K % 16 == 0 && K <= CHIPMUNK_QUANTIZE_ROWWISE_MAX_K,
+             "quantize_fp8_rowwise: K must be a positive multiple of 16, at most %d (got %d)", CHIPMUNK_QUANTIZE_ROWWISE_MAX_K, K);
+    CM_CHECK(max_value > 0.f, "quantize_fp8_rowwise: max_value must be positive");
+    CM_CHECK((((uintptr_t)x & 15) | ((uintptr_t)out & 7) | ((uintptr_t)scale_recip & 3)) == 0,
+             "quantize_fp8_rowwise: x must be 16-byte, out 8-byte and scale_recip 4-byte aligned");
+    if (rows == 0) return CHIPMUNK_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int nv = (K + 511) / 512;
+#define CM_QROW_CASE(NV) if (nv <= NV) { launch_quantize_rowwise<NV>(x, out, scale_recip, rows, K, max_value, s); } else
+    CM_QROW_CASE(1) CM_QROW_CASE(2) CM_QROW_CASE(3) CM_QROW_CASE(4) CM_QROW_CASE(6) CM_QROW_CASE(8) CM_QROW_CASE(12) CM_QROW_CASE(16)
+    CM_QROW_CASE(24) launch_quantize_rowwise<32>(x, out, scale_recip, rows, K, max_value, s);
+#undef CM_QROW_CASE
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- Wan attention operands
 // Wan's blocks (reference examples/wan/wan/modules/model.py:81-97, 154-164, 195-196, 236-239) normalise q and k over the WHOLE
 // projection row -- WanRMSNorm(dim), dim = heads * 128 channels, a dim-entry weight -- then rotate (rope_apply, :49-78: complex

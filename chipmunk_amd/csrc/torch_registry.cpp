@@ -545,10 +545,11 @@ void csp_mlp_mm1_fp8_scatter(at::Tensor a, at::Tensor b, at::Tensor c, at::Tenso
 
 // addition: the ungated GEMM1 with the activation by name and an optional bias, c = bf16(act(a b^T + bias) - cache); bf16 operands, or
 // (scale_a / scale_b given) e4m3 a / b in the arithmetic of csp_mlp_mm1_fp8.  2-D operands or the 3-D batch, always the ragged contract.
-// update_cache: the C entries' (bf16 0 / 1; fp8 0 / 1 / 2).
+// update_cache: the C entries' (bf16 0 / 1; fp8 0 / 1 / 2).  rs: scale_a is a vector over the token rows ([M]; [B, M] for a batch), scale_b one
+// over the fc1 columns ([F]) -- csp_mlp_mm1_fp8_act_rs.
 static void mm1_act_impl(const char *who, at::Tensor a, at::Tensor b, at::Tensor c, const c10::optional<at::Tensor> &bias,
                          at::Tensor pa_cache_colmajor, at::Tensor indices, at::Tensor indices_counts, const at::Tensor *scale_a,
-                         const at::Tensor *scale_b, const std::string &act, int update_cache) {
+                         const at::Tensor *scale_b, const std::string &act, int update_cache, bool rs = false) {
     const bool fp8 = scale_a != nullptr;
     CHECK_DEV(a); CHECK_DEV(b); CHECK_DEV(c); CHECK_DEV(pa_cache_colmajor);
     CHECK_DEV(indices); CHECK_DEV(indices_counts);
@@ -556,8 +557,17 @@ static void mm1_act_impl(const char *who, at::Tensor a, at::Tensor b, at::Tensor
         TORCH_CHECK(a.scalar_type() == at::kFloat8_e4m3fn && b.scalar_type() == at::kFloat8_e4m3fn,
                     who, ": a and b must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
         for (const at::Tensor *s : {scale_a, scale_b})
-            TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->numel() == 1,
-                        who, ": scale_a and scale_b must be one-element float32 tensors on the GPU");
+            TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && (rs || s->numel() == 1), who,
+                        rs ? ": scale_a and scale_b must be float32 tensors on the GPU" : ": scale_a and scale_b must be one-element float32 tensors on the GPU");
+        if (rs) {
+            TORCH_CHECK(scale_a->device() == a.device() && scale_b->device() == a.device(), who, ": scale_a and scale_b must be on the device of a");
+            TORCH_CHECK(scale_a->is_contiguous() && scale_b->is_contiguous(), who, ": scale_a and scale_b must be contiguous");
+            TORCH_CHECK((a.dim() == 2 && scale_a->dim() == 1 && scale_a->size(0) == a.size(0)) ||
+                            (a.dim() == 3 && scale_a->dim() == 2 && scale_a->size(0) == a.size(0) && scale_a->size(1) == a.size(1)),
+                        who, ": scale_a must be [M], one reciprocal scale per row of a ([B, M] for a batched a)");
+            TORCH_CHECK(scale_b->dim() == 1 && b.dim() == 2 && scale_b->size(0) == b.size(0), who,
+                        ": scale_b must be [F], one reciprocal scale per row of b");
+        }
     } else {
         CHECK_BF16(a); CHECK_BF16(b);
     }
@@ -581,7 +591,15 @@ static void mm1_act_impl(const char *who, at::Tensor a, at::Tensor b, at::Tensor
     c10::DeviceGuard guard(a.device());
     int *ip = indices.data_ptr<int>(), *cp = indices_counts.data_ptr<int>();
     const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc;
-    if (fp8 && sh.batched())
+    if (rs && sh.batched())
+        check(chipmunk_csp_mlp_mm1_fp8_act_rs_batched(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp,
+                                                      scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), M, K, F, ldc, code,
+                                                      update_cache, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (rs)
+        check(chipmunk_csp_mlp_mm1_fp8_act_rs(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp,
+                                              scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), M, K, F, ldc, code, update_cache,
+                                              cur_stream(a)), who);
+    else if (fp8 && sh.batched())
         check(chipmunk_csp_mlp_mm1_fp8_act_batched(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp,
                                                    scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), M, K, F, ldc, code,
                                                    update_cache, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
@@ -605,6 +623,14 @@ void csp_mlp_mm1_fp8_act(at::Tensor a, at::Tensor b, at::Tensor c, const c10::op
                          int64_t update_cache) {
     TORCH_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8_act: update_cache must be 0, 1 or 2 (got ", update_cache, ")");
     mm1_act_impl("csp_mlp_mm1_fp8_act", a, b, c, bias, pa_cache, indices, counts, &scale_a, &scale_b, act, (int)update_cache);
+}
+// addition: csp_mlp_mm1_fp8_act with one reciprocal scale per token row (scale_a [M] / [B, M]) and one per fc1 column (scale_b [F], read at
+// the gathered column): t = bf16(act((a b^T * scale_a[m]) * scale_b[i] + bias[i])), c = bf16(t - cache)
+void csp_mlp_mm1_fp8_act_rs(at::Tensor a, at::Tensor b, at::Tensor c, const c10::optional<at::Tensor> &bias, at::Tensor pa_cache,
+                            at::Tensor indices, at::Tensor counts, at::Tensor scale_a, at::Tensor scale_b, std::string act,
+                            int64_t update_cache) {
+    TORCH_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8_act_rs: update_cache must be 0, 1 or 2 (got ", update_cache, ")");
+    mm1_act_impl("csp_mlp_mm1_fp8_act_rs", a, b, c, bias, pa_cache, indices, counts, &scale_a, &scale_b, act, (int)update_cache, true);
 }
 
 int64_t check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, const at::Tensor &inds,
@@ -970,6 +996,22 @@ at::Tensor quantize_fp8(at::Tensor x, at::Tensor scale, double max_value) {
     at::Tensor out = at::empty(x.sizes(), x.options().dtype(at::kFloat8_e4m3fn));
     check(chipmunk_quantize_fp8(x.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), x.numel(), (float)max_value, cur_stream(x)), "quantize_fp8");
     return out;
+}
+
+// F8Linear.quantize_input_rowwise as one kernel: x [..., K] bf16 -> (e4m3 [..., K], float32 [...] reciprocal scales), one scale per row
+std::vector<at::Tensor> quantize_fp8_rowwise(at::Tensor x, double max_value) {
+    CHECK_DEV(x);
+    TORCH_CHECK(x.scalar_type() == at::kBFloat16, "quantize_fp8_rowwise: x must be bfloat16");
+    TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0 && x.size(-1) % 16 == 0 && x.size(-1) <= CHIPMUNK_QUANTIZE_ROWWISE_MAX_K,
+                "quantize_fp8_rowwise: the last dimension must be a positive multiple of 16, at most ", CHIPMUNK_QUANTIZE_ROWWISE_MAX_K);
+    x = x.contiguous();
+    c10::DeviceGuard guard(x.device());
+    const int64_t K = x.size(-1), rows = x.numel() / K;
+    at::Tensor out = at::empty(x.sizes(), x.options().dtype(at::kFloat8_e4m3fn));
+    at::Tensor recip = at::empty(x.sizes().slice(0, x.dim() - 1), x.options().dtype(at::kFloat));
+    check(chipmunk_quantize_fp8_rowwise(x.data_ptr(), out.data_ptr(), recip.data_ptr<float>(), rows, (int)K, (float)max_value, cur_stream(x)),
+          "quantize_fp8_rowwise");
+    return {out, recip};
 }
 
 // ascending-order variant of (packed_)mask_to_indices (same set / counts / padding; see chipmunk_hip.h)
@@ -1358,6 +1400,8 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("transpose_last2_pitched(Tensor x, int ld) -> Tensor");
     m.def("block_mean(Tensor x, int mbm) -> Tensor");
     m.def("quantize_fp8(Tensor x, Tensor scale, float max_value) -> Tensor");
+    m.def("quantize_fp8_rowwise(Tensor x, float max_value) -> Tensor[]");
+    m.def("csp_mlp_mm1_fp8_act_rs(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, Tensor scale_a, Tensor scale_b, str act, int update_cache) -> ()");
     m.def("bitpack(Tensor mask) -> Tensor");
     m.def("bitunpack(Tensor packed, int[] shape) -> Tensor");
     m.def("gather_rows(Tensor src, Tensor map) -> Tensor");
@@ -1413,6 +1457,8 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("transpose_last2_pitched", &transpose_last2_pitched);
     m.impl("block_mean", &block_mean);
     m.impl("quantize_fp8", &quantize_fp8);
+    m.impl("quantize_fp8_rowwise", &quantize_fp8_rowwise);
+    m.impl("csp_mlp_mm1_fp8_act_rs", &csp_mlp_mm1_fp8_act_rs);
     m.impl("bitpack", &bitpack);
     m.impl("bitunpack", &bitunpack);
     m.impl("gather_rows", &gather_rows);

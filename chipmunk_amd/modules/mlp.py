@@ -6,6 +6,10 @@ most since they were last computed (``topk_indices`` on |delta|), recompute only
 scatter the activation deltas into the cache and add ``delta @ fc2^T`` onto the cached output
 (``csp_mlp_mm2_and_scatter_add``).  The fc2 bias is already inside the cached output.
 
+An e4m3 ``fc1`` built with row scaling (``F8Linear(scaling="row")``, config key ``mlp.fp8_scaling``) quantises the sparse steps' input with
+one dynamic scale per token (``fc1.quantize_input_rowwise``) and hands GEMM1 the ``[N]`` row scales with the ``[F]`` weight scales
+(``csp_mlp_mm1_fp8_act_rs``); everything else on the route is unchanged.
+
 ``fc2`` is bf16, or -- with ``mlp.fp8_fc2`` on -- an ``F8Linear`` with e4m3 weights: dense and full steps call its forward as it is
 (``torch._scaled_mm``), the sparse steps gather e4m3 rows of ``fc2.weight^T`` (``csp_mlp_mm2_w8``) with ``fc2.scale_reciprocal``.
 """
@@ -72,6 +76,10 @@ def check_fc2(who: str, fc2: torch.nn.Module) -> None:
     if fc2.weight.dtype != torch.float8_e4m3fn or getattr(fc2, "scale_reciprocal", None) is None:
         raise ValueError(f"{who}: with mlp.fp8_fc2 the fp8 fc2 must be an F8Linear with float8_e4m3fn weights and their scale_reciprocal "
                          f"(got weight {fc2.weight.dtype}); e5m2 weights are refused")
+    if getattr(fc2, "scaling", "tensor") != "tensor" or fc2.scale_reciprocal.numel() != 1:
+        raise ValueError(f"{who}: a row-scaled fc2 (F8Linear scaling='row': one scale per output feature) is refused: GEMM2's weight-only "
+                         "gather takes one scale per tensor; build fc2 with scaling='tensor' (recursive_swap_linears does, whatever "
+                         "mlp.fp8_scaling says)")
 
 
 def fc2_scale_of(fc2: torch.nn.Module):
@@ -220,7 +228,11 @@ class SparseDiffMlp:
         sparse_act_T = sparse_act_T[..., : x.shape[1]] if batched else sparse_act_T[0][:, : x.shape[1]]   # the [F, N] view of the pitched cache
 
         scale_a = scale_b = None
-        if fc1.weight.dtype == torch.float8_e4m3fn:
+        if fc1.weight.dtype == torch.float8_e4m3fn and getattr(fc1, "scaling", "tensor") == "row":
+            x, scale_a = fc1.quantize_input_rowwise(x)          # one reciprocal scale per token: [B, N]
+            scale_a = scale_a if batched else scale_a[0]
+            scale_b = fc1.scale_reciprocal.view(-1)             # one per fc1 column: [F]
+        elif fc1.weight.dtype == torch.float8_e4m3fn:
             x = fc1.quantize_input(x)
             scale_a, scale_b = fc1.input_scale_reciprocal, fc1.scale_reciprocal
 

@@ -6,6 +6,10 @@ clamped to the fp8 range and cast; the matmul result is multiplied by the RECIPR
 (``input_scale_reciprocal``, ``scale_reciprocal``) -- the two numbers ``SparseDiffMlp`` hands to ``csp_mlp_mm1_fp8``.
 The input scale is calibrated over the first ``num_scale_trials`` calls and then frozen.
 gfx950 implements the OCP formats (``float8_e4m3fn`` / ``float8_e5m2``), the same dtypes the reference uses on H100.
+
+Row scaling (``scaling="row"``, config key ``mlp.fp8_scaling``; not in the reference): one scale per output feature of the weight
+(``scale`` / ``scale_reciprocal`` are ``[out, 1]``) and one DYNAMIC scale per token row of the input, computed on every call
+(``quantize_input_rowwise``: no calibration trials, nothing frozen).  The product is ``bf16((sum_k xq wq) * sa[m] * sb[n] + bias[n])``.
 """
 from __future__ import annotations
 
@@ -27,12 +31,49 @@ def to_fp8_saturated(x: torch.Tensor, scale: torch.Tensor, max_val: float) -> to
     return (x * scale).clamp(-max_val, max_val)
 
 
+SCALINGS = ("tensor", "row")
+ROWWISE_MAX_K = 16384      # include/chipmunk_hip.h, CHIPMUNK_QUANTIZE_ROWWISE_MAX_K
+
+
+def quantize_rowwise_torch(x: torch.Tensor, max_val: float, float8_dtype=torch.float8_e4m3fn):
+    """The row-wise chain in torch, over the last dimension, all in fp32: ``amax = max_k |x|``, ``scale = amax_to_scale(amax)`` per row,
+    ``xq = fp8((x.float() * scale).clamp(-max, max))`` -- the product is fp32 and rounded once, into fp8.  Returns ``(xq, 1 / scale)``,
+    the reciprocal scales fp32 of shape ``x.shape[:-1]``.  What ``chipmunk_quantize_fp8_rowwise`` computes, bit for bit where the
+    division is IEEE's -- so the quotient is tensor / tensor here: ``amax_to_scale``'s ``number / tensor`` is torch's reciprocal-then-multiply,
+    two roundings, one ulp off the correctly rounded quotient for some rows."""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    scale = (torch.full_like(amax, max_val) / torch.clamp(amax, min=1e-12)).clamp(max=max_val)
+    xq = (xf * scale.unsqueeze(-1)).clamp(-max_val, max_val).to(float8_dtype)
+    return xq, scale.reciprocal()
+
+
+_SCALED_MM_ROWWISE = {}     # device -> does torch._scaled_mm take [M, 1] / [1, N] scales there (probed once, on a tiny call)
+
+
+def scaled_mm_takes_row_scales(device: torch.device) -> bool:
+    key = str(device)
+    if key not in _SCALED_MM_ROWWISE:
+        try:
+            a = torch.ones(16, 32, device=device).to(torch.float8_e4m3fn)
+            b = torch.ones(16, 32, device=device).to(torch.float8_e4m3fn)
+            out = torch._scaled_mm(a, b.T, scale_a=torch.full((16, 1), 0.5, device=device), scale_b=torch.full((1, 16), 2.0, device=device),
+                                   out_dtype=torch.bfloat16)
+            _SCALED_MM_ROWWISE[key] = bool((out.float() == 32.0).all())
+        except (RuntimeError, NotImplementedError, ValueError):      # refused by this build: an answer, the fallback below computes the same formula
+            _SCALED_MM_ROWWISE[key] = False
+    return _SCALED_MM_ROWWISE[key]
+
+
 class F8Linear(nn.Module):
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=torch.float16,
                  float8_dtype=torch.float8_e4m3fn, float_weight: Optional[torch.Tensor] = None,
                  float_bias: Optional[torch.Tensor] = None, num_scale_trials: int = 12,
-                 input_float8_dtype=torch.float8_e4m3fn) -> None:
+                 input_float8_dtype=torch.float8_e4m3fn, scaling: str = "tensor") -> None:
         super().__init__()
+        if scaling not in SCALINGS:
+            raise ValueError(f"F8Linear: unknown scaling {scaling!r} (one of {', '.join(SCALINGS)})")
+        self.scaling = scaling
         self.in_features, self.out_features = in_features, out_features
         self.float8_dtype, self.input_float8_dtype = float8_dtype, input_float8_dtype
         self.max_value = torch.finfo(float8_dtype).max
@@ -79,8 +120,18 @@ class F8Linear(nn.Module):
             raise RuntimeError(f"Weight tensor not found or has incorrect shape in state dict: {sd.keys()}")
         self._parameters["weight"] = nn.Parameter(fp8.to(self.float8_dtype), requires_grad=False)
         self.weight_initialized = True
-        self.scale = sd["scale"].float()
-        self.scale_reciprocal = sd["scale_reciprocal"].float() if "scale_reciprocal" in sd else self.scale.reciprocal()
+        # the checkpoint's granularity decides the mode: one scale per output feature = row scaling, one number = per tensor
+        n_scales = sd["scale"].numel()
+        if n_scales not in (1, self.out_features) or ("scale_reciprocal" in sd and sd["scale_reciprocal"].numel() != n_scales):
+            raise RuntimeError(f"F8Linear: a quantised checkpoint carries one scale, or one per output feature ({self.out_features}); "
+                               f"got {n_scales}")
+        if self.out_features > 1:           # (a one-feature layer keeps the mode it was built with: both forms have one scale)
+            self.scaling = "row" if n_scales == self.out_features else "tensor"
+        shape_of = (lambda t: t.float().reshape(-1, 1)) if self.scaling == "row" else (lambda t: t.float())
+        self.scale = shape_of(sd["scale"])
+        self.scale_reciprocal = shape_of(sd["scale_reciprocal"]) if "scale_reciprocal" in sd else self.scale.reciprocal()
+        if self.scaling == "row":           # dynamic input scales: nothing to load, nothing to calibrate
+            return
         if "input_scale" in sd and "input_scale_reciprocal" in sd:
             self.input_scale = sd["input_scale"].float()
             self.input_scale_reciprocal = sd["input_scale_reciprocal"].float()
@@ -102,6 +153,14 @@ class F8Linear(nn.Module):
     def quantize_weight(self) -> None:
         if self.weight_initialized:
             return
+        if self.scaling == "row":           # one scale per output feature: amax over the input dimension, everything in fp32
+            w = self.weight.data.float()
+            self.scale = amax_to_scale(w.abs().amax(dim=1, keepdim=True), self.max_value)          # [out, 1]
+            self.scale_reciprocal = self.scale.reciprocal()
+            fp8 = (w * self.scale).clamp(-self.max_value, self.max_value).to(self.float8_dtype)
+            self.weight = nn.Parameter(fp8, requires_grad=False)
+            self.weight_initialized = True
+            return
         amax = self.weight.data.abs().max().float()
         self.scale = amax_to_scale(amax, self.max_value)
         self.scale_reciprocal = self.scale.reciprocal()
@@ -114,7 +173,23 @@ class F8Linear(nn.Module):
         self.weight_initialized = False
         self.quantize_weight()
 
+    def quantize_input_rowwise(self, x: torch.Tensor):
+        """Row scaling: ``x [..., K] -> (xq [..., K] fp8, scale_recip [...] fp32)``, one dynamic scale per row of the last dimension
+        (``quantize_rowwise_torch``'s chain).  A bf16 GPU tensor with e4m3 inputs and ``K % 16 == 0``, ``K <= ROWWISE_MAX_K`` takes the
+        one-pass kernel; everything else the torch chain."""
+        if self.scaling != "row":
+            raise RuntimeError("F8Linear.quantize_input_rowwise: this layer scales per tensor (scaling='tensor'): call quantize_input")
+        K = x.shape[-1]
+        if (x.is_cuda and x.dtype == torch.bfloat16 and self.input_float8_dtype == torch.float8_e4m3fn and K % 16 == 0
+                and 0 < K <= ROWWISE_MAX_K and x.numel() > 0):
+            xq, recip = torch.ops.chipmunk.quantize_fp8_rowwise(x, float(self.input_max_value))
+            return xq, recip
+        return quantize_rowwise_torch(x, self.input_max_value, self.input_float8_dtype)
+
     def quantize_input(self, x: torch.Tensor) -> torch.Tensor:
+        if self.scaling == "row":
+            raise RuntimeError("F8Linear.quantize_input: this layer scales per row (scaling='row'), there is no frozen input scale: call "
+                               "quantize_input_rowwise, which returns (xq, scale_recip)")
         if not self.input_scale_initialized:
             if self.trial_index < self.num_scale_trials:
                 self.input_amax_trials[self.trial_index] = x.abs().max().float()
@@ -149,7 +224,25 @@ class F8Linear(nn.Module):
             init.uniform_(self.bias, -bound, bound)
         self.quantize_weight()
 
+    def _forward_rowwise(self, x: torch.Tensor) -> torch.Tensor:
+        """``bf16((sum_k xq wq) * sa[m] * sb[n] + bias[n])``, fp32 sums: ``torch._scaled_mm`` with ``[M, 1]`` / ``[1, N]`` scales where
+        this torch build takes them on the device (probed once), otherwise the same formula as a matmul over the widened operands
+        (e4m3 -> fp32 is exact)."""
+        xq, sa = self.quantize_input_rowwise(x)
+        lead = xq.shape[:-1]
+        xq2, sa2 = xq.reshape(-1, self.in_features), sa.reshape(-1, 1)
+        sb = self.scale_reciprocal.reshape(1, -1)
+        if xq2.is_cuda and xq2.shape[0] > 0 and scaled_mm_takes_row_scales(xq2.device):
+            out = torch._scaled_mm(xq2, self.weight.T, scale_a=sa2.contiguous(), scale_b=sb.contiguous(), bias=self.bias,
+                                   out_dtype=torch.bfloat16)
+        else:
+            acc = (xq2.float() @ self.weight.float().T) * sa2 * sb
+            out = (acc if self.bias is None else acc + self.bias.float()).to(torch.bfloat16)
+        return out.view(*lead, self.out_features)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.scaling == "row":
+            return self._forward_rowwise(x)
         xq = self.quantize_input(x)
         lead = xq.shape[:-1]
         out = torch._scaled_mm(xq.view(-1, self.in_features), self.weight.T, scale_a=self.input_scale_reciprocal,
@@ -159,10 +252,10 @@ class F8Linear(nn.Module):
 
     @classmethod
     def from_linear(cls, linear: nn.Linear, float8_dtype=torch.float8_e4m3fn,
-                    input_float8_dtype=torch.float8_e5m2) -> "F8Linear":
+                    input_float8_dtype=torch.float8_e5m2, scaling: str = "tensor") -> "F8Linear":
         f8 = cls(linear.in_features, linear.out_features, bias=linear.bias is not None, device=linear.weight.device,
                  dtype=linear.weight.dtype, float8_dtype=float8_dtype, float_weight=linear.weight.data,
-                 float_bias=None if linear.bias is None else linear.bias.data, input_float8_dtype=input_float8_dtype)
+                 float_bias=None if linear.bias is None else linear.bias.data, input_float8_dtype=input_float8_dtype, scaling=scaling)
         f8.quantize_weight()
         return f8
 
@@ -170,31 +263,37 @@ class F8Linear(nn.Module):
 @torch.inference_mode()
 def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
                            input_float8_dtype=torch.float8_e4m3fn, parent_name: Optional[str] = None,
-                           quantize_modulation: bool = True, ignore_keys=("modulation",)) -> None:
+                           quantize_modulation: bool = True, ignore_keys=("modulation",), scaling: Optional[str] = None) -> None:
     """Replace the ``nn.Linear`` children below ``model`` by ``F8Linear`` in place, with the reference's exclusions
     (mlp_fp8.py:295-350): children named in ``ignore_keys``, children whose name contains ``mod`` (the modulation
     layers -- skipped regardless of ``quantize_modulation``, exactly as the reference does), and ``fc2`` of a sparse
     image MLP (child ``"2"`` of an ``nn.Sequential`` named ``img_mlp``) while ``mlp.is_enabled``: the sparse step's
     GEMM2 gathers bf16 rows of ``fc2.weight.T``.  With ``mlp.fp8_fc2`` on (and e4m3 weights asked for) that ``fc2`` is swapped too:
-    the sparse step's GEMM2 then gathers e4m3 rows (``csp_mlp_mm2_w8``)."""
+    the sparse step's GEMM2 then gathers e4m3 rows (``csp_mlp_mm2_w8``).  ``scaling`` (default: the config key ``mlp.fp8_scaling``) is the
+    layers' scale granularity; that ``fc2`` of a sparse image MLP is built per tensor whatever it says (GEMM2's gather takes one scale)."""
     from ..util.config import GLOBAL_CONFIG
+    if scaling is None:
+        scaling = amd_key("mlp", "fp8_scaling")
+    if scaling not in SCALINGS:
+        raise ValueError(f"recursive_swap_linears: mlp.fp8_scaling must be one of {', '.join(SCALINGS)} (got {scaling!r})")
     for name, child in list(model.named_children()):
         if name in ignore_keys or "mod" in name:
             continue
-        if (isinstance(model, nn.Sequential) and str(name) == "2" and isinstance(child, nn.Linear)
-                and parent_name == "img_mlp" and GLOBAL_CONFIG["mlp"]["is_enabled"]
-                and not (amd_key("mlp", "fp8_fc2") and float8_dtype == torch.float8_e4m3fn)):
+        sparse_fc2 = (isinstance(model, nn.Sequential) and str(name) == "2" and isinstance(child, nn.Linear)
+                      and parent_name == "img_mlp" and GLOBAL_CONFIG["mlp"]["is_enabled"])
+        if sparse_fc2 and not (amd_key("mlp", "fp8_fc2") and float8_dtype == torch.float8_e4m3fn):
             print("skipping fc2 of sparse img mlp")
             continue
         if isinstance(child, nn.Linear) and not isinstance(child, F8Linear):
-            setattr(model, name, F8Linear.from_linear(child, float8_dtype, input_float8_dtype))
+            setattr(model, name, F8Linear.from_linear(child, float8_dtype, input_float8_dtype,
+                                                      scaling="tensor" if sparse_fc2 else scaling))
         else:
-            recursive_swap_linears(child, float8_dtype, input_float8_dtype, name, quantize_modulation, ignore_keys)
+            recursive_swap_linears(child, float8_dtype, input_float8_dtype, name, quantize_modulation, ignore_keys, scaling)
 
 
 @torch.inference_mode()
 def quantize_fp8(flow_model: nn.Module, device=torch.device("cuda"), float8_dtype=torch.float8_e4m3fn,
-                 input_float8_dtype=torch.float8_e4m3fn, quantize_modulation: bool = True) -> nn.Module:
+                 input_float8_dtype=torch.float8_e4m3fn, quantize_modulation: bool = True, scaling: Optional[str] = None) -> nn.Module:
     """Move the transformer blocks to ``device`` one at a time and swap their linear layers to fp8 (reference
     mlp_fp8.py:352-400; called as ``quantize_fp8(model, device=device)`` by examples/flux/src/flux/util.py:350).
     The reference walks ``flow_model.double_blocks`` and ``.single_blocks``; a module without those attributes is
@@ -209,7 +308,7 @@ def quantize_fp8(flow_model: nn.Module, device=torch.device("cuda"), float8_dtyp
         module.to(device)
         module.eval()
         recursive_swap_linears(module, float8_dtype=float8_dtype, input_float8_dtype=input_float8_dtype,
-                               quantize_modulation=quantize_modulation)
+                               quantize_modulation=quantize_modulation, scaling=scaling)
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
     return flow_model

@@ -79,6 +79,9 @@ class SparseDiffGatedMlp:
                 raise ValueError(f"SparseDiffGatedMlp: the gated fp8 GEMM1 reads float8_e4m3fn weights and inputs only (got weight "
                                  f"{p.weight.dtype}, input_float8_dtype {getattr(p, 'input_float8_dtype', None)}); build the projection with "
                                  "F8Linear.from_linear(..., input_float8_dtype=torch.float8_e4m3fn)")
+            if getattr(p, "scaling", "tensor") != "tensor":
+                raise ValueError("SparseDiffGatedMlp: a row-scaled projection (F8Linear scaling='row', mlp.fp8_scaling: row) is refused: the "
+                                 "gated fp8 GEMM1 takes one scale per tensor; build the gate and up projections with scaling='tensor'")
         check_fc2("SparseDiffGatedMlp", fc2)    # bf16, or an e4m3 F8Linear with mlp.fp8_fc2 on
         self.fc2 = [fc2]
         self._fc2w_T = None             # ((address, dtype, device) of the fc2.weight it was made from, its transpose)

@@ -219,6 +219,28 @@ def _register():
         torch._check(update_cache in (0, 1, 2), lambda: "csp_mlp_mm1_fp8_act: update_cache must be 0, 1 or 2")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm1_fp8_act_rs")
+    def _(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, act, update_cache):
+        # as csp_mlp_mm1_fp8_act, with scale_a float32 [M] ([B, M] for a batched a) and scale_b float32 [F]
+        f8 = torch.float8_e4m3fn
+        torch._check(a.dtype == f8 and b.dtype == f8, lambda: "a and b must be float8_e4m3fn")
+        torch._check(c.dtype == torch.bfloat16 and pa_cache.dtype == torch.bfloat16, lambda: "c and pa_cache must be bfloat16")
+        torch._check(a.ndim in (2, 3) and b.ndim == 2 and a.shape[-1] == b.shape[1], lambda: "a and b must share the K dimension")
+        torch._check(c.shape == a.shape[:-1] + (b.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        torch._check(bias is None or bias.numel() == b.shape[0], lambda: "bias must have F entries")
+        torch._check(scale_a.dtype == torch.float32 and scale_b.dtype == torch.float32, lambda: "scale_a and scale_b must be float32")
+        torch._check(scale_a.shape == a.shape[:-1] and scale_a.is_contiguous(), lambda: "scale_a must be [M] ([B, M] for a batched a), contiguous")
+        torch._check(scale_b.shape == (b.shape[0],) and scale_b.is_contiguous(), lambda: "scale_b must be [F], contiguous")
+        torch._check(scale_a.device == a.device and scale_b.device == a.device, lambda: "scale_a and scale_b must be on the device of a")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_fp8_act_rs: unknown activation '{act}'")
+        torch._check(update_cache in (0, 1, 2), lambda: "csp_mlp_mm1_fp8_act_rs: update_cache must be 0, 1 or 2")
+        return None
+
+    @lib.register_fake("chipmunk::quantize_fp8_rowwise")
+    def _(x, max_value):
+        torch._check(x.dtype == torch.bfloat16 and x.ndim >= 1 and x.shape[-1] % 16 == 0, lambda: "x must be bfloat16 [..., K] with K % 16 == 0")
+        return [x.new_empty(x.shape, dtype=torch.float8_e4m3fn), x.new_empty(x.shape[:-1], dtype=torch.float32)]
+
     @lib.register_fake("chipmunk::csp_mlp_mm2_w8")
     def _(mma_a, mma_b, scale_b, indices, counts, mma_c):
         # accumulates into mma_c in place and returns nothing

@@ -29,6 +29,24 @@ def _default_form(who: str, act: str, fc1b: Optional[torch.Tensor]) -> bool:
     return act == "gelu_tanh" and fc1b is not None
 
 
+def _row_scales(who: str, x: torch.Tensor, fc1w: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor) -> bool:
+    """The granularity of an fp8 GEMM1's reciprocal scales.  False: one number each (0-dim, or any one-element tensor) -- the operators
+    GEMM1 always had.  True: ``scale_a`` one per token row of ``x`` (``[M]``, ``[B, M]`` for a batch) with ``scale_b`` one per row of
+    ``fc1w`` (``[F]``) -- ``csp_mlp_mm1_fp8_act_rs``.  A mixed pair raises."""
+    if scale_a is None or scale_b is None:
+        raise ValueError(f"{who}: an fp8 GEMM1 needs scale_a and scale_b, the reciprocal quantisation scales")
+    F = fc1w.shape[0] if fc1w.shape[-1] == x.shape[-1] else fc1w.shape[-1]
+    rows = scale_a.dim() in (1, 2) and tuple(scale_a.shape) == tuple(x.shape[:-1])
+    cols = scale_b.dim() == 1 and scale_b.shape[0] == F
+    if rows and cols and (F > 1 or scale_a.numel() > 1):
+        return True
+    if scale_a.numel() == 1 and scale_b.numel() == 1:
+        return False
+    raise ValueError(f"{who}: scale_a {tuple(scale_a.shape)} with scale_b {tuple(scale_b.shape)} is a mixed pair: pass one number each "
+                     f"(per-tensor scales), or scale_a {tuple(x.shape[:-1])} -- one per token row -- with scale_b ({F},) -- one per fc1 "
+                     "column; a vector on one side only has no kernel")
+
+
 def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
         sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
         scale_a: Optional[torch.Tensor] = None, scale_b: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
@@ -67,7 +85,11 @@ def mm1_fp8_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torc
     """fp8 GEMM1 + ``csp_scatter_add`` of its output into ``sparse_act_T`` in one kernel (the fp8 counterpart of ``mm1_scatter``;
     bit-identical in the packed deltas and in the cache to ``csp_mlp_mm1_fp8`` followed by the scatter-add)."""
     assert x.dtype == torch.float8_e4m3fn and fc1w.dtype == torch.float8_e4m3fn
-    if _default_form("mm1_fp8_scatter", act, fc1b):
+    default = _default_form("mm1_fp8_scatter", act, fc1b)      # (the name is checked before anything else)
+    if _row_scales("mm1_fp8_scatter", x, fc1w, scale_a, scale_b):   # update_cache 2: the scatter-add of the deltas
+        torch.ops.chipmunk.csp_mlp_mm1_fp8_act_rs(x, fc1w.contiguous(), sparse_act_packed, fc1b, sparse_act_T, indices, counts,
+                                                  scale_a.float().contiguous(), scale_b.float().contiguous(), act, 2)
+    elif default:
         torch.ops.chipmunk.csp_mlp_mm1_fp8_scatter(x, fc1w.contiguous(), sparse_act_packed, fc1b, sparse_act_T, indices, counts,
                                                    scale_a.reshape(1).float(), scale_b.reshape(1).float())
     else:   # update_cache 2: the scatter-add of the deltas
@@ -86,7 +108,12 @@ def csp_mlp_mm1_fp8(a: torch.Tensor, b: torch.Tensor, fc1b: Optional[torch.Tenso
     the same storage); scales are the RECIPROCAL quantisation scales (modules/mlp.py:98-99)."""
     if b.shape[0] == a.shape[1] and b.shape[1] != a.shape[1]:
         b = b.T  # accept the reference's fc1w.T view
-    if _default_form("csp_mlp_mm1_fp8", act, fc1b):
+    default = _default_form("csp_mlp_mm1_fp8", act, fc1b)      # (the name is checked before anything else)
+    if _row_scales("csp_mlp_mm1_fp8", a, b, scale_a, scale_b):   # one scale per token row and per fc1 column: every activation / bias form
+        torch.ops.chipmunk.csp_mlp_mm1_fp8_act_rs(a, b.contiguous(), sparse_act_packed_out, fc1b, sparse_act_unpacked_inout, indices,
+                                                  counts, scale_a.float().contiguous(), scale_b.float().contiguous(), act,
+                                                  1 if FP8_MM1_UPDATES_CACHE else 0)
+    elif default:
         torch.ops.chipmunk.csp_mlp_mm1_fp8(a, b.contiguous(), sparse_act_packed_out, fc1b, sparse_act_unpacked_inout,
                                            indices, counts, scale_a.reshape(1).float(), scale_b.reshape(1).float(),
                                            FP8_MM1_UPDATES_CACHE)
@@ -158,6 +185,8 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
     # cached_out [B, M, N] -- one launch per kernel for all B sequences, the bits of B calls on the slices.
     # fc2w_T float8_e4m3fn with fc2_scale (F8Linear.scale_reciprocal): the scatter-add is GEMM1's own (or csp_scatter_add with
     # mlp.fused_scatter off) and GEMM2 gathers e4m3 rows.
+    # mm1_scale_a / mm1_scale_b (fp8 fc1): one number each, or mm1_scale_a [M] ([B, M]) -- one per token row -- with mm1_scale_b [F] -- one
+    # per fc1 column (csp_mlp_mm1_fp8_act_rs in GEMM1's place); a mixed pair raises.
     # act (one of GLU_ACTS) names fc1's activation and fc1b may be None: anything but tanh-GELU with a bias takes csp_mlp_mm1_act /
     # csp_mlp_mm1_fp8_act in GEMM1's place, everything behind GEMM1 is unchanged.
     assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"

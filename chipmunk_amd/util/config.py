@@ -134,6 +134,11 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     "mlp.top_p": 0.0,
     # ... and never fewer than this fraction of the columns (a sampled quantile like top_keys'; at most top_keys)
     "mlp.top_p_min_keys": 0.0,
+    # granularity of the fp8 scales of the layers recursive_swap_linears / quantize_fp8 build (not in the reference): "tensor" = one scale per
+    # tensor, the input's calibrated over the first calls and frozen, as in the reference; "row" = one dynamic scale per token row of the
+    # input (recomputed on every call, one HIP pass) and one per output feature of the weight -- fc1's sparse steps then run
+    # csp_mlp_mm1_fp8_act_rs.  fc2 under mlp.fp8_fc2 keeps one scale per tensor either way (GEMM2's weight-only gather takes one).
+    "mlp.fp8_scaling": "tensor",
 }
 BASE_CONFIG["offloading"]["keep_resident_if_fits"] = AMD_EXTRA_KEYS["offloading.keep_resident_if_fits"]
 BASE_CONFIG["offloading"]["hbm_budget_gb"] = AMD_EXTRA_KEYS["offloading.hbm_budget_gb"]
@@ -155,6 +160,7 @@ BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
 BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]
 BASE_CONFIG["mlp"]["top_p_min_keys"] = AMD_EXTRA_KEYS["mlp.top_p_min_keys"]
+BASE_CONFIG["mlp"]["fp8_scaling"] = AMD_EXTRA_KEYS["mlp.fp8_scaling"]
 
 GLOBAL_CONFIG: Dict[str, Any] = copy.deepcopy(BASE_CONFIG)
 

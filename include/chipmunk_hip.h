@@ -294,6 +294,22 @@ int chipmunk_csp_mlp_mm1_fp8_act_batched(const void *a, const void *b, void *c, 
                                          int M, int K, int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
                                          void *stream);
 
+/* fp8 row scales: chipmunk_csp_mlp_mm1_fp8_act[_batched] with one activation scale per token row and one weight scale per fc1 column
+ * (dynamic per-token x per-output-channel quantisation; no reference counterpart).  The contract is that of the entries above -- any
+ * M >= 1, ldc, act, update_cache 0 / 1 / 2, bias bf16 [F] or NULL -- except that
+ *   scale_a is fp32 [M] ([B, M] for the batched entry): the RECIPROCAL scale of row m (chipmunk_quantize_fp8_rowwise's scale_recip),
+ *   scale_b is fp32 [F]: the RECIPROCAL scale of weight row i, read at the GATHERED column i = idx[g,j],
+ *   t = bf16( act((a[m,:].b[i,:] * scale_a[m]) * scale_b[i] + bias[i]) );  c[m,j] = bf16( t - pa_cache[i, m] )
+ * in the multiplication order of the scalar form: constant vectors give the bits of chipmunk_csp_mlp_mm1_fp8_act.  No element of scale_a
+ * at or past M (B * M) and none of scale_b at or past F is read. */
+int chipmunk_csp_mlp_mm1_fp8_act_rs(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                    const int32_t *counts, const float *scale_a, const float *scale_b, int M, int K, int F, int ldc,
+                                    int act, int update_cache, void *stream);
+int chipmunk_csp_mlp_mm1_fp8_act_rs_batched(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                            const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                            int M, int K, int F, int ldc, int act, int update_cache, int B,
+                                            int64_t cache_batch_stride, void *stream);
+
 /* fp8 fc2: GEMM (ii) over e4m3 rows of fc2^T (weight-only fp8).  mma_a [M,F] bf16 packed deltas, mma_b [F,N2] OCP e4m3 bytes
  * (float8_e4m3fn), plain row-major, scale_b one device float -- the weight's RECIPROCAL quantisation scale --, mma_c [M,N2] bf16:
  *   mma_c[m,:] = bf16( bf16( (sum_{c < counts[g]} mma_a[m,c] * f(mma_b[indices[g,c],:])) * scale_b[0] ) + mma_c[m,:] )
@@ -488,6 +504,18 @@ int chipmunk_block_mean_ragged(const void *x, void *out, int64_t rows, int C, in
  * src/chipmunk/modules/mlp_fp8.py, the input side of csp_mlp_mm1_fp8) as one pass with the same roundings (fp32 product -> bf16 -> clamp ->
  * e4m3, round-to-nearest-even).  scale: one float on the device.  n % 8 == 0. */
 int chipmunk_quantize_fp8(const void *x, const float *scale, void *out, int64_t n, float max_value, void *stream);
+
+/* bf16 [rows, K] -> OCP fp8 e4m3 [rows, K] with one dynamic scale per row (F8Linear.quantize_input_rowwise; no reference counterpart), in
+ * one pass over HBM.  Per row r, in fp32 with IEEE division:
+ *   amax = max_k |x[r,k]|;  scale = min(max_value / max(amax, 1e-12), max_value)
+ *   out[r,k] = e4m3_rne( clamp(float(x[r,k]) * scale, -max_value, max_value) );  scale_recip[r] = 1 / scale
+ * The product is fp32 and rounded once, into e4m3: torch's `x.float() * scale[:, None]` chain, NOT chipmunk_quantize_fp8's (which rounds
+ * the product to bf16 first, as torch's bf16 x 0-dim product does).  scale_recip is fp32 [rows], the number GEMM1 multiplies its sums by.
+ * rows >= 0, K % 16 == 0, K <= CHIPMUNK_QUANTIZE_ROWWISE_MAX_K; x 16-byte, out 8-byte, scale_recip 4-byte aligned; anything else returns
+ * CHIPMUNK_ERR_INVALID before anything is enqueued.  A row that holds a NaN or an Inf is outside the contract: its bytes and its scale
+ * are unspecified. */
+#define CHIPMUNK_QUANTIZE_ROWWISE_MAX_K 16384
+int chipmunk_quantize_fp8_rowwise(const void *x, void *out, float *scale_recip, int64_t rows, int K, float max_value, void *stream);
 
 /* bitpack / bitunpack (reference src/chipmunk/ops/bitpack.py:4-69): 8 bools -> 1 byte, little-endian, flat. */
 int chipmunk_bitpack(const void *mask, void *packed, int64_t n, void *stream);

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan fp8_rs_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -333,6 +333,49 @@ def bench_fp8_wan(M=32768, ldc=None):
     print(f"mm1 bf16 same shape: {ms*1e3:8.1f} us  {flops/ms/1e9:7.1f} TFLOP/s")
 
 
+def bench_fp8_rs_wan(M=32768, act="silu"):
+    """fp8 row scales at the Wan fp8 shape (M = 32768, K = 1536, F = 8960, keep 0.3): csp_mlp_mm1_fp8_act_rs (scale vectors [M] / [F])
+    against csp_mlp_mm1_fp8_act (two numbers) on the same operands, alternating; then the row-wise input quantiser against the torch
+    chain it replaces and against the per-tensor quantize_fp8, in us and GB/s of the 3 * rows * K + 4 * rows bytes it has to move."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    K, F, keep = 1536, 8960, 2688
+    a = torch.randn(M, K, device=dev, generator=g)
+    w = torch.randn(F, K, device=dev, generator=g) * 0.02
+    a8, w8 = (a * 16).clamp(-448, 448).to(torch.float8_e4m3fn), (w * 512).clamp(-448, 448).to(torch.float8_e4m3fn)
+    sa, sb = torch.tensor([1 / 16.0], device=dev), torch.tensor([1 / 512.0], device=dev)
+    sav, sbv = sa.expand(M).contiguous(), sb.expand(F).contiguous()
+    bias = torch.zeros(F, device=dev, dtype=torch.bfloat16)
+    cache = torch.randn(F, M, device=dev, dtype=torch.bfloat16, generator=g)
+    packed = torch.empty(M, F, device=dev, dtype=torch.bfloat16)
+    G = (M + 127) // 128
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    flops = 2.0 * M * K * keep
+    runs = {"scalar": lambda: torch.ops.chipmunk.csp_mlp_mm1_fp8_act(a8, w8, packed, bias, cache, inds, counts, sa, sb, act, 0),
+            "vectors": lambda: torch.ops.chipmunk.csp_mlp_mm1_fp8_act_rs(a8, w8, packed, bias, cache, inds, counts, sav, sbv, act, 0)}
+    t = {k: [] for k in runs}
+    for _ in range(5):      # alternating, so that a drift of the box falls on both
+        for k, fn in runs.items():
+            t[k].append(timeit(fn, reps=5) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    for k in runs:
+        print(f"mm1_fp8_act {k:8s} {act}: {med[k]:8.1f} us  [{min(t[k]):.1f} .. {max(t[k]):.1f}]  {flops/med[k]/1e6:7.1f} TFLOP/s   (M={M} K={K} F={F} keep={keep})")
+    print(f"vectors / scalar: {med['vectors'] / med['scalar']:7.3f}")
+    x = a.to(torch.bfloat16)
+    scale = torch.tensor(16.0, device=dev)
+
+    def chain():
+        xf = x.float()
+        s = (torch.full((M,), 448.0, device=dev) / xf.abs().amax(dim=-1).clamp(min=1e-12)).clamp(max=448.0)
+        return (xf * s[:, None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn), s.reciprocal()
+    qs = {"quantize_fp8_rowwise": lambda: torch.ops.chipmunk.quantize_fp8_rowwise(x, 448.0), "torch row chain": chain,
+          "quantize_fp8 (per tensor)": lambda: torch.ops.chipmunk.quantize_fp8(x, scale.reshape(1), 448.0)}
+    bytes_moved = 3.0 * M * K + 4.0 * M
+    for k, fn in qs.items():
+        us = sorted(timeit(fn, reps=10) * 1e3 for _ in range(3))
+        print(f"{k:26s}: {us[1]:8.1f} us  [{us[0]:.1f} .. {us[2]:.1f}]  {bytes_moved / us[1] / 1e3:7.1f} GB/s of 3 * rows * K + 4 * rows bytes   (rows={M} K={K})")
+
+
 def sorted_random_indices(H, G, n_keys, count, width, g):
     inds = torch.zeros(1, H, G, width, dtype=torch.int32, device=dev)
     for h in range(H):
@@ -456,6 +499,8 @@ def main():
             bench_mm2_w8(M=32760, F=8960, N2=1536, keep=2816)
         elif w == "fp8_wan":
             bench_fp8_wan()
+        elif w == "fp8_rs_wan":       # fp8 GEMM1 with scale vectors against the scalar launch, and the row-wise input quantiser (KB_GLU_ACT as mm1_glu)
+            bench_fp8_rs_wan(act=os.environ.get("KB_GLU_ACT", "silu"))
         elif w == "mm2_wan":          # GEMM2 at the Wan2.1 1.3B shape (configs[4]): M = 32 768 rows, N2 = 1 536, F = 8 960, 30 % kept
             bench_mlp("mm2", variants, M=32768, K=1536, F=8960, keep=2816)
         elif w == "fp8_wan_ragged":   # the same launches on Wan2.1's 32 760 tokens as they are: 255 groups + 120 rows
