@@ -222,7 +222,7 @@ struct Mm1GluF8Params : Mm1Params {
 // (and with it the weight the rows are gathered from) is uniform per instruction.  Cache block and output image are TN/2 columns wide.
 // FP8 && GLU (P = Mm1GluF8Params): the k loop of the fp8 form (e4m3 fragments, 32x32x64 MFMA, accumulators from zero) under the B-row gather
 // and the epilogue of the gated form; each branch's sum is scaled by scale_x and its own weight scale, then biased, in the fp8 form's order.
-// Ungated forms with ACT != 0 or NULLB (mm1_act_kernel): c = bf16(act(x W + b) - cache) with act one of CHIPMUNK_ACT_*, and a null bias vector
+// Ungated forms with ACT != 0 or NULLB (mm1_form_kernel): c = bf16(act(x W + b) - cache) with act one of CHIPMUNK_ACT_*, and a null bias vector
 // read as zero -- bf16 seeds its accumulators with 0, fp8 adds 0 behind the scales.  ACT = 0 without NULLB is the code mm1_kernel always had.
 // RS (ungated fp8 only; chipmunk_csp_mlp_mm1_fp8_act_rs): scale_a is a vector over the token rows ([M]), scale_b one over the fc1 columns ([F]).
 // The column's scale is a per-lane scalar like its bias -- gathered through the indices in the prologue --, the row scales of a lane's runs of
@@ -231,7 +231,7 @@ struct Mm1GluF8Params : Mm1Params {
 template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params, bool NULLB = false,
           bool RS = false>
 __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
-    static_assert(!RS || (FP8 && !GLU && NULLB), "row / column scale vectors: the ungated fp8 form with a nullable bias (mm1_rs_kernel) only");
+    static_assert(!RS || (FP8 && !GLU && NULLB), "row / column scale vectors: the ungated fp8 form with a nullable bias (mm1_form_kernel) only");
     using KT = KTile<BK>;
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
     constexpr int A_TILE = TM * BK * 2, B_TILE = TN * BK * 2, STAGE = A_TILE + B_TILE;
@@ -624,6 +624,13 @@ struct Mm1Batch : Mm1Params {
     int B;
     int64_t cache_bs;   // elements between the caches of consecutive sequences (>= F * ldc)
 };
+struct Mm1GluF8Batch : Mm1GluF8Params {
+    int B;
+    int64_t cache_bs;   // as Mm1Batch
+};
+// (the gated fp8 form?, batched?) -> the parameter block a kernel takes
+template <bool F8GLU, bool BATCHED> struct Mm1Block { using type = typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type; };
+template <bool BATCHED> struct Mm1Block<true, BATCHED> { using type = typename std::conditional<BATCHED, Mm1GluF8Batch, Mm1GluF8Params>::type; };
 
 template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false>
 __global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type p) {
@@ -635,66 +642,6 @@ __global__ __launch_bounds__(NW * 64, WPS) void mm1_kernel(const typename std::c
     // (kernel arguments, the live-tile map, wave start-up: 5.4 k of a 41 k-cycle tile at the Wan2.1 fp8 shape, tools/mlp_prof.py) and
     // with the previous tile's stores draining under the next tile's index loads.  (Requesting the NEXT tile's gather indices during
     // the current tile -- one exposed round trip less -- measured no gain at the fp8 shape, 209 vs 209-224 us, for 40 more registers.)
-    if constexpr (BATCHED) {
-        const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence; the map runs over all B * Gs
-        const TilePlan pl = plan_tiles<BN>(p.counts, p.B * Gs, p.NT, p.NR, p.slots_per_xcd, NSUB);
-        const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
-        for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
-            const TileMap tm = tile_at(pl, slot);
-            if (!tm.live) continue;
-            const int cnt = p.counts[tm.g];
-            const int b = tm.g / Gs, g = tm.g - b * Gs;   // sequence, group inside it
-            Mm1Params q = p;                              // the tile sees its sequence's operands
-            q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)b * p.M * p.K * (FP8 ? 1 : 2));
-            q.c = p.c + (int64_t)b * p.M * p.F;
-            q.cache = p.cache + (int64_t)b * p.cache_bs;
-            q.indices = p.indices + (int64_t)b * Gs * p.F;
-            if (tm.sub < 0) {
-                const int n0 = tm.nt * BN;
-                if (n0 >= cnt) continue;  // tiles past counts[g] are skipped (csp_mlp_mm1.cu:233-243)
-                mm1_tile<BM, BN, BK, NST, FP8, NW>(q, smem, g, 0, n0, cnt);
-            } else if constexpr (NW == 4) {
-                constexpr int SUB_NST = (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
-                const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
-                if (n0 >= cnt || p.probe == 3) continue;  // probe 3: time the launch without its tail
-                if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
-                mm1_tile<64, 64, BK, (SUB_NST > 4 ? 4 : SUB_NST), FP8>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
-            }
-            __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
-        }
-    } else {
-        const TilePlan pl = plan_tiles<BN>(p.counts, (p.M + BM - 1) / BM, p.NT, p.NR, p.slots_per_xcd, NSUB);
-        const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
-        for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
-            const TileMap tm = tile_at(pl, slot);
-            if (!tm.live) continue;
-            const int g = tm.g;
-            const int cnt = p.counts[g];
-            if (tm.sub < 0) {
-                const int n0 = tm.nt * BN;
-                if (n0 >= cnt) continue;  // tiles past counts[g] are skipped (csp_mlp_mm1.cu:233-243)
-                mm1_tile<BM, BN, BK, NST, FP8, NW>(p, smem, g, 0, n0, cnt);
-            } else if constexpr (NW == 4) {
-                constexpr int SUB_NST = (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
-                const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
-                if (n0 >= cnt || p.probe == 3) continue;  // probe 3: time the launch without its tail
-                if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
-                mm1_tile<64, 64, BK, (SUB_NST > 4 ? 4 : SUB_NST), FP8>(p, smem, g, (tm.sub & 1) * 64, n0, cnt);
-            }
-            __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
-        }
-    }
-}
-
-// The ungated GEMM1 with the activation as a template parameter (CHIPMUNK_ACT_*) and a bias that may be null (= zero): a kernel of its
-// own, so that mm1_kernel's instantiations keep their names and their code (a walk shared through a device function moved mm1_kernel's
-// scalar register allocation).  mm1_kernel's 4-wave form line for line -- the persistent walk, tail split, ragged last group, batch pointer
-// advance -- with mm1_tile's ACT and NULLB set.
-template <int BN, int BK, int NST, int WPS, bool FP8, int ACT, bool BATCHED = false>
-__global__ __launch_bounds__(256, WPS) void mm1_act_kernel(const typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int NSUB = 2 * (BN / 64);  // 64 x 64 sub-tiles per tile
-    constexpr int SUB_NST = (NST * (BM + BN)) / 128 > 4 ? 4 : (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
     const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
     int G = Gs;
     if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
@@ -705,7 +652,7 @@ __global__ __launch_bounds__(256, WPS) void mm1_act_kernel(const typename std::c
         if (!tm.live) continue;
         const int cnt = p.counts[tm.g];
         int g = tm.g;
-        Mm1Params q = p;                              // the tile sees its sequence's operands
+        typename std::conditional<BATCHED, Mm1Params, const Mm1Params &>::type q = p;   // the tile sees its sequence's operands
         if constexpr (BATCHED) {
             const int b = tm.g / Gs;
             g = tm.g - b * Gs;                        // group inside sequence b
@@ -716,129 +663,78 @@ __global__ __launch_bounds__(256, WPS) void mm1_act_kernel(const typename std::c
         }
         if (tm.sub < 0) {
             const int n0 = tm.nt * BN;
-            if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
-            mm1_tile<BM, BN, BK, NST, FP8, 4, false, ACT, Mm1Params, true>(q, smem, g, 0, n0, cnt);
-        } else {
+            if (n0 >= cnt) continue;  // tiles past counts[g] are skipped (csp_mlp_mm1.cu:233-243)
+            mm1_tile<BM, BN, BK, NST, FP8, NW>(q, smem, g, 0, n0, cnt);
+        } else if constexpr (NW == 4) {
+            constexpr int SUB_NST = (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
             const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
-            if (n0 >= cnt) continue;
+            if (n0 >= cnt || p.probe == 3) continue;  // probe 3: time the launch without its tail
             if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
-            mm1_tile<64, 64, BK, SUB_NST, FP8, 4, false, ACT, Mm1Params, true>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
+            mm1_tile<64, 64, BK, (SUB_NST > 4 ? 4 : SUB_NST), FP8>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
         }
         __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
     }
 }
 
-// The ungated fp8 GEMM1 with scale VECTORS (mm1_tile's RS form: scale_a [M] per token row, [B, M] for a batch; scale_b [F] per fc1 column):
-// mm1_act_kernel's fp8 walk line for line with RS set and the sequence's row scales behind the batch pointer advance -- a kernel of its own,
-// so that mm1_act_kernel's instantiations keep their names and their code.
-template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED = false>
-__global__ __launch_bounds__(256, WPS) void mm1_rs_kernel(const typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type p) {
+// Every GEMM1 form but mm1_kernel's (4 waves, the shipped tile shape's walk): the persistent walk over the live-tile map, the ragged last
+// group and the batch pointer advance written once, mm1_tile's form chosen by the flags:
+//   FP8      e4m3 operands (a sequence of a batch then starts M * K bytes behind the one before, not 2 * M * K);
+//   GLU      the gated form: a whole tile covers BN / 2 packed columns, no tail split (slots_per_xcd is not read: the launch is correct either
+//            way), tiles past counts[g] are skipped BEFORE the batch advance; with FP8 the parameter block is Mm1GluF8Params (Mm1Block);
+//   ACT      CHIPMUNK_ACT_*; the ungated forms also read a null bias as zero (mm1_tile's NULLB);
+//   RS       (ungated fp8) scale_a / scale_b are vectors; scale_a is [B, M] for a batch and advances with the sequence;
+//   BATCHED  the parameter block carries B and cache_bs, and a tile sees its sequence's operands; otherwise the kernel's own block.
+// mm1_kernel stays a kernel of its own: the benchmark times it, it carries the MLP_PROF marks, probe == 3 and the 8-wave / probe-build
+// shapes, and a walk shared with other instantiations through a device function moved its scalar register allocation.  The order of the
+// statements below is the order each form's code was first compiled from (tools/mlp_isa_diff.py compares the instruction streams).
+template <int BN, int BK, int NST, int WPS, bool FP8, bool GLU, int ACT, bool RS, bool BATCHED>
+__global__ __launch_bounds__(256, WPS) void mm1_form_kernel(const typename Mm1Block<FP8 && GLU, BATCHED>::type p) {
+    using P = typename Mm1Block<FP8 && GLU, false>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int NSUB = 2 * (BN / 64);  // 64 x 64 sub-tiles per tile
+    constexpr int PBN = GLU ? BN / 2 : BN;            // packed columns of a whole tile: the gated B tile's BN rows are {gate, up} pairs
+    constexpr int NSUB = GLU ? 1 : 2 * (BN / 64);     // 64 x 64 sub-tiles per tile
     constexpr int SUB_NST = (NST * (BM + BN)) / 128 > 4 ? 4 : (NST * (BM + BN)) / 128;  // same LDS bytes, stages of 64 + 64 rows
     const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
     int G = Gs;
     if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
-    const TilePlan pl = plan_tiles<BN>(p.counts, G, p.NT, p.NR, p.slots_per_xcd, NSUB);
+    const TilePlan pl = plan_tiles<PBN>(p.counts, G, p.NT, p.NR, GLU ? 0 : p.slots_per_xcd, NSUB);
     const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
     for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
         const TileMap tm = tile_at(pl, slot);
         if (!tm.live) continue;
         const int cnt = p.counts[tm.g];
+        if constexpr (GLU) {
+            if (tm.nt * PBN >= cnt) continue;  // tiles past counts[g] are skipped
+        }
         int g = tm.g;
-        Mm1Params q = p;                              // the tile sees its sequence's operands
+        // the tile sees its sequence's operands (a gated single sequence: the kernel's own block, no copy -- the copy costs it SGPR spills)
+        typename std::conditional<BATCHED || !GLU, P, const P &>::type q = p;
         if constexpr (BATCHED) {
             const int b = tm.g / Gs;
             g = tm.g - b * Gs;                        // group inside sequence b
-            q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)b * p.M * p.K);
+            if constexpr (GLU && !FP8) q.a = p.a + (int64_t)b * p.M * p.K;   // (in elements: in bytes this form compiles to other code)
+            else q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)b * p.M * p.K * (FP8 ? 1 : 2));
             q.c = p.c + (int64_t)b * p.M * p.F;
             q.cache = p.cache + (int64_t)b * p.cache_bs;
             q.indices = p.indices + (int64_t)b * Gs * p.F;
-            q.scale_a = p.scale_a + (int64_t)b * p.M;   // [B, M]: the sequence's row scales
+            if constexpr (RS) q.scale_a = p.scale_a + (int64_t)b * p.M;   // [B, M]: the sequence's row scales
         }
-        if (tm.sub < 0) {
+        if constexpr (GLU) {
+            mm1_tile<BM, BN, BK, NST, FP8, 4, true, ACT, P>(q, smem, g, 0, tm.nt * PBN, cnt);
+        } else if (tm.sub < 0) {
             const int n0 = tm.nt * BN;
             if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
-            mm1_tile<BM, BN, BK, NST, true, 4, false, ACT, Mm1Params, true, true>(q, smem, g, 0, n0, cnt);
+            mm1_tile<BM, BN, BK, NST, FP8, 4, false, ACT, P, true, RS>(q, smem, g, 0, n0, cnt);
         } else {
             const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
             if (n0 >= cnt) continue;
             if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
-            mm1_tile<64, 64, BK, SUB_NST, true, 4, false, ACT, Mm1Params, true, true>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
+            mm1_tile<64, 64, BK, SUB_NST, FP8, 4, false, ACT, P, true, RS>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
         }
         __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
     }
 }
 
-// The gated GEMM1 (mm1_tile's GLU form; bf16, 4 waves): a kernel of its own, so that mm1_kernel's instantiations keep their names and their
-// code.  The same persistent walk over the same live-tile map, with a whole tile covering BN / 2 packed columns and without the tail
-// split (slots_per_xcd = 0: the launch is correct either way); ragged M through mm1_tile's `rows`, a batch through the pointer advance of
-// mm1_kernel's BATCHED form.
-template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED = false>
-__global__ __launch_bounds__(256, WPS) void mm1_glu_kernel(const typename std::conditional<BATCHED, Mm1Batch, Mm1Params>::type p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int PBN = BN / 2;           // packed columns of a tile: its BN B-tile rows are {gate, up} pairs
-    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
-    int G = Gs;
-    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
-    const TilePlan pl = plan_tiles<PBN>(p.counts, G, p.NT, p.NR, 0, 1);
-    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
-    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
-        const TileMap tm = tile_at(pl, slot);
-        if (!tm.live) continue;
-        const int cnt = p.counts[tm.g];
-        const int n0 = tm.nt * PBN;
-        if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
-        if constexpr (BATCHED) {
-            const int b = tm.g / Gs, g = tm.g - b * Gs;   // sequence, group inside it
-            Mm1Params q = p;                              // the tile sees its sequence's operands
-            q.a = p.a + (int64_t)b * p.M * p.K;
-            q.c = p.c + (int64_t)b * p.M * p.F;
-            q.cache = p.cache + (int64_t)b * p.cache_bs;
-            q.indices = p.indices + (int64_t)b * Gs * p.F;
-            mm1_tile<BM, BN, BK, NST, false, 4, true, ACT>(q, smem, g, 0, n0, cnt);
-        } else {
-            mm1_tile<BM, BN, BK, NST, false, 4, true, ACT>(p, smem, tm.g, 0, n0, cnt);
-        }
-        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
-    }
-}
-
-// The gated fp8 GEMM1 (mm1_tile's FP8 && GLU form): mm1_glu_kernel's walk with a parameter block and a name of its own -- the operands of
-// a and the weights are e4m3 bytes, so a sequence of a batch starts M * K bytes behind the one before.
-struct Mm1GluF8Batch : Mm1GluF8Params {
-    int B;
-    int64_t cache_bs;   // as Mm1Batch
-};
-template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED = false>
-__global__ __launch_bounds__(256, WPS) void mm1_glu_fp8_kernel(const typename std::conditional<BATCHED, Mm1GluF8Batch, Mm1GluF8Params>::type p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int PBN = BN / 2;           // packed columns of a tile: its BN B-tile rows are {gate, up} pairs
-    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
-    int G = Gs;
-    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
-    const TilePlan pl = plan_tiles<PBN>(p.counts, G, p.NT, p.NR, 0, 1);
-    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
-    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
-        const TileMap tm = tile_at(pl, slot);
-        if (!tm.live) continue;
-        const int cnt = p.counts[tm.g];
-        const int n0 = tm.nt * PBN;
-        if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
-        if constexpr (BATCHED) {
-            const int b = tm.g / Gs, g = tm.g - b * Gs;   // sequence, group inside it
-            Mm1GluF8Params q = p;                         // the tile sees its sequence's operands
-            q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)b * p.M * p.K);
-            q.c = p.c + (int64_t)b * p.M * p.F;
-            q.cache = p.cache + (int64_t)b * p.cache_bs;
-            q.indices = p.indices + (int64_t)b * Gs * p.F;
-            mm1_tile<BM, BN, BK, NST, true, 4, true, ACT>(q, smem, g, 0, n0, cnt);
-        } else {
-            mm1_tile<BM, BN, BK, NST, true, 4, true, ACT>(p, smem, tm.g, 0, n0, cnt);
-        }
-        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
-    }
-}
 
 // The tile shapes and producer / consumer forms measured against the shipped kernels (docs/EXPERIMENTS_r04.md / _r05.md) are
 // not part of the product library: tools/probes/mm1_forms/build.sh compiles this file with -DCHIPMUNK_MM1_PROBES into
@@ -1682,30 +1578,22 @@ int launch_mm2_w8(const void *, const void *, const float *, void *, const int32
 }
 #endif   // CHIPMUNK_MM1_PROBES
 
-// (parameter block -> its batched form)
-template <class P> struct Mm1BatchOf { using type = Mm1Batch; };
-template <> struct Mm1BatchOf<Mm1GluF8Params> { using type = Mm1GluF8Batch; };
-
-// ACTK: the ungated form through mm1_act_kernel (activation ACT, nullable bias) instead of mm1_kernel
-template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false, bool GLU = false, int ACT = 0, class P = Mm1Params,
-          bool ACTK = false, bool RS = false>
-int launch_mm1_variant(const P &p0, hipStream_t s, bool *cache_updated = nullptr, int B = 1, int64_t cache_bs = 0) {
+// ACT < 0: mm1_kernel (tanh-GELU, a bias that must be there; every tile shape); ACT = CHIPMUNK_ACT_*: mm1_form_kernel
+template <int BN, int BK, int NST, int WPS, bool FP8 = false, int NW = 4, bool BATCHED = false, bool GLU = false, int ACT = -1, bool RS = false>
+int launch_mm1_variant(const typename Mm1Block<FP8 && GLU, false>::type &p0, hipStream_t s, bool *cache_updated = nullptr, int B = 1,
+                       int64_t cache_bs = 0) {
+    using P = typename Mm1Block<FP8 && GLU, false>::type;
     constexpr int PBN = GLU ? BN / 2 : BN;   // packed columns per whole tile (gated form: the B tile's rows are {gate, up} pairs)
     constexpr int STAGE = BM * BK * 2 + BN * BK * 2, LDS = NST * STAGE, EPI = BM * PBN * 2;
     // mm1_tile's staged epilogue (the one that can scatter): one stage each for cache block and outputs, or the FLAT layout
     constexpr bool STAGED = EPI <= STAGE || (NW == 8 && EPI <= (NST - 1) * STAGE && 2 * EPI <= NST * STAGE && STAGE % (BN * 2) == 0);
     auto kern = [] {
-        if constexpr (GLU && FP8) return mm1_glu_fp8_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
-        else if constexpr (GLU) return mm1_glu_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
-        else if constexpr (ACTK && RS) return mm1_rs_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
-        else if constexpr (ACTK) return mm1_act_kernel<BN, BK, NST, WPS, FP8, ACT, BATCHED>;
+        if constexpr (ACT >= 0) return mm1_form_kernel<BN, BK, NST, WPS, FP8, GLU, ACT, RS, BATCHED>;
         else return mm1_kernel<BN, BK, NST, WPS, FP8, NW, BATCHED>;
     }();
-    static_assert(!GLU || NW == 4, "the gated GEMM1 has 4 waves");
-    static_assert(!ACTK || (NW == 4 && !GLU), "mm1_act_kernel is the ungated 4-wave form");
-    static_assert(!RS || (ACTK && FP8), "scale vectors (mm1_rs_kernel): the ungated fp8 form only");
-    static_assert(ACTK || GLU || ACT == 0, "mm1_kernel computes tanh-GeLU only");
-    static_assert(std::is_same<P, Mm1GluF8Params>::value == (GLU && FP8), "the gated fp8 form, and only it, takes Mm1GluF8Params");
+    static_assert(ACT < 0 || NW == 4, "mm1_form_kernel has 4 waves");
+    static_assert(ACT >= 0 || (!GLU && !RS), "mm1_kernel is ungated and takes scalar scales");
+    static_assert(!RS || (FP8 && !GLU), "scale vectors: the ungated fp8 form only");
     static uint64_t lds_set = 0;
     ensure_dynamic_lds((const void *)kern, LDS, lds_set);
     P p = p0;
@@ -1725,7 +1613,7 @@ int launch_mm1_variant(const P &p0, hipStream_t s, bool *cache_updated = nullptr
     const int tiles_per_xcd = (B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8;
     const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
     if constexpr (BATCHED) {
-        typename Mm1BatchOf<P>::type q;
+        typename Mm1Block<FP8 && GLU, true>::type q;
         static_cast<P &>(q) = p;
         q.B = B, q.cache_bs = cache_bs;
         hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(NW * 64), LDS, s, q);
@@ -1739,19 +1627,36 @@ int launch_mm1_variant(const P &p0, hipStream_t s, bool *cache_updated = nullptr
 }  // namespace
 
 namespace {
-// `ragged`: the *_ragged entries' contract (any M, cache pitch ldc); otherwise the reference's (M % 128 == 0, ldc == M)
-int mm1_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
-              const int32_t *counts, int M, int K, int F, int ldc, bool ragged, hipStream_t stream, int update_cache, bool *cache_updated,
-              int B = 0, int64_t cache_bs = 0) {   // B > 0: the *_batched entries
-    CM_CHECK(a && b && c && bias && pa_cache, "csp_mlp_mm1: null tensor pointer");
+// What every GEMM1 entry checks behind its null pointers, `who` being the entry's name in the messages.  ragged: the *_ragged entries'
+// contract (any M), otherwise the reference's (M % 128 == 0); B > 0: a *_batched entry; KM: what K must be a multiple of; coded: the entry
+// takes an activation code, act; upd_max: the largest update_cache (< 0: the library's own value, not checked).  The two entries of the
+// reference's contract (not coded) look at K first and do not print the update_cache they refuse.
+int check_mm1(const char *who, bool ragged, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int B,
+              int64_t cache_bs, int KM, bool coded, int act, int update_cache, int upd_max) {
     if (int e = ragged ? check_mlp_ragged(M, F, indices, counts) : check_mlp_common(M, F, indices, counts)) return e;
     if (int e = check_cache_pitch(M, F, ldc)) return e;
     if (B > 0) {
         if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
     }
-    CM_CHECK(K > 0 && K % 64 == 0, "csp_mlp_mm1: K must be a positive multiple of 64 (got %d)", K);
+    if (coded) {
+        CM_CHECK(act == CHIPMUNK_ACT_GELU_TANH || act == CHIPMUNK_ACT_SILU || act == CHIPMUNK_ACT_GELU_ERF,
+                 "%s: unknown activation %d (0 = gelu_tanh, 1 = silu, 2 = gelu)", who, act);
+        CM_CHECK(update_cache >= 0 && update_cache <= upd_max, "%s: update_cache must be %s (got %d)", who, upd_max == 2 ? "0, 1 or 2" : "0 or 1",
+                 update_cache);
+    }
+    CM_CHECK(K > 0 && K % KM == 0, "%s: K must be a positive multiple of %d (got %d)", who, KM, K);
+    if (!coded && upd_max >= 0) CM_CHECK(update_cache >= 0 && update_cache <= upd_max, "%s: update_cache must be 0, 1 or 2", who);
     CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
-             "csp_mlp_mm1: operand too large for 32-bit offsets");
+             "%s: operand too large for 32-bit offsets", who);
+    return CHIPMUNK_OK;
+}
+
+// `ragged`: the *_ragged entries' contract (any M, cache pitch ldc); otherwise the reference's (M % 128 == 0, ldc == M)
+int mm1_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+              const int32_t *counts, int M, int K, int F, int ldc, bool ragged, hipStream_t stream, int update_cache, bool *cache_updated,
+              int B = 0, int64_t cache_bs = 0) {   // B > 0: the *_batched entries
+    CM_CHECK(a && b && c && bias && pa_cache, "csp_mlp_mm1: null tensor pointer");
+    if (int e = check_mm1("csp_mlp_mm1", ragged, indices, counts, M, K, F, ldc, B, cache_bs, 64, false, 0, update_cache, -1)) return e;
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, chipmunk_get_option("mm1_probe"), 0, update_cache, nullptr, nullptr, ldc};
     if (B > 0) return launch_mm1_variant<128, 64, 2, 2, false, 4, true>(p, stream, cache_updated, B, cache_bs);   // the shipped form only
@@ -1798,15 +1703,7 @@ int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void 
                   const int32_t *counts, const float *scale_a, const float *scale_b, int M, int K, int F, int ldc, bool ragged,
                   int update_cache, hipStream_t stream, int B = 0, int64_t cache_bs = 0) {
     CM_CHECK(a && b && c && bias && pa_cache && scale_a && scale_b, "csp_mlp_mm1_fp8: null tensor pointer");
-    if (int e = ragged ? check_mlp_ragged(M, F, indices, counts) : check_mlp_common(M, F, indices, counts)) return e;
-    if (int e = check_cache_pitch(M, F, ldc)) return e;
-    if (B > 0) {
-        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
-    }
-    CM_CHECK(K > 0 && K % 128 == 0, "csp_mlp_mm1_fp8: K must be a positive multiple of 128 (got %d)", K);
-    CM_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8: update_cache must be 0, 1 or 2");
-    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
-             "csp_mlp_mm1_fp8: operand too large for 32-bit offsets");
+    if (int e = check_mm1("csp_mlp_mm1_fp8", ragged, indices, counts, M, K, F, ldc, B, cache_bs, 128, false, 0, update_cache, 2)) return e;
     // same tile machinery as the bf16 kernel (buffer-form DMA, tail split, staged epilogue); a k step is 128 fp8 values
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache, (uint16_t *)c,
                    indices, counts, M, K, F, 0, 0, chipmunk_get_option("mm1_probe"), 0, update_cache == 1 ? 2 : update_cache == 2 ? 1 : 0, scale_a, scale_b, ldc};
@@ -1821,118 +1718,70 @@ int mm1_fp8_entry(const void *a, const void *b, void *c, const void *bias, void 
     return launch_mm1_variant<128, 64, 2, 2, true>(p, stream);
 }
 
-// Ungated GEMM1 with an activation code and a nullable bias (mm1_act_kernel): the *_ragged / *_batched contract, the shipped tile shape only
-// (option mm1_variant is ignored; the probe-forms library does not carry these kernels)
-#ifndef CHIPMUNK_MM1_PROBES
-template <bool FP8, bool BATCHED, bool RS = false>   // RS: scale_a [M] / scale_b [F] vectors (fp8 only)
-int launch_mm1_act(const Mm1Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
+// The forms behind mm1_form_kernel -- an activation code, a nullable bias, the *_ragged / *_batched contract --, the shipped tile shape only
+// (option mm1_variant is ignored): the activation code becomes the kernel's template argument here
+template <bool FP8, bool GLU, bool RS, bool BATCHED>
+int launch_mm1_form_b(const typename Mm1Block<FP8 && GLU, false>::type &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
+#ifdef CHIPMUNK_MM1_PROBES
+    if constexpr (!GLU) {   // the probe-forms library does not carry the ungated forms
+        CM_CHECK(false, "csp_mlp_mm1_act: not part of the probe-forms library");
+        return CHIPMUNK_OK;
+    } else
+#endif
     switch (act) {
-        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 0, Mm1Params, true, RS>(p, stream, nullptr, B, cache_bs);
-        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 1, Mm1Params, true, RS>(p, stream, nullptr, B, cache_bs);
-        default: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, false, 2, Mm1Params, true, RS>(p, stream, nullptr, B, cache_bs);
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, GLU, 0, RS>(p, stream, nullptr, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, GLU, 1, RS>(p, stream, nullptr, B, cache_bs);
+        default: return launch_mm1_variant<128, 64, 2, 2, FP8, 4, BATCHED, GLU, 2, RS>(p, stream, nullptr, B, cache_bs);
     }
 }
-#else
-template <bool FP8, bool BATCHED, bool RS = false>
-int launch_mm1_act(const Mm1Params &, int, hipStream_t, int, int64_t) {
-    CM_CHECK(false, "csp_mlp_mm1_act: not part of the probe-forms library");
-    return CHIPMUNK_OK;
+// (B > 0: the *_batched entries)
+template <bool FP8, bool GLU, bool RS = false>
+int launch_mm1_form(const typename Mm1Block<FP8 && GLU, false>::type &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
+    return B > 0 ? launch_mm1_form_b<FP8, GLU, RS, true>(p, act, stream, B, cache_bs) : launch_mm1_form_b<FP8, GLU, RS, false>(p, act, stream, 1, 0);
 }
-#endif
-// scale_a / scale_b null: the bf16 form (update_cache 0 / 1); both given: the e4m3 form (update_cache 0 / 1 / 2 as chipmunk_csp_mlp_mm1_fp8)
+
+// Ungated.  scale_a / scale_b null: the bf16 form (update_cache 0 / 1); both given: the e4m3 form (update_cache 0 / 1 / 2 as chipmunk_csp_mlp_mm1_fp8)
 int mm1_act_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices, const int32_t *counts,
                   const float *scale_a, const float *scale_b, bool fp8, int M, int K, int F, int ldc, int act, int update_cache,
                   hipStream_t stream, int B = 0, int64_t cache_bs = 0, bool rs = false) {   // B > 0: the *_batched entries; rs: the *_rs entries
     if (fp8) CM_CHECK(a && b && c && pa_cache && scale_a && scale_b, "csp_mlp_mm1_fp8_act: null tensor or scale pointer");
     else CM_CHECK(a && b && c && pa_cache, "csp_mlp_mm1_act: null tensor pointer");
     CM_CHECK(!rs || (((uintptr_t)scale_a | (uintptr_t)scale_b) & 3) == 0, "csp_mlp_mm1_fp8_act_rs: scale_a and scale_b must be 4-byte aligned");
-    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
-    if (int e = check_cache_pitch(M, F, ldc)) return e;
-    if (B > 0) {
-        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
-    }
-    const char *who = fp8 ? "csp_mlp_mm1_fp8_act" : "csp_mlp_mm1_act";
-    CM_CHECK(act == CHIPMUNK_ACT_GELU_TANH || act == CHIPMUNK_ACT_SILU || act == CHIPMUNK_ACT_GELU_ERF,
-             "%s: unknown activation %d (0 = gelu_tanh, 1 = silu, 2 = gelu)", who, act);
-    if (fp8) {
-        CM_CHECK(update_cache >= 0 && update_cache <= 2, "csp_mlp_mm1_fp8_act: update_cache must be 0, 1 or 2 (got %d)", update_cache);
-        CM_CHECK(K > 0 && K % 128 == 0, "csp_mlp_mm1_fp8_act: K must be a positive multiple of 128 (got %d)", K);
-    } else {
-        CM_CHECK(update_cache == 0 || update_cache == 1, "csp_mlp_mm1_act: update_cache must be 0 or 1 (got %d)", update_cache);
-        CM_CHECK(K > 0 && K % 64 == 0, "csp_mlp_mm1_act: K must be a positive multiple of 64 (got %d)", K);
-    }
-    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
-             "%s: operand too large for 32-bit offsets", who);
+    if (int e = check_mm1(fp8 ? "csp_mlp_mm1_fp8_act" : "csp_mlp_mm1_act", true, indices, counts, M, K, F, ldc, B, cache_bs, fp8 ? 128 : 64, true, act,
+                          update_cache, fp8 ? 2 : 1))
+        return e;
     // the kernel's update_cache: 1 = scatter-add of the deltas, 2 (fp8) = store the new activation -- the fp8 entries' 2 and 1
     const int upd = fp8 ? (update_cache == 1 ? 2 : update_cache == 2 ? 1 : 0) : update_cache;
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, upd, scale_a, scale_b, ldc};
-    if (rs) return B > 0 ? launch_mm1_act<true, true, true>(p, act, stream, B, cache_bs) : launch_mm1_act<true, false, true>(p, act, stream, 1, 0);
-    if (fp8) return B > 0 ? launch_mm1_act<true, true>(p, act, stream, B, cache_bs) : launch_mm1_act<true, false>(p, act, stream, 1, 0);
-    return B > 0 ? launch_mm1_act<false, true>(p, act, stream, B, cache_bs) : launch_mm1_act<false, false>(p, act, stream, 1, 0);
+    if (rs) return launch_mm1_form<true, false, true>(p, act, stream, B, cache_bs);
+    return fp8 ? launch_mm1_form<true, false>(p, act, stream, B, cache_bs) : launch_mm1_form<false, false>(p, act, stream, B, cache_bs);
 }
 
-// Gated GEMM1 (SwiGLU / GEGLU): the *_ragged / *_batched contract, bf16 (the e4m3 form is mm1_glu_fp8_entry below), the shipped tile shape only
-template <bool BATCHED>
-int launch_mm1_glu(const Mm1Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
-    switch (act) {
-        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, false, 4, BATCHED, true, 0>(p, stream, nullptr, B, cache_bs);
-        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, false, 4, BATCHED, true, 1>(p, stream, nullptr, B, cache_bs);
-        default: return launch_mm1_variant<128, 64, 2, 2, false, 4, BATCHED, true, 2>(p, stream, nullptr, B, cache_bs);
-    }
-}
+// Gated (SwiGLU / GEGLU), bf16
 int mm1_glu_entry(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
                   const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream,
                   int B = 0, int64_t cache_bs = 0) {   // B > 0: the *_batched entry
     CM_CHECK(a && b_gate && b_up && c && pa_cache, "csp_mlp_mm1_glu: null tensor pointer");
-    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
-    if (int e = check_cache_pitch(M, F, ldc)) return e;
-    if (B > 0) {
-        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
-    }
-    CM_CHECK(act == CHIPMUNK_ACT_GELU_TANH || act == CHIPMUNK_ACT_SILU || act == CHIPMUNK_ACT_GELU_ERF,
-             "csp_mlp_mm1_glu: unknown activation %d (0 = gelu_tanh, 1 = silu, 2 = gelu)", act);
-    CM_CHECK(update_cache == 0 || update_cache == 1, "csp_mlp_mm1_glu: update_cache must be 0 or 1 (got %d)", update_cache);
-    CM_CHECK(K > 0 && K % 64 == 0, "csp_mlp_mm1_glu: K must be a positive multiple of 64 (got %d)", K);
-    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
-             "csp_mlp_mm1_glu: operand too large for 32-bit offsets");
+    if (int e = check_mm1("csp_mlp_mm1_glu", true, indices, counts, M, K, F, ldc, B, cache_bs, 64, true, act, update_cache, 1)) return e;
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b_gate, (const uint16_t *)bias_gate, (uint16_t *)pa_cache,
                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
     p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
-    return B > 0 ? launch_mm1_glu<true>(p, act, stream, B, cache_bs) : launch_mm1_glu<false>(p, act, stream, 1, 0);
+    return launch_mm1_form<false, true>(p, act, stream, B, cache_bs);
 }
 
-// Gated fp8 GEMM1: the contract of mm1_glu_entry with e4m3 a / weights (1 byte per element), K % 128 as csp_mlp_mm1_fp8, and the three
-// reciprocal quantisation scales; the shipped tile shape only (option mm1_variant is ignored)
-template <bool BATCHED>
-int launch_mm1_glu_fp8(const Mm1GluF8Params &p, int act, hipStream_t stream, int B, int64_t cache_bs) {
-    switch (act) {
-        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_variant<128, 64, 2, 2, true, 4, BATCHED, true, 0>(p, stream, nullptr, B, cache_bs);
-        case CHIPMUNK_ACT_SILU: return launch_mm1_variant<128, 64, 2, 2, true, 4, BATCHED, true, 1>(p, stream, nullptr, B, cache_bs);
-        default: return launch_mm1_variant<128, 64, 2, 2, true, 4, BATCHED, true, 2>(p, stream, nullptr, B, cache_bs);
-    }
-}
+// Gated, e4m3 a / weights (1 byte per element): K % 128 as csp_mlp_mm1_fp8, and the three reciprocal quantisation scales
 int mm1_glu_fp8_entry(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
                       const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b_gate, const float *scale_b_up,
                       int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream, int B = 0, int64_t cache_bs = 0) {
     CM_CHECK(a && b_gate && b_up && c && pa_cache && scale_a && scale_b_gate && scale_b_up, "csp_mlp_mm1_glu_fp8: null tensor or scale pointer");
-    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
-    if (int e = check_cache_pitch(M, F, ldc)) return e;
-    if (B > 0) {
-        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
-    }
-    CM_CHECK(act == CHIPMUNK_ACT_GELU_TANH || act == CHIPMUNK_ACT_SILU || act == CHIPMUNK_ACT_GELU_ERF,
-             "csp_mlp_mm1_glu_fp8: unknown activation %d (0 = gelu_tanh, 1 = silu, 2 = gelu)", act);
-    CM_CHECK(update_cache == 0 || update_cache == 1, "csp_mlp_mm1_glu_fp8: update_cache must be 0 or 1 (got %d)", update_cache);
-    CM_CHECK(K > 0 && K % 128 == 0, "csp_mlp_mm1_glu_fp8: K must be a positive multiple of 128 (got %d)", K);
-    CM_CHECK((int64_t)F * K < (1ll << 31) && (int64_t)M * K < (1ll << 31) && (int64_t)F * ldc < (1ll << 31),
-             "csp_mlp_mm1_glu_fp8: operand too large for 32-bit offsets");
+    if (int e = check_mm1("csp_mlp_mm1_glu_fp8", true, indices, counts, M, K, F, ldc, B, cache_bs, 128, true, act, update_cache, 1)) return e;
     Mm1GluF8Params p;
     static_cast<Mm1Params &>(p) = {(const uint16_t *)a, (const uint16_t *)b_gate, (const uint16_t *)bias_gate, (uint16_t *)pa_cache,
                                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
     p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
     p.scale_x = scale_a, p.scale_gate = scale_b_gate, p.scale_up = scale_b_up;
-    return B > 0 ? launch_mm1_glu_fp8<true>(p, act, stream, B, cache_bs) : launch_mm1_glu_fp8<false>(p, act, stream, 1, 0);
+    return launch_mm1_form<true, true>(p, act, stream, B, cache_bs);
 }
 }  // namespace
 

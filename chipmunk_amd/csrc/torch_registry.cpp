@@ -340,159 +340,121 @@ Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c
     return mm1_shape(a, b, c, &bias, cache, indices, counts);
 }
 
-// reference csrc/mlp/csp_mlp_mm1.cu:625-702
-void csp_mlp_mm1(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
-                 at::Tensor indices, at::Tensor indices_counts) {
-    CHECK_DEV(a); CHECK_DEV(b_colmajor); CHECK_DEV(c); CHECK_DEV(bias); CHECK_DEV(pa_cache_colmajor);
-    CHECK_DEV(indices); CHECK_DEV(indices_counts);
-    CHECK_BF16(a); CHECK_BF16(b_colmajor); CHECK_BF16(c); CHECK_BF16(bias); CHECK_BF16(pa_cache_colmajor);
-    CHECK_I32(indices); CHECK_I32(indices_counts);
-    CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias);
-    CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
-    const Mm1Shape sh = mm1_shape(a, b_colmajor, c, bias, pa_cache_colmajor, indices, indices_counts);
-    const int64_t M = sh.M, K = sh.K, F = sh.F, ldc = sh.ldc;
-    c10::DeviceGuard guard(a.device());
-    if (sh.batched())
-        check(chipmunk_csp_mlp_mm1_batched(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                                           pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                                           (int)M, (int)K, (int)F, (int)ldc, (int)sh.B, sh.cache_bs, cur_stream(a)),
-              "csp_mlp_mm1");
-    else if (whole_groups(M, ldc))
-        check(chipmunk_csp_mlp_mm1(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                                   pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                                   (int)M, (int)K, (int)F, cur_stream(a)),
-              "csp_mlp_mm1");
-    else
-        check(chipmunk_csp_mlp_mm1_ragged(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                                          pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                                          (int)M, (int)K, (int)F, (int)ldc, cur_stream(a)),
-              "csp_mlp_mm1");
-}
-
-// addition: GEMM1 + the scatter-add of its output into the activation cache, one kernel
-void csp_mlp_mm1_scatter(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
-                         at::Tensor indices, at::Tensor indices_counts) {
-    CHECK_DEV(a); CHECK_DEV(b_colmajor); CHECK_DEV(c); CHECK_DEV(bias); CHECK_DEV(pa_cache_colmajor);
-    CHECK_DEV(indices); CHECK_DEV(indices_counts);
-    CHECK_BF16(a); CHECK_BF16(b_colmajor); CHECK_BF16(c); CHECK_BF16(bias); CHECK_BF16(pa_cache_colmajor);
-    CHECK_I32(indices); CHECK_I32(indices_counts);
-    CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias);
-    CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
-    const Mm1Shape sh = mm1_shape(a, b_colmajor, c, bias, pa_cache_colmajor, indices, indices_counts);
-    const int64_t M = sh.M, K = sh.K, F = sh.F, ldc = sh.ldc;
-    c10::DeviceGuard guard(a.device());
-    if (sh.batched())
-        check(chipmunk_csp_mlp_mm1_scatter_batched(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                                                   pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                                                   (int)M, (int)K, (int)F, (int)ldc, (int)sh.B, sh.cache_bs, cur_stream(a)),
-              "csp_mlp_mm1_scatter");
-    else if (whole_groups(M, ldc))
-        check(chipmunk_csp_mlp_mm1_scatter(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                                           pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
-                                           indices_counts.data_ptr<int>(), (int)M, (int)K, (int)F, cur_stream(a)),
-              "csp_mlp_mm1_scatter");
-    else
-        check(chipmunk_csp_mlp_mm1_scatter_ragged(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(),
-                                                  pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(),
-                                                  indices_counts.data_ptr<int>(), (int)M, (int)K, (int)F, (int)ldc, cur_stream(a)),
-              "csp_mlp_mm1_scatter");
-}
-
-// addition: gated GEMM1 (SwiGLU / GEGLU), c = bf16(act(a b_gate^T + bias_gate) * (a b_up^T + bias_up) - cache); update_cache also applies
-// the scatter-add of c to the cache.  2-D operands or the 3-D batch, the cache checks of csp_mlp_mm1; bf16 only.
-void csp_mlp_mm1_glu(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor c, const c10::optional<at::Tensor> &bias_gate,
-                     const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache_colmajor, at::Tensor indices, at::Tensor indices_counts,
-                     std::string act, bool update_cache) {
-    CHECK_DEV(a); CHECK_DEV(b_gate); CHECK_DEV(b_up); CHECK_DEV(c); CHECK_DEV(pa_cache_colmajor);
-    CHECK_DEV(indices); CHECK_DEV(indices_counts);
-    CHECK_BF16(a); CHECK_BF16(b_gate); CHECK_BF16(b_up); CHECK_BF16(c); CHECK_BF16(pa_cache_colmajor);
-    CHECK_I32(indices); CHECK_I32(indices_counts);
-    CHECK_CONTIG(a); CHECK_CONTIG(b_gate); CHECK_CONTIG(b_up); CHECK_CONTIG(c);
-    CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
-    const Mm1Shape sh = mm1_shape(a, b_gate, c, nullptr, pa_cache_colmajor, indices, indices_counts);
-    TORCH_CHECK(b_up.dim() == 2 && b_up.size(0) == sh.F && b_up.size(1) == sh.K, "b_up must have the shape of b_gate ([F, K])");
-    const void *bg = nullptr, *bu = nullptr;
-    if (bias_gate.has_value()) {
-        const at::Tensor &t = *bias_gate;
-        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
-        TORCH_CHECK(t.numel() == sh.F, "bias_gate must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
-        bg = t.data_ptr();
-    }
-    if (bias_up.has_value()) {
-        const at::Tensor &t = *bias_up;
-        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
-        TORCH_CHECK(t.numel() == sh.F, "bias_up must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
-        bu = t.data_ptr();
-    }
+// activation by name -> CHIPMUNK_ACT_*; who: the operator's name for the message
+static int act_code(const char *who, const std::string &act) {
     int code = -1;
     if (act == "gelu_tanh") code = CHIPMUNK_ACT_GELU_TANH;
     else if (act == "silu") code = CHIPMUNK_ACT_SILU;
     else if (act == "gelu") code = CHIPMUNK_ACT_GELU_ERF;
-    TORCH_CHECK(code >= 0, "csp_mlp_mm1_glu: unknown activation '", act, "' (one of gelu_tanh, silu, gelu)");
-    c10::DeviceGuard guard(a.device());
-    if (sh.batched())
-        check(chipmunk_csp_mlp_mm1_glu_batched(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
-                                               pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                                               (int)sh.M, (int)sh.K, (int)sh.F, (int)sh.ldc, code, update_cache ? 1 : 0, (int)sh.B,
-                                               sh.cache_bs, cur_stream(a)),
-              "csp_mlp_mm1_glu");
-    else
-        check(chipmunk_csp_mlp_mm1_glu(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
-                                       pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                                       (int)sh.M, (int)sh.K, (int)sh.F, (int)sh.ldc, code, update_cache ? 1 : 0, cur_stream(a)),
-              "csp_mlp_mm1_glu");
+    TORCH_CHECK(code >= 0, who, ": unknown activation '", act, "' (one of gelu_tanh, silu, gelu)");
+    return code;
+}
+// an optional bias vector (bf16, F entries; name: the argument's, for the message): its pointer, null when it is not given
+static const void *optional_bias(const c10::optional<at::Tensor> &bias, const char *name, int64_t F) {
+    if (!bias.has_value()) return nullptr;
+    const at::Tensor &t = *bias;
+    CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
+    TORCH_CHECK(t.numel() == F, name, " must have F entries (got ", t.numel(), ", F = ", F, ")");
+    return t.data_ptr();
 }
 
-// addition: the gated GEMM1 over fp8 projections -- a, b_gate, b_up float8_e4m3fn, the three reciprocal quantisation scales as
-// one-element float32 device tensors; everything else as csp_mlp_mm1_glu (which keeps refusing fp8 operands)
-void csp_mlp_mm1_glu_fp8(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor c, const c10::optional<at::Tensor> &bias_gate,
-                         const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache_colmajor, at::Tensor indices, at::Tensor indices_counts,
-                         at::Tensor scale_a, at::Tensor scale_b_gate, at::Tensor scale_b_up, std::string act, bool update_cache) {
+// csp_mlp_mm1 (reference csrc/mlp/csp_mlp_mm1.cu:625-702) and csp_mlp_mm1_scatter: the same operands and checks in front of the
+// operator's three C entries -- the batch, whole groups (the reference's contract), everything else
+template <auto BATCHED, auto WHOLE, auto RAGGED>
+static void mm1_impl(const char *who, at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
+                     at::Tensor indices, at::Tensor indices_counts) {
+    CHECK_DEV(a); CHECK_DEV(b_colmajor); CHECK_DEV(c); CHECK_DEV(bias); CHECK_DEV(pa_cache_colmajor);
+    CHECK_DEV(indices); CHECK_DEV(indices_counts);
+    CHECK_BF16(a); CHECK_BF16(b_colmajor); CHECK_BF16(c); CHECK_BF16(bias); CHECK_BF16(pa_cache_colmajor);
+    CHECK_I32(indices); CHECK_I32(indices_counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(b_colmajor); CHECK_CONTIG(c); CHECK_CONTIG(bias);
+    CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
+    const Mm1Shape sh = mm1_shape(a, b_colmajor, c, bias, pa_cache_colmajor, indices, indices_counts);
+    const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc;
+    int *ip = indices.data_ptr<int>(), *cp = indices_counts.data_ptr<int>();
+    c10::DeviceGuard guard(a.device());
+    if (sh.batched())
+        check(BATCHED(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(), pa_cache_colmajor.data_ptr(), ip, cp, M, K, F, ldc,
+                      (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (whole_groups(sh.M, sh.ldc))
+        check(WHOLE(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(), pa_cache_colmajor.data_ptr(), ip, cp, M, K, F,
+                    cur_stream(a)), who);
+    else
+        check(RAGGED(a.data_ptr(), b_colmajor.data_ptr(), c.data_ptr(), bias.data_ptr(), pa_cache_colmajor.data_ptr(), ip, cp, M, K, F, ldc,
+                     cur_stream(a)), who);
+}
+void csp_mlp_mm1(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
+                 at::Tensor indices, at::Tensor indices_counts) {
+    mm1_impl<chipmunk_csp_mlp_mm1_batched, chipmunk_csp_mlp_mm1, chipmunk_csp_mlp_mm1_ragged>(
+        "csp_mlp_mm1", a, b_colmajor, c, bias, pa_cache_colmajor, indices, indices_counts);
+}
+// addition: GEMM1 + the scatter-add of its output into the activation cache, one kernel
+void csp_mlp_mm1_scatter(at::Tensor a, at::Tensor b_colmajor, at::Tensor c, at::Tensor bias, at::Tensor pa_cache_colmajor,
+                         at::Tensor indices, at::Tensor indices_counts) {
+    mm1_impl<chipmunk_csp_mlp_mm1_scatter_batched, chipmunk_csp_mlp_mm1_scatter, chipmunk_csp_mlp_mm1_scatter_ragged>(
+        "csp_mlp_mm1_scatter", a, b_colmajor, c, bias, pa_cache_colmajor, indices, indices_counts);
+}
+
+// addition: gated GEMM1 (SwiGLU / GEGLU), c = bf16(act(a b_gate^T + bias_gate) * (a b_up^T + bias_up) - cache); update_cache also applies
+// the scatter-add of c to the cache.  2-D operands or the 3-D batch, the cache checks of csp_mlp_mm1.  bf16 operands (csp_mlp_mm1_glu, which
+// refuses fp8 ones), or -- scales given -- a, b_gate, b_up float8_e4m3fn with the three reciprocal quantisation scales as one-element
+// float32 device tensors (csp_mlp_mm1_glu_fp8).
+static void mm1_glu_impl(const char *who, at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor c,
+                         const c10::optional<at::Tensor> &bias_gate, const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache_colmajor,
+                         at::Tensor indices, at::Tensor indices_counts, const at::Tensor *scale_a, const at::Tensor *scale_b_gate,
+                         const at::Tensor *scale_b_up, const std::string &act, bool update_cache) {
+    const bool fp8 = scale_a != nullptr;
     CHECK_DEV(a); CHECK_DEV(b_gate); CHECK_DEV(b_up); CHECK_DEV(c); CHECK_DEV(pa_cache_colmajor);
     CHECK_DEV(indices); CHECK_DEV(indices_counts);
-    TORCH_CHECK(a.scalar_type() == at::kFloat8_e4m3fn && b_gate.scalar_type() == at::kFloat8_e4m3fn && b_up.scalar_type() == at::kFloat8_e4m3fn,
-                "csp_mlp_mm1_glu_fp8: a, b_gate and b_up must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+    if (fp8) {
+        TORCH_CHECK(a.scalar_type() == at::kFloat8_e4m3fn && b_gate.scalar_type() == at::kFloat8_e4m3fn && b_up.scalar_type() == at::kFloat8_e4m3fn,
+                    who, ": a, b_gate and b_up must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+    } else {
+        CHECK_BF16(a); CHECK_BF16(b_gate); CHECK_BF16(b_up);
+    }
     CHECK_BF16(c); CHECK_BF16(pa_cache_colmajor);
     CHECK_I32(indices); CHECK_I32(indices_counts);
     CHECK_CONTIG(a); CHECK_CONTIG(b_gate); CHECK_CONTIG(b_up); CHECK_CONTIG(c);
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
-    for (const at::Tensor *s : {&scale_a, &scale_b_gate, &scale_b_up})
-        TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->numel() == 1,
-                    "csp_mlp_mm1_glu_fp8: scale_a, scale_b_gate and scale_b_up must be one-element float32 tensors on the GPU");
+    if (fp8)
+        for (const at::Tensor *s : {scale_a, scale_b_gate, scale_b_up})
+            TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->numel() == 1, who,
+                        ": scale_a, scale_b_gate and scale_b_up must be one-element float32 tensors on the GPU");
     const Mm1Shape sh = mm1_shape(a, b_gate, c, nullptr, pa_cache_colmajor, indices, indices_counts);
     TORCH_CHECK(b_up.dim() == 2 && b_up.size(0) == sh.F && b_up.size(1) == sh.K, "b_up must have the shape of b_gate ([F, K])");
-    const void *bg = nullptr, *bu = nullptr;
-    if (bias_gate.has_value()) {
-        const at::Tensor &t = *bias_gate;
-        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
-        TORCH_CHECK(t.numel() == sh.F, "bias_gate must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
-        bg = t.data_ptr();
-    }
-    if (bias_up.has_value()) {
-        const at::Tensor &t = *bias_up;
-        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
-        TORCH_CHECK(t.numel() == sh.F, "bias_up must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
-        bu = t.data_ptr();
-    }
-    int code = -1;
-    if (act == "gelu_tanh") code = CHIPMUNK_ACT_GELU_TANH;
-    else if (act == "silu") code = CHIPMUNK_ACT_SILU;
-    else if (act == "gelu") code = CHIPMUNK_ACT_GELU_ERF;
-    TORCH_CHECK(code >= 0, "csp_mlp_mm1_glu_fp8: unknown activation '", act, "' (one of gelu_tanh, silu, gelu)");
+    const void *bg = optional_bias(bias_gate, "bias_gate", sh.F), *bu = optional_bias(bias_up, "bias_up", sh.F);
+    const int code = act_code(who, act);
     c10::DeviceGuard guard(a.device());
-    if (sh.batched())
+    int *ip = indices.data_ptr<int>(), *cp = indices_counts.data_ptr<int>();
+    const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc, upd = update_cache ? 1 : 0;
+    if (fp8 && sh.batched())
         check(chipmunk_csp_mlp_mm1_glu_fp8_batched(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
-                                                   pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                                                   scale_a.data_ptr<float>(), scale_b_gate.data_ptr<float>(), scale_b_up.data_ptr<float>(),
-                                                   (int)sh.M, (int)sh.K, (int)sh.F, (int)sh.ldc, code, update_cache ? 1 : 0, (int)sh.B,
-                                                   sh.cache_bs, cur_stream(a)),
-              "csp_mlp_mm1_glu_fp8");
+                                                   pa_cache_colmajor.data_ptr(), ip, cp, scale_a->data_ptr<float>(),
+                                                   scale_b_gate->data_ptr<float>(), scale_b_up->data_ptr<float>(), M, K, F, ldc, code, upd,
+                                                   (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (fp8)
+        check(chipmunk_csp_mlp_mm1_glu_fp8(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu, pa_cache_colmajor.data_ptr(),
+                                           ip, cp, scale_a->data_ptr<float>(), scale_b_gate->data_ptr<float>(),
+                                           scale_b_up->data_ptr<float>(), M, K, F, ldc, code, upd, cur_stream(a)), who);
+    else if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_glu_batched(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
+                                               pa_cache_colmajor.data_ptr(), ip, cp, M, K, F, ldc, code, upd, (int)sh.B, sh.cache_bs,
+                                               cur_stream(a)), who);
     else
-        check(chipmunk_csp_mlp_mm1_glu_fp8(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
-                                           pa_cache_colmajor.data_ptr(), indices.data_ptr<int>(), indices_counts.data_ptr<int>(),
-                                           scale_a.data_ptr<float>(), scale_b_gate.data_ptr<float>(), scale_b_up.data_ptr<float>(),
-                                           (int)sh.M, (int)sh.K, (int)sh.F, (int)sh.ldc, code, update_cache ? 1 : 0, cur_stream(a)),
-              "csp_mlp_mm1_glu_fp8");
+        check(chipmunk_csp_mlp_mm1_glu(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu, pa_cache_colmajor.data_ptr(), ip,
+                                       cp, M, K, F, ldc, code, upd, cur_stream(a)), who);
+}
+void csp_mlp_mm1_glu(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor c, const c10::optional<at::Tensor> &bias_gate,
+                     const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache_colmajor, at::Tensor indices, at::Tensor indices_counts,
+                     std::string act, bool update_cache) {
+    mm1_glu_impl("csp_mlp_mm1_glu", a, b_gate, b_up, c, bias_gate, bias_up, pa_cache_colmajor, indices, indices_counts, nullptr, nullptr, nullptr,
+                 act, update_cache);
+}
+void csp_mlp_mm1_glu_fp8(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor c, const c10::optional<at::Tensor> &bias_gate,
+                         const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache_colmajor, at::Tensor indices, at::Tensor indices_counts,
+                         at::Tensor scale_a, at::Tensor scale_b_gate, at::Tensor scale_b_up, std::string act, bool update_cache) {
+    mm1_glu_impl("csp_mlp_mm1_glu_fp8", a, b_gate, b_up, c, bias_gate, bias_up, pa_cache_colmajor, indices, indices_counts, &scale_a,
+                 &scale_b_gate, &scale_b_up, act, update_cache);
 }
 
 // native counterpart of the reference's Triton csp_mlp_mm1_fp8 (src/chipmunk/triton/csp_mlp_mm1.py:143-164)
@@ -576,18 +538,8 @@ static void mm1_act_impl(const char *who, at::Tensor a, at::Tensor b, at::Tensor
     CHECK_CONTIG(a); CHECK_CONTIG(b); CHECK_CONTIG(c);
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
     const Mm1Shape sh = mm1_shape(a, b, c, nullptr, pa_cache_colmajor, indices, indices_counts);
-    const void *bp = nullptr;
-    if (bias.has_value()) {
-        const at::Tensor &t = *bias;
-        CHECK_DEV(t); CHECK_BF16(t); CHECK_CONTIG(t);
-        TORCH_CHECK(t.numel() == sh.F, "bias must have F entries (got ", t.numel(), ", F = ", sh.F, ")");
-        bp = t.data_ptr();
-    }
-    int code = -1;
-    if (act == "gelu_tanh") code = CHIPMUNK_ACT_GELU_TANH;
-    else if (act == "silu") code = CHIPMUNK_ACT_SILU;
-    else if (act == "gelu") code = CHIPMUNK_ACT_GELU_ERF;
-    TORCH_CHECK(code >= 0, who, ": unknown activation '", act, "' (one of gelu_tanh, silu, gelu)");
+    const void *bp = optional_bias(bias, "bias", sh.F);
+    const int code = act_code(who, act);
     c10::DeviceGuard guard(a.device());
     int *ip = indices.data_ptr<int>(), *cp = indices_counts.data_ptr<int>();
     const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc;

@@ -174,6 +174,33 @@ def mm2_unfused(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, cached_out
     csp_mlp_mm2(sparse_act_packed, fc2wT, indices, counts, cached_out, 132 - num_sms_scatter_add)
 
 
+def _check_batch(x: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor) -> None:
+    """``x`` is ``[M, K]`` or a batch ``[B, M, K]``, and a batch takes every other per-sequence tensor with the same leading ``B``."""
+    assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
+    if x.ndim == 3:
+        B = x.shape[0]
+        assert indices.ndim == 3 and counts.ndim == 2 and sparse_act_T.ndim == 3 and cached_out.ndim == 3, \
+            "a batched x [B, M, K] takes indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] and cached_out [B, M, N]"
+        assert indices.shape[0] == B and counts.shape[0] == B and sparse_act_T.shape[0] == B and cached_out.shape[0] == B, \
+            f"the batch size of indices / counts / sparse_act_T / cached_out must be that of x ({B})"
+
+
+def _after_gemm1(cache_updated: bool, sparse_act_packed: torch.Tensor, fc2w_T: torch.Tensor, fc2_scale: Optional[torch.Tensor],
+                 indices: torch.Tensor, counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor,
+                 num_sms_scatter_add: int) -> None:
+    """Everything behind GEMM1, whatever its form -- the packed deltas are bf16.  ``cache_updated``: GEMM1 applied the scatter-add of its
+    own deltas (same bits as the two-kernel form), so GEMM2 runs alone; otherwise the scatter-add and GEMM2, in the form ``fc2w_T`` takes.
+    (The operators are looked up in the module when they are called: a benchmark may have put timing wrappers in their place.)"""
+    if cache_updated:
+        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
+    elif fc2w_T.dtype == torch.float8_e4m3fn:
+        _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
+    elif USE_FUSED_MLP_MATMUL_2:
+        mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out, num_sms_scatter_add)
+    else:
+        mm2_unfused(sparse_act_packed, fc2w_T, cached_out, sparse_act_T, indices, counts, num_sms_scatter_add)
+
+
 @torch.compiler.disable
 def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], fc2w_T: torch.Tensor, indices: torch.Tensor,
             counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
@@ -189,41 +216,41 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
     # per fc1 column (csp_mlp_mm1_fp8_act_rs in GEMM1's place); a mixed pair raises.
     # act (one of GLU_ACTS) names fc1's activation and fc1b may be None: anything but tanh-GELU with a bias takes csp_mlp_mm1_act /
     # csp_mlp_mm1_fp8_act in GEMM1's place, everything behind GEMM1 is unchanged.
-    assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
-    if x.ndim == 3:
-        B = x.shape[0]
-        assert indices.ndim == 3 and counts.ndim == 2 and sparse_act_T.ndim == 3 and cached_out.ndim == 3, \
-            "a batched x [B, M, K] takes indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] and cached_out [B, M, N]"
-        assert indices.shape[0] == B and counts.shape[0] == B and sparse_act_T.shape[0] == B and cached_out.shape[0] == B, \
-            f"the batch size of indices / counts / sparse_act_T / cached_out must be that of x ({B})"
+    _check_batch(x, indices, counts, sparse_act_T, cached_out)
     M, K1 = x.shape[-2:]
     K2, K1_ = fc1w.shape
     assert K1 == K1_, "K1 must match"
     K2_, _N = fc2w_T.shape
     assert K2 == K2_, "K2 must match"
     sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)  # bf16 also when x is fp8
+    tail = (sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
     if (x.is_cuda and fc1w.dtype == torch.bfloat16
             and amd_key("mlp", "fused_scatter")):
-        # GEMM1 applies the scatter-add of its own deltas (same bits as the two-kernel form), GEMM2 runs alone
         mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act)
-        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
-        return
+        return _after_gemm1(True, *tail)
     if (x.is_cuda and fc1w.dtype == torch.float8_e4m3fn and x.dtype == torch.float8_e4m3fn and amd_key("mlp", "fused_scatter")
             and not FP8_MM1_UPDATES_CACHE and K1 % 128 == 0):
         mm1_fp8_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b, act)
-        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
-        return
+        return _after_gemm1(True, *tail)
     mm1(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b, act)
-    if fc2w_T.dtype == torch.float8_e4m3fn:
-        if fc1w.dtype == torch.float8_e4m3fn and FP8_MM1_UPDATES_CACHE:
-            raise ValueError("run_e2e: FP8_MM1_UPDATES_CACHE (GEMM1 stores the activation, the scatter-add adds the delta again) has no e4m3 fc2 form")
-        _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
-        return
-    if USE_FUSED_MLP_MATMUL_2:
-        mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out,
-                  num_sms_scatter_add)
-    else:
-        mm2_unfused(sparse_act_packed, fc2w_T, cached_out, sparse_act_T, indices, counts, num_sms_scatter_add)
+    if fc2w_T.dtype == torch.float8_e4m3fn and fc1w.dtype == torch.float8_e4m3fn and FP8_MM1_UPDATES_CACHE:
+        raise ValueError("run_e2e: FP8_MM1_UPDATES_CACHE (GEMM1 stores the activation, the scatter-add adds the delta again) has no e4m3 fc2 form")
+    _after_gemm1(False, *tail)
+
+
+def _run_e2e_gated(gemm1, x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, fc2w_T: torch.Tensor, indices: torch.Tensor,
+                   counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
+                   fc2_scale: Optional[torch.Tensor]) -> None:
+    """``run_e2e_glu`` / ``run_e2e_glu_fp8`` around their GEMM1, ``gemm1(sparse_act_packed, update_cache)``."""
+    _check_batch(x, indices, counts, sparse_act_T, cached_out)
+    K1 = x.shape[-1]
+    K2, K1_ = w_gate.shape
+    assert K1 == K1_ and tuple(w_up.shape) == (K2, K1), "K1 must match, w_up must have the shape of w_gate"
+    assert fc2w_T.shape[0] == K2, "K2 must match"
+    sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)   # bf16 also when x is fp8
+    fused = bool(amd_key("mlp", "fused_scatter"))
+    gemm1(sparse_act_packed, fused)
+    _after_gemm1(fused, sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
 
 
 def mm1_glu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sparse_act_packed: torch.Tensor,
@@ -249,31 +276,8 @@ def run_e2e_glu(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b_gat
                 fc2_scale: Optional[torch.Tensor] = None) -> None:
     """``run_e2e`` for a gated feed-forward ``fc2(act(x Wg^T + bg) * (x Wu^T + bu))``: only GEMM1 differs, GEMM2 and the scatter-add see
     the same packed deltas.  Shapes, pitched cache, batches and an e4m3 ``fc2w_T`` with ``fc2_scale`` as for ``run_e2e``."""
-    assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
-    if x.ndim == 3:
-        B = x.shape[0]
-        assert indices.ndim == 3 and counts.ndim == 2 and sparse_act_T.ndim == 3 and cached_out.ndim == 3, \
-            "a batched x [B, M, K] takes indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] and cached_out [B, M, N]"
-        assert indices.shape[0] == B and counts.shape[0] == B and sparse_act_T.shape[0] == B and cached_out.shape[0] == B, \
-            f"the batch size of indices / counts / sparse_act_T / cached_out must be that of x ({B})"
-    K1 = x.shape[-1]
-    K2, K1_ = w_gate.shape
-    assert K1 == K1_ and tuple(w_up.shape) == (K2, K1), "K1 must match, w_up must have the shape of w_gate"
-    assert fc2w_T.shape[0] == K2, "K2 must match"
-    sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)
-    if amd_key("mlp", "fused_scatter"):
-        # GEMM1 applies the scatter-add of its own deltas (same bits as the two-kernel form), GEMM2 runs alone
-        mm1_glu(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, update_cache=True)
-        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
-        return
-    mm1_glu(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, update_cache=False)
-    if fc2w_T.dtype == torch.float8_e4m3fn:
-        _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
-        return
-    if USE_FUSED_MLP_MATMUL_2:
-        mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out, num_sms_scatter_add)
-    else:
-        mm2_unfused(sparse_act_packed, fc2w_T, cached_out, sparse_act_T, indices, counts, num_sms_scatter_add)
+    _run_e2e_gated(lambda packed, upd: mm1_glu(x, w_gate, w_up, packed, b_gate, b_up, act, sparse_act_T, indices, counts, update_cache=upd),
+                   x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
 
 
 def mm1_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sparse_act_packed: torch.Tensor,
@@ -301,31 +305,9 @@ def run_e2e_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b
                     scale_b_gate: torch.Tensor, scale_b_up: torch.Tensor, fc2_scale: Optional[torch.Tensor] = None) -> None:
     """``run_e2e_glu`` with the gated fp8 GEMM1 (``x`` already quantised to e4m3): the packed deltas are bf16, so GEMM2 (``fc2w_T`` bf16, or
     e4m3 with ``fc2_scale``) and the scatter-add are the operators of the bf16 route."""
-    assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
-    if x.ndim == 3:
-        B = x.shape[0]
-        assert indices.ndim == 3 and counts.ndim == 2 and sparse_act_T.ndim == 3 and cached_out.ndim == 3, \
-            "a batched x [B, M, K] takes indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] and cached_out [B, M, N]"
-        assert indices.shape[0] == B and counts.shape[0] == B and sparse_act_T.shape[0] == B and cached_out.shape[0] == B, \
-            f"the batch size of indices / counts / sparse_act_T / cached_out must be that of x ({B})"
-    K1 = x.shape[-1]
-    K2, K1_ = w_gate.shape
-    assert K1 == K1_ and tuple(w_up.shape) == (K2, K1), "K1 must match, w_up must have the shape of w_gate"
-    assert fc2w_T.shape[0] == K2, "K2 must match"
-    scales = (scale_a, scale_b_gate, scale_b_up)
-    sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)   # bf16: x is fp8
-    if amd_key("mlp", "fused_scatter"):
-        mm1_glu_fp8(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, *scales, update_cache=True)
-        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
-        return
-    mm1_glu_fp8(x, w_gate, w_up, sparse_act_packed, b_gate, b_up, act, sparse_act_T, indices, counts, *scales, update_cache=False)
-    if fc2w_T.dtype == torch.float8_e4m3fn:
-        _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
-        return
-    if USE_FUSED_MLP_MATMUL_2:
-        mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out, num_sms_scatter_add)
-    else:
-        mm2_unfused(sparse_act_packed, fc2w_T, cached_out, sparse_act_T, indices, counts, num_sms_scatter_add)
+    _run_e2e_gated(lambda packed, upd: mm1_glu_fp8(x, w_gate, w_up, packed, b_gate, b_up, act, sparse_act_T, indices, counts, scale_a,
+                                                   scale_b_gate, scale_b_up, update_cache=upd),
+                   x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
 
 
 __all__ = ["mm1", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",

@@ -103,7 +103,8 @@ def test_model_constants_are_the_kernels():
     assert len(re.findall(r'chipmunk_get_option\("mm[12]_nr"\) : (\d+);', src)) == 2
     assert set(re.findall(r'chipmunk_get_option\("mm[12]_nr"\) : (\d+);', src)) == {str(tm.NR)}
     # the walk the model writes out: sequence = group / groups-per-sequence, in all three kernels
-    assert "const int b = tm.g / Gs, g = tm.g - b * Gs;" in src and "bseq = gi / Gs;" in src and "b = blockIdx.y / Gs;" in src
+    assert src.count("const int b = tm.g / Gs;") == src.count(" g = tm.g - b * Gs;") == 2      # (mm1_kernel, mm1_form_kernel)
+    assert "bseq = gi / Gs;" in src and "b = blockIdx.y / Gs;" in src
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI

@@ -5,7 +5,9 @@
 compiles both sources with ``hipcc --offload-arch=gfx950 -O3 -S`` (device side only; needs no GPU), cuts every kernel's instruction
 stream out of the assembly, normalises what a rename moves (mangled symbol names, local label numbers, comments) and compares the streams of
 the kernels both trees have: GEMM1 bf16, GEMM1 fp8, GEMM2 and scatter-add as the existing entry points launch them.  A kernel is matched by
-its demangled name with the trailing ``BATCHED = false`` template argument and the parameter list dropped.  Also prints the register counts
+its demangled name with the trailing ``BATCHED = false`` template argument and the parameter list dropped; the GEMM1 kernels of a tree from
+before ``mm1_form_kernel`` (``mm1_act_kernel``, ``mm1_rs_kernel``, ``mm1_glu_kernel``, ``mm1_glu_fp8_kernel``) are matched with the
+``mm1_form_kernel`` instantiation that took their place.  Also prints the register counts
 of every kernel of both trees.  Exit status 0: every shared kernel is instruction-for-instruction identical.
 """
 import os
@@ -17,6 +19,9 @@ import tempfile
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "chipmunk_amd", "csrc")
+# the GEMM1 kernels that became mm1_form_kernel: old name -> its (FP8, GLU, RS) arguments (FP8 None: the old kernel's own fifth argument)
+FORMS = {"mm1_act_kernel": (None, "false", "false"), "mm1_rs_kernel": ("true", "false", "true"),
+         "mm1_glu_kernel": ("false", "true", "false"), "mm1_glu_fp8_kernel": ("true", "true", "false")}
 
 
 def assembly(src: str) -> str:
@@ -35,9 +40,14 @@ def key(mangled: str) -> str:
     name = re.sub(r"\(anonymous namespace\)::", "", name)
     m = re.match(r"(\w+)(<[^>]*>)?", name)
     base, targs = m.group(1), m.group(2) or ""
+    args = [a.strip() for a in targs[1:-1].split(",")]
+    if base in FORMS:    # a tree from before mm1_form_kernel<BN, BK, NST, WPS, FP8, GLU, ACT, RS, BATCHED>: the kernel's name said the form
+        fp8, glu, rs = FORMS[base]
+        shape, (act, batched) = args[:4], args[-2:]
+        base, args = "mm1_form_kernel", shape + [args[4] if fp8 is None else fp8, glu, act, rs, batched]
+        targs = "<" + ", ".join(args) + ">"
     if base in ("mm1_kernel", "mm2_kernel"):
         full = 7 if base == "mm1_kernel" else 6
-        args = [a.strip() for a in targs[1:-1].split(",")]
         if len(args) == full and args[-1] == "false":
             args = args[:-1]
         targs = "<" + ", ".join(args) + ">"
