@@ -599,3 +599,102 @@ def mlp2_base(p, kind, exact):
     g = torch.Generator().manual_seed(p["seed"] + 7)
     scale = {"zero": 0.0, "product": float(exact.pow(2).mean().sqrt()), "unit": 1.0}[kind]
     return (torch.randn(p["M"], p["N2"], generator=g) * scale).to(torch.bfloat16)
+
+
+# --------------------------------------------------------------------------- column sums: exact reference + element metric
+# cs[b, h, g, j] = sum_{i in group g} exp(s_ij) p_i is a sum of positive terms: no cancellation, so EVERY element carries a small
+# relative error, and the number of bf16 roundings on its path can be read from the source.  A column sum over n keys is about
+# 192 / n, so the absolute tolerance the suite used (2e-3 + 3e-2 |x|) is 7 % of the signal at 4 160 keys and larger than it at the
+# HunyuanVideo size.  The guard is the relative error per element against plain fp64 (docs/TEST_SENSITIVITY.md, "Column sums";
+# the bound's numbers live in tests/colsum_model.py and are pinned by tests/test_colsum_metric_cpu.py).
+COLSUM_SEG_W = 64             # the segment metric's width: the 64-row kernels' key tile
+
+
+def colsum_exact(q, k, p, k_lens=None, scale_mul=1.0, chunk_bytes=1 << 28):
+    """fp64 ``cs[b, h, g, j] = sum_{i in group g} exp(q_i . k_j / sqrt(D)) p_i`` with plain torch on the operands' device:
+    ``[B, H, ceil(Nq / 192), Nk]`` float64.  p ``[B, H, >= Nq, 1]`` or ``[B, H, >= Nq]`` (the padded ``l`` of a previous call is
+    taken up to ``Nq``).  Group rows past ``Nq`` add nothing; columns at and past ``k_lens[b]`` are 0.  scale_mul multiplies the
+    ``1 / sqrt(D)`` scale (a defect of tests/test_colsum_metric_cpu.py, and the rest of a scale that was folded into q)."""
+    B, H, Nq, D = q.shape
+    Nk = k.shape[2]
+    G = (Nq + GROUP_ROWS - 1) // GROUP_ROWS
+    scale = scale_mul / (D ** 0.5)
+    pd = p.to(q.device).double().reshape(B, H, -1)[..., :Nq]
+    out = torch.zeros(B, H, G, Nk, dtype=torch.float64, device=q.device)
+    rows_per = max(1, chunk_bytes // (8 * Nk * GROUP_ROWS)) * GROUP_ROWS
+    for b in range(B):
+        L = Nk if k_lens is None else max(1, min(Nk, int(k_lens[b])))
+        for h in range(H):
+            kd = k[b, h, :L].double()
+            for a in range(0, Nq, rows_per):
+                e = min(Nq, a + rows_per)
+                w = torch.exp((q[b, h, a:e].double() @ kd.T) * scale) * pd[b, h, a:e, None]
+                g0, ng = a // GROUP_ROWS, (e - a + GROUP_ROWS - 1) // GROUP_ROWS
+                w = torch.nn.functional.pad(w, (0, 0, 0, ng * GROUP_ROWS - (e - a)))
+                out[b, h, g0:g0 + ng, :L] = w.view(ng, GROUP_ROWS, L).sum(1)
+    return out
+
+
+def colsum_elem_err(cs, exact):
+    """Per element ``|cs - x| / max(x, 2^-60 max_j x[g, :])`` in fp64, the shape of ``exact``.  A non-finite result is an infinite
+    error.  The clamp only gives a definition to a column whose exact sum is (nearly) 0 -- a spike pattern, a column past
+    ``k_lens`` (where a value of the signal's size is then an error of 2^60; the tests assert an exact 0 there on their own); on
+    `randn` inputs no element is clamped."""
+    x = exact.double()
+    c = cs.to(x.device).double()
+    den = torch.maximum(x, 2.0 ** -60 * x.max(dim=-1, keepdim=True).values)
+    err = (c - x).abs() / den
+    err = torch.where(den == 0, torch.where(c == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))), err)
+    return torch.where(torch.isfinite(c) & ~torch.isnan(err), err, torch.full_like(err, float("inf")))
+
+
+def colsum_seg_err(cs, exact, width=COLSUM_SEG_W):
+    """Per (group, `width`-key tile) ``||cs[g, seg] - x[g, seg]||_2 / ||x[g, seg]||_2`` (`seg_rel_err` with the groups as rows):
+    ``[B, H, G, ceil(Nk / width)]``."""
+    return seg_rel_err(cs, exact, width)
+
+
+def assert_colsums_close(cs, exact, rounds, extra=None, what="", fp32_term=0.0, seg_bound=None):
+    """Every element of ``cs`` ``[B, H, G, Nk]`` within ``rounds[g] * 2^-8 + fp32_term + extra`` (relative, `colsum_elem_err`) of
+    ``exact``.  rounds: per group the bf16 roundings on the element's path (a list / tensor ``[G]``, or one number); extra: a
+    derived term of one route (a number or broadcastable to ``exact``); seg_bound (per group like rounds, or a number): also hold
+    the segment metric `colsum_seg_err` under it.  Appends ``what <tab> worst element <tab> bound <tab> worst segment`` to
+    CHIPMUNK_ROW_ERR_LOG as `assert_rows_close` does.  Returns (worst element error / its bound, worst segment error)."""
+    assert cs.shape == exact.shape, (cs.shape, exact.shape)
+    dev = exact.device
+    G = exact.shape[2]
+    per_group = lambda t: torch.as_tensor(t, dtype=torch.float64, device=dev).expand(G).view(1, 1, G, 1)      # noqa: E731
+    bound = per_group(rounds) * BF16_EPS + fp32_term
+    if extra is not None:
+        bound = bound + torch.as_tensor(extra, dtype=torch.float64, device=dev)
+    err = colsum_elem_err(cs, exact)
+    ratio = err / bound
+    worst, worst_ratio = (float(err.max()), float(ratio.max())) if err.numel() else (0.0, 0.0)
+    seg = colsum_seg_err(cs, exact)
+    worst_seg = float(seg.max()) if seg.numel() else 0.0
+    import os
+    path = os.environ.get("CHIPMUNK_ROW_ERR_LOG")
+    print(f"column sums {what}: worst element {worst:.5f} ({worst_ratio:.2f} of its bound), worst segment {worst_seg:.5f}")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"colsum {what}\t{worst:.6f}\t{float(bound.max()):.6f}\t{worst_seg:.6f}\t{worst_ratio:.4f}\n")
+    bad = ~(ratio <= 1.0)
+    if bad.any():
+        flat = int(torch.nan_to_num(ratio, nan=float("inf")).argmax())
+        Nk = exact.shape[3]
+        b, h, g, j = flat // (exact.shape[1] * G * Nk), (flat // (G * Nk)) % exact.shape[1], (flat // Nk) % G, flat % Nk
+        raise AssertionError(
+            f"{what}: column-sum element error {float(err[b, h, g, j]):.4g} > {float(bound.expand_as(err)[b, h, g, j]):.4g} at batch {b} "
+            f"head {h} group {g} column {j} (column {j % COLSUM_SEG_W} of key tile {j // COLSUM_SEG_W}): got {float(cs[b, h, g, j]):.6g}, exact "
+            f"{float(exact[b, h, g, j]):.6g}; {int(bad.sum())} / {bad.numel()} elements over the bound, "
+            f"{int((~torch.isfinite(cs.float())).sum())} non-finite")
+    if seg_bound is not None:
+        sb = per_group(seg_bound)
+        sbad = ~(seg <= sb)
+        if sbad.any():
+            flat = int(torch.nan_to_num(seg / sb, nan=float("inf")).argmax())
+            S = seg.shape[3]
+            b, h, g, s = flat // (seg.shape[1] * G * S), (flat // (G * S)) % seg.shape[1], (flat // S) % G, flat % S
+            raise AssertionError(f"{what}: column-sum segment error {float(seg[b, h, g, s]):.4g} > {float(sb.expand_as(seg)[b, h, g, s]):.4g} at "
+                                 f"batch {b} head {h} group {g} key tile {s}; {int(sbad.sum())} / {sbad.numel()} segments over the bound")
+    return worst_ratio, worst_seg

@@ -19,8 +19,8 @@ import pytest
 import torch
 
 from helpers import (ORACLE_ROWSUM_ERR, ROW_ERR_MARGIN, assert_close_bf16, assert_delta_rows_close,
-                     assert_rows_close, attn_exact, attn_exact_csp96, attn_exact_dense64, gathered_matrix_inputs, indicator_v, randn_bf16, straddle_inputs,
-                     STRADDLE_PATTERNS)
+                     assert_rows_close, attn_exact, attn_exact_csp96, attn_exact_dense64, colsum_exact, gathered_matrix_inputs, indicator_v, randn_bf16,
+                     straddle_inputs, STRADDLE_PATTERNS)
 
 pytestmark = pytest.mark.gpu
 
@@ -79,9 +79,7 @@ def dense_case(dev):
     case = {"q": q, "k": k, "v": v, "exact": attn_exact(q, k, v)}
     s = (q.double() @ k.double().transpose(-1, -2)) / math.sqrt(128)
     case["l"] = 1.0 / torch.exp(s).sum(-1, keepdim=True)
-    G = math.ceil(nq / 192)
-    p = torch.nn.functional.pad(torch.exp(s) * case["l"], (0, 0, 0, G * 192 - nq))
-    case["cs"] = p.view(1, H, G, 192, nk).sum(3)          # softmax column sums per 192-row group, fp64
+    case["cs"] = colsum_exact(q, k, case["l"])            # softmax column sums per 192-row group, fp64
     for kind in ("key", "tile"):
         vi = indicator_v(nk, kind, dev).expand(1, H, nk, 128).contiguous()
         case[kind] = (vi, attn_exact(q, k, vi))
@@ -232,8 +230,7 @@ def test_fused_column_sum_fixed_reference_point_threshold(dev, align, pattern):
     nq, nk = q.shape[2], k.shape[2]
     s = (q.double() @ k.double().transpose(-1, -2)) / math.sqrt(128)
     lx = 1.0 / torch.exp(s).sum(-1, keepdim=True)
-    G = math.ceil(nq / 192)
-    cs_x = torch.nn.functional.pad(torch.exp(s) * lx, (0, 0, 0, G * 192 - nq)).view(1, 2, G, 192, nk).sum(3)
+    cs_x = colsum_exact(q, k, lx)
     with options(attn_dense64=1, attn_colsum64=1):
         o, cs, l = torch.ops.chipmunk.dense_colsum_attn(q, k, v, lx.float())
     assert_rows_close(o, attn_exact_dense64(q, k, v), what=f"column-sum pass o at the fixed-reference threshold, {align} queries, {pattern}")
@@ -256,8 +253,7 @@ def test_column_sum_unit_weight_threshold(dev, pattern):
     p = torch.exp2(f * 80.0 - m)[..., None].float()                    # [1, H, nq, 1]
     assert (((m + p[..., 0].double().log2().abs()) / 80.0 - f).abs() < 1e-3).all()
     s = (q.double() @ k.double().transpose(-1, -2)) / math.sqrt(128)
-    G = math.ceil(nq / 192)
-    cs_x = torch.nn.functional.pad(torch.exp(s) * p.double(), (0, 0, 0, G * 192 - nq)).view(1, 2, G, 192, nk).sum(3)
+    cs_x = colsum_exact(q, k, p)
     with options(attn_dense64=1, attn_colsum64=1):
         o, cs, l = torch.ops.chipmunk.dense_colsum_attn(q, k, v, p)
     assert_rows_close(o, attn_exact_dense64(q, k, v), what=f"column-sum pass o at the unit-weight threshold, {pattern}")

@@ -15,7 +15,7 @@ import math
 import pytest
 import torch
 
-from helpers import assert_rows_close, attn_exact, attn_exact_dense64, randn_bf16
+from helpers import assert_rows_close, attn_exact, attn_exact_dense64, colsum_exact, randn_bf16
 
 pytestmark = pytest.mark.gpu
 
@@ -66,12 +66,11 @@ def _reference(n, lens, dense64):
         keep = torch.arange(n, device=dev)[None, None, :] < torch.tensor(lens, device=dev)[:, None, None]
         exact = attn_exact(q, k, v, keep=keep)
     l = torch.zeros(B, H, n, 1, dtype=torch.float64, device=dev)
-    cs = torch.zeros(B, H, G, n, dtype=torch.float64, device=dev)
     for b, L in enumerate(lens):
         e = torch.exp((q[b].double() @ k[b, :, :L].double().transpose(-1, -2)) / math.sqrt(D))      # [H, n, L]
         l[b] = 1.0 / e.sum(-1, keepdim=True)
-        w = torch.nn.functional.pad(e * l[b], (0, 0, 0, G * 192 - n))
-        cs[b, :, :, :L] = w.view(H, G, 192, L).sum(-2)
+    cs = colsum_exact(q, k, l, lens)
+    assert cs.shape == (B, H, G, n)
     return exact, l.float(), cs.float()
 
 
