@@ -195,6 +195,10 @@ struct Mm1Params {
     union { const float *scale_a; const uint16_t *b_up; };
     union { const float *scale_b; const uint16_t *bias_up; };
     int ldc;           // pitch of the column-major cache in elements: ldc >= M, ldc % 8 == 0 (M itself for the [F, M] contiguous cache)
+    // elements between the row groups of one column: element (column i, row g * BM + r) of the cache is cache[i * ldc + g * gs + r].
+    // BM: the column-major cache [F, ldc].  F * BM with ldc = BM: the group-major cache [G, F, BM] (the *_gm entries), whose 256-byte
+    // pieces of one group lie on a 256-byte grid inside one F * 256-byte window.  (The field fills the block's tail padding: no size change.)
+    int gs = BM;
 };
 // The gated fp8 form needs both at once -- the up projection's weight / bias AND scales -- so it has a parameter block of its own behind the
 // shared one (which keeps its size): b / bias / b_up / bias_up as in the gated bf16 form (weights e4m3 bytes), then the three reciprocal
@@ -298,7 +302,8 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     constexpr int C_INST = STAGED ? EPI / (1024 * NW) : 1;            // DMA instructions per wave
     // The cache is [F, ldc]: a 16-byte piece that starts below M lies inside its column (ldc >= ceil8(M)), so the masks are
     // piece-granular; pieces that start at or past M re-read the column's first piece of this tile and are not written back.
-    const __amdgpu_buffer_rsrc_t rc = make_rsrc(p.cache, (uint32_t)p.F * p.ldc * 2u);
+    // (group-major, gs != BM: the G * gs = G * F * BM elements of the sequence's block)
+    const __amdgpu_buffer_rsrc_t rc = make_rsrc(p.cache, (uint32_t)(p.gs == BM ? p.F * p.ldc : (p.M + BM - 1) / BM * p.gs) * 2u);
     uint32_t coff[C_INST];
     auto piece_row = [&](int jj) { return ((lane % LPR) ^ (jj & (LPR - 1))) << 3; };   // first tile row of the lane's piece of column jj
     if constexpr (STAGED) {
@@ -308,7 +313,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
             const int j = n0 + jj;
             const int col = idxg[j < cnt ? j : n0];
             const int ms = piece_row(jj);
-            coff[i] = ((uint32_t)col * p.ldc + g * BM + m_off + (ms < rows ? ms : 0)) * 2u;
+            coff[i] = ((uint32_t)col * p.ldc + g * p.gs + m_off + (ms < rows ? ms : 0)) * 2u;
         }
     }
     auto issue_cache = [&](int buf) {
@@ -582,7 +587,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
             const int j = n0 + wn * (TN / WNC) + n4 * 32 + (lane & 31);
             const bool live = j < cnt;
             const int col = live ? idxg[j] : 0;
-            const uint16_t *crow = p.cache + (int64_t)col * p.ldc;
+            const uint16_t *crow = p.cache + (int64_t)col * p.ldc + (int64_t)g * (p.gs - BM);   // (+ m below: g * BM of it is in m)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
@@ -1366,9 +1371,11 @@ constexpr int SC_LD = 136;  // padded row length of the transposed tile (bf16 el
 
 // Batched launch (one trailing argument: the elements between the caches of consecutive sequences): blockIdx.y walks the B * G groups
 // of indices [B, G, F] / counts [B, G]; packed is [B, M, F].  The pointers move to the group's sequence, then everything is as below.
+// gs: the elements between the row groups of a cache column, as Mm1Params::gs (128: column-major [F, ldc]; F * 128 with ldc = 128: group-major).
 template <class... BS>
 __global__ __launch_bounds__(256) void scatter_add_kernel(const uint16_t *packed, uint16_t *unpacked,
-                                                          const int32_t *indices, const int32_t *counts, int M, int F, int ldc, BS... cache_bs) {
+                                                          const int32_t *indices, const int32_t *counts, int M, int F, int ldc, int gs,
+                                                          BS... cache_bs) {
     static_assert(sizeof...(BS) <= 1, "at most the cache batch stride");
     __shared__ __attribute__((aligned(16))) uint16_t tile[SC_COLS * SC_LD];
     if constexpr (sizeof...(BS) == 1) {
@@ -1406,7 +1413,7 @@ __global__ __launch_bounds__(256) void scatter_add_kernel(const uint16_t *packed
         olds[i] = (u32x4){0u, 0u, 0u, 0u};
         if (c0 + c >= cnt || ch * 8 >= rows) continue;   // a piece that starts below M lies inside its column (ldc >= ceil8(M))
         const int col = indices[(int64_t)g * F + c0 + c];
-        src[i] = unpacked + (int64_t)col * ldc + g * 128 + ch * 8;
+        src[i] = unpacked + (int64_t)col * ldc + (int64_t)g * gs + ch * 8;
         olds[i] = *(const u32x4 *)src[i];
     }
 #pragma unroll
@@ -1422,6 +1429,45 @@ __global__ __launch_bounds__(256) void scatter_add_kernel(const uint16_t *packed
             out[e] = pack_bf16x2(__uint_as_float(old[e] << 16) + __uint_as_float(add[e] << 16),
                                  __uint_as_float(old[e] & 0xffff0000u) + __uint_as_float(add[e] & 0xffff0000u));
         *(u32x4 *)const_cast<uint16_t *>(src[i]) = out;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ full step: rows to row groups
+// [B, R, C] -> [B, G, C, 128] for 16-bit elements, G = ceil(R / 128): the group-major activation cache of a full step, element
+// (b, g, c, r) = src[b, g * 128 + r, c], the rows of the last group at or past R zero.  transpose16's 64 x 64 tiles through LDS (128-byte
+// row segments on both sides); a tile lies inside one group (64 divides 128), so its 64 output rows are 128-byte halves of 256-byte
+// group columns, and the tile rows past R are written as the zeros they were loaded as.
+__global__ __launch_bounds__(256) void transpose16_groups_kernel(const uint16_t *src, uint16_t *dst, int R, int C) {
+    __shared__ __attribute__((aligned(16))) uint16_t tile[64][72];
+    const int G = (R + 127) / 128;
+    const int64_t boff = (int64_t)blockIdx.z * R * C;
+    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;   // blockIdx.y < 2 * G
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int item = i * 256 + tid, r = item >> 3, ch = item & 7;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (r0 + r < R && c0 + ch * 8 + 8 <= C && (C & 7) == 0) v = *(const u32x4 *)(src + boff + (int64_t)(r0 + r) * C + c0 + ch * 8);
+        else if (r0 + r < R)
+            for (int e = 0; e < 8; ++e)
+                if (c0 + ch * 8 + e < C) {
+                    const uint32_t x = src[boff + (int64_t)(r0 + r) * C + c0 + ch * 8 + e];
+                    v[e >> 1] |= x << (16 * (e & 1));
+                }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            tile[ch * 8 + 2 * e][r] = (uint16_t)(v[e] & 0xffffu);
+            tile[ch * 8 + 2 * e + 1][r] = (uint16_t)(v[e] >> 16);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int item = i * 256 + tid, c = item >> 3, ch = item & 7;
+        if (c0 + c >= C) continue;
+        // group r0 / 128, row r0 % 128 + ch * 8 of column c0 + c: 16-byte aligned, inside the [G, C, 128] block of sequence blockIdx.z
+        uint16_t *d = dst + (((int64_t)blockIdx.z * G + (r0 >> 7)) * C + c0 + c) * 128 + (r0 & 127) + ch * 8;
+        *(u32x4 *)d = *(const u32x4 *)&tile[c][ch * 8];
     }
 }
 
@@ -1460,17 +1506,27 @@ int check_cache_batch_stride(int F, int ldc, int64_t cache_bs) {
     return CHIPMUNK_OK;
 }
 
+// The *_gm entries: the group-major cache [G, F, 128] of a sequence (G = ceil(M / 128)), [B, G, F, 128] with a batch stride of its own
+int check_cache_groups(int M, int F, int64_t cache_bs) {
+    const int64_t block = (int64_t)((M + BM - 1) / BM) * F * BM;
+    CM_CHECK(block < (1ll << 31), "mlp: G * F * 128 too large for 32-bit offsets (the group-major cache of one sequence, G = ceil(M / 128))");
+    CM_CHECK(cache_bs >= block && cache_bs % 8 == 0,
+             "mlp: the cache batch stride must be at least G * F * 128 and a multiple of 8 elements (got %lld, G * F * 128 = %lld)",
+             (long long)cache_bs, (long long)block);
+    return CHIPMUNK_OK;
+}
+
 int launch_scatter_add(const void *packed, void *unpacked, const int32_t *indices, const int32_t *counts, int M, int F, int ldc,
-                       hipStream_t s) {
+                       hipStream_t s, int gs = BM) {
     hipLaunchKernelGGL(scatter_add_kernel<>, dim3(F / SC_COLS, (M + BM - 1) / BM), dim3(256), 0, s, (const uint16_t *)packed,
-                       (uint16_t *)unpacked, indices, counts, M, F, ldc);
+                       (uint16_t *)unpacked, indices, counts, M, F, ldc, gs);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }
 int launch_scatter_add_batched(const void *packed, void *unpacked, const int32_t *indices, const int32_t *counts, int B, int M, int F,
-                               int ldc, int64_t cache_bs, hipStream_t s) {
+                               int ldc, int64_t cache_bs, hipStream_t s, int gs = BM) {
     hipLaunchKernelGGL(scatter_add_kernel<int64_t>, dim3(F / SC_COLS, B * ((M + BM - 1) / BM)), dim3(256), 0, s, (const uint16_t *)packed,
-                       (uint16_t *)unpacked, indices, counts, M, F, ldc, cache_bs);
+                       (uint16_t *)unpacked, indices, counts, M, F, ldc, gs, cache_bs);
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }
@@ -1630,13 +1686,18 @@ namespace {
 // What every GEMM1 entry checks behind its null pointers, `who` being the entry's name in the messages.  ragged: the *_ragged entries'
 // contract (any M), otherwise the reference's (M % 128 == 0); B > 0: a *_batched entry; KM: what K must be a multiple of; coded: the entry
 // takes an activation code, act; upd_max: the largest update_cache (< 0: the library's own value, not checked).  The two entries of the
-// reference's contract (not coded) look at K first and do not print the update_cache they refuse.
+// reference's contract (not coded) look at K first and do not print the update_cache they refuse.  gm: a *_gm entry -- the group-major cache
+// (ldc is then 128, the pitch of a column inside its group) with B >= 1 and a batch stride.
 int check_mm1(const char *who, bool ragged, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int B,
-              int64_t cache_bs, int KM, bool coded, int act, int update_cache, int upd_max) {
+              int64_t cache_bs, int KM, bool coded, int act, int update_cache, int upd_max, bool gm = false) {
     if (int e = ragged ? check_mlp_ragged(M, F, indices, counts) : check_mlp_common(M, F, indices, counts)) return e;
-    if (int e = check_cache_pitch(M, F, ldc)) return e;
-    if (B > 0) {
-        if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
+    if (gm) {
+        if (int e = check_cache_groups(M, F, cache_bs)) return e;
+    } else {
+        if (int e = check_cache_pitch(M, F, ldc)) return e;
+        if (B > 0) {
+            if (int e = check_cache_batch_stride(F, ldc, cache_bs)) return e;
+        }
     }
     if (coded) {
         CM_CHECK(act == CHIPMUNK_ACT_GELU_TANH || act == CHIPMUNK_ACT_SILU || act == CHIPMUNK_ACT_GELU_ERF,
@@ -1743,17 +1804,19 @@ int launch_mm1_form(const typename Mm1Block<FP8 && GLU, false>::type &p, int act
 // Ungated.  scale_a / scale_b null: the bf16 form (update_cache 0 / 1); both given: the e4m3 form (update_cache 0 / 1 / 2 as chipmunk_csp_mlp_mm1_fp8)
 int mm1_act_entry(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices, const int32_t *counts,
                   const float *scale_a, const float *scale_b, bool fp8, int M, int K, int F, int ldc, int act, int update_cache,
-                  hipStream_t stream, int B = 0, int64_t cache_bs = 0, bool rs = false) {   // B > 0: the *_batched entries; rs: the *_rs entries
+                  hipStream_t stream, int B = 0, int64_t cache_bs = 0, bool rs = false, bool gm = false) {
+    // B > 0: the *_batched entries; rs: the *_rs entries; gm: the *_gm entries (group-major cache, ldc = BM, B >= 1 with 1 the single-sequence launch)
     if (fp8) CM_CHECK(a && b && c && pa_cache && scale_a && scale_b, "csp_mlp_mm1_fp8_act: null tensor or scale pointer");
     else CM_CHECK(a && b && c && pa_cache, "csp_mlp_mm1_act: null tensor pointer");
     CM_CHECK(!rs || (((uintptr_t)scale_a | (uintptr_t)scale_b) & 3) == 0, "csp_mlp_mm1_fp8_act_rs: scale_a and scale_b must be 4-byte aligned");
     if (int e = check_mm1(fp8 ? "csp_mlp_mm1_fp8_act" : "csp_mlp_mm1_act", true, indices, counts, M, K, F, ldc, B, cache_bs, fp8 ? 128 : 64, true, act,
-                          update_cache, fp8 ? 2 : 1))
+                          update_cache, fp8 ? 2 : 1, gm))
         return e;
     // the kernel's update_cache: 1 = scatter-add of the deltas, 2 (fp8) = store the new activation -- the fp8 entries' 2 and 1
     const int upd = fp8 ? (update_cache == 1 ? 2 : update_cache == 2 ? 1 : 0) : update_cache;
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, upd, scale_a, scale_b, ldc};
+    if (gm) p.gs = F * BM, B = B == 1 ? 0 : B;
     if (rs) return launch_mm1_form<true, false, true>(p, act, stream, B, cache_bs);
     return fp8 ? launch_mm1_form<true, false>(p, act, stream, B, cache_bs) : launch_mm1_form<false, false>(p, act, stream, B, cache_bs);
 }
@@ -1761,26 +1824,29 @@ int mm1_act_entry(const void *a, const void *b, void *c, const void *bias, void 
 // Gated (SwiGLU / GEGLU), bf16
 int mm1_glu_entry(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
                   const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream,
-                  int B = 0, int64_t cache_bs = 0) {   // B > 0: the *_batched entry
+                  int B = 0, int64_t cache_bs = 0, bool gm = false) {   // B > 0: the *_batched entry; gm: the *_gm entry, as mm1_act_entry
     CM_CHECK(a && b_gate && b_up && c && pa_cache, "csp_mlp_mm1_glu: null tensor pointer");
-    if (int e = check_mm1("csp_mlp_mm1_glu", true, indices, counts, M, K, F, ldc, B, cache_bs, 64, true, act, update_cache, 1)) return e;
+    if (int e = check_mm1("csp_mlp_mm1_glu", true, indices, counts, M, K, F, ldc, B, cache_bs, 64, true, act, update_cache, 1, gm)) return e;
     Mm1Params p = {(const uint16_t *)a, (const uint16_t *)b_gate, (const uint16_t *)bias_gate, (uint16_t *)pa_cache,
                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
     p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
+    if (gm) p.gs = F * BM, B = B == 1 ? 0 : B;
     return launch_mm1_form<false, true>(p, act, stream, B, cache_bs);
 }
 
 // Gated, e4m3 a / weights (1 byte per element): K % 128 as csp_mlp_mm1_fp8, and the three reciprocal quantisation scales
 int mm1_glu_fp8_entry(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
                       const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b_gate, const float *scale_b_up,
-                      int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream, int B = 0, int64_t cache_bs = 0) {
+                      int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream, int B = 0, int64_t cache_bs = 0,
+                      bool gm = false) {
     CM_CHECK(a && b_gate && b_up && c && pa_cache && scale_a && scale_b_gate && scale_b_up, "csp_mlp_mm1_glu_fp8: null tensor or scale pointer");
-    if (int e = check_mm1("csp_mlp_mm1_glu_fp8", true, indices, counts, M, K, F, ldc, B, cache_bs, 128, true, act, update_cache, 1)) return e;
+    if (int e = check_mm1("csp_mlp_mm1_glu_fp8", true, indices, counts, M, K, F, ldc, B, cache_bs, 128, true, act, update_cache, 1, gm)) return e;
     Mm1GluF8Params p;
     static_cast<Mm1Params &>(p) = {(const uint16_t *)a, (const uint16_t *)b_gate, (const uint16_t *)bias_gate, (uint16_t *)pa_cache,
                                    (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
     p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
     p.scale_x = scale_a, p.scale_gate = scale_b_gate, p.scale_up = scale_b_up;
+    if (gm) p.gs = F * BM, B = B == 1 ? 0 : B;
     return launch_mm1_form<true, true>(p, act, stream, B, cache_bs);
 }
 }  // namespace
@@ -2002,4 +2068,65 @@ extern "C" int chipmunk_csp_mlp_mm2_w8_batched(const void *mma_a, const void *mm
                                                const int32_t *indices, const int32_t *counts, int M, int F, int N2, int B, void *stream) {
     CM_CHECK(B >= 1, "mlp: the batch size B must be at least 1 (got %d)", B);
     return launch_mm2_w8(mma_a, mma_b, scale_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream, B);
+}
+
+// ---- group-major activation cache (include/chipmunk_hip.h, "Group-major cache"): the *_gm entries.  The cache of sequence b is the
+// [G, F, 128] block at pa_cache + b * cache_batch_stride; everything else is the *_batched entry's contract, B = 1 the single-sequence launch.
+extern "C" int chipmunk_csp_mlp_mm1_act_gm(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                           const int32_t *counts, int M, int K, int F, int act, int update_cache, int B,
+                                           int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, nullptr, nullptr, false, M, K, F, BM, act, update_cache, (hipStream_t)stream,
+                         B, cache_batch_stride, false, true);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_act_gm(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                               const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                               int M, int K, int F, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                               void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, true, M, K, F, BM, act, update_cache, (hipStream_t)stream,
+                         B, cache_batch_stride, false, true);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_act_rs_gm(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                                  const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                                  int M, int K, int F, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                                  void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_act_entry(a, b, c, bias, pa_cache, indices, counts, scale_a, scale_b, true, M, K, F, BM, act, update_cache, (hipStream_t)stream,
+                         B, cache_batch_stride, true, true);
+}
+extern "C" int chipmunk_csp_mlp_mm1_glu_gm(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                           const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K,
+                                           int F, int act, int update_cache, int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_glu_entry(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache, indices, counts, M, K, F, BM, act, update_cache,
+                         (hipStream_t)stream, B, cache_batch_stride, true);
+}
+extern "C" int chipmunk_csp_mlp_mm1_glu_fp8_gm(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                               const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts,
+                                               const float *scale_a, const float *scale_b_gate, const float *scale_b_up, int M, int K,
+                                               int F, int act, int update_cache, int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_glu_fp8_entry(a, b_gate, b_up, c, bias_gate, bias_up, pa_cache, indices, counts, scale_a, scale_b_gate, scale_b_up, M, K, F, BM,
+                             act, update_cache, (hipStream_t)stream, B, cache_batch_stride, true);
+}
+extern "C" int chipmunk_csp_scatter_add_gm(const void *packed, void *unpacked_groups, const int32_t *indices, const int32_t *counts, int M,
+                                           int F, int B, int64_t cache_batch_stride, void *stream) {
+    CM_CHECK(packed && unpacked_groups, "csp_scatter_add_gm: null tensor pointer");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (int e = check_mlp_batch(B, M)) return e;
+    if (int e = check_cache_groups(M, F, cache_batch_stride)) return e;
+    if (B == 1) return launch_scatter_add(packed, unpacked_groups, indices, counts, M, F, BM, (hipStream_t)stream, F * BM);
+    return launch_scatter_add_batched(packed, unpacked_groups, indices, counts, B, M, F, BM, cache_batch_stride, (hipStream_t)stream, F * BM);
+}
+extern "C" int chipmunk_transpose16_groups(const void *src, void *dst, int B, int R, int C, void *stream) {
+    CM_CHECK(src && dst, "transpose16_groups: null tensor pointer");
+    CM_CHECK(B > 0 && R > 0 && C > 0, "transpose16_groups: B, R and C must be positive (got %d, %d, %d)", B, R, C);
+    CM_CHECK(B <= 65535 && (R + 127) / 128 <= 32767, "transpose16_groups: B must not exceed 65535 and ceil(R / 128) not 32767 (got B = %d, R = %d)",
+             B, R);
+    CM_CHECK((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "transpose16_groups: src and dst must be 16-byte aligned");
+    hipLaunchKernelGGL(transpose16_groups_kernel, dim3((C + 63) / 64, 2 * ((R + 127) / 128), B), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t *)src, (uint16_t *)dst, R, C);
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
 }

@@ -287,6 +287,9 @@ std::vector<at::Tensor> dense_colsum_attn(at::Tensor q, at::Tensor k, at::Tensor
 // contiguous, columns `ldc` elements apart -- a contiguous tensor (ldc = M) or the [:, :M] view of a buffer with padded columns.
 // M % 128 == 0 with ldc == M goes to the reference's entry points, everything else to the *_ragged ones (include/chipmunk_hip.h).
 int64_t cache_pitch(const at::Tensor &t, int64_t F, int64_t M, const char *name) {
+    // (a group-major cache [G, F, 128] of whole groups has the F * M elements of the column-major one: it is told apart by its shape)
+    TORCH_CHECK(!(M > 128 && t.dim() >= 3 && t.size(-1) == 128 && t.size(-2) == F && t.size(-3) * 128 == M), name,
+                " is a group-major cache [G, F, 128]: this operator takes the column-major [F, M] only");
     if (t.is_contiguous() && t.numel() == F * M) return M;
     TORCH_CHECK(t.dim() >= 2 && t.size(-2) == F && t.size(-1) == M && t.numel() == F * M, name, " must be [F, M]");
     TORCH_CHECK(t.stride(-1) == 1, name, ": the M elements of a column must be contiguous");
@@ -301,13 +304,17 @@ int64_t groups_of(int64_t M) { return (M + 127) / 128; }
 
 // Batches (B > 1 sequences in one launch): a [B, M, K], c [B, M, F], the cache [B, F, M] (or the [..., :M] view of [B, F, ldc], any batch
 // stride the C entry accepts), indices [B, G, F], counts [B, G].  2-D operands and B == 1 take exactly the entries they always took.
+// Group-major cache (the operators added here, never the reference-schema ones): a cache of one dimension more than a -- [G, F, 128] for
+// a [M, K], [B, G, F, 128] for a [B, M, K], G = ceil(M / 128) -- with each [G, F, 128] block contiguous; the batch stride is the tensor's.
+// (A shape that is also a column-major one, [1, F, 128] for M = 128, holds the same elements either way and stays column-major.)
 struct Mm1Shape {
     int64_t B, M, K, F, ldc, cache_bs;
+    bool gm = false;
     bool batched() const { return B > 1; }
 };
 // (bias: null for the gated operator, which checks its two optional vectors itself)
 Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c, const at::Tensor *bias, const at::Tensor &cache,
-                   const at::Tensor &indices, const at::Tensor &counts) {
+                   const at::Tensor &indices, const at::Tensor &counts, bool allow_gm = false) {
     TORCH_CHECK((a.dim() == 2 || a.dim() == 3) && b.dim() == 2 && c.dim() == a.dim(), "a and c must both be 2D ([M, .]) or 3D ([B, M, .]), b 2D");
     Mm1Shape s;
     s.B = a.dim() == 3 ? a.size(0) : 1;
@@ -316,7 +323,20 @@ Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c
     TORCH_CHECK(b.size(1) == s.K, "a and b must share the K dimension");
     TORCH_CHECK(c.size(-2) == s.M && c.size(-1) == s.F && c.numel() == s.B * s.M * s.F, "c must be [M, F] ([B, M, F] with the batch size of a)");
     if (bias) TORCH_CHECK(bias->numel() == s.F, "bias must have F entries");
-    if (!s.batched()) {
+    const int64_t G = groups_of(s.M);
+    s.gm = allow_gm && cache.dim() == a.dim() + 1 &&
+           !(cache.size(-2) == s.F && cache.size(-1) == s.M && cache.numel() == s.F * s.M && cache.is_contiguous());
+    if (s.gm) {
+        TORCH_CHECK(cache.size(-1) == 128 && cache.size(-2) == s.F && cache.size(-3) == G && (a.dim() == 2 || cache.size(0) == s.B),
+                    "a group-major pa_cache must be [G, F, 128] ([B, G, F, 128] with the batch size of a), G = ceil(M / 128) = ", G, ", F = ", s.F,
+                    " (got ", cache.sizes(), ")");
+        TORCH_CHECK(cache.stride(-1) == 1 && cache.stride(-2) == 128 && (G == 1 || cache.stride(-3) == s.F * 128),
+                    "a group-major pa_cache: each [G, F, 128] block must be contiguous");
+        TORCH_CHECK(G * s.F * 128 < (1ll << 31), "a group-major pa_cache: G * F * 128 too large for 32-bit offsets");
+        s.ldc = 128, s.cache_bs = a.dim() == 3 && s.B > 1 ? cache.stride(0) : G * s.F * 128;
+        TORCH_CHECK(s.cache_bs >= G * s.F * 128 && s.cache_bs % 8 == 0, "a group-major pa_cache: the batch stride (", s.cache_bs,
+                    " elements) must be at least G * F * 128 = ", G * s.F * 128, " and a multiple of 8");
+    } else if (!s.batched()) {
         s.ldc = cache_pitch(cache, s.F, s.M, "pa_cache_colmajor");
         s.cache_bs = s.F * s.ldc;
     } else {
@@ -327,8 +347,7 @@ Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c
         TORCH_CHECK(s.cache_bs >= s.F * s.ldc && s.cache_bs % 8 == 0, "pa_cache_colmajor: the batch stride (", s.cache_bs,
                     " elements) must be at least F * ldc = ", s.F * s.ldc, " and a multiple of 8");
     }
-    check_pitch(s.ldc, s.M, "pa_cache_colmajor");
-    const int64_t G = groups_of(s.M);
+    if (!s.gm) check_pitch(s.ldc, s.M, "pa_cache_colmajor");
     TORCH_CHECK(indices.numel() == s.B * G * s.F && counts.numel() == s.B * G,
                 "indices must be [ceil(M/128), F], counts [ceil(M/128)] ([B, ceil(M/128), F] and [B, ceil(M/128)] with the batch size of a)");
     TORCH_CHECK(s.B * G <= 65535, "B * ceil(M/128) groups must not exceed 65535 (got ", s.B * G, ")");
@@ -420,14 +439,21 @@ static void mm1_glu_impl(const char *who, at::Tensor a, at::Tensor b_gate, at::T
         for (const at::Tensor *s : {scale_a, scale_b_gate, scale_b_up})
             TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->numel() == 1, who,
                         ": scale_a, scale_b_gate and scale_b_up must be one-element float32 tensors on the GPU");
-    const Mm1Shape sh = mm1_shape(a, b_gate, c, nullptr, pa_cache_colmajor, indices, indices_counts);
+    const Mm1Shape sh = mm1_shape(a, b_gate, c, nullptr, pa_cache_colmajor, indices, indices_counts, true);
     TORCH_CHECK(b_up.dim() == 2 && b_up.size(0) == sh.F && b_up.size(1) == sh.K, "b_up must have the shape of b_gate ([F, K])");
     const void *bg = optional_bias(bias_gate, "bias_gate", sh.F), *bu = optional_bias(bias_up, "bias_up", sh.F);
     const int code = act_code(who, act);
     c10::DeviceGuard guard(a.device());
     int *ip = indices.data_ptr<int>(), *cp = indices_counts.data_ptr<int>();
     const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc, upd = update_cache ? 1 : 0;
-    if (fp8 && sh.batched())
+    if (fp8 && sh.gm)
+        check(chipmunk_csp_mlp_mm1_glu_fp8_gm(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu, pa_cache_colmajor.data_ptr(),
+                                              ip, cp, scale_a->data_ptr<float>(), scale_b_gate->data_ptr<float>(),
+                                              scale_b_up->data_ptr<float>(), M, K, F, code, upd, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (sh.gm)
+        check(chipmunk_csp_mlp_mm1_glu_gm(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu, pa_cache_colmajor.data_ptr(),
+                                          ip, cp, M, K, F, code, upd, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (fp8 && sh.batched())
         check(chipmunk_csp_mlp_mm1_glu_fp8_batched(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), c.data_ptr(), bg, bu,
                                                    pa_cache_colmajor.data_ptr(), ip, cp, scale_a->data_ptr<float>(),
                                                    scale_b_gate->data_ptr<float>(), scale_b_up->data_ptr<float>(), M, K, F, ldc, code, upd,
@@ -537,13 +563,24 @@ static void mm1_act_impl(const char *who, at::Tensor a, at::Tensor b, at::Tensor
     CHECK_I32(indices); CHECK_I32(indices_counts);
     CHECK_CONTIG(a); CHECK_CONTIG(b); CHECK_CONTIG(c);
     CHECK_CONTIG(indices); CHECK_CONTIG(indices_counts);
-    const Mm1Shape sh = mm1_shape(a, b, c, nullptr, pa_cache_colmajor, indices, indices_counts);
+    const Mm1Shape sh = mm1_shape(a, b, c, nullptr, pa_cache_colmajor, indices, indices_counts, true);
     const void *bp = optional_bias(bias, "bias", sh.F);
     const int code = act_code(who, act);
     c10::DeviceGuard guard(a.device());
     int *ip = indices.data_ptr<int>(), *cp = indices_counts.data_ptr<int>();
     const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc;
-    if (rs && sh.batched())
+    if (rs && sh.gm)
+        check(chipmunk_csp_mlp_mm1_fp8_act_rs_gm(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp,
+                                                 scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), M, K, F, code, update_cache,
+                                                 (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (fp8 && sh.gm)
+        check(chipmunk_csp_mlp_mm1_fp8_act_gm(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp,
+                                              scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), M, K, F, code, update_cache,
+                                              (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (sh.gm)
+        check(chipmunk_csp_mlp_mm1_act_gm(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp, M, K, F, code,
+                                          update_cache, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (rs && sh.batched())
         check(chipmunk_csp_mlp_mm1_fp8_act_rs_batched(a.data_ptr(), b.data_ptr(), c.data_ptr(), bp, pa_cache_colmajor.data_ptr(), ip, cp,
                                                       scale_a->data_ptr<float>(), scale_b->data_ptr<float>(), M, K, F, ldc, code,
                                                       update_cache, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
@@ -640,6 +677,31 @@ void csp_scatter_add(at::Tensor packed, at::Tensor unpacked_colmajor, at::Tensor
                                               sp_counts.data_ptr<int>(), (int)packed.size(1), (int)packed.size(2), (int)ldc,
                                               cur_stream(packed)),
               "csp_scatter_add");
+}
+
+// addition: csp_scatter_add on the group-major cache.  packed [B, M, F], unpacked_groups [B, G, F, 128] (each [G, F, 128] block contiguous,
+// any batch stride the C entry accepts), sp_inds [B, G, F], sp_counts [B, G]
+void csp_scatter_add_gm(at::Tensor packed, at::Tensor unpacked_groups, at::Tensor sp_inds, at::Tensor sp_counts) {
+    CHECK_DEV(packed); CHECK_DEV(unpacked_groups); CHECK_DEV(sp_inds); CHECK_DEV(sp_counts);
+    CHECK_CONTIG(packed); CHECK_CONTIG(sp_inds); CHECK_CONTIG(sp_counts);
+    CHECK_BF16(packed); CHECK_BF16(unpacked_groups);
+    CHECK_I32(sp_inds); CHECK_I32(sp_counts);
+    TORCH_CHECK(packed.dim() == 3 && unpacked_groups.dim() == 4 && sp_inds.dim() == 3 && sp_counts.dim() == 2,
+                "csp_scatter_add_gm: packed [B, M, F], unpacked_groups [B, G, F, 128], sp_inds [B, G, F], sp_counts [B, G]");
+    const int64_t B = packed.size(0), M = packed.size(1), F = packed.size(2), G = groups_of(M);
+    TORCH_CHECK(B >= 1 && M >= 1, "csp_scatter_add_gm: batch size and M must be at least 1");
+    TORCH_CHECK(unpacked_groups.size(0) == B && unpacked_groups.size(1) == G && unpacked_groups.size(2) == F && unpacked_groups.size(3) == 128,
+                "csp_scatter_add_gm: unpacked_groups must be [B, G, F, 128] with G = ceil(M / 128) = ", G, ", F = ", F, " (got ",
+                unpacked_groups.sizes(), ")");
+    TORCH_CHECK(unpacked_groups.stride(3) == 1 && unpacked_groups.stride(2) == 128 && (G == 1 || unpacked_groups.stride(1) == F * 128),
+                "csp_scatter_add_gm: each [G, F, 128] block of unpacked_groups must be contiguous");
+    TORCH_CHECK(sp_inds.size(0) == B && sp_inds.size(1) == G && sp_inds.size(2) == F && sp_counts.size(0) == B && sp_counts.size(1) == G,
+                "csp_scatter_add_gm: sp_inds must be [B, ceil(M/128), F], sp_counts [B, ceil(M/128)]");
+    const int64_t cache_bs = B > 1 ? unpacked_groups.stride(0) : G * F * 128;
+    c10::DeviceGuard guard(packed.device());
+    check(chipmunk_csp_scatter_add_gm(packed.data_ptr(), unpacked_groups.data_ptr(), sp_inds.data_ptr<int>(), sp_counts.data_ptr<int>(), (int)M,
+                                      (int)F, (int)B, cache_bs, cur_stream(packed)),
+          "csp_scatter_add_gm");
 }
 
 // reference csrc/mlp/csp_mlp_mm2_and_scatter_add.cu:96-259.  `matmul_kernel` is the reference's Triton CUfunction
@@ -916,6 +978,25 @@ at::Tensor transpose_last2_pitched(at::Tensor x, int64_t ld) {
     c10::DeviceGuard guard(x.device());
     at::Tensor out = at::empty(sizes, x.options());
     check(chipmunk_transpose16_pitched(x.data_ptr(), out.data_ptr(), (int)B, (int)R, (int)C, (int)ld, cur_stream(x)), "transpose_last2_pitched");
+    return out;
+}
+
+// [..., R, C] -> [..., ceil(R / 128), C, 128] for a 16-bit dtype: out[..., g, c, r] = x[..., g * 128 + r, c], the rows of the last group at
+// or past R zero -- the group-major activation cache of a full step
+at::Tensor transpose_to_groups(at::Tensor x) {
+    CHECK_DEV(x);
+    TORCH_CHECK(x.dim() >= 2 && x.element_size() == 2, "transpose_to_groups: need a >=2-D tensor of a 16-bit dtype");
+    x = x.contiguous();
+    const int64_t R = x.size(-2), C = x.size(-1);
+    TORCH_CHECK(R > 0 && C > 0, "transpose_to_groups: the last two dimensions must not be empty");
+    const int64_t B = x.numel() / (R * C);
+    auto sizes = x.sizes().vec();
+    sizes[sizes.size() - 2] = groups_of(R);
+    sizes[sizes.size() - 1] = C;
+    sizes.push_back(128);
+    c10::DeviceGuard guard(x.device());
+    at::Tensor out = at::empty(sizes, x.options());
+    check(chipmunk_transpose16_groups(x.data_ptr(), out.data_ptr(), (int)B, (int)R, (int)C, cur_stream(x)), "transpose_to_groups");
     return out;
 }
 
@@ -1350,6 +1431,8 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("residual_ln_modulate(Tensor x, Tensor? y, Tensor? gate, Tensor shift, Tensor scale, float eps) -> Tensor[]");
     m.def("transpose_last2(Tensor x) -> Tensor");
     m.def("transpose_last2_pitched(Tensor x, int ld) -> Tensor");
+    m.def("transpose_to_groups(Tensor x) -> Tensor");
+    m.def("csp_scatter_add_gm(Tensor packed, Tensor(unpacked_groups!) unpacked_groups, Tensor sp_inds, Tensor sp_counts) -> ()");
     m.def("block_mean(Tensor x, int mbm) -> Tensor");
     m.def("quantize_fp8(Tensor x, Tensor scale, float max_value) -> Tensor");
     m.def("quantize_fp8_rowwise(Tensor x, float max_value) -> Tensor[]");
@@ -1407,6 +1490,8 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("topk_mask_p", &topk_mask_p);
     m.impl("transpose_last2", &transpose_last2);
     m.impl("transpose_last2_pitched", &transpose_last2_pitched);
+    m.impl("transpose_to_groups", &transpose_to_groups);
+    m.impl("csp_scatter_add_gm", &csp_scatter_add_gm);
     m.impl("block_mean", &block_mean);
     m.impl("quantize_fp8", &quantize_fp8);
     m.impl("quantize_fp8_rowwise", &quantize_fp8_rowwise);

@@ -62,6 +62,41 @@ def _transposed(x: torch.Tensor) -> torch.Tensor:
     return x.transpose(-1, -2).contiguous()
 
 
+CACHE_LAYOUTS = ("column", "group")
+
+
+def _to_groups(x: torch.Tensor) -> torch.Tensor:
+    """[..., N, F] -> [..., ceil(N/128), F, 128]: element (g, f, r) is column f of token g * 128 + r, the rows of the last group at or past
+    N zero -- the group-major activation cache.  One HBM-rate kernel for 16-bit GPU tensors, plain torch otherwise."""
+    if x.is_cuda and x.element_size() == 2:
+        return torch.ops.chipmunk.transpose_to_groups(x)
+    n, f = x.shape[-2:]
+    g = (n + 127) // 128
+    padded = torch.nn.functional.pad(x, (0, 0, 0, g * 128 - n))
+    return padded.reshape(x.shape[:-2] + (g, 128, f)).transpose(-1, -2).contiguous()
+
+
+def activation_cache_of(who: str, act: torch.Tensor) -> torch.Tensor:
+    """The activation cache a full step stores for ``act`` ``[B, N, F]``, in the layout ``mlp.cache_layout`` names at that moment:
+    ``"column"`` -- ``[B, F, ceil8(N)]`` with zeroed padding (``[B, F, N]``, the reference's contiguous cache, for every N % 8 == 0) --
+    or ``"group"`` -- ``[B, ceil(N/128), F, 128]``.  Stored (and offloaded) whole either way."""
+    layout = amd_key("mlp", "cache_layout")
+    if layout not in CACHE_LAYOUTS:
+        raise ValueError(f"{who}: mlp.cache_layout must be one of {', '.join(CACHE_LAYOUTS)} (got {layout!r})")
+    if layout == "group":
+        return _to_groups(act)
+    n = act.shape[1]
+    return _transposed(act) if n % 8 == 0 else _transposed_pitched(act, _ceil8(n))
+
+
+def activation_cache_view(stored: torch.Tensor, n: int, batched: bool) -> torch.Tensor:
+    """What the sparse-MLP operators take of the stored activation cache, by its rank: a group-major ``[B, G, F, 128]`` whole (its
+    ``[G, F, 128]`` block for one sequence), of a column-major ``[B, F, ld]`` the ``[F, N]`` view of the pitched columns."""
+    if stored.ndim == 4:
+        return stored if batched else stored[0]
+    return stored[..., :n] if batched else stored[0][:, :n]
+
+
 _F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
 
@@ -161,8 +196,8 @@ class SparseDiffMlp:
             out = fc2(act)
             # the module owns the activation cache: [B, F, ld] with ld = ceil8(N) and zeroed padding, stored (and offloaded) whole; the
             # operators get its [F, N] view ([B, F, N] for a batch).  ld == N for every N % 8 == 0: the contiguous cache of the reference.
-            n = x.shape[1]
-            self.storage.set_sparse_act_T(_transposed(act) if n % 8 == 0 else _transposed_pitched(act, _ceil8(n)))
+            # (mlp.cache_layout "group": [B, ceil(N/128), F, 128] instead, handed to the operators whole)
+            self.storage.set_sparse_act_T(activation_cache_of("SparseDiffMlp", act))
             self.storage.set_out_cache(out)
             self.storage.set_blockmean_mid_cache(block_mean(mid, mbm))
             return out
@@ -224,8 +259,8 @@ class SparseDiffMlp:
         indices = inds if batched else inds[0]
         counts = counts if batched else counts[0]
         out_cache = stored if batched else stored[0]
-        sparse_act_T = self.storage.get_sparse_act_T()
-        sparse_act_T = sparse_act_T[..., : x.shape[1]] if batched else sparse_act_T[0][:, : x.shape[1]]   # the [F, N] view of the pitched cache
+        # (the [F, N] view of the pitched cache, or the group-major cache whole: the stored tensor's rank decides, not the config key)
+        sparse_act_T = activation_cache_view(self.storage.get_sparse_act_T(), x.shape[1], batched)
 
         scale_a = scale_b = None
         if fc1.weight.dtype == torch.float8_e4m3fn and getattr(fc1, "scaling", "tensor") == "row":

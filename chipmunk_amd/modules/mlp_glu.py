@@ -24,7 +24,7 @@ from .. import ops
 from ..util.config import GLOBAL_CONFIG
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
-from .mlp import _ceil8, _transposed, _transposed_pitched, activation_code, block_mean, check_fc2, fc2_scale_of, top_p_of
+from .mlp import activation_cache_of, activation_cache_view, activation_code, block_mean, check_fc2, fc2_scale_of, top_p_of
 
 _F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
@@ -158,8 +158,9 @@ class SparseDiffGatedMlp:
             g, u = self._pre(x)
             act = self.activation(g) * u
             out = self.fc2[0](act)
-            # the module owns the activation cache: [B, F, ld] with ld = ceil8(N) and zeroed padding (see SparseDiffMlp)
-            self.storage.set_sparse_act_T(_transposed(act) if n % 8 == 0 else _transposed_pitched(act, _ceil8(n)))
+            # the module owns the activation cache: [B, F, ld] with ld = ceil8(N) and zeroed padding, or -- mlp.cache_layout "group" --
+            # [B, ceil(N/128), F, 128] (see SparseDiffMlp)
+            self.storage.set_sparse_act_T(activation_cache_of("SparseDiffGatedMlp", act))
             self.storage.set_out_cache(out)
             self.storage.set_blockmean_mid_cache(self._paired_block_means(block_mean(g, mbm), block_mean(u, mbm), bm_rows))
             return out
@@ -201,8 +202,7 @@ class SparseDiffGatedMlp:
         indices = inds if batched else inds[0]
         counts = counts if batched else counts[0]
         out_cache = stored if batched else stored[0]
-        sparse_act_T = self.storage.get_sparse_act_T()
-        sparse_act_T = sparse_act_T[..., :n] if batched else sparse_act_T[0][:, :n]   # the [F, N] view of the pitched cache
+        sparse_act_T = activation_cache_view(self.storage.get_sparse_act_T(), n, batched)   # by the stored tensor's rank
 
         gate, up = self.gate, self.up
         if self.fp8:

@@ -79,6 +79,21 @@ def _register():
     def _(x, ld):
         return x.new_empty(x.shape[:-2] + (x.shape[-1], ld))
 
+    @lib.register_fake("chipmunk::transpose_to_groups")
+    def _(x):
+        torch._check(x.ndim >= 2 and x.element_size() == 2, lambda: "transpose_to_groups: need a >=2-D tensor of a 16-bit dtype")
+        return x.new_empty(x.shape[:-2] + ((x.shape[-2] + 127) // 128, x.shape[-1], 128))   # the last group may be short: zero rows
+
+    @lib.register_fake("chipmunk::csp_scatter_add_gm")
+    def _(packed, unpacked_groups, sp_inds, sp_counts):
+        # accumulates into unpacked_groups in place and returns nothing
+        torch._check(packed.ndim == 3 and unpacked_groups.ndim == 4, lambda: "packed must be [B, M, F], unpacked_groups [B, G, F, 128]")
+        b, m, f = packed.shape
+        g = (m + 127) // 128
+        torch._check(unpacked_groups.shape == (b, g, f, 128), lambda: "unpacked_groups must be [B, ceil(M/128), F, 128]")
+        torch._check(sp_inds.shape == (b, g, f) and sp_counts.shape == (b, g), lambda: "sp_inds must be [B, ceil(M/128), F], sp_counts [B, ceil(M/128)]")
+        return None
+
     @lib.register_fake("chipmunk::quantize_fp8")
     def _(x, scale, max_value):
         return x.new_empty(x.shape, dtype=torch.float8_e4m3fn)

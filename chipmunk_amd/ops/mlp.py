@@ -47,6 +47,26 @@ def _row_scales(who: str, x: torch.Tensor, fc1w: torch.Tensor, scale_a: torch.Te
                      "column; a vector on one side only has no kernel")
 
 
+def group_major(x: torch.Tensor, sparse_act_T: torch.Tensor) -> bool:
+    """The operators' rule: a cache of one dimension more than ``x`` -- ``[G, F, 128]`` for ``x [M, K]``, ``[B, G, F, 128]`` for
+    ``x [B, M, K]``, G = ceil(M / 128) -- is group-major (``mlp.cache_layout: group``), unless its shape is also a column-major one
+    (``[1, F, M]``: M = 128, the same elements either way).  Only the operators this project added take it: on that route tanh-GELU
+    with a bias goes through ``csp_mlp_mm1_act`` / ``csp_mlp_mm1_fp8_act`` as well, and the tail is GEMM1's own scatter-add or
+    ``csp_scatter_add_gm``, then GEMM2 alone."""
+    if sparse_act_T.ndim != x.ndim + 1:
+        return False
+    M = x.shape[-2]
+    return not (sparse_act_T.shape[-1] == M and sparse_act_T.numel() == sparse_act_T.shape[-2] * M)
+
+
+def scatter_add_gm(packed: torch.Tensor, unpacked_groups: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor) -> None:
+    """``csp_scatter_add`` on the group-major cache: ``unpacked_groups[g, idx[g, j], r] += packed[g * 128 + r, j]``; 2-D ``packed`` with
+    ``[G, F, 128]`` or a batch ``[B, M, F]`` with ``[B, G, F, 128]``."""
+    if packed.ndim == 2:
+        packed, unpacked_groups, indices, counts = packed.unsqueeze(0), unpacked_groups.unsqueeze(0), indices.unsqueeze(0), counts.unsqueeze(0)
+    torch.ops.chipmunk.csp_scatter_add_gm(packed, unpacked_groups, indices, counts)
+
+
 def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
         sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
         scale_a: Optional[torch.Tensor] = None, scale_b: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
@@ -54,7 +74,7 @@ def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc
     assert x.dtype == (torch.float8_e4m3fn if fc1w.dtype == torch.float8_e4m3fn else torch.bfloat16)
     assert sparse_act_packed.dtype == torch.bfloat16
     assert sparse_act_T.dtype == torch.bfloat16
-    default = _default_form("mm1", act, fc1b)
+    default = _default_form("mm1", act, fc1b) and not group_major(x, sparse_act_T)
     if fc1w.dtype == torch.bfloat16:
         if default:
             torch.ops.chipmunk.csp_mlp_mm1(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
@@ -73,7 +93,7 @@ def mm1_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Te
                 sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, act: str = "gelu_tanh") -> None:
     """GEMM1 + ``csp_scatter_add`` of its output into ``sparse_act_T`` in one kernel (bf16 only)."""
     assert x.dtype == torch.bfloat16 and sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
-    if _default_form("mm1_scatter", act, fc1b):
+    if _default_form("mm1_scatter", act, fc1b) and not group_major(x, sparse_act_T):
         torch.ops.chipmunk.csp_mlp_mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
     else:
         torch.ops.chipmunk.csp_mlp_mm1_act(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, True)
@@ -85,7 +105,7 @@ def mm1_fp8_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torc
     """fp8 GEMM1 + ``csp_scatter_add`` of its output into ``sparse_act_T`` in one kernel (the fp8 counterpart of ``mm1_scatter``;
     bit-identical in the packed deltas and in the cache to ``csp_mlp_mm1_fp8`` followed by the scatter-add)."""
     assert x.dtype == torch.float8_e4m3fn and fc1w.dtype == torch.float8_e4m3fn
-    default = _default_form("mm1_fp8_scatter", act, fc1b)      # (the name is checked before anything else)
+    default = _default_form("mm1_fp8_scatter", act, fc1b) and not group_major(x, sparse_act_T)      # (the name is checked before anything else)
     if _row_scales("mm1_fp8_scatter", x, fc1w, scale_a, scale_b):   # update_cache 2: the scatter-add of the deltas
         torch.ops.chipmunk.csp_mlp_mm1_fp8_act_rs(x, fc1w.contiguous(), sparse_act_packed, fc1b, sparse_act_T, indices, counts,
                                                   scale_a.float().contiguous(), scale_b.float().contiguous(), act, 2)
@@ -108,7 +128,7 @@ def csp_mlp_mm1_fp8(a: torch.Tensor, b: torch.Tensor, fc1b: Optional[torch.Tenso
     the same storage); scales are the RECIPROCAL quantisation scales (modules/mlp.py:98-99)."""
     if b.shape[0] == a.shape[1] and b.shape[1] != a.shape[1]:
         b = b.T  # accept the reference's fc1w.T view
-    default = _default_form("csp_mlp_mm1_fp8", act, fc1b)      # (the name is checked before anything else)
+    default = _default_form("csp_mlp_mm1_fp8", act, fc1b) and not group_major(a, sparse_act_unpacked_inout)   # (the name is checked first)
     if _row_scales("csp_mlp_mm1_fp8", a, b, scale_a, scale_b):   # one scale per token row and per fc1 column: every activation / bias form
         torch.ops.chipmunk.csp_mlp_mm1_fp8_act_rs(a, b.contiguous(), sparse_act_packed_out, fc1b, sparse_act_unpacked_inout, indices,
                                                   counts, scale_a.float().contiguous(), scale_b.float().contiguous(), act,
@@ -179,8 +199,9 @@ def _check_batch(x: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, s
     assert x.ndim in (2, 3), "x must be [M, K] or [B, M, K]"
     if x.ndim == 3:
         B = x.shape[0]
-        assert indices.ndim == 3 and counts.ndim == 2 and sparse_act_T.ndim == 3 and cached_out.ndim == 3, \
-            "a batched x [B, M, K] takes indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] and cached_out [B, M, N]"
+        assert indices.ndim == 3 and counts.ndim == 2 and sparse_act_T.ndim in (3, 4) and cached_out.ndim == 3, \
+            "a batched x [B, M, K] takes indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] (group-major: [B, G, F, 128]) and " \
+            "cached_out [B, M, N]"
         assert indices.shape[0] == B and counts.shape[0] == B and sparse_act_T.shape[0] == B and cached_out.shape[0] == B, \
             f"the batch size of indices / counts / sparse_act_T / cached_out must be that of x ({B})"
 
@@ -192,6 +213,9 @@ def _after_gemm1(cache_updated: bool, sparse_act_packed: torch.Tensor, fc2w_T: t
     own deltas (same bits as the two-kernel form), so GEMM2 runs alone; otherwise the scatter-add and GEMM2, in the form ``fc2w_T`` takes.
     (The operators are looked up in the module when they are called: a benchmark may have put timing wrappers in their place.)"""
     if cache_updated:
+        csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
+    elif group_major(sparse_act_packed, sparse_act_T):   # csp_mlp_mm2_and_scatter_add knows the column-major cache only
+        scatter_add_gm(sparse_act_packed, sparse_act_T, indices, counts)
         csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
     elif fc2w_T.dtype == torch.float8_e4m3fn:
         _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
@@ -206,6 +230,7 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
             counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
             mm1_scale_a: Optional[torch.Tensor] = None, mm1_scale_b: Optional[torch.Tensor] = None,
             fc2_scale: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
+    # sparse_act_T of one dimension more than x ([G, F, 128] / [B, G, F, 128]) is the group-major cache: see group_major.  Otherwise:
     # M is any positive row count (ceil(M / 128) groups, the last one short); sparse_act_T is [F, M], contiguous or -- required when
     # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers.
     # A batch: x [B, M, K1] with indices [B, G, F], counts [B, G], sparse_act_T [B, F, M] (or the [..., :M] view of [B, F, ldc]) and
@@ -310,5 +335,5 @@ def run_e2e_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b
                    x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
 
 
-__all__ = ["mm1", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
+__all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
            "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8"]

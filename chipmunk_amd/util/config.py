@@ -139,6 +139,11 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # input (recomputed on every call, one HIP pass) and one per output feature of the weight -- fc1's sparse steps then run
     # csp_mlp_mm1_fp8_act_rs.  fc2 under mlp.fp8_fc2 keeps one scale per tensor either way (GEMM2's weight-only gather takes one).
     "mlp.fp8_scaling": "tensor",
+    # layout of the sparse MLP's activation cache (not in the reference; read at every full step, the sparse steps follow the stored tensor):
+    # "column" = [B, F, ceil8(N)], column-major as in the reference; "group" = [B, ceil(N/128), F, 128] -- the 256-byte pieces GEMM1 gathers
+    # for a 128-row group then lie on a 256-byte grid inside one F * 256-byte window instead of 2 * N bytes apart over the whole tensor, and
+    # a token count that is no multiple of 8 needs no pitched columns (the last group is short).  Same bits; any other string raises.
+    "mlp.cache_layout": "column",
 }
 BASE_CONFIG["offloading"]["keep_resident_if_fits"] = AMD_EXTRA_KEYS["offloading.keep_resident_if_fits"]
 BASE_CONFIG["offloading"]["hbm_budget_gb"] = AMD_EXTRA_KEYS["offloading.hbm_budget_gb"]
@@ -161,6 +166,7 @@ BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
 BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]
 BASE_CONFIG["mlp"]["top_p_min_keys"] = AMD_EXTRA_KEYS["mlp.top_p_min_keys"]
 BASE_CONFIG["mlp"]["fp8_scaling"] = AMD_EXTRA_KEYS["mlp.fp8_scaling"]
+BASE_CONFIG["mlp"]["cache_layout"] = AMD_EXTRA_KEYS["mlp.cache_layout"]
 
 GLOBAL_CONFIG: Dict[str, Any] = copy.deepcopy(BASE_CONFIG)
 

@@ -322,6 +322,38 @@ int chipmunk_csp_mlp_mm2_w8(const void *mma_a, const void *mma_b, const float *s
 int chipmunk_csp_mlp_mm2_w8_batched(const void *mma_a, const void *mma_b, const float *scale_b, void *mma_c, const int32_t *indices,
                                     const int32_t *counts, int M, int F, int N2, int B, void *stream);
 
+/* Group-major cache: the activation cache of one sequence as [G, F, 128] bf16, contiguous, G = ceil(M / 128) -- element (g, i, r) is
+ * activation column i of token row g * 128 + r -- instead of the column-major [F, ldc] (no reference counterpart).  The 256-byte pieces of
+ * a group's kept columns then lie on a 256-byte grid inside one F * 256-byte window.  Rows of the last group at or past M are never
+ * read for a result and never written.  A batch is [B, G, F, 128]: sequence b's block starts at element b * cache_batch_stride, with
+ * cache_batch_stride >= G * F * 128 and a multiple of 8 elements (checked for B = 1 as well); nothing outside the blocks is touched.
+ * G * F * 128 < 2^31.  Each *_gm entry is its *_batched namesake without `ldc`: same operands, same arithmetic and the same bits for
+ * c and for every cache element, B >= 1 with B = 1 the single-sequence launch, B * G <= 65535.  Each failed check returns
+ * CHIPMUNK_ERR_INVALID with a message that names the rule, before anything is enqueued. */
+int chipmunk_csp_mlp_mm1_act_gm(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                const int32_t *counts, int M, int K, int F, int act, int update_cache, int B,
+                                int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_fp8_act_gm(const void *a, const void *b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                                    const int32_t *counts, const float *scale_a, const float *scale_b, int M, int K, int F, int act,
+                                    int update_cache, int B, int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_fp8_act_rs_gm(const void *a, const void *b, void *c, const void *bias, void *pa_cache,
+                                       const int32_t *indices, const int32_t *counts, const float *scale_a, const float *scale_b,
+                                       int M, int K, int F, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                       void *stream);
+int chipmunk_csp_mlp_mm1_glu_gm(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K,
+                                int F, int act, int update_cache, int B, int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_glu_fp8_gm(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
+                                    const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts,
+                                    const float *scale_a, const float *scale_b_gate, const float *scale_b_up, int M, int K, int F,
+                                    int act, int update_cache, int B, int64_t cache_batch_stride, void *stream);
+/* chipmunk_csp_scatter_add_batched on the group-major cache: unpacked_groups[b][g, idx[b,g,j], r] += packed[b, g * 128 + r, j] */
+int chipmunk_csp_scatter_add_gm(const void *packed, void *unpacked_groups, const int32_t *indices, const int32_t *counts, int M,
+                                int F, int B, int64_t cache_batch_stride, void *stream);
+/* [B,R,C] -> [B, ceil(R/128), C, 128] for 16-bit elements: builds the group-major cache of a full step, dst[b, g, c, r] =
+ * src[b, g * 128 + r, c], the rows of the last group at or past R zero.  src and dst contiguous and 16-byte aligned. */
+int chipmunk_transpose16_groups(const void *src, void *dst, int B, int R, int C, void *stream);
+
 /* ---------------------------------------------------------------- indexed IO
  * Replaces chipmunk::topk_indices (reference csrc/indexed_io/topk_indices.cu:145-218; schema chipmunk.cpp:58).
  * activation [B*R, C] of `dtype`; indices [B*R, C] int32; counts [B*R] int32.  Threshold = element

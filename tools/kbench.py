@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan fp8_rs_wan mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -376,6 +376,67 @@ def bench_fp8_rs_wan(M=32768, act="silu"):
         print(f"{k:26s}: {us[1]:8.1f} us  [{us[0]:.1f} .. {us[2]:.1f}]  {bytes_moved / us[1] / 1e3:7.1f} GB/s of 3 * rows * K + 4 * rows bytes   (rows={M} K={K})")
 
 
+def bench_cache_groups(which, M, K, F, keep, fp8):
+    """The two layouts of the activation cache under one GEMM1 (mlp.cache_layout; DESIGN 4.2, "Group-major cache"): the column-major
+    [F, M] against the group-major [ceil(M/128), F, 128] holding the same values, same operator (csp_mlp_mm1_fp8_act with the scatter-add
+    of its deltas at the Wan fp8 shape, csp_mlp_mm1_act with it at the FLUX bf16 shape), same operands, alternating in one process
+    (KB_ROUNDS pairs, default 5); median and range over the rounds of `timeit`'s median bracket.  KB_LAYERS=n rotates n sets of weights /
+    caches / outputs (n = 30: the loop's cold-cache condition, every layer's cache pieces come from HBM)."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    G = (M + 127) // 128
+    a = torch.randn(M, K, device=dev, generator=g)
+    a = (a * 16).clamp(-448, 448).to(torch.float8_e4m3fn) if fp8 else a.to(torch.bfloat16)
+    sa, sb = torch.tensor([1 / 16.0], device=dev), torch.tensor([1 / 512.0], device=dev)
+    bias = torch.zeros(F, device=dev, dtype=torch.bfloat16)
+    packed = torch.empty(M, F, device=dev, dtype=torch.bfloat16)
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    sets = []
+    for _ in range(L):
+        w = torch.randn(F, K, device=dev, generator=g) * 0.02
+        w = (w * 512).clamp(-448, 448).to(torch.float8_e4m3fn) if fp8 else w.to(torch.bfloat16)
+        col = torch.randn(F, M, device=dev, dtype=torch.bfloat16, generator=g) * 0.1
+        grp = torch.nn.functional.pad(col, (0, G * 128 - M)).view(F, G, 128).permute(1, 0, 2).contiguous()
+        sets.append((w, col, grp))
+    state = {"i": 0}
+
+    def run(layout):
+        state["i"] = (state["i"] + 1) % L
+        w, col, grp = sets[state["i"]]
+        cache = grp if layout == "group" else col
+        if fp8:
+            torch.ops.chipmunk.csp_mlp_mm1_fp8_act(a, w, packed, bias, cache, inds, counts, sa, sb, "gelu_tanh", 2)
+        else:
+            torch.ops.chipmunk.csp_mlp_mm1_act(a, w, packed, bias, cache, inds, counts, "gelu_tanh", True)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {"column": [], "group": []}
+    for _ in range(rounds):      # alternating, so that a drift of the box falls on both
+        for k in t:
+            t[k].append(timeit(lambda: run(k), reps=5 if M > 8192 else 20) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * K * keep
+    tag = f"(M={M} K={K} F={F} keep={keep} layers={L}, {rounds} alternating rounds)"
+    for k in t:
+        print(f"{which} cache {k:6s}: {med[k]:8.1f} us  [{min(t[k]):.1f} .. {max(t[k]):.1f}]  {flops/med[k]/1e6:7.1f} TFLOP/s   {tag}")
+    print(f"{which} group / column: {med['group'] / med['column']:7.3f}")
+
+
+def bench_to_groups(R, C, B=1):
+    """transpose_to_groups ([B, R, C] -> [B, ceil(R/128), C, 128], the full step's cache of mlp.cache_layout: group) against transpose_last2
+    ([B, C, R]) on the same activations, alternating; us and GB/s of the 4 * B * R * C bytes both have to move."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(B, R, C, device=dev, dtype=torch.bfloat16, generator=g)
+    runs = {"transpose_last2": lambda: torch.ops.chipmunk.transpose_last2(x), "transpose_to_groups": lambda: torch.ops.chipmunk.transpose_to_groups(x)}
+    t = {k: [] for k in runs}
+    for _ in range(int(os.environ.get("KB_ROUNDS", "5"))):
+        for k, fn in runs.items():
+            t[k].append(timeit(fn, reps=10) * 1e3)
+    for k, v in t.items():
+        med = sorted(v)[len(v) // 2]
+        print(f"{k:20s}: {med:8.1f} us  [{min(v):.1f} .. {max(v):.1f}]  {4.0 * B * R * C / med / 1e3:7.1f} GB/s   (B={B} R={R} C={C})")
+
+
 def sorted_random_indices(H, G, n_keys, count, width, g):
     inds = torch.zeros(1, H, G, width, dtype=torch.int32, device=dev)
     for h in range(H):
@@ -501,6 +562,13 @@ def main():
             bench_fp8_wan()
         elif w == "fp8_rs_wan":       # fp8 GEMM1 with scale vectors against the scalar launch, and the row-wise input quantiser (KB_GLU_ACT as mm1_glu)
             bench_fp8_rs_wan(act=os.environ.get("KB_GLU_ACT", "silu"))
+        elif w == "fp8_wan_groups":   # fp8 GEMM1 + scatter-add at the Wan shape: column-major against group-major cache (KB_LAYERS, KB_ROUNDS)
+            bench_cache_groups("mm1_fp8 (Wan C5)", M=32768, K=1536, F=8960, keep=2688, fp8=True)
+        elif w == "mm1s_groups":      # bf16 GEMM1 + scatter-add at the FLUX shape: column-major against group-major cache
+            bench_cache_groups("mm1s (FLUX)", M=4352, K=3072, F=12288, keep=int(os.environ.get("KB_KEEP", "3840")), fp8=False)
+        elif w == "to_groups":        # the full step's layout kernel against transpose_last2 at the Wan and HunyuanVideo activation shapes
+            bench_to_groups(32760, 8960)
+            bench_to_groups(119056, 12288)
         elif w == "mm2_wan":          # GEMM2 at the Wan2.1 1.3B shape (configs[4]): M = 32 768 rows, N2 = 1 536, F = 8 960, 30 % kept
             bench_mlp("mm2", variants, M=32768, K=1536, F=8960, keep=2816)
         elif w == "fp8_wan_ragged":   # the same launches on Wan2.1's 32 760 tokens as they are: 255 groups + 120 rows
