@@ -25,7 +25,7 @@ SYMBOLS = [
     "chipmunk_csp_mlp_mm1_fp8_act_rs", "chipmunk_csp_mlp_mm1_fp8_act_rs_batched", "chipmunk_quantize_fp8_rowwise",
     "chipmunk_csp_mlp_mm1_act_gm", "chipmunk_csp_mlp_mm1_fp8_act_gm", "chipmunk_csp_mlp_mm1_fp8_act_rs_gm", "chipmunk_csp_mlp_mm1_glu_gm",
     "chipmunk_csp_mlp_mm1_glu_fp8_gm", "chipmunk_csp_scatter_add_gm", "chipmunk_transpose16_groups",
-    "chipmunk_topk_indices", "chipmunk_topk_delta_indices", "chipmunk_topk_indices_p", "chipmunk_topk_delta_indices_p", "chipmunk_topk_mask", "chipmunk_topk_mask_p", "chipmunk_dense_colsum_topk_mask_p_strided", "chipmunk_mask_to_indices", "chipmunk_mask_to_sorted_indices", "chipmunk_packed_mask_to_indices", "chipmunk_mask_row_counts", "chipmunk_mask_to_ragged_indices", "chipmunk_copy_indices",
+    "chipmunk_topk_indices", "chipmunk_topk_delta_indices", "chipmunk_topk_indices_p", "chipmunk_topk_delta_indices_p", "chipmunk_topk_group_delta_indices", "chipmunk_topk_group_delta_indices_p", "chipmunk_topk_mask", "chipmunk_topk_mask_p", "chipmunk_dense_colsum_topk_mask_p_strided", "chipmunk_mask_to_indices", "chipmunk_mask_to_sorted_indices", "chipmunk_packed_mask_to_indices", "chipmunk_mask_row_counts", "chipmunk_mask_to_ragged_indices", "chipmunk_copy_indices",
     "chipmunk_bitpack", "chipmunk_bitunpack", "chipmunk_transpose16", "chipmunk_block_mean", "chipmunk_quantize_fp8", "chipmunk_gather_rows", "chipmunk_qkv_split_norm", "chipmunk_split_heads_rownorm", "chipmunk_dense_colsum_topk_mask", "chipmunk_dense_attn_strided", "chipmunk_csp_attn_out_ragged", "chipmunk_compact_indices", "chipmunk_residual_ln_modulate", "chipmunk_dense_colsum_attn_strided", "chipmunk_dense_colsum_topk_mask_strided", "chipmunk_release_scratch", "chipmunk_big_scratch_fallbacks",
     "chipmunk_dense_attn_varlen", "chipmunk_dense_colsum_attn_varlen", "chipmunk_dense_colsum_topk_mask_varlen",
     "chipmunk_dense_colsum_topk_mask_p_varlen", "chipmunk_topk_mask_varlen", "chipmunk_topk_mask_p_varlen",
@@ -45,6 +45,11 @@ def lib() -> ctypes.CDLL:
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.chipmunk_last_error.restype = ctypes.c_char_p
         _lib.chipmunk_abi_version.restype = ctypes.c_int
+        vp, i, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+        # (activation, cache, dtype, indices, counts, B, rows, R, cols, sparsity_amount[, top_p, min_keys], multiple_of, random_amount, stream)
+        if hasattr(_lib, "chipmunk_topk_group_delta_indices"):      # (CHIPMUNK_HIP_LIB may name an older build)
+            _lib.chipmunk_topk_group_delta_indices.argtypes = [vp, vp, i, vp, vp, i, i, i, i, d, i, d, vp]
+            _lib.chipmunk_topk_group_delta_indices_p.argtypes = [vp, vp, i, vp, vp, i, i, i, i, d, d, d, i, d, vp]
         # A/B experiments without code edits: CHIPMUNK_AMD_OPTIONS="mm2_variant=12,mm1_nr=8" (tuning knobs only;
         # unknown names raise)
         for item in filter(None, os.environ.get("CHIPMUNK_AMD_OPTIONS", "").split(",")):

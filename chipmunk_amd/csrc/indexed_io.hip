@@ -294,6 +294,9 @@ struct TopkParams {
     int rows, cols, multiple_of;
     float quantile, random_amount;
     uint32_t salt;  // per-launch value (host counter mixed with the seed, see chipmunk_next_random_salt)
+    // GROUP form only: act / cache are [batches, src_rows, cols]; workgroup b * groups + g owns rows [g * group_rows, (g + 1) * group_rows)
+    // of sequence b, cut at src_rows (the last group may be short)
+    int group_rows, src_rows, groups;
 };
 
 template <typename T>
@@ -369,26 +372,56 @@ struct TopkPParams : TopkParams {
     int k_min;  // index of thr_min in the sorted sample; >= 1024: no floor
 };
 
-template <typename T, bool DELTA, bool TOPP = false>
+// GROUP = true (with DELTA; topk_group_delta_indices, not in the reference) is the delta form over the nr <= group_rows block-mean rows
+// a 128-row group owns (bm > mbm, and the gate / up pairs of the gated MLP): the ranked value of column c is
+//     s_c = T( sum_i float( T(|b_i[c] - cache_i[c]|) ) ),   i ascending over the group's rows, fp32, rounded to T once
+// -- what (b - cache).abs().reshape(B, G, R, F).sum(2) gives for R = 2 bit for bit (one fp32 add, one rounding), and for R = 1 the
+// plain delta form's value.  The sum starts at +0: the terms are |.|, never -0, so 0 + t_0 is t_0 in every bit (NaN included).  The
+// scores are non-negative and rounded to T, so the low-bit shortcuts below hold; the workgroup (one per (sequence, group)) lists into
+// row b * groups + g of indices / counts and copies a listed column in every row the group owns.  The first pass walks the rows in the
+// outer loop, so a thread has its 16 columns of a row in flight at once; columns past 16 384 are summed again where they are needed.
+template <typename T, bool DELTA, bool TOPP = false, bool GROUP = false>
 __global__ __launch_bounds__(1024) void topk_indices_kernel(const typename std::conditional<TOPP, TopkPParams, TopkParams>::type p) {
+    static_assert(DELTA || !GROUP, "the group form is a delta form");
     __shared__ uint32_t wave_tot[16];
     __shared__ float thr_s;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x;
-    const T *x = (const T *)p.act + (int64_t)row * p.cols;
-    T *xc = DELTA ? (T *)p.cache + (int64_t)row * p.cols : nullptr;
-    int32_t *out = p.indices + (int64_t)row * p.cols;
     const int cols = p.cols;
+    int64_t first = row;   // first row of act / cache this workgroup reads
+    int nr = 1;            // ... and how many
+    if constexpr (GROUP) {
+        const int b = row / p.groups, g = row - b * p.groups;
+        first = (int64_t)b * p.src_rows + (int64_t)g * p.group_rows;
+        nr = min(p.group_rows, p.src_rows - g * p.group_rows);
+    }
+    const T *x = (const T *)p.act + first * cols;
+    T *xc = DELTA ? (T *)p.cache + first * cols : nullptr;
+    int32_t *out = p.indices + (int64_t)row * cols;
     auto value = [&](int c) {
-        const float b = load_as_float<T>(x, c);
-        if constexpr (DELTA) return fabsf(round_to<T>(b - load_as_float<T>(xc, c)));
-        else return b;
+        if constexpr (GROUP) {
+            float s = 0.f;
+            for (int i = 0; i < nr; ++i)
+                s += fabsf(round_to<T>(load_as_float<T>(x + (int64_t)i * cols, c) - load_as_float<T>(xc + (int64_t)i * cols, c)));
+            return round_to<T>(s);
+        } else {
+            const float b = load_as_float<T>(x, c);
+            if constexpr (DELTA) return fabsf(round_to<T>(b - load_as_float<T>(xc, c)));
+            else return b;
+        }
+    };
+    auto refresh = [&](int c) {  // DELTA: column c of the activations into the cache, in every row this workgroup owns
+        if constexpr (GROUP) {
+            for (int i = 0; i < nr; ++i) xc[(int64_t)i * cols + c] = x[(int64_t)i * cols + c];
+        } else {
+            xc[c] = x[c];
+        }
     };
 
     const uint32_t salt = p.salt ^ (__float_as_uint(value(0)) * 0x27D4EB2Fu);  // the fused (delta) form sees what the unfused op sees
     if (!TOPP && p.quantile == 0.f) {  // keep everything (topk_indices.cu:51-59); the _p form has no cap there and still selects by mass
         if constexpr (DELTA)
-            for (int c = tid; c < cols; c += 1024) xc[c] = x[c];
+            for (int c = tid; c < cols; c += 1024) refresh(c);
         for (int c = tid; c < cols; c += 1024) out[c] = c;
         if (tid == 0) p.counts[row] = cols;
         return;
@@ -406,10 +439,25 @@ __global__ __launch_bounds__(1024) void topk_indices_kernel(const typename std::
     // round trip for sample and first pass instead of two (the rows are cold in the real loop: 31 -> 25 us)
     __shared__ float sample[1024];
     float v_first[16];
+    if constexpr (GROUP) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int c = j * 1024 + tid;
-        v_first[j] = c < cols ? value(c) : 0.f;
+        for (int j = 0; j < 16; ++j) v_first[j] = 0.f;
+        for (int i = 0; i < nr; ++i) {
+            const T *xi = x + (int64_t)i * cols, *ci = xc + (int64_t)i * cols;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int c = j * 1024 + tid;
+                if (c < cols) v_first[j] += fabsf(round_to<T>(load_as_float<T>(xi, c) - load_as_float<T>(ci, c)));
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v_first[j] = round_to<T>(v_first[j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int c = j * 1024 + tid;
+            v_first[j] = c < cols ? value(c) : 0.f;
+        }
     }
     sample[tid] = v_first[0];
     if constexpr (TOPP) {
@@ -560,7 +608,7 @@ __global__ __launch_bounds__(1024) void topk_indices_kernel(const typename std::
             if (keepbits & (1u << j)) {
                 const int c = pass0 + j * 1024 + tid;
                 out[base + tot[j * 16 + w] + before[j]] = c;
-                if constexpr (DELTA) xc[c] = x[c];
+                if constexpr (DELTA) refresh(c);
             }
         base += tot[256];
         __syncthreads();
@@ -575,7 +623,7 @@ __global__ __launch_bounds__(1024) void topk_indices_kernel(const typename std::
         const int slot = compact_slot(my_last_invalid != -1, lane, w, wave_tot, pbase);
         if (slot >= 0 && slot < pad) {
             out[kept + slot] = my_last_invalid;
-            if constexpr (DELTA) xc[my_last_invalid] = x[my_last_invalid];
+            if constexpr (DELTA) refresh(my_last_invalid);
         }
     }
 }
@@ -1442,8 +1490,27 @@ extern "C" int chipmunk_packed_mask_to_indices(const void *packed, int32_t *indi
     return launch_m2i<true>(packed, indices, counts, rows, n, pad_n, multiple_of, stream);
 }
 
+// the group forms (topk_group_delta_indices[_p]): the shape of the operands, checked here; the launch is launch_topk[_p]'s with one
+// workgroup per (sequence, group)
+struct TopkGroups {
+    int batches, src_rows, group_rows;
+    int groups() const { return (src_rows + group_rows - 1) / group_rows; }
+};
+static int check_topk_groups(const char *who, const TopkGroups &gs, const void *activation, const void *cache, const int32_t *indices,
+                             const int32_t *counts, int cols, int *rows) {
+    CM_CHECK(activation && cache && indices && counts, "%s: null pointer", who);
+    CM_CHECK(cols >= 1024, "%s: cols >= 1024 required (the quantile is taken over the first 1024 columns); got cols=%d", who, cols);
+    CM_CHECK(gs.group_rows >= 1 && gs.group_rows <= 64, "%s: rows_per_group must be in [1, 64] (got %d)", who, gs.group_rows);
+    CM_CHECK(gs.batches >= 0 && gs.src_rows >= 1, "%s: B >= 0 and rows >= 1 required; got B=%d rows=%d", who, gs.batches, gs.src_rows);
+    CM_CHECK((int64_t)gs.batches * gs.groups() < (1ll << 31), "%s: too many groups (B=%d times %d)", who, gs.batches, gs.groups());
+    *rows = gs.batches * gs.groups();
+    return CHIPMUNK_OK;
+}
+
 static int launch_topk(const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts, int rows,
-                       int cols, double sparsity_amount, int multiple_of, double random_amount, void *stream) {
+                       int cols, double sparsity_amount, int multiple_of, double random_amount, void *stream,
+                       const TopkGroups *gs = nullptr) {
+    if (gs && check_topk_groups("topk_group_delta_indices", *gs, activation, cache, indices, counts, cols, &rows)) return CHIPMUNK_ERR_INVALID;
     CM_CHECK(activation && indices && counts, "topk_indices: null pointer");
     CM_CHECK(rows >= 0 && cols >= 1024, "topk_indices: rows >= 0 and cols >= 1024 required (the quantile is taken over the first 1024 columns); got rows=%d cols=%d", rows, cols);
     CM_CHECK(multiple_of > 0, "topk_indices: multiple_of must be positive");
@@ -1451,10 +1518,12 @@ static int launch_topk(const void *activation, void *cache, int dtype, int32_t *
     if (rows == 0) return CHIPMUNK_OK;
     TopkParams p = {activation, cache, indices, counts, rows, cols, multiple_of, (float)sparsity_amount, (float)random_amount,
                     random_amount > 0.0 ? chipmunk_next_random_salt() : 0u};
+    if (gs) p.group_rows = gs->group_rows, p.src_rows = gs->src_rows, p.groups = gs->groups();
     hipStream_t s = (hipStream_t)stream;
 #define LAUNCH_TOPK(T)                                                                                           \
     do {                                                                                                         \
-        if (cache) hipLaunchKernelGGL((topk_indices_kernel<T, true>), dim3(rows), dim3(1024), 0, s, p);          \
+        if (gs) hipLaunchKernelGGL((topk_indices_kernel<T, true, false, true>), dim3(rows), dim3(1024), 0, s, p); \
+        else if (cache) hipLaunchKernelGGL((topk_indices_kernel<T, true>), dim3(rows), dim3(1024), 0, s, p);          \
         else hipLaunchKernelGGL((topk_indices_kernel<T, false>), dim3(rows), dim3(1024), 0, s, p);               \
     } while (0)
     switch (dtype) {
@@ -1471,7 +1540,8 @@ static int launch_topk(const void *activation, void *cache, int dtype, int32_t *
 // the _p forms: `who` names the entry point in the messages
 static int launch_topk_p(const char *who, const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts, int rows,
                          int cols, double sparsity_amount, double top_p, double min_keys, int multiple_of, double random_amount,
-                         void *stream) {
+                         void *stream, const TopkGroups *gs = nullptr) {
+    if (gs && check_topk_groups(who, *gs, activation, cache, indices, counts, cols, &rows)) return CHIPMUNK_ERR_INVALID;
     CM_CHECK(activation && indices && counts, "%s: null pointer", who);
     CM_CHECK(rows >= 0 && cols >= 1024, "%s: rows >= 0 and cols >= 1024 required (the quantiles are taken over the first 1024 columns); got rows=%d cols=%d", who, rows, cols);
     CM_CHECK(multiple_of > 0, "%s: multiple_of must be positive", who);
@@ -1487,12 +1557,14 @@ static int launch_topk_p(const char *who, const void *activation, void *cache, i
     p.quantile = (float)sparsity_amount, p.random_amount = (float)random_amount;
     p.salt = random_amount > 0.0 ? chipmunk_next_random_salt() : 0u;
     p.top_p = (float)top_p;
+    p.group_rows = gs ? gs->group_rows : 0, p.src_rows = gs ? gs->src_rows : 0, p.groups = gs ? gs->groups() : 0;
     // the floor's index in the sorted sample, never below the cap's (in exact arithmetic it is not): the kept set stays a subset of the cap's
     p.k_min = min_keys == 0.0 ? 1024 : std::max((int)(1024 * (float)(1.0 - min_keys)), (int)(1024 * p.quantile));
     hipStream_t s = (hipStream_t)stream;
 #define LAUNCH_TOPK_P(T)                                                                                         \
     do {                                                                                                         \
-        if (cache) hipLaunchKernelGGL((topk_indices_kernel<T, true, true>), dim3(rows), dim3(1024), 0, s, p);    \
+        if (gs) hipLaunchKernelGGL((topk_indices_kernel<T, true, true, true>), dim3(rows), dim3(1024), 0, s, p); \
+        else if (cache) hipLaunchKernelGGL((topk_indices_kernel<T, true, true>), dim3(rows), dim3(1024), 0, s, p);    \
         else hipLaunchKernelGGL((topk_indices_kernel<T, false, true>), dim3(rows), dim3(1024), 0, s, p);         \
     } while (0)
     switch (dtype) {
@@ -1567,6 +1639,21 @@ extern "C" int chipmunk_topk_delta_indices_p(const void *activation, void *cache
     CM_CHECK(cache != nullptr, "topk_delta_indices_p: cache missing");
     return launch_topk_p("topk_delta_indices_p", activation, cache, dtype, indices, counts, rows, cols, sparsity_amount, top_p,
                          min_keys, multiple_of, random_amount, stream);
+}
+
+extern "C" int chipmunk_topk_group_delta_indices(const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts, int B,
+                                                 int rows, int R, int cols, double sparsity_amount, int multiple_of,
+                                                 double random_amount, void *stream) {
+    const TopkGroups gs = {B, rows, R};
+    return launch_topk(activation, cache, dtype, indices, counts, 0, cols, sparsity_amount, multiple_of, random_amount, stream, &gs);
+}
+
+extern "C" int chipmunk_topk_group_delta_indices_p(const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts,
+                                                   int B, int rows, int R, int cols, double sparsity_amount, double top_p,
+                                                   double min_keys, int multiple_of, double random_amount, void *stream) {
+    const TopkGroups gs = {B, rows, R};
+    return launch_topk_p("topk_group_delta_indices_p", activation, cache, dtype, indices, counts, 0, cols, sparsity_amount, top_p, min_keys,
+                         multiple_of, random_amount, stream, &gs);
 }
 
 extern "C" int chipmunk_copy_indices(const void *src, void *dst, const int32_t *inds, const int32_t *counts, int B,

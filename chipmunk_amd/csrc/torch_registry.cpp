@@ -913,6 +913,54 @@ void topk_delta_indices_p(at::Tensor activation, at::Tensor cache, at::Tensor in
     topk_p_common("topk_delta_indices_p", activation, &cache, indices, counts, sparsity_amount, top_p, min_keys, multiple_of, random_amount);
 }
 
+// topk_delta_indices over rows_per_group block-mean rows per 128-row group (mlp.fused_group_topk_delta; not in the reference): the score of
+// a column is the fp32 sum of the rows' |delta|, rounded once; `top_p` null: the top-k selection, otherwise the _p one
+static void topk_group_common(const char *who, const at::Tensor &activation, const at::Tensor &cache, const at::Tensor &indices,
+                              const at::Tensor &counts, int64_t rows_per_group, double sparsity_amount, const double *top_p, double min_keys,
+                              int64_t multiple_of, double random_amount) {
+    CHECK_DEV(activation); CHECK_DEV(cache); CHECK_DEV(indices); CHECK_DEV(counts);
+    CHECK_CONTIG(activation); CHECK_CONTIG(cache); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
+    TORCH_CHECK(activation.dim() == 3 && cache.sizes() == activation.sizes(), who, ": activation and cache must be [batch, rows, cols]");
+    TORCH_CHECK(cache.scalar_type() == activation.scalar_type(), who, ": activation and cache must have the same dtype");
+    CHECK_I32(indices); CHECK_I32(counts);
+    TORCH_CHECK(rows_per_group >= 1 && rows_per_group <= 64, who, ": rows_per_group must be in [1, 64] (got ", rows_per_group, ")");
+    const int64_t B = activation.size(0), rows = activation.size(1), F = activation.size(2);
+    TORCH_CHECK(rows >= 1 && rows < (1ll << 31) && F < (1ll << 31), who, ": activation must have 1 .. 2^31 - 1 rows and columns");
+    const int64_t G = (rows + rows_per_group - 1) / rows_per_group;
+    TORCH_CHECK(indices.dim() == 3 && indices.size(0) == B && indices.size(1) == G && indices.size(2) == F, who,
+                ": indices must be [batch, ceil(rows / rows_per_group), cols] = [", B, ", ", G, ", ", F, "]");
+    TORCH_CHECK(counts.dim() == 2 && counts.size(0) == B && counts.size(1) == G, who, ": counts must be [batch, ceil(rows / rows_per_group)]");
+    TORCH_CHECK(B * G < (1ll << 31), who, ": too many groups");
+    int dtype;
+    switch (activation.scalar_type()) {
+        case at::kBFloat16: dtype = CHIPMUNK_DTYPE_BF16; break;
+        case at::kHalf: dtype = CHIPMUNK_DTYPE_FP16; break;
+        case at::kFloat: dtype = CHIPMUNK_DTYPE_FP32; break;
+        default: TORCH_CHECK(false, "Unsupported dtype for ", who);
+    }
+    c10::DeviceGuard guard(activation.device());
+    if (top_p)
+        check(chipmunk_topk_group_delta_indices_p(activation.data_ptr(), cache.data_ptr(), dtype, indices.data_ptr<int>(), counts.data_ptr<int>(),
+                                                  (int)B, (int)rows, (int)rows_per_group, (int)F, sparsity_amount, *top_p, min_keys,
+                                                  (int)multiple_of, random_amount, cur_stream(activation)), who);
+    else
+        check(chipmunk_topk_group_delta_indices(activation.data_ptr(), cache.data_ptr(), dtype, indices.data_ptr<int>(), counts.data_ptr<int>(),
+                                                (int)B, (int)rows, (int)rows_per_group, (int)F, sparsity_amount, (int)multiple_of,
+                                                random_amount, cur_stream(activation)), who);
+}
+
+void topk_group_delta_indices(at::Tensor activation, at::Tensor cache, at::Tensor indices, at::Tensor counts, int64_t rows_per_group,
+                              double sparsity_amount, int64_t multiple_of, double random_amount) {
+    topk_group_common("topk_group_delta_indices", activation, cache, indices, counts, rows_per_group, sparsity_amount, nullptr, 0.0,
+                      multiple_of, random_amount);
+}
+
+void topk_group_delta_indices_p(at::Tensor activation, at::Tensor cache, at::Tensor indices, at::Tensor counts, int64_t rows_per_group,
+                                double sparsity_amount, double top_p, double min_keys, int64_t multiple_of, double random_amount) {
+    topk_group_common("topk_group_delta_indices_p", activation, cache, indices, counts, rows_per_group, sparsity_amount, &top_p, min_keys,
+                      multiple_of, random_amount);
+}
+
 // reference csrc/indexed_io/mask_to_indices.cu:92-143
 std::vector<at::Tensor> mask_to_indices(at::Tensor mask, int64_t multiple_of, int64_t pad_to_multiple_of) {
     TORCH_CHECK(mask.dim() == 4, "mask must be 4-dimensional [b, h, m, n]");
@@ -1409,6 +1457,8 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
     m.def("topk_indices_p(Tensor activation, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
     m.def("topk_delta_indices_p(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
+    m.def("topk_group_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, int rows_per_group, float sparsity_amount, int multiple_of, float random_amount) -> ()");
+    m.def("topk_group_delta_indices_p(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, int rows_per_group, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
     m.def("packed_mask_to_indices(Tensor packed, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
     m.def("mask_to_sorted_indices(Tensor mask, int[] shape, int multiple_of, int pad_to_multiple_of) -> Tensor[]");
     m.def("topk_mask(Tensor cs, int k, float random_amount, Tensor? groups, Tensor? static_mask) -> Tensor");
@@ -1483,6 +1533,8 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("topk_delta_indices", &topk_delta_indices);
     m.impl("topk_indices_p", &topk_indices_p);
     m.impl("topk_delta_indices_p", &topk_delta_indices_p);
+    m.impl("topk_group_delta_indices", &topk_group_delta_indices);
+    m.impl("topk_group_delta_indices_p", &topk_group_delta_indices_p);
     m.impl("packed_mask_to_indices", &packed_mask_to_indices);
     m.impl("mask_to_sorted_indices", &mask_to_sorted_indices);
     m.impl("mask_to_ragged_indices", &mask_to_ragged_indices);

@@ -227,6 +227,17 @@ class SparseDiffMlp:
                 else:
                     torch.ops.chipmunk.topk_delta_indices(bmfc1, cache, inds, counts, 1 - cfg["top_keys"],
                                                           cfg["counts_multiple_of"], cfg["random_keys"])
+            elif r > 1 and bmfc1.is_cuda and amd_key("mlp", "fused_group_topk_delta") and bmfc1.is_contiguous():
+                # the same over the r block-mean rows of a group (a ragged last group sums and refreshes the rows it has)
+                b, rows, f = bmfc1.shape
+                inds = torch.empty((b, (rows + r - 1) // r, f), dtype=torch.int32, device=x.device)
+                counts = torch.empty((b, (rows + r - 1) // r), dtype=torch.int32, device=x.device)
+                if top_p > 0.0:
+                    ops.topk_group_delta_indices_p(bmfc1, cache, inds, counts, r, 1 - cfg["top_keys"], top_p, min_keys,
+                                                   cfg["counts_multiple_of"], cfg["random_keys"])
+                else:
+                    ops.topk_group_delta_indices(bmfc1, cache, inds, counts, r, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
+                                                 cfg["random_keys"])
             else:
                 mdiff = (bmfc1 - cache).abs()
                 b, rows, f = mdiff.shape

@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import ops
-from ..util.config import GLOBAL_CONFIG
+from ..util.config import GLOBAL_CONFIG, amd_key
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
 from .mlp import activation_cache_of, activation_cache_view, activation_code, block_mean, check_fc2, fc2_scale_of, top_p_of
@@ -179,16 +179,29 @@ class SparseDiffGatedMlp:
             bmpre = self._paired_block_means(*self._pre(bmx), bm_rows)
             cache = self.storage.get_blockmean_mid_cache()
             # a column's movement is the movement of its two inputs: |delta| summed over the group's 2 r rows (gate and up means)
-            mdiff = (bmpre - cache).abs()
-            b, _rows, f = mdiff.shape
-            mdiff = mdiff.reshape(b, -1, 2 * r, f).sum(dim=2)
-            inds = torch.empty_like(mdiff, dtype=torch.int32, device=x.device)
-            counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=x.device)
-            if top_p > 0.0:
-                ops.topk_indices_p(mdiff, inds, counts, 1 - cfg["top_keys"], top_p, min_keys, cfg["counts_multiple_of"], cfg["random_keys"])
+            if bmpre.is_cuda and amd_key("mlp", "fused_group_topk_delta"):
+                # one kernel for that sum -> top-k indices -> copy of the listed columns into the group's 2 r rows of the cache
+                b, rows, f = bmpre.shape
+                inds = torch.empty((b, rows // (2 * r), f), dtype=torch.int32, device=x.device)
+                counts = torch.empty((b, rows // (2 * r)), dtype=torch.int32, device=x.device)
+                if top_p > 0.0:
+                    ops.topk_group_delta_indices_p(bmpre, cache, inds, counts, 2 * r, 1 - cfg["top_keys"], top_p, min_keys,
+                                                   cfg["counts_multiple_of"], cfg["random_keys"])
+                else:
+                    ops.topk_group_delta_indices(bmpre, cache, inds, counts, 2 * r, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
+                                                 cfg["random_keys"])
             else:
-                ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"], cfg["random_keys"])
-            ops.copy_indices(bmpre, cache, inds, counts)     # rows [2 r g, 2 r (g + 1)) take group g's list
+                mdiff = (bmpre - cache).abs()
+                b, _rows, f = mdiff.shape
+                mdiff = mdiff.reshape(b, -1, 2 * r, f).sum(dim=2)
+                inds = torch.empty_like(mdiff, dtype=torch.int32, device=x.device)
+                counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=x.device)
+                if top_p > 0.0:
+                    ops.topk_indices_p(mdiff, inds, counts, 1 - cfg["top_keys"], top_p, min_keys, cfg["counts_multiple_of"],
+                                       cfg["random_keys"])
+                else:
+                    ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"], cfg["random_keys"])
+                ops.copy_indices(bmpre, cache, inds, counts)     # rows [2 r g, 2 r (g + 1)) take group g's list
             # the selected columns of the block means were refreshed in the LOADED tensor; a host copy has to follow
             holder = self.storage.blockmean_mid_cache
             if holder is not None and not holder.is_resident():

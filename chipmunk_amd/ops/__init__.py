@@ -4,7 +4,7 @@ from .mlp import run_e2e_glu as mlp_glu, run_e2e_glu, mm1_glu
 from .mlp import run_e2e_glu_fp8 as mlp_glu_fp8, run_e2e_glu_fp8, mm1_glu_fp8
 from .indexed_io import (copy_indices, topk_indices, mask_to_indices, scatter_add, packed_mask_to_indices,
                          mask_to_sorted_indices, mask_to_ragged_indices, topk_mask, topk_mask_p, topk_indices_p, topk_delta_indices_p, manual_seed,
-                         TOPK_MASK_MAX_N)
+                         topk_group_delta_indices, topk_group_delta_indices_p, TOPK_MASK_MAX_N)
 from .attn import compact_indices, csp_attn, csp_attn_inplace, csp_attn_out, csp_attn_out_ragged, dense_attn, dense_colsum_attn, dense_colsum_topk_mask, dense_colsum_topk_mask_p
 from .patch import patchify, unpatchify, patchify_rope
 from .bitpack import bitpack, bitunpack
@@ -16,6 +16,6 @@ __all__ = ["mlp", "copy_indices", "topk_indices", "mask_to_indices", "scatter_ad
            "packed_mask_to_indices", "mask_to_sorted_indices", "csp_attn_inplace", "csp_attn_out", "topk_mask", "TOPK_MASK_MAX_N", "voxel", "manual_seed", "qkv_split_norm", "dense_colsum_topk_mask", "compact_indices", "csp_attn_out_ragged", "residual_ln_modulate",
            "split_heads_rownorm", "wan_rope_table", "mask_to_ragged_indices", "mlp_glu", "run_e2e_glu", "mm1_glu",
            "mlp_glu_fp8", "run_e2e_glu_fp8", "mm1_glu_fp8", "topk_mask_p", "dense_colsum_topk_mask_p",
-           "topk_indices_p", "topk_delta_indices_p"]
+           "topk_indices_p", "topk_delta_indices_p", "topk_group_delta_indices", "topk_group_delta_indices_p"]
 
 from . import _fake  # noqa: E402,F401  shape-only ("fake") kernels so torch.compile can trace through the ops

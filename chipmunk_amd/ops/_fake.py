@@ -178,6 +178,25 @@ def _register():
                      lambda: "indices must have the shape of activation, counts must be [batch, rows]")
         return None
 
+    def _check_group_delta(activation, cache, indices, counts, rows_per_group):
+        torch._check(activation.ndim == 3 and activation.shape[-1] >= 1024, lambda: "activation must be [batch, rows, cols] with cols >= 1024")
+        torch._check(cache.shape == activation.shape and cache.dtype == activation.dtype, lambda: "cache must have the shape and dtype of activation")
+        torch._check(1 <= rows_per_group <= 64, lambda: "rows_per_group must be in [1, 64]")
+        groups = (activation.shape[1] + rows_per_group - 1) // rows_per_group
+        torch._check(tuple(indices.shape) == (activation.shape[0], groups, activation.shape[2]) and tuple(counts.shape) == (activation.shape[0], groups),
+                     lambda: "indices must be [batch, ceil(rows / rows_per_group), cols], counts [batch, ceil(rows / rows_per_group)]")
+
+    @lib.register_fake("chipmunk::topk_group_delta_indices")
+    def _(activation, cache, indices, counts, rows_per_group, sparsity_amount, multiple_of, random_amount):
+        # writes indices, counts and the listed columns of cache in place and returns nothing
+        _check_group_delta(activation, cache, indices, counts, rows_per_group)
+        return None
+
+    @lib.register_fake("chipmunk::topk_group_delta_indices_p")
+    def _(activation, cache, indices, counts, rows_per_group, sparsity_amount, top_p, min_keys, multiple_of, random_amount):
+        _check_group_delta(activation, cache, indices, counts, rows_per_group)
+        return None
+
     @lib.register_fake("chipmunk::qkv_split_norm")
     def _(qkv, q_weight, k_weight, heads, eps, freqs_cos=None, freqs_sin=None):
         out = qkv.new_empty((3, 1, heads, qkv.shape[0], 128))

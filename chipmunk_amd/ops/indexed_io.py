@@ -92,6 +92,26 @@ def topk_delta_indices_p(activations: torch.Tensor, cache: torch.Tensor, indices
     torch.ops.chipmunk.topk_delta_indices_p(activations, cache, indices_out, counts_out, sparsity_amount, top_p, min_keys, multiple_of, rk)
 
 
+def topk_group_delta_indices(activations: torch.Tensor, cache: torch.Tensor, indices_out: torch.Tensor, counts_out: torch.Tensor,
+                             rows_per_group: int, sparsity_amount: float, multiple_of: int, rk: float) -> None:
+    """``topk_delta_indices`` over ``R = rows_per_group`` block-mean rows per 128-row group (not in the reference; ``bm > mbm`` and the
+    gate / up pairs of the gated MLP), as one kernel.  ``activations`` and ``cache`` are ``[B, rows, F]``; group ``g`` of
+    ``G = ceil(rows / R)`` owns rows ``[g R, min((g + 1) R, rows))``; ``indices_out [B, G, F]``, ``counts_out [B, G]``.  The score of a
+    column is ``T(sum_i float(T(|a_i - cache_i|)))``: rows ascending, summed in fp32, rounded to the element type once -- for ``R == 2``
+    the bits of ``(a - cache).abs().reshape(B, G, 2, F).sum(2)``.  ``topk_indices`` on the scores; every listed column is copied from
+    ``activations`` into ``cache`` in every row of the group, as ``copy_indices`` does.  GPU tensors only."""
+    torch.ops.chipmunk.topk_group_delta_indices(activations, cache, indices_out, counts_out, rows_per_group, sparsity_amount, multiple_of, rk)
+
+
+def topk_group_delta_indices_p(activations: torch.Tensor, cache: torch.Tensor, indices_out: torch.Tensor, counts_out: torch.Tensor,
+                               rows_per_group: int, sparsity_amount: float, top_p: float, min_keys: float, multiple_of: int,
+                               rk: float) -> None:
+    """``topk_group_delta_indices`` with the selection of ``topk_indices_p`` on the scores.  GPU tensors only."""
+    _check_top_p("topk_group_delta_indices_p", sparsity_amount, top_p, min_keys)
+    torch.ops.chipmunk.topk_group_delta_indices_p(activations, cache, indices_out, counts_out, rows_per_group, sparsity_amount, top_p,
+                                                  min_keys, multiple_of, rk)
+
+
 def scatter_add(packed: torch.Tensor, unpacked: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
                 num_sms: int) -> None:
     if packed.ndim == 3:   # a batch [B, M, F] with unpacked [B, F, M], indices [B, G, F], counts [B, G]: one launch

@@ -144,6 +144,10 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # for a 128-row group then lie on a 256-byte grid inside one F * 256-byte window instead of 2 * N bytes apart over the whole tensor, and
     # a token count that is no multiple of 8 needs no pitched columns (the last group is short).  Same bits; any other string raises.
     "mlp.cache_layout": "column",
+    # selection of a sparse MLP step whose 128-row groups own more than one block-mean row (mlp.bm > mlp.mbm; SparseDiffGatedMlp always: gate
+    # and up means) as ONE kernel, topk_group_delta_indices[_p], instead of sub / abs / sum / topk_indices / copy_indices: same indices,
+    # counts and cache bits for two rows per group, and a ragged last group works on the bm > mbm route.  Off: that chain.
+    "mlp.fused_group_topk_delta": False,
 }
 BASE_CONFIG["offloading"]["keep_resident_if_fits"] = AMD_EXTRA_KEYS["offloading.keep_resident_if_fits"]
 BASE_CONFIG["offloading"]["hbm_budget_gb"] = AMD_EXTRA_KEYS["offloading.hbm_budget_gb"]
@@ -167,6 +171,7 @@ BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]
 BASE_CONFIG["mlp"]["top_p_min_keys"] = AMD_EXTRA_KEYS["mlp.top_p_min_keys"]
 BASE_CONFIG["mlp"]["fp8_scaling"] = AMD_EXTRA_KEYS["mlp.fp8_scaling"]
 BASE_CONFIG["mlp"]["cache_layout"] = AMD_EXTRA_KEYS["mlp.cache_layout"]
+BASE_CONFIG["mlp"]["fused_group_topk_delta"] = AMD_EXTRA_KEYS["mlp.fused_group_topk_delta"]
 
 GLOBAL_CONFIG: Dict[str, Any] = copy.deepcopy(BASE_CONFIG)
 

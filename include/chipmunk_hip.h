@@ -398,6 +398,24 @@ int chipmunk_topk_delta_indices_p(const void *activation, void *cache, int dtype
                                   int cols, double sparsity_amount, double top_p, double min_keys, int multiple_of,
                                   double random_amount, void *stream);
 
+/* chipmunk_topk_delta_indices over several block-mean rows per 128-row group (not in the reference's kernels; its modules/mlp.py:70-85
+ * with bm > mbm does this in torch, and the gated MLP pairs gate and up means; config mlp.fused_group_topk_delta).
+ * activation, cache [B, rows, cols] of `dtype`; G = ceil(rows / R) groups per sequence, group g owns rows [g*R, min((g+1)*R, rows));
+ * indices [B, G, cols] int32; counts [B, G] int32.  The ranked value of column c in a group is
+ *   s_c = T( sum_i float( T(|activation_i[c] - cache_i[c]|) ) ),  i ascending over the group's rows, summed in fp32, rounded to T once
+ * -- for R == 2 bit for bit what (activation - cache).abs().reshape(B, G, 2, cols).sum(2) gives, for R == 1 chipmunk_topk_delta_indices'
+ * value.  Threshold, random keys (hashed on row b*G + g), order, padding and counts are chipmunk_topk_indices' on the row of scores;
+ * every listed column (padding included) of `activation` is copied into `cache` in every row the group owns.  sparsity_amount == 0
+ * lists and copies everything, == 1 nothing.  cols >= 1024, 1 <= R <= 64, rows >= 1, B*G < 2^31. */
+int chipmunk_topk_group_delta_indices(const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts, int B,
+                                      int rows, int R, int cols, double sparsity_amount, int multiple_of, double random_amount,
+                                      void *stream);
+
+/* ... with the selection of chipmunk_topk_indices_p on the row of scores (the masses are the scores). */
+int chipmunk_topk_group_delta_indices_p(const void *activation, void *cache, int dtype, int32_t *indices, int32_t *counts, int B,
+                                        int rows, int R, int cols, double sparsity_amount, double top_p, double min_keys,
+                                        int multiple_of, double random_amount, void *stream);
+
 /* chipmunk_dense_colsum_attn + chipmunk_topk_mask without the cs tensor between them (reference modules/attn.py:131-141 calls
  * dense_colsum_attn, then random_and_topk on its 3.55 GB result at HunyuanVideo size): o, l as chipmunk_dense_colsum_attn,
  * mask [B*H*ceil(Nq/192), Nk] bool bytes as chipmunk_topk_mask would produce from that call's cs -- bit for bit.

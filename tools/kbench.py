@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -535,6 +535,83 @@ def bench_io(which):
         print(f"copy_indices [1,34,12288] keep 4096: {ms*1e3:8.1f} us")
 
 
+def bench_group_delta():
+    """The selection of a sparse MLP step whose groups own R block-mean rows: the modules' torch chain (sub, abs, reshape + sum, two
+    empties, topk_indices, copy_indices -- temporaries included) against topk_group_delta_indices, same box, both orders.
+    Cold rows: every launch of a bracket takes another (activation, cache) set, enough sets for ~1 GB in all (the LLC holds 256 MB), and
+    the caches are put back before every bracket, outside it, in the order the bracket visits them -- the copy makes the listed columns
+    of the cache equal the activations, so a second launch on the same set would rank another row of scores.
+    KB_ROUNDS brackets per side and order (default 5); the figure is the median, with the range."""
+    ops = chipmunk_amd.ops
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    g = torch.Generator(device=dev).manual_seed(0)
+    #        name                                rows      F      R
+    shapes = [("Wan-sized gated", 2 * 256, 8960, 2), ("FLUX-sized gated", 2 * 36, 12288, 2), ("HunyuanVideo-sized gated", 2 * 930, 13824, 2),
+              ("Wan-sized ungated, bm = 4 mbm", 2 * 256, 8960, 4)]
+    for name, rows, F, R in shapes:
+        G = rows // R
+        set_bytes = 2 * rows * F * 2 + G * F * 4
+        L = min(256, max(16, -(-(1 << 30) // set_bytes)))
+        sets = []
+        for _ in range(L):
+            b = torch.randn(1, rows, F, device=dev, generator=g).to(torch.bfloat16)
+            c0 = (b.float() + 0.3 * torch.randn(1, rows, F, device=dev, generator=g)).to(torch.bfloat16)
+            sets.append((b, c0, c0.clone()))
+        inds_f = [torch.empty(1, G, F, dtype=torch.int32, device=dev) for _ in range(L)]
+        counts_f = torch.empty(1, G, dtype=torch.int32, device=dev)
+
+        def unfused(b, cache):
+            mdiff = (b - cache).abs()
+            bsz, _rows, f = mdiff.shape
+            mdiff = mdiff.reshape(bsz, -1, R, f).sum(dim=2)
+            inds = torch.empty_like(mdiff, dtype=torch.int32, device=dev)
+            counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=dev)
+            ops.topk_indices(mdiff, inds, counts, 0.7, 256, 0.0)
+            ops.copy_indices(b, cache, inds, counts)
+            return inds, counts
+
+        def fused(b, cache, i):
+            ops.topk_group_delta_indices(b, cache, inds_f[i], counts_f, R, 0.7, 256, 0.0)
+
+        def bracket(side):
+            for b, c0, c in sets:
+                c.copy_(c0)
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for i, (b, _c0, c) in enumerate(sets):
+                unfused(b, c) if side == "unfused" else fused(b, c, i)
+            e.record()
+            e.synchronize()
+            return s.elapsed_time(e) / L * 1e3      # us per selection
+
+        warm_gpu()
+        # same results at the timed size (R == 2: bit for bit; R > 2: torch's reduction order is not the contract -- reported, not asserted)
+        b, c0, c = sets[0]
+        ui, uc = unfused(b, c)
+        ucache = c.clone()
+        c.copy_(c0)
+        fused(b, c, 0)
+        torch.cuda.synchronize()
+        listed = torch.arange(F, device=dev) < uc[..., None]
+        same = (torch.equal(uc, counts_f) and torch.equal(torch.where(listed, ui, -1), torch.where(listed, inds_f[0], -1))
+                and torch.equal(ucache.view(torch.int16), c.view(torch.int16)))
+        for side in ("unfused", "fused"):      # every shape once before anything is timed
+            bracket(side)
+        res = {"unfused first": {"unfused": [], "fused": []}, "fused first": {"unfused": [], "fused": []}}
+        for _ in range(rounds):
+            for order in ("unfused first", "fused first"):
+                for side in (("unfused", "fused") if order == "unfused first" else ("fused", "unfused")):
+                    res[order][side].append(bracket(side))
+        print(f"group_delta {name} [1,{rows},{F}] R={R} G={G} sets={L} rounds={rounds} same_result={same}")
+        for order, sides in res.items():
+            for side, v in sides.items():
+                v = sorted(v)
+                print(f"  {order:13s} {side:8s} median {v[len(v) // 2]:8.1f} us  range {v[0]:8.1f} .. {v[-1]:8.1f}")
+        del sets, inds_f
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["mm1", "mm2", "scatter", "csp_flux", "dense_flux", "sdpa_flux", "topk"])
@@ -581,6 +658,8 @@ def main():
             bench_mlp(w.split("_")[0], variants, M=119056, K=3072, F=12288, keep=3840)
         elif w in ("topk", "topkd", "m2i", "copy"):
             bench_io(w)
+        elif w == "group_delta":      # selection over R block-mean rows per group: the modules' torch chain against the fused operator
+            bench_group_delta()
         else:
             bench_attn(w, variants)
 
