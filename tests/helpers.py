@@ -424,6 +424,49 @@ def assert_segs_close(got, exact, bound, what, extra=None, width=MLP_SEG_W1, col
     return worst
 
 
+def assert_rowwise_close(got, exact, bound, what, width=None, copy_of=None):
+    """The four assertions of every row-wise norm case (docs/TEST_SENSITIVITY.md, "Row-wise norm kernels"; tests/rowwise_model.py has the
+    bounds): ``got`` is finite; where ``copy_of`` is given it is that tensor bit for bit; every segment whose exact value is all zero
+    (an all-zero input row of an RMSNorm part) is exactly zero; every segment is within `bound` -- a number, or a tensor of the
+    error's shape: the class of each segment -- of ``exact``.  A segment is a row of the last dimension (``[B, H, n, 128]``:
+    `row_rel_err`) or, with `width`, that many consecutive columns of it (``xm [rows, C]``: `seg_rel_err`, the last segment short).  No
+    segment is left out.  Appends ``rowwise <what> <tab> worst <tab> its bound <tab> worst error / bound`` to CHIPMUNK_ROW_ERR_LOG.
+    Returns the worst error."""
+    assert got.shape == exact.shape, (got.shape, exact.shape)
+    g = got.to(exact.device)
+    nonfinite = int((~torch.isfinite(g.float())).sum())
+    assert nonfinite == 0, f"{what}: {nonfinite} non-finite elements of {g.numel()}"
+    if copy_of is not None:
+        c = copy_of.to(exact.device)
+        assert g.dtype == c.dtype and torch.equal(g.view(torch.int16), c.view(torch.int16)), f"{what}: a copied part must be a bit copy"
+    w = exact.shape[-1] if width is None else width
+    zero = _segments(exact.double(), w).abs().amax(-1) == 0
+    dirty = (_segments(g.double(), w) != 0).any(-1) & zero
+    assert not dirty.any(), f"{what}: {int(dirty.sum())} of {int(zero.sum())} segments whose exact value is 0 are not exactly zero"
+    err = seg_rel_err(g, exact, w)
+    if width is None:
+        err = err[..., 0]
+    b = torch.as_tensor(bound, dtype=torch.float64, device=err.device).expand_as(err)
+    ratio = torch.where(b > 0, err / b, torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
+    flat = int(torch.nan_to_num(ratio, nan=float("inf")).argmax()) if err.numel() else 0
+    worst, at, share = (float(err.max()), float(b.flatten()[flat]), float(ratio.flatten()[flat])) if err.numel() else (0.0, 0.0, 0.0)
+    import os
+    path = os.environ.get("CHIPMUNK_ROW_ERR_LOG")
+    print(f"rowwise {what}: worst segment {worst:.5f}, {share:.2f} of its bound")
+    if path:
+        with open(path, "a") as f:
+            f.write(f"rowwise {what}\t{worst:.6f}\t{at:.6f}\t{share:.4f}\n")
+    bad = ~(ratio <= 1.0)
+    if bad.any():
+        idx = []
+        for s in reversed(err.shape):
+            idx.append(flat % s)
+            flat //= s
+        raise AssertionError(f"{what}: segment error {float(err[tuple(reversed(idx))]):.4g} > {at:.4g} at index {tuple(reversed(idx))} of {tuple(err.shape)} "
+                             f"(segments of {w} columns); {int(bad.sum())} / {bad.numel()} segments over the bound")
+    return worst
+
+
 def mlp_act64(act, x):
     """the activations of DESIGN "Gated MLPs" in the precision of ``x``"""
     if act == "gelu_tanh":
