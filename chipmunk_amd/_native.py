@@ -26,7 +26,7 @@ SYMBOLS = [
     "chipmunk_csp_mlp_mm1_act_gm", "chipmunk_csp_mlp_mm1_fp8_act_gm", "chipmunk_csp_mlp_mm1_fp8_act_rs_gm", "chipmunk_csp_mlp_mm1_glu_gm",
     "chipmunk_csp_mlp_mm1_glu_fp8_gm", "chipmunk_csp_scatter_add_gm", "chipmunk_transpose16_groups",
     "chipmunk_topk_indices", "chipmunk_topk_delta_indices", "chipmunk_topk_indices_p", "chipmunk_topk_delta_indices_p", "chipmunk_topk_group_delta_indices", "chipmunk_topk_group_delta_indices_p", "chipmunk_topk_mask", "chipmunk_topk_mask_p", "chipmunk_dense_colsum_topk_mask_p_strided", "chipmunk_mask_to_indices", "chipmunk_mask_to_sorted_indices", "chipmunk_packed_mask_to_indices", "chipmunk_mask_row_counts", "chipmunk_mask_to_ragged_indices", "chipmunk_copy_indices",
-    "chipmunk_bitpack", "chipmunk_bitunpack", "chipmunk_transpose16", "chipmunk_block_mean", "chipmunk_quantize_fp8", "chipmunk_gather_rows", "chipmunk_qkv_split_norm", "chipmunk_split_heads_rownorm", "chipmunk_dense_colsum_topk_mask", "chipmunk_dense_attn_strided", "chipmunk_csp_attn_out_ragged", "chipmunk_compact_indices", "chipmunk_residual_ln_modulate", "chipmunk_dense_colsum_attn_strided", "chipmunk_dense_colsum_topk_mask_strided", "chipmunk_release_scratch", "chipmunk_big_scratch_fallbacks",
+    "chipmunk_bitpack", "chipmunk_bitunpack", "chipmunk_transpose16", "chipmunk_block_mean", "chipmunk_quantize_fp8", "chipmunk_gather_rows", "chipmunk_qkv_split_norm", "chipmunk_split_heads_rownorm", "chipmunk_dense_colsum_topk_mask", "chipmunk_dense_attn_strided", "chipmunk_csp_attn_out_ragged", "chipmunk_compact_indices", "chipmunk_residual_ln_modulate", "chipmunk_residual_ln_modulate_f32", "chipmunk_dense_colsum_attn_strided", "chipmunk_dense_colsum_topk_mask_strided", "chipmunk_release_scratch", "chipmunk_big_scratch_fallbacks",
     "chipmunk_dense_attn_varlen", "chipmunk_dense_colsum_attn_varlen", "chipmunk_dense_colsum_topk_mask_varlen",
     "chipmunk_dense_colsum_topk_mask_p_varlen", "chipmunk_topk_mask_varlen", "chipmunk_topk_mask_p_varlen",
     "chipmunk_host_alloc", "chipmunk_host_free", "chipmunk_copy_d2h_async", "chipmunk_copy_h2d_async", "chipmunk_host_bytes",

@@ -566,3 +566,213 @@ extern "C" int chipmunk_split_heads_rownorm(const void *x, int64_t batch_stride,
     CM_LAUNCH_CHECK();
     return CHIPMUNK_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- Wan block glue
+// Wan's blocks (reference examples/wan/wan/modules/model.py:317-334) keep the residual stream in fp32 and take their six modulation
+// vectors as fp32 [B, 6, C], one set per SEQUENCE:
+//     x  = x + y * e[2]                                   fp32 (:326-327, :333-334; `x + cross_attn(..)` without a gate, :331)
+//     xm = norm(x).float() * (1 + e[1]) + e[0]            fp32, bf16 only at the next Linear (:324, :332)
+//     xm = norm3(x)                                       LayerNorm with affine weight and bias (:283-285, :331)
+// with WanLayerNorm = LayerNorm(x.float()).type_as(x) (:100-110) -- 3 - 5 torch kernels over an fp32 [B, L, C] stream per use.
+// Here one pass: read x (fp32, or the bf16 of block 0) and y (bf16), write x_out (fp32) and xm (bf16): 12 bytes per element, 6 without y.
+//
+// As residual_ln_modulate_kernel above: one wave per row, the row in registers as fp32 between the two reductions (mean, then the
+// centred sum of squares), row16_sum + sum_across_rows in a fixed order (a row's result does not depend on the wave that took it, nor on
+// the batch it came in), no LDS, a wave walks rows with the grid's stride and RowWalk gives the row's sequence.  Rounding points are
+// torch's: fp32(fp32(y) * gate), fp32(x + that) -- two operations, never a fused multiply-add --; for a bf16 x without y and with a
+// modulation bf16(xn) (.type_as); then xm = bf16(fma(xn, mult, add)), mult = fp32(1 + scale) or the affine weight: ONE rounding.
+//
+// Lane-to-column mapping: a lane owns the 8 columns (lane + 64 j) * 8 .. + 7 of vector j, as everywhere in this file.  The bf16
+// operands (y, xm, a bf16 x) are then one 16-byte access per lane and 1 KiB contiguous per wave instruction; an fp32 operand is the
+// lane's 32 contiguous bytes as two 16-byte accesses issued back to back: each instruction touches every 128-byte line of the wave's
+// 2 KiB span and takes half of it, the pair takes all of it, so every line is fetched from HBM once and wholly used while L1 serves
+// two requests per line -- 32 useful bytes per L1 clock and CU, three times what a CU's share of HBM delivers.  The alternative (lane l
+// reads fp32 columns 4 l .. 4 l + 3 of each 256-column half: 1 KiB contiguous per instruction) leaves a lane with two separate groups
+// of 4 columns: 8-byte bf16 accesses, or a lane-pair exchange of 4 registers per load and store.  Not taken: the fp32 stream is the
+// larger one but it is HBM, not L1, that bounds this kernel.
+//
+// The three fp32 vectors are 24 registers per row vector: HELD in registers where they fit beside the row (NV <= 6, C <= 3072: Wan
+// 1.3B's 1536), re-read per row from L2 otherwise (C = 5120: 60 KB for the three, resident), the trade rownorm_rows makes.  Held
+// vectors are re-read when the wave's row walk enters another sequence.
+namespace {
+struct GlueArgs {
+    const void *x;                       // [rows, C] fp32 or bf16
+    const uint16_t *y;                   // [rows, C] bf16 or nullptr
+    const float *gate, *mult, *add;      // gate: nullptr = 1; mult: scale (modulation) or weight (affine); add: shift or bias
+    float *x_out;                        // [rows, C] fp32 (with y)
+    uint16_t *xm;                        // [rows, C] bf16
+    int64_t rows, L, gate_bs, mod_bs;    // L rows per sequence; batch strides of the vectors in elements (0: one vector for all)
+    int C, affine, round_xn;
+    float eps;
+};
+
+// the launcher's row-length classes: a row of class NV has more than 512 * glue_sure(NV) columns, so its first glue_sure(NV) vectors lie
+// wholly inside the row and need no bounds test
+constexpr int glue_sure(int nv) { return nv == 3 ? 2 : nv == 6 ? 3 : nv == 10 ? 6 : nv == 16 ? 10 : 0; }
+
+template <int NV, bool XBF, bool RES>   // NV 16-byte bf16 vectors per lane: 512 * glue_sure(NV) < C <= 512 * NV
+__global__ __launch_bounds__(256) void residual_ln_modulate_f32_kernel(const GlueArgs a) {
+    const int lane = threadIdx.x & 63, C = a.C;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    const float inv_c = 1.0f / (float)C;
+    const bool affine = a.affine != 0, round_xn = a.round_xn != 0;
+    constexpr bool HELD = NV <= 6;
+    constexpr int NH = HELD ? NV : 1, SURE = glue_sure(NV);
+    f32x4 g[RES ? NH : 1][2], mu[NH][2], ad[NH][2];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f}, ones = {1.f, 1.f, 1.f, 1.f};
+    // one vector j of the sequence's gate / multiplier / addend; columns past the row count as gate 1, multiplier 0, addend 0
+    auto load_gate = [&](int64_t b, int j, f32x4 (&o)[2]) {
+        const int c = (lane + 64 * j) * 8;
+        o[0] = o[1] = ones;
+        if (a.gate && (j < SURE || c < C)) {
+            const float *p = a.gate + b * a.gate_bs + c;
+            o[0] = *(const f32x4 *)p, o[1] = *(const f32x4 *)(p + 4);
+        }
+    };
+    auto load_mod = [&](int64_t b, int j, f32x4 (&m)[2], f32x4 (&s)[2]) {
+        const int c = (lane + 64 * j) * 8;
+        m[0] = m[1] = s[0] = s[1] = zero;
+        if (j < SURE || c < C) {
+            const float *pm = a.mult + b * a.mod_bs + c, *ps = a.add + b * a.mod_bs + c;
+            m[0] = *(const f32x4 *)pm, m[1] = *(const f32x4 *)(pm + 4), s[0] = *(const f32x4 *)ps, s[1] = *(const f32x4 *)(ps + 4);
+            if (!affine) m[0] += 1.0f, m[1] += 1.0f;   // fp32(1 + scale), the tensor torch materialises
+        }
+    };
+    int64_t held_b = -1;
+    RowWalk w(wave, nwaves, a.L);
+    for (int64_t r = wave; r < a.rows; r += nwaves, w.next()) {
+        const int64_t b = w.b;
+        if (HELD && b != held_b) {   // (wave-uniform: at most once per sequence the wave's rows reach)
+            held_b = b;
+#pragma unroll
+            for (int j = 0; j < NH; ++j) {
+                if constexpr (RES) load_gate(b, j, g[j]);
+                load_mod(b, j, mu[j], ad[j]);
+            }
+        }
+        float f[NV][8];
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = (lane + 64 * j) * 8;
+            const bool in = j < SURE || c < C;
+            if constexpr (XBF) {
+                u32x4 xv = {0u, 0u, 0u, 0u};
+                if (in) xv = *(const u32x4 *)((const uint16_t *)a.x + r * C + c);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) f[j][2 * e] = __uint_as_float(xv[e] << 16), f[j][2 * e + 1] = __uint_as_float(xv[e] & 0xffff0000u);
+            } else {
+                f32x4 x0 = zero, x1 = zero;
+                if (in) x0 = *(const f32x4 *)((const float *)a.x + r * C + c), x1 = *(const f32x4 *)((const float *)a.x + r * C + c + 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) f[j][e] = x0[e], f[j][4 + e] = x1[e];
+            }
+            if constexpr (RES) {
+                u32x4 yv = {0u, 0u, 0u, 0u};
+                if (in) yv = *(const u32x4 *)(a.y + r * C + c);
+                f32x4 gj[2];
+                if constexpr (HELD) gj[0] = g[j][0], gj[1] = g[j][1];
+                else load_gate(b, j, gj);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+#pragma clang fp contract(off)
+                    const float yf = (e & 1) ? __uint_as_float(yv[e >> 1] & 0xffff0000u) : __uint_as_float(yv[e >> 1] << 16);
+                    const float p = yf * gj[e >> 2][e & 3];   // rounded to fp32 (gate 1: y itself), then the sum: torch's two kernels
+                    f[j][e] = f[j][e] + p;
+                }
+                if (in) {
+                    float *dst = a.x_out + r * C + c;
+                    *(f32x4 *)dst = (f32x4){f[j][0], f[j][1], f[j][2], f[j][3]};
+                    *(f32x4 *)(dst + 4) = (f32x4){f[j][4], f[j][5], f[j][6], f[j][7]};
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) sum += f[j][e] + f[j][e + 1];
+        }
+        const float mean = sum_across_rows(row16_sum(sum)) * inv_c;
+        float ss = 0.f;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const bool in = j < SURE || (lane + 64 * j) * 8 < C;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                f[j][e] -= mean;
+                ss = in ? __builtin_fmaf(f[j][e], f[j][e], ss) : ss;
+            }
+        }
+        const float var = sum_across_rows(row16_sum(ss)) * inv_c;
+        const float rstd = 1.0f / __builtin_sqrtf(var + a.eps);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = (lane + 64 * j) * 8;
+            f32x4 m[2], s[2];
+            if constexpr (HELD) m[0] = mu[j][0], m[1] = mu[j][1], s[0] = ad[j][0], s[1] = ad[j][1];
+            else load_mod(b, j, m, s);
+            u32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float p = f[j][2 * e] * rstd, q = f[j][2 * e + 1] * rstd;
+                if (round_xn) round_bf16_pair(p, q);   // .type_as(x) of a bf16 x
+                p = __builtin_fmaf(p, m[e >> 1][2 * (e & 1)], s[e >> 1][2 * (e & 1)]);
+                q = __builtin_fmaf(q, m[e >> 1][2 * (e & 1) + 1], s[e >> 1][2 * (e & 1) + 1]);
+                o[e] = pack_bf16x2(p, q);
+            }
+            if (j < SURE || c < C) *(u32x4 *)(a.xm + r * C + c) = o;
+        }
+    }
+}
+
+template <int NV>
+void launch_glue(const GlueArgs &a, bool xbf, hipStream_t s) {
+    // 4 rows per workgroup at a time; enough workgroups for 8 per CU, the rest of the rows by stride
+    const int64_t want = (a.rows + 3) / 4;
+    const dim3 grid((unsigned)(want < 256 * 8 ? want : 256 * 8)), block(256);
+    if (a.y) {
+        if (xbf) hipLaunchKernelGGL((residual_ln_modulate_f32_kernel<NV, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((residual_ln_modulate_f32_kernel<NV, false, true>), grid, block, 0, s, a);
+    } else {
+        if (xbf) hipLaunchKernelGGL((residual_ln_modulate_f32_kernel<NV, true, false>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((residual_ln_modulate_f32_kernel<NV, false, false>), grid, block, 0, s, a);
+    }
+}
+}  // namespace
+
+extern "C" int chipmunk_residual_ln_modulate_f32(const void *x, int x_dtype, const void *y, const float *gate, int64_t gate_batch_stride,
+                                                 const float *shift, const float *scale, int64_t mod_batch_stride, const float *weight,
+                                                 const float *bias, float *x_out, void *xm, int64_t B, int64_t L, int cols, double eps,
+                                                 void *stream) {
+    CM_CHECK(x && xm, "residual_ln_modulate_f32: null pointer");
+    CM_CHECK(x_dtype == 1 || x_dtype == 2, "residual_ln_modulate_f32: x dtype code must be 1 (bf16) or 2 (fp32) (got %d)", x_dtype);
+    CM_CHECK((y == nullptr) == (x_out == nullptr), "residual_ln_modulate_f32: y and x_out come together (both set: residual form; both null: LayerNorm only)");
+    CM_CHECK(y || !gate, "residual_ln_modulate_f32: a gate without y");
+    CM_CHECK(!(x_dtype == 1 && y && !gate), "residual_ln_modulate_f32: a bf16 x takes its residual with a gate (an ungated bf16 sum would stay bf16)");
+    CM_CHECK((shift == nullptr) == (scale == nullptr) && (weight == nullptr) == (bias == nullptr),
+             "residual_ln_modulate_f32: shift / scale come together, and so do weight / bias");
+    CM_CHECK((shift != nullptr) != (weight != nullptr), "residual_ln_modulate_f32: exactly one of modulation (shift, scale) and affine (weight, bias)");
+    CM_CHECK(cols > 0 && cols % 8 == 0 && cols <= 512 * 16, "residual_ln_modulate_f32: cols must be a multiple of 8, at most 8192 (got %d)", cols);
+    CM_CHECK(B >= 1 && B < (1 << 24) && L >= 0 && L < ((int64_t)1 << 31), "residual_ln_modulate_f32: B must be in 1 .. 2^24 - 1 and L in 0 .. 2^31 - 1 (got B=%lld L=%lld)",
+             (long long)B, (long long)L);
+    CM_CHECK((gate_batch_stride == 0 || (gate && gate_batch_stride >= cols && gate_batch_stride % 4 == 0)) &&
+                 (mod_batch_stride == 0 || (shift && mod_batch_stride >= cols && mod_batch_stride % 4 == 0)),
+             "residual_ln_modulate_f32: a batch stride is 0 (one vector for every sequence) or a multiple of 4 elements that covers cols; weight / bias have none");
+    CM_CHECK(((((uintptr_t)x | (uintptr_t)y | (uintptr_t)gate | (uintptr_t)shift | (uintptr_t)scale | (uintptr_t)weight | (uintptr_t)bias |
+                (uintptr_t)x_out | (uintptr_t)xm)) & 15) == 0, "residual_ln_modulate_f32: pointers must be 16-byte aligned");
+    if (L == 0) return CHIPMUNK_OK;
+    GlueArgs a;
+    a.x = x, a.y = (const uint16_t *)y, a.gate = gate;
+    a.mult = shift ? scale : weight, a.add = shift ? shift : bias;
+    a.x_out = x_out, a.xm = (uint16_t *)xm;
+    a.rows = B * L, a.L = L, a.gate_bs = gate_batch_stride, a.mod_bs = mod_batch_stride;
+    a.C = cols, a.affine = weight != nullptr, a.round_xn = x_dtype == 1 && !y && !weight;
+    a.eps = (float)eps;
+    hipStream_t s = (hipStream_t)stream;
+    const int nv = (cols + 511) / 512;
+    const bool xbf = x_dtype == 1;
+    if (nv <= 2) launch_glue<2>(a, xbf, s);   // (the classes of glue_sure)
+    else if (nv <= 3) launch_glue<3>(a, xbf, s);
+    else if (nv <= 6) launch_glue<6>(a, xbf, s);
+    else if (nv <= 10) launch_glue<10>(a, xbf, s);
+    else launch_glue<16>(a, xbf, s);
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}

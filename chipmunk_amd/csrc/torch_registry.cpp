@@ -181,6 +181,64 @@ std::vector<at::Tensor> residual_ln_modulate(at::Tensor x, const c10::optional<a
     return {xm};
 }
 
+// addition (Wan's block glue, model code in the reference: examples/wan/wan/modules/model.py:100-110, 317-334): fp32 residual stream,
+// fp32 vectors per sequence ([C], [B, C] or [B, 1, C]), modulation (shift, scale) or affine (weight, bias); returns {x_out fp32, xm bf16}
+// with y, {xm} without (the Python wrapper hands the caller's x back: an operator's outputs never alias its inputs)
+std::vector<at::Tensor> residual_ln_modulate_f32(at::Tensor x, const c10::optional<at::Tensor> &y, const c10::optional<at::Tensor> &gate,
+                                                 const c10::optional<at::Tensor> &shift, const c10::optional<at::Tensor> &scale,
+                                                 const c10::optional<at::Tensor> &weight, const c10::optional<at::Tensor> &bias, double eps) {
+    auto has = [](const c10::optional<at::Tensor> &t) { return t.has_value() && t->defined(); };
+    CHECK_DEV(x); CHECK_CONTIG(x);
+    TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, "x must be float32 or bfloat16");
+    TORCH_CHECK(x.dim() == 2 || x.dim() == 3, "x must be [B, L, C] or [L, C]");
+    const int64_t C = x.size(-1), L = x.size(-2), B = x.dim() == 3 ? x.size(0) : 1;
+    TORCH_CHECK(B >= 1 && C >= 1, "x must not be empty in its batch or column dimension");
+    const bool res = has(y), mod = has(shift) || has(scale), aff = has(weight) || has(bias);
+    TORCH_CHECK(has(shift) == has(scale) && has(weight) == has(bias), "shift / scale come together, and so do weight / bias");
+    TORCH_CHECK(mod != aff, "exactly one of modulation (shift, scale) and affine (weight, bias)");
+    TORCH_CHECK(res || !has(gate), "a gate without y");
+    TORCH_CHECK(!(res && !has(gate) && x.scalar_type() == at::kBFloat16), "a bfloat16 x takes its residual with a gate");
+    // a vector per sequence: fp32 [C], [B, C] or [B, 1, C] -> (contiguous tensor, batch stride in elements)
+    auto vec = [&](const at::Tensor &t, const char *name, int64_t &stride) {
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat, name, " must be a float32 GPU tensor");
+        const bool one = t.dim() == 1 && t.size(0) == C;
+        const bool per = (t.dim() == 2 && t.size(1) == C) || (t.dim() == 3 && t.size(1) == 1 && t.size(2) == C);
+        TORCH_CHECK(one || (per && (t.size(0) == 1 || t.size(0) == B)), name, " must be [C], [B, C] or [B, 1, C] with a batch dimension of 1 or B");
+        stride = (per && t.size(0) == B && B > 1) ? C : 0;
+        return t.contiguous();
+    };
+    at::Tensor yc, gc, sh, sc, wt, bs, xo;
+    int64_t gs = 0, ms = 0, ms2 = 0, none = 0;
+    if (res) {
+        yc = *y;
+        CHECK_DEV(yc); CHECK_BF16(yc); CHECK_CONTIG(yc);
+        TORCH_CHECK(yc.sizes() == x.sizes(), "y must have the shape of x");
+        if (has(gate)) gc = vec(*gate, "gate", gs);
+    }
+    if (mod) {
+        sh = vec(*shift, "shift", ms), sc = vec(*scale, "scale", ms2);
+        if (ms != ms2) {   // one of the two is a single vector: give both the batch stride
+            if (ms == 0) sh = sh.reshape({1, C}).expand({B, C}).contiguous();
+            else sc = sc.reshape({1, C}).expand({B, C}).contiguous();
+            ms = C;
+        }
+    } else {
+        TORCH_CHECK(weight->dim() == 1 && bias->dim() == 1, "weight / bias must be [C]");
+        wt = vec(weight->to(at::kFloat), "weight", none), bs = vec(bias->to(at::kFloat), "bias", none);   // widening is exact
+    }
+    c10::DeviceGuard guard(x.device());
+    if (res) xo = at::empty(x.sizes(), x.options().dtype(at::kFloat));
+    at::Tensor xm = at::empty(x.sizes(), x.options().dtype(at::kBFloat16));
+    check(chipmunk_residual_ln_modulate_f32(x.data_ptr(), x.scalar_type() == at::kBFloat16 ? 1 : 2, res ? yc.data_ptr() : nullptr,
+                                            gc.defined() ? gc.data_ptr<float>() : nullptr, gs, mod ? sh.data_ptr<float>() : nullptr,
+                                            mod ? sc.data_ptr<float>() : nullptr, ms, mod ? nullptr : wt.data_ptr<float>(),
+                                            mod ? nullptr : bs.data_ptr<float>(), res ? xo.data_ptr<float>() : nullptr, xm.data_ptr(), B, L,
+                                            (int)C, eps, cur_stream(x)),
+          "residual_ln_modulate_f32");
+    if (res) return {xo, xm};
+    return {xm};
+}
+
 // reference csrc/attn/csp_128_attn.cu:355-461
 at::Tensor csp_128_attn(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor indices, at::Tensor indices_counts) {
     check_attn_shapes(q, k, v);
@@ -1479,6 +1537,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("mask_to_ragged_indices(Tensor mask, int[] shape, int multiple_of, int pad_to_multiple_of, bool sorted) -> Tensor[]");
     m.def("csp_attn_out_ragged(Tensor q, Tensor k, Tensor v, Tensor o_in, Tensor indices, Tensor offsets, Tensor indices_counts, int o_scale) -> Tensor");
     m.def("residual_ln_modulate(Tensor x, Tensor? y, Tensor? gate, Tensor shift, Tensor scale, float eps) -> Tensor[]");
+    m.def("residual_ln_modulate_f32(Tensor x, Tensor? y, Tensor? gate, Tensor? shift, Tensor? scale, Tensor? weight, Tensor? bias, float eps) -> Tensor[]");
     m.def("transpose_last2(Tensor x) -> Tensor");
     m.def("transpose_last2_pitched(Tensor x, int ld) -> Tensor");
     m.def("transpose_to_groups(Tensor x) -> Tensor");
@@ -1512,6 +1571,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("dense_colsum_attn", &dense_colsum_attn);
     m.impl("compact_indices", &compact_indices);
     m.impl("residual_ln_modulate", &residual_ln_modulate);
+    m.impl("residual_ln_modulate_f32", &residual_ln_modulate_f32);
     m.impl("csp_attn_out_ragged", &csp_attn_out_ragged);
     m.impl("dense_attn_varlen", &dense_attn_varlen);
     m.impl("dense_colsum_attn_varlen", &dense_colsum_attn_varlen);

@@ -25,6 +25,11 @@ def _register():
     def _(x, y, gate, shift, scale, eps):
         return [torch.empty_like(x), torch.empty_like(x)] if y is not None else [torch.empty_like(x)]
 
+    @lib.register_fake("chipmunk::residual_ln_modulate_f32")
+    def _(x, y, gate, shift, scale, weight, bias, eps):
+        xm = torch.empty_like(x, dtype=torch.bfloat16)
+        return [torch.empty_like(x, dtype=torch.float32), xm] if y is not None else [xm]
+
     @lib.register_fake("chipmunk::csp_attn_out_ragged")
     def _(q, k, v, o_in, indices, offsets, indices_counts, o_scale):
         return torch.empty_like(o_in)

@@ -156,3 +156,63 @@ def residual_ln_modulate(x: torch.Tensor, y: Optional[torch.Tensor], gate: Optio
         x = torch.addcmul(x, gate, y)
     xn = torch.nn.functional.layer_norm(x, (x.shape[-1],), eps=eps)
     return x, torch.addcmul(shift, xn, 1 + scale)
+
+
+def _per_sequence(v: torch.Tensor, name: str, B: int, C: int) -> torch.Tensor:
+    """A per-sequence vector as ``[1 or B, 1, C]``: fp32 ``[C]``, ``[B, C]`` or ``[B, 1, C]`` with a batch dimension of 1 or B."""
+    if v.dtype != torch.float32:
+        raise ValueError(f"residual_ln_modulate_f32: {name} must be float32 (Wan's modulation is, model.py:317)")
+    ok = (v.dim() == 1 and v.shape[0] == C) or (v.dim() == 2 and v.shape[1] == C) or (v.dim() == 3 and v.shape[1] == 1 and v.shape[2] == C)
+    if not ok or (v.dim() > 1 and v.shape[0] not in (1, B)):
+        raise ValueError(f"residual_ln_modulate_f32: {name} must be [C], [B, C] or [B, 1, C] with a batch dimension of 1 or B = {B} "
+                         f"(got {tuple(v.shape)})")
+    return v.reshape(-1, 1, C)
+
+
+def _wan_block_glue_reference(x, y, gate, shift, scale, weight, bias, eps):
+    """The reference's torch sequence for one use of the block glue, on ``x [B, L, C]`` with vectors ``[1 or B, 1, C]``: ``x + y * e``
+    (``model.py:327, 334``; fp32 by promotion, what the fp32 autocast around those lines leaves) or ``x + y`` (``:331``), ``WanLayerNorm``
+    (``:110``), then the modulation in fp32 (``:324, :332``) or the affine ``norm3`` (``:283-285``), bf16 as the next Linear takes it."""
+    C = x.shape[-1]
+    if y is not None:
+        x = x + (y * gate if gate is not None else y)
+    norm = lambda w, b: torch.nn.functional.layer_norm(x.float(), (C,), w, b, eps).type_as(x)      # noqa: E731
+    if weight is not None:
+        return x, norm(weight.float(), bias.float()).to(torch.bfloat16)
+    return x, (norm(None, None).float() * (1 + scale) + shift).to(torch.bfloat16)
+
+
+def residual_ln_modulate_f32(x: torch.Tensor, y: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
+                             shift: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                             weight: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, eps: float = 1e-6):
+    """A Wan block's row-wise chain between two GEMMs as one HBM pass (``chipmunk_residual_ln_modulate_f32``): the residual stream
+    is fp32 and the vectors are fp32, one set per sequence (``examples/wan/wan/modules/model.py:317-334``).
+
+    ``x [B, L, C]`` or ``[L, C]``, fp32 or (before the first block) bf16; ``y`` bf16 of that shape or ``None``; ``gate`` and the pair
+    ``shift`` / ``scale`` fp32 ``[C]``, ``[B, C]`` or ``[B, 1, C]``; or, instead of the modulation, ``weight`` / ``bias`` ``[C]``
+    (``norm3``, ``:283-285``).  With ``y``: ``x_out = x.float() + y.float() * gate`` (``:327, :334``; without a gate ``x + y``, ``:331``),
+    fp32.  Then ``xm = bf16(norm(x_out).float() * (1 + scale) + shift)`` (``:324, :332``) or ``bf16(norm3(x_out))``, where ``norm`` is
+    ``WanLayerNorm`` (``:100-110``): statistics in fp32, ``.type_as(x)`` -- a rounding only for a bf16 ``x``.  Returns ``(x_out, xm)``;
+    without ``y`` the caller's ``x`` comes back as ``x_out``.  On CPU tensors: the reference's torch sequence."""
+    if x.dim() not in (2, 3) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous():
+        raise ValueError("residual_ln_modulate_f32: x must be a contiguous float32 or bfloat16 [B, L, C] or [L, C]")
+    B, C = (x.shape[0] if x.dim() == 3 else 1), x.shape[-1]
+    if C % 8 or C > 8192:
+        raise ValueError(f"residual_ln_modulate_f32: C must be a multiple of 8, at most 8192 (got {C})")
+    if y is None and gate is not None:
+        raise ValueError("residual_ln_modulate_f32: a gate without y")
+    if y is not None and (y.dtype != torch.bfloat16 or y.shape != x.shape):
+        raise ValueError("residual_ln_modulate_f32: y must be bfloat16 of x's shape")
+    if y is not None and gate is None and x.dtype == torch.bfloat16:
+        raise ValueError("residual_ln_modulate_f32: a bfloat16 x takes its residual with a gate (torch would keep x + y in bfloat16)")
+    if (shift is None) != (scale is None) or (weight is None) != (bias is None) or (shift is None) == (weight is None):
+        raise ValueError("residual_ln_modulate_f32: exactly one pair of (shift, scale) and (weight, bias)")
+    vecs = {n: _per_sequence(v, n, B, C) for n, v in (("gate", gate), ("shift", shift), ("scale", scale)) if v is not None}
+    if weight is not None and (weight.shape != (C,) or bias.shape != (C,)):
+        raise ValueError("residual_ln_modulate_f32: weight / bias must be [C]")
+    if x.is_cuda:
+        out = torch.ops.chipmunk.residual_ln_modulate_f32(x, y, gate, shift, scale, weight, bias, eps)
+        return (out[0], out[1]) if y is not None else (x, out[0])      # (the operator never returns its own input)
+    x_out, xm = _wan_block_glue_reference(x if x.dim() == 3 else x.unsqueeze(0), None if y is None else y.reshape(B, -1, C), vecs.get("gate"),
+                                          vecs.get("shift"), vecs.get("scale"), weight, bias, eps)
+    return (x_out.reshape(x.shape) if y is not None else x), xm.reshape(x.shape)

@@ -130,6 +130,26 @@ int chipmunk_dense_colsum_attn(const void *q, const void *k, const void *v, cons
 int chipmunk_residual_ln_modulate(const void *x, const void *y, const void *gate, const void *shift, const void *scale,
                                   void *x_out, void *xm, int64_t rows, int cols, double eps, void *stream);
 
+/* The same pass for Wan's blocks (reference examples/wan/wan/modules/model.py:100-110, 317-334): an fp32 residual stream, fp32
+ * vectors given per SEQUENCE, and a LayerNorm that is either modulated or affine.  Rows are B sequences of L rows of cols columns.
+ *   x [B*L, cols]: x_dtype 2 = fp32, 1 = bf16 (the stream before the first block).  xm [B*L, cols] bf16.
+ *   y [B*L, cols] bf16 and x_out [B*L, cols] fp32 come together (x_out may be an fp32 x):
+ *       x_out = fp32(fp32(x) + fp32(fp32(y) * gate))   -- two roundings, never a fused multiply-add; gate = NULL: fp32(x) + fp32(y).
+ *     A gate without y is refused, and so is a bf16 x with y and no gate (torch would keep that sum in bf16).
+ *   gate, shift, scale fp32: sequence b reads its vector at p + b * batch_stride (elements); stride 0 = one vector [cols] for all.
+ *   Exactly one pair of (shift, scale) and (weight, bias) is set; weight, bias fp32 [cols].  With v = x_out (x without y) and
+ *   xn = (v - mean) / sqrt(var + eps) over cols (biased variance, statistics in fp32, two passes over the row in registers):
+ *       xm = bf16(xn * fp32(1 + scale) + shift)    or    xm = bf16(xn * weight + bias)        -- evaluated in fp32, rounded once;
+ *     for a bf16 x without y and with a modulation xn is rounded to bf16 first (WanLayerNorm's .type_as; with the affine pair that
+ *     cast is the one rounding above).
+ * cols % 8 == 0, cols <= 8192; 16-byte aligned pointers, batch strides 0 or multiples of 4 that cover cols.  A batch of B sequences
+ * gives the bits of B calls.  One read of x and y, one write of x_out and xm; the vectors stay in registers up to cols = 3072 and are
+ * re-read per row (from L2) above. */
+int chipmunk_residual_ln_modulate_f32(const void *x, int x_dtype, const void *y, const float *gate, int64_t gate_batch_stride,
+                                      const float *shift, const float *scale, int64_t mod_batch_stride, const float *weight,
+                                      const float *bias, float *x_out, void *xm, int64_t B, int64_t L, int cols, double eps,
+                                      void *stream);
+
 /* ---------------------------------------------------------------- column-sparse MLP
  * Replaces chipmunk::csp_mlp_mm1 (reference csrc/mlp/csp_mlp_mm1.cu:625-702; schema csrc/chipmunk.cpp:47).
  * For 128-row group g and packed column j < counts[g]:
