@@ -14,6 +14,8 @@
 // GEMM2 also exists over e4m3 rows of fc2^T (mm2_w8_kernel, weight-only fp8): the gathered row slice is N2 BYTES, the transpose read runs over
 // the byte image with a column pair as its 16-bit element, v_perm_b32 + v_cvt_scalef32_pk_bf16_fp8 widen to bf16 in registers in front of the
 // same bf16 MFMA, and the freed half of the B tile is a fourth ring stage <256, 32, 4, 2, 8 waves>.
+// GEMM1 has the same weight-only form over e4m3 rows of fc1 (mm1_w8_kernel, mm1_tile's W8): the gathered piece of a k step is 64 BYTES, k-contiguous,
+// so a fragment is one ds_read_b64 widened by v_cvt_scalef32_pk_bf16_fp8, no transpose; three stages of 16 + 8 KiB under the FLAT epilogue.
 #include "common.h"
 #include "attn64_util.h"
 #include <type_traits>
@@ -90,6 +92,13 @@ __device__ __forceinline__ float glu_act(float x) {
     if constexpr (ACT == 0) return gelu_tanh(x);
     else if constexpr (ACT == 1) return x * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(x * -1.44269504089f) + 1.0f);
     else return (x * 0.5f) * (erff(x * 0.70710678118654752f) + 1.0f);
+}
+
+// a * s + b as a multiplication and an addition, each rounded: never contracted into an fma
+__device__ __forceinline__ f32x2 scale_then_bias2(f32x2 a, f32x2 s, f32x2 b) {
+#pragma clang fp contract(off)
+    const f32x2 t = a * s;
+    return t + b;
 }
 
 template <int N>
@@ -206,6 +215,11 @@ struct Mm1Params {
 struct Mm1GluF8Params : Mm1Params {
     const float *scale_x, *scale_gate, *scale_up;
 };
+// The weight-only form (mm1_w8_kernel): b is the e4m3 weight [F, K], scale_b its reciprocal scale -- one number (scale_n == 1) or one per
+// fc1 row (scale_n == F); which, is this run-time field behind the shared block.  scale_a is not read.
+struct Mm1W8Params : Mm1Params {
+    int scale_n;
+};
 
 // One TM x TN output tile (TM rows of group g starting at m_off, packed columns n0 .. n0+TN-1): 4 waves as 2 x 2, each a
 // (TM/2) x (TN/2) accumulator of 32x32x16 MFMA tiles; NST-deep LDS ring of [A tile | B tile] stages.
@@ -232,14 +246,30 @@ struct Mm1GluF8Params : Mm1Params {
 // The column's scale is a per-lane scalar like its bias -- gathered through the indices in the prologue --, the row scales of a lane's runs of
 // four rows are fetched behind the k loop, under the wait for the cache block: the loop carries nothing new.  Rows at or past M read a live
 // row's scale (as their A rows do) and are never stored.  (acc * scale_a[m]) * scale_b[i] + bias[i]: the scalar form's order and its bits.
+// W8 (mm1_w8_kernel; P = Mm1W8Params): bf16 a, e4m3 weight rows, weight-only.  The A tile and its fragments are the bf16 form's; a B row piece
+// of one k step is BK BYTES, so the B tile has KTile<BK / 2>'s shape (64-byte rows, 16 per DMA instruction).  A lane's fragment of MFMA slice kk
+// is the 8 bytes at byte (kk * 2 + (lane >> 5)) * 8 of its row -- half (lane >> 5) of 16-byte chunk kk --, one ds_read_b64, widened to bf16x8 by
+// v_cvt_scalef32_pk_bf16_fp8 at scale 1.0 (exact) in front of the bf16 MFMA: k sits where the bf16 form puts it, so the fp32 sums are the bf16
+// form's on the widened weight.  Banks: the 32 lanes of a ds_read_b64 group share their chunk HALF, so on a 16-byte grid they can reach only 32 of
+// the 64 banks whatever the chunk swizzle does; the swizzle (chunk c of row r at chunk c ^ (r / 4 & 3): 16 rows x 4 chunks -> the 16 chunk positions
+// of a 256-byte bank row) is therefore completed by a shift of every odd 1-KiB DMA piece by 8 bytes -- rows 0 .. 15 of a 32-row fragment read the
+// dword pairs {4p, 4p + 1}, rows 16 .. 31 the pairs {4p + 2, 4p + 3} (+ 2 for the upper lane half): 64 banks, once each.  A shifted piece
+// ends 8 bytes behind its KiB, so every PAIR of pieces (one 32-row fragment) owns 2 KiB + 16 bytes: an even piece at the pair's start, the odd
+// one 1 KiB + 8 behind it (a pair's start moves all its 32 rows by the same number of banks).  The sum starts from zero, is multiplied by the gathered column's reciprocal scale (p.scale_n == 1:
+// one number for all) and then biased, two roundings, never an fma; act and the subtraction are the bf16 form's, one rounding.
 template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params, bool NULLB = false,
-          bool RS = false>
+          bool RS = false, bool W8 = false>
 __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
     static_assert(!RS || (FP8 && !GLU && NULLB), "row / column scale vectors: the ungated fp8 form with a nullable bias (mm1_form_kernel) only");
+    static_assert(!W8 || (!FP8 && !GLU && !RS && NULLB && NW == 4 && BK == 64), "the weight-only form: ungated, bf16 a, 4 waves, 64-byte B row pieces");
     using KT = KTile<BK>;
+    using KTB = KTile<W8 ? BK / 2 : BK>;     // the B tile's geometry
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
-    constexpr int A_TILE = TM * BK * 2, B_TILE = TN * BK * 2, STAGE = A_TILE + B_TILE;
-    constexpr int A_INST = A_TILE / (1024 * NW), B_INST = B_TILE / (1024 * NW);  // DMA instructions per wave per tile
+    constexpr uint32_t BSZ = W8 ? 1u : ESZ;  // ... of the weight
+    constexpr int B_PAD = W8 ? TN / 32 * 16 : 0;   // (W8: 16 bytes per pair of DMA pieces, room for the odd piece's 8-byte shift)
+    constexpr int B_PAIR = 2048 + 16;              // (W8: bytes a pair of pieces owns)
+    constexpr int A_TILE = TM * BK * 2, B_TILE = TN * BK * (int)(W8 ? 1 : 2) + B_PAD, STAGE = A_TILE + B_TILE;
+    constexpr int A_INST = A_TILE / (1024 * NW), B_INST = (B_TILE - B_PAD) / (1024 * NW);  // DMA instructions per wave per tile
     constexpr int WNC = NW / 2;                                     // waves across the tile's columns (2 down its rows)
     constexpr int MT = TM / 64, NT4 = TN / (32 * WNC);              // 32-wide m / n tiles per wave
     static_assert(A_INST >= 1 && B_INST >= 1, "tile too small for one DMA instruction per wave");
@@ -267,10 +297,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     }
 #pragma unroll
     for (int i = 0; i < B_INST; ++i) {
-        const int row = KT::lane_row(w * B_INST + i, lane);
+        const int row = KTB::lane_row(w * B_INST + i, lane);
         const int j = GLU ? n0 + (row >> 6) * 32 + (row & 31) : n0 + row;   // gated: tile rows [64 wn + 32 half, +32) = packed columns [32 wn, +32)
         const int key = idxg[j < cnt ? j : n0];  // rows past the count re-read a live row and are never stored
-        boff[i] = (uint32_t)key * p.K * ESZ + KT::src_chunk_elems(row, lane) * 2u;
+        boff[i] = (uint32_t)key * p.K * BSZ + KTB::src_chunk_elems(row, lane) * 2u;
     }
     auto issue = [&](int kb, int buf) {
         unsigned char *st = smem + buf * STAGE;
@@ -281,6 +311,8 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
             if constexpr (GLU) {
                 const bool up = (((w * B_INST + i) * KT::RPI) >> 5) & 1;   // wave-uniform: the instruction's rows lie in one half
                 blds16(up ? rb_up : rb, boff[i], kb * BK * 2, st + A_TILE + (w * B_INST + i) * 1024);
+            } else if constexpr (W8) {   // BK bytes of a row per k step; the odd pieces land 8 bytes up
+                blds16(rb, boff[i], kb * BK, st + A_TILE + ((w * B_INST + i) >> 1) * B_PAIR + ((w * B_INST + i) & 1) * (1024 + 8));
             } else {
                 blds16(rb, boff[i], kb * BK * 2, st + A_TILE + (w * B_INST + i) * 1024);
             }
@@ -294,7 +326,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     // FLAT (tiles whose outputs exceed one stage): the ring starts at the stage that makes the LAST k step compute out of stage 0, the
     // cache block lands behind it in [STAGE, STAGE + TM*TN*2) and the outputs leave through stage 0 plus the bytes behind the cache block.
     constexpr int EPI = TM * PW * 2;   // (gated form: half the columns -- cache block PW columns x TM rows, output image TM x PW)
-    constexpr bool FLAT = NW == 8 && EPI > STAGE && EPI <= (NST - 1) * STAGE && 2 * EPI <= NST * STAGE && STAGE % (TN * 2) == 0;
+    // (W8: a stage is no whole number of output rows -- the rows behind the cache block start FLAT_SKIP behind their place in a contiguous image)
+    constexpr int FLAT_ROWS = STAGE / (TN * 2), FLAT_SKIP = EPI + STAGE - FLAT_ROWS * TN * 2;
+    constexpr bool FLAT = (NW == 8 || W8) && EPI > STAGE && EPI <= (NST - 1) * STAGE && EPI + FLAT_SKIP <= NST * STAGE &&
+                          (W8 ? FLAT_ROWS % 4 == 0 : STAGE % (TN * 2) == 0);
     constexpr bool STAGED = EPI <= STAGE || FLAT;
     static_assert(!FP8 || STAGED, "the fp8 form is only built for tile shapes with the staged epilogue");
     static_assert(!GLU || (STAGED && !FLAT), "the gated form is only built for tile shapes with the staged epilogue");
@@ -325,10 +360,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
 
     // bf16: the bias seeds the fp32 accumulators, as in the reference (csp_mlp_mm1.cu:347-350) -- its two dependent loads (index,
     // then bias) fly during the prologue instead of in front of the epilogue.  fp8 scales the sum first, so it starts from zero.
-    constexpr bool SEED_BIAS = !FP8;
+    constexpr bool SEED_BIAS = !FP8 && !W8;
     float bias_v[NT4], sa = 1.f, sb = 1.f;   // loaded here for both forms: in front of the epilogue the round trips would be exposed
     float sb_up = 1.f;                       // (gated fp8 form: sb is the gate weight's scale, sb_up the up weight's)
-    float sb_col[RS ? NT4 : 1];              // (RS: the weight scale of the lane's column of every 32-wide tile)
+    float sb_col[RS || W8 ? NT4 : 1];        // (RS, W8: the weight scale of the lane's column of every 32-wide tile)
     if constexpr (FP8 && GLU) sa = p.scale_x[0], sb = p.scale_gate[0], sb_up = p.scale_up[0];
     else if constexpr (FP8 && !RS) sa = p.scale_a[0], sb = p.scale_b[0];
     f32x16 acc[MT][NT4];
@@ -341,6 +376,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         } else if constexpr (NULLB) {
             bias_v[n4] = p.bias ? bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]) : 0.f;
             if constexpr (RS) sb_col[n4] = p.scale_b[idxg[j < cnt ? j : n0]];
+            if constexpr (W8) sb_col[n4] = p.scale_b[p.scale_n > 1 ? idxg[j < cnt ? j : n0] : 0];   // one per fc1 row, or one number
         } else {
             bias_v[n4] = bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]);
         }
@@ -353,6 +389,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
 
     const int nkb = (int)((uint32_t)p.K * ESZ / (BK * 2));
     int buf = FLAT ? (NST - (nkb - 1) % NST) % NST : 0;   // FLAT: k step nkb-1 computes out of stage 0
+    // W8: every register load of the tile -- gather indices, bias, scale -- has landed before the first LDS-DMA is issued, so none of them is
+    // consumed under a counted vmcnt with LDS-DMAs behind it (an LDS-DMA may retire ahead of an older register load).  The counted
+    // waits the compiler still puts in front of their uses then wait for nothing; the loop and the epilogue issue no register load of their own.
+    if constexpr (W8) wait_vmcnt<0>();
 #pragma unroll
     for (int s = 0; s < NST - 1; ++s)
         if (s < nkb) issue(s, (buf + s) % NST);
@@ -388,6 +428,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         constexpr int KK = FP8 ? BK * 2 / 64 : BK / 16;
         using Frag = typename std::conditional<FP8, i32x8, bf16x8>::type;
         Frag af[2][MT], bfr[2][NT4];
+        u32x2 bw8[2][W8 ? NT4 : 1];   // (W8: the fragments' e4m3 bytes, widened in front of their MFMAs)
         auto frag = [&](const unsigned char *tile, int row, int kk) -> Frag {
             if constexpr (FP8) {
                 const int c0 = kk * 4 + (lane >> 5) * 2;
@@ -402,13 +443,29 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) af[set][mt] = frag(At, wm * (TM / 2) + mt * 32 + (lane & 31), kk);
 #pragma unroll
-            for (int n4 = 0; n4 < NT4; ++n4) bfr[set][n4] = frag(Bt, wn * (TN / WNC) + n4 * 32 + (lane & 31), kk);
+            for (int n4 = 0; n4 < NT4; ++n4) {
+                const int row = wn * (TN / WNC) + n4 * 32 + (lane & 31);
+                if constexpr (W8)
+                    bw8[set][n4] = *(const u32x2 *)(Bt + (row >> 5) * B_PAIR + ((row >> 4) & 1) * (1024 + 8) + (row & 15) * KTB::ROWB +
+                                                    ((kk ^ KTB::swz(row)) << 4) + (lane >> 5) * 8);
+                else
+                    bfr[set][n4] = frag(Bt, row, kk);
+            }
         };
         load_frags(0, 0);
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk) {
             if (kk + 1 < KK) load_frags(kk + 1, (kk + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);  // keep the next slice's reads ahead of this slice's MFMAs
+            if constexpr (W8) {
+#pragma unroll
+                for (int n4 = 0; n4 < NT4; ++n4) {
+                    const u32x2 r = bw8[kk & 1][n4];
+                    const bf16x2 f0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r[0], 1.0f, false), f1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r[0], 1.0f, true);
+                    const bf16x2 f2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r[1], 1.0f, false), f3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r[1], 1.0f, true);
+                    bfr[kk & 1][n4] = (bf16x8){f0[0], f0[1], f1[0], f1[1], f2[0], f2[1], f3[0], f3[1]};
+                }
+            }
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -445,7 +502,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         const int cst = last + NST - 1 >= NST ? last - 1 : last + NST - 1;  // nbuf at kb = nkb-1
         unsigned char *Ct = smem + (FLAT ? 1 : cst) * STAGE, *Ot = smem + (FLAT ? 0 : last) * STAGE;
         // output row r of the stage image (FLAT: the rows that do not fit stage 0 continue behind the cache block)
-        auto ot_row = [&](int r) { return Ot + r * (PW * 2) + ((FLAT && r >= STAGE / (TN * 2)) ? EPI : 0); };
+        auto ot_row = [&](int r) { return Ot + r * (PW * 2) + ((FLAT && r >= FLAT_ROWS) ? FLAT_SKIP : 0); };
         constexpr int LPO = PW * 2 / 16;  // 16-byte chunks per output row
         // RS: the reciprocal scales of the lane's rows, runs of four (ml .. ml + 3 per (mt, q4)), requested here so that they land under the
         // wait for the cache block.  M % 4 == 0 and a 16-byte aligned vector (wave-uniform): a run is live or dead as a whole and arrives as
@@ -526,6 +583,11 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                             const f32x2 u01 = {acc[mt][1][q4 * 4 + 0], acc[mt][1][q4 * 4 + 1]}, u23 = {acc[mt][1][q4 * 4 + 2], acc[mt][1][q4 * 4 + 3]};
                             d01 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>(a01), u01, -c01));
                             d23 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>(a23), u23, -c23));
+                        } else if constexpr (W8) {
+                            // sum * scale, then + bias: two fp32 roundings (scale_then_bias2), then the bf16 form's one rounding
+                            const f32x2 sbv = {sb_col[n4], sb_col[n4]}, bv = {bia, bia};
+                            d01 = pack_bf16x2_v(glu_act2<ACT>(scale_then_bias2(a01, sbv, bv)) - c01);
+                            d23 = pack_bf16x2_v(glu_act2<ACT>(scale_then_bias2(a23, sbv, bv)) - c23);
                         } else {
                             // the bias is already in the sum (SEED_BIAS)
                             d01 = pack_bf16x2_v(glu_act2<ACT>(a01) - c01), d23 = pack_bf16x2_v(glu_act2<ACT>(a23) - c23);
@@ -543,7 +605,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
             }
         };
         if (p.update_cache == 0) arith(ic<0>{});
-        else if constexpr (GLU) arith(ic<1>{});   // (the gated entry admits 0 and 1 only: no third copy of its epilogue)
+        else if constexpr (GLU || W8) arith(ic<1>{});   // (the gated and the weight-only entries admit 0 and 1 only: no third copy of the epilogue)
         else if (p.update_cache == 1) arith(ic<1>{});
         else arith(ic<2>{});
         __syncthreads();
@@ -740,6 +802,57 @@ __global__ __launch_bounds__(256, WPS) void mm1_form_kernel(const typename Mm1Bl
     }
 }
 
+
+#ifndef CHIPMUNK_MM1_PROBES
+// Weight-only e4m3 fc1 (mm1_tile's W8 form): c = bf16(act((a . f(b[i, :])) * scale_b[i] + bias[i]) - cache[i, m]) with bf16 a and f the exact
+// e4m3 -> bf16 widening.  mm1_form_kernel's walk for an ungated form -- live-tile map, tail split into 64 x 64 sub-tiles, ragged last group,
+// batch pointer advance -- under a name of its own.  A stage is 16 KiB of A + 8 KiB of B (+ 64), smaller than the 32 KiB images of the staged
+// epilogue, so the whole tile runs NST = 3 stages with mm1_tile's FLAT epilogue: the last k step computes out of stage 0, the cache block
+// lands in the two stages behind it, and the outputs leave through stage 0 and the bytes behind the cache block.
+struct Mm1W8Batch : Mm1W8Params {
+    int B;
+    int64_t cache_bs;   // as Mm1Batch
+};
+template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED>
+__global__ __launch_bounds__(256, WPS) void mm1_w8_kernel(const typename std::conditional<BATCHED, Mm1W8Batch, Mm1W8Params>::type p) {
+    using P = Mm1W8Params;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int NSUB = 2 * (BN / 64);                                   // 64 x 64 sub-tiles per tile
+    constexpr int LDS = NST * (BM * BK * 2 + BN * BK + BN / 32 * 16), SUB_STAGE = 64 * BK * 2 + 64 * BK + 32;
+    constexpr int SUB_NST = LDS / SUB_STAGE > 4 ? 4 : LDS / SUB_STAGE;    // inside the same LDS bytes
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
+    const TilePlan pl = plan_tiles<BN>(p.counts, G, p.NT, p.NR, p.slots_per_xcd, NSUB);
+    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+        const TileMap tm = tile_at(pl, slot);
+        if (!tm.live) continue;
+        const int cnt = p.counts[tm.g];
+        int g = tm.g;
+        typename std::conditional<BATCHED, P, const P &>::type q = p;   // the tile sees its sequence's operands (one sequence: the kernel's own block)
+        if constexpr (BATCHED) {
+            const int seq = tm.g / Gs;
+            g = tm.g - seq * Gs;                      // group inside sequence seq
+            q.a = p.a + (int64_t)seq * p.M * p.K;
+            q.c = p.c + (int64_t)seq * p.M * p.F;
+            q.cache = p.cache + (int64_t)seq * p.cache_bs;
+            q.indices = p.indices + (int64_t)seq * Gs * p.F;
+        }
+        if (tm.sub < 0) {
+            const int n0 = tm.nt * BN;
+            if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
+            mm1_tile<BM, BN, BK, NST, false, 4, false, ACT, P, true, false, true>(q, smem, g, 0, n0, cnt);
+        } else {
+            const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
+            if (n0 >= cnt) continue;
+            if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
+            mm1_tile<64, 64, BK, SUB_NST, false, 4, false, ACT, P, true, false, true>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
+        }
+        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
+    }
+}
+#endif   // CHIPMUNK_MM1_PROBES
 
 // The tile shapes and producer / consumer forms measured against the shipped kernels (docs/EXPERIMENTS_r04.md / _r05.md) are
 // not part of the product library: tools/probes/mm1_forms/build.sh compiles this file with -DCHIPMUNK_MM1_PROBES into
@@ -1849,7 +1962,88 @@ int mm1_glu_fp8_entry(const void *a, const void *b_gate, const void *b_up, void 
     if (gm) p.gs = F * BM, B = B == 1 ? 0 : B;
     return launch_mm1_form<true, true>(p, act, stream, B, cache_bs);
 }
+
+// Weight-only e4m3 fc1: mm1_w8_kernel at its one tile shape -- <128 columns, k step 64, 3 stages, 2 workgroups per CU> --, grid and tail
+// split as launch_mm1_variant sets them for the ungated forms
+#ifndef CHIPMUNK_MM1_PROBES
+template <int ACT, bool BATCHED>
+int launch_mm1_w8_kernel(Mm1W8Params p, hipStream_t s, int B, int64_t cache_bs) {
+    constexpr int BN = 128, BK = 64, NST = 3, WPS = 2;
+    constexpr int LDS = NST * (BM * BK * 2 + BN * BK + BN / 32 * 16);
+    static_assert(LDS <= 80 * 1024, "two workgroups share a CU's 160 KiB");
+    auto kern = mm1_w8_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+    static uint64_t lds_set = 0;
+    ensure_dynamic_lds((const void *)kern, LDS, lds_set);
+    p.NT = (p.F + BN - 1) / BN;
+    const int nr_option = chipmunk_get_option("mm1_nr");   // column tiles per walk: launch_mm1_variant's
+    p.NR = nr_option > 0 ? nr_option : 4;
+    if (p.NR > p.NT) p.NR = p.NT;
+    const int resident_per_xcd = WPS * device_cu_count() / 8;
+    p.slots_per_xcd = chipmunk_get_option("mm1_no_split") ? 0 : resident_per_xcd;
+    const int tiles_per_xcd = (B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8;
+    const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
+    if constexpr (BATCHED) {
+        Mm1W8Batch q;
+        static_cast<Mm1W8Params &>(q) = p;
+        q.B = B, q.cache_bs = cache_bs;
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(256), LDS, s, q);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(256), LDS, s, p);
+    }
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+template <bool BATCHED>
+int launch_mm1_w8(const Mm1W8Params &p, int act, hipStream_t s, int B, int64_t cache_bs) {
+    switch (act) {
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_w8_kernel<0, BATCHED>(p, s, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_w8_kernel<1, BATCHED>(p, s, B, cache_bs);
+        default: return launch_mm1_w8_kernel<2, BATCHED>(p, s, B, cache_bs);
+    }
+}
+#endif
+
+// B > 0: the *_batched entry; gm: the *_gm entry (group-major cache, ldc = BM, B >= 1 with 1 the single-sequence launch)
+int mm1_w8_entry(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias, void *pa_cache,
+                 const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream,
+                 int B = 0, int64_t cache_bs = 0, bool gm = false) {
+#ifdef CHIPMUNK_MM1_PROBES
+    CM_CHECK(false, "csp_mlp_mm1_w8: not part of the probe-forms build");
+#else
+    CM_CHECK(a && b && scale_b && c && pa_cache, "csp_mlp_mm1_w8: null tensor or scale pointer");
+    CM_CHECK(scale_n == 1 || scale_n == F, "csp_mlp_mm1_w8: scale_n must be 1 (one reciprocal scale) or F = %d (one per fc1 row), got %d", F, scale_n);
+    CM_CHECK(((uintptr_t)scale_b & 3) == 0, "csp_mlp_mm1_w8: scale_b must be 4-byte aligned");
+    if (int e = check_mm1("csp_mlp_mm1_w8", true, indices, counts, M, K, F, ldc, B, cache_bs, 64, true, act, update_cache, 1, gm)) return e;
+    Mm1W8Params p;
+    static_cast<Mm1Params &>(p) = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
+                                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
+    p.scale_b = scale_b, p.scale_n = scale_n;
+    if (gm) p.gs = F * BM, B = B == 1 ? 0 : B;
+    return B > 0 ? launch_mm1_w8<true>(p, act, stream, B, cache_bs) : launch_mm1_w8<false>(p, act, stream, 1, 0);
+#endif
+}
 }  // namespace
+
+// ---- weight-only e4m3 fc1 (include/chipmunk_hip.h, "fp8 fc1, weight-only")
+extern "C" int chipmunk_csp_mlp_mm1_w8(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias,
+                                       void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
+                                       int update_cache, void *stream) {
+    return mm1_w8_entry(a, b, scale_b, scale_n, c, bias, pa_cache, indices, counts, M, K, F, ldc, act, update_cache, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_w8_batched(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias,
+                                               void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc,
+                                               int act, int update_cache, int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_w8_entry(a, b, scale_b, scale_n, c, bias, pa_cache, indices, counts, M, K, F, ldc, act, update_cache, (hipStream_t)stream, B,
+                        cache_batch_stride);
+}
+extern "C" int chipmunk_csp_mlp_mm1_w8_gm(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias,
+                                          void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int act,
+                                          int update_cache, int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_w8_entry(a, b, scale_b, scale_n, c, bias, pa_cache, indices, counts, M, K, F, BM, act, update_cache, (hipStream_t)stream, B,
+                        cache_batch_stride, true);
+}
 
 extern "C" int chipmunk_csp_mlp_mm1_glu_fp8(const void *a, const void *b_gate, const void *b_up, void *c, const void *bias_gate,
                                             const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts,

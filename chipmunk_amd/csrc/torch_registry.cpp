@@ -680,6 +680,38 @@ void csp_mlp_mm1_fp8_act_rs(at::Tensor a, at::Tensor b, at::Tensor c, const c10:
     mm1_act_impl("csp_mlp_mm1_fp8_act_rs", a, b, c, bias, pa_cache, indices, counts, &scale_a, &scale_b, act, (int)update_cache, true);
 }
 
+// addition: csp_mlp_mm1_act over an e4m3 weight with bf16 activations (weight-only fp8, chipmunk_csp_mlp_mm1_w8): scale_b is the weight's
+// float32 reciprocal scale -- one element, or [F] with one per row of b --, c = bf16(act((a f(b)^T) * scale_b + bias) - cache)
+void csp_mlp_mm1_w8(at::Tensor a, at::Tensor b, at::Tensor scale_b, at::Tensor c, const c10::optional<at::Tensor> &bias, at::Tensor pa_cache,
+                    at::Tensor indices, at::Tensor counts, std::string act, bool update_cache) {
+    const char *who = "csp_mlp_mm1_w8";
+    CHECK_DEV(a); CHECK_DEV(b); CHECK_DEV(scale_b); CHECK_DEV(c); CHECK_DEV(pa_cache); CHECK_DEV(indices); CHECK_DEV(counts);
+    CHECK_BF16(a);
+    TORCH_CHECK(b.scalar_type() == at::kFloat8_e4m3fn, who, ": b must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+    CHECK_BF16(c); CHECK_BF16(pa_cache);
+    CHECK_I32(indices); CHECK_I32(counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(b); CHECK_CONTIG(c); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
+    const Mm1Shape sh = mm1_shape(a, b, c, nullptr, pa_cache, indices, counts, true);
+    TORCH_CHECK(scale_b.scalar_type() == at::kFloat && scale_b.is_contiguous() && scale_b.device() == a.device() &&
+                    (scale_b.numel() == 1 || (scale_b.dim() == 1 && scale_b.size(0) == sh.F)),
+                who, ": scale_b must be a contiguous float32 tensor on the device of a with one element, or [F] with one reciprocal scale per row of b");
+    const void *bp = optional_bias(bias, "bias", sh.F);
+    const int code = act_code(who, act);
+    c10::DeviceGuard guard(a.device());
+    int *ip = indices.data_ptr<int>(), *cp = counts.data_ptr<int>();
+    const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc, sn = (int)scale_b.numel(), upd = update_cache ? 1 : 0;
+    const float *sp = scale_b.data_ptr<float>();
+    if (sh.gm)
+        check(chipmunk_csp_mlp_mm1_w8_gm(a.data_ptr(), b.data_ptr(), sp, sn, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, M, K, F, code, upd,
+                                         (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_w8_batched(a.data_ptr(), b.data_ptr(), sp, sn, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, M, K, F, ldc,
+                                              code, upd, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else
+        check(chipmunk_csp_mlp_mm1_w8(a.data_ptr(), b.data_ptr(), sp, sn, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, M, K, F, ldc, code,
+                                      upd, cur_stream(a)), who);
+}
+
 int64_t check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, const at::Tensor &inds,
                            const at::Tensor &counts, int64_t *cache_bs) {   // returns the cache pitch; *cache_bs: the cache's batch stride
     // reference csrc/indexed_io/scatter_add.cu:111-142 (B is hard-wired to 1, :58-59,138)
@@ -1511,6 +1543,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_glu(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_fp8(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b_gate, Tensor scale_b_up, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
+    m.def("csp_mlp_mm1_w8(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_fp8_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, Tensor scale_a, Tensor scale_b, str act, int update_cache) -> ()");
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
     m.def("topk_indices_p(Tensor activation, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
@@ -1589,6 +1622,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_glu", &csp_mlp_mm1_glu);
     m.impl("csp_mlp_mm1_glu_fp8", &csp_mlp_mm1_glu_fp8);
     m.impl("csp_mlp_mm1_act", &csp_mlp_mm1_act);
+    m.impl("csp_mlp_mm1_w8", &csp_mlp_mm1_w8);
     m.impl("csp_mlp_mm1_fp8_act", &csp_mlp_mm1_fp8_act);
     m.impl("topk_delta_indices", &topk_delta_indices);
     m.impl("topk_indices_p", &topk_indices_p);

@@ -12,6 +12,10 @@ one dynamic scale per token (``fc1.quantize_input_rowwise``) and hands GEMM1 the
 
 ``fc2`` is bf16, or -- with ``mlp.fp8_fc2`` on -- an ``F8Linear`` with e4m3 weights: dense and full steps call its forward as it is
 (``torch._scaled_mm``), the sparse steps gather e4m3 rows of ``fc2.weight^T`` (``csp_mlp_mm2_w8``) with ``fc2.scale_reciprocal``.
+
+A weight-only ``fc1`` (``W8Linear``, ``mlp.fp8_weight_only``: e4m3 weight, power-of-two scales, bf16 activations) keeps ``x`` in bf16: dense and
+full steps and the block-mean probe call its forward (the bf16 linear layer over the widened weight), the sparse steps gather e4m3 rows of
+``fc1.weight`` (``csp_mlp_mm1_w8``) with ``fc1.scale_reciprocal``.  A ``W8Linear`` ``fc2`` (per tensor) is taken under ``mlp.fp8_fc2`` like an ``F8Linear``.
 """
 from __future__ import annotations
 
@@ -102,7 +106,8 @@ _F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 
 def check_fc2(who: str, fc2: torch.nn.Module) -> None:
     """An fp8 ``fc2`` is taken with ``mlp.fp8_fc2`` on, as an ``F8Linear`` with e4m3 weights: the sparse steps' GEMM2 then gathers e4m3
-    rows of ``fc2.weight^T`` and multiplies its sums by ``fc2.scale_reciprocal``.  Everything else raises at construction."""
+    rows of ``fc2.weight^T`` and multiplies its sums by ``fc2.scale_reciprocal``.  A ``W8Linear`` (weight-only, per tensor) carries the
+    same attributes and is taken the same way.  Everything else raises at construction."""
     if fc2.weight.dtype not in _F8:
         return
     if not amd_key("mlp", "fp8_fc2"):
@@ -273,8 +278,10 @@ class SparseDiffMlp:
         # (the [F, N] view of the pitched cache, or the group-major cache whole: the stored tensor's rank decides, not the config key)
         sparse_act_T = activation_cache_view(self.storage.get_sparse_act_T(), x.shape[1], batched)
 
-        scale_a = scale_b = None
-        if fc1.weight.dtype == torch.float8_e4m3fn and getattr(fc1, "scaling", "tensor") == "row":
+        scale_a = scale_b = fc1_scale = None
+        if getattr(fc1, "weight_only", False):                  # W8Linear: x stays bf16, GEMM1 gathers e4m3 rows of fc1.weight
+            fc1_scale = fc1.scale_reciprocal                    # one number, or one per fc1 column: [F]
+        elif fc1.weight.dtype == torch.float8_e4m3fn and getattr(fc1, "scaling", "tensor") == "row":
             x, scale_a = fc1.quantize_input_rowwise(x)          # one reciprocal scale per token: [B, N]
             scale_a = scale_a if batched else scale_a[0]
             scale_b = fc1.scale_reciprocal.view(-1)             # one per fc1 column: [F]
@@ -285,7 +292,7 @@ class SparseDiffMlp:
         ops.mlp(x=x if batched else x[0], fc1w=fc1.weight.data, fc1b=None if fc1.bias is None else fc1.bias.data,
                 fc2w_T=self.fc2w_T[0], indices=indices, counts=counts, sparse_act_T=sparse_act_T, cached_out=out_cache,
                 num_sms_scatter_add=self.num_sms_scatter_add, mm1_scale_a=scale_a, mm1_scale_b=scale_b, fc2_scale=fc2_scale_of(fc2),
-                act=self.act_code)
+                act=self.act_code, **({} if fc1_scale is None else {"fc1_scale": fc1_scale}))
 
         # the operators updated the LOADED activation cache in place.  When it lives in host memory (offloading on, not kept resident) the
         # host copy has to follow, or the next step's load brings back the cache of the last full step and that step's deltas are taken

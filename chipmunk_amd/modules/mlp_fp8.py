@@ -260,6 +260,70 @@ class F8Linear(nn.Module):
         return f8
 
 
+def pow2_scale_reciprocal(amax: torch.Tensor, max_val: float = 448.0) -> torch.Tensor:
+    """The smallest power of two ``2^e`` with ``amax / 2^e <= max_val``, fp32, elementwise (``amax == 0`` gives 1).  ``amax`` and
+    ``max_val * 2^e`` are compared as they are, so the choice does not depend on how a logarithm rounds."""
+    amax = amax.float()
+    _, e = torch.frexp(amax / max_val)                      # amax / max_val = m * 2^e with m in [0.5, 1), up to one rounding
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    for _ in range(2):                                      # the rounding of the quotient can leave e one off, either way
+        e = torch.where(amax > torch.ldexp(torch.full_like(amax, max_val), e), e + 1, e)
+        e = torch.where((amax > 0) & (amax <= torch.ldexp(torch.full_like(amax, max_val), e - 1)), e - 1, e)
+    return torch.ldexp(torch.ones_like(amax), e)
+
+
+class W8Linear(nn.Module):
+    """Weight-only fp8 linear layer (``mlp.fp8_weight_only``; not in the reference): ``weight`` ``[out, in]`` ``float8_e4m3fn``,
+    ``scale_reciprocal`` fp32 -- ``[]`` (``scaling="tensor"``) or ``[out]`` (``scaling="row"``: one per output feature) --, an optional bias,
+    bf16 activations.  The scales are POWERS OF TWO (``pow2_scale_reciprocal``), so ``weight.to(bf16) * scale_reciprocal`` is exact in bf16:
+    the layer IS the bf16 linear layer over that widened weight, and ``forward`` computes it as such -- widening on every call, so that
+    the weight costs one byte per element; no widened copy is kept.  As ``fc1`` of a ``SparseDiffMlp`` its sparse steps gather the e4m3
+    rows themselves (``csp_mlp_mm1_w8``); as ``fc2`` under ``mlp.fp8_fc2`` (per tensor only) GEMM2 does (``csp_mlp_mm2_w8``)."""
+    weight_only = True
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=torch.bfloat16,
+                 scaling: str = "tensor") -> None:
+        super().__init__()
+        if scaling not in SCALINGS:
+            raise ValueError(f"W8Linear: unknown scaling {scaling!r} (one of {', '.join(SCALINGS)})")
+        self.scaling = scaling
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = nn.Parameter(torch.zeros((out_features, in_features), dtype=torch.float8_e4m3fn, device=device), requires_grad=False)
+        self.register_buffer("scale_reciprocal", torch.ones((out_features,) if scaling == "row" else (), dtype=torch.float32, device=device))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_features, dtype=dtype, device=device), requires_grad=False)
+        else:
+            self.register_parameter("bias", None)
+
+    @property
+    def scale(self) -> torch.Tensor:
+        return self.scale_reciprocal.reciprocal()
+
+    def widened(self) -> torch.Tensor:
+        """``weight.to(bf16) * scale_reciprocal``: exact (every e4m3 value is a bf16 value, the scale a power of two).  A new tensor per call."""
+        s = self.scale_reciprocal.to(torch.bfloat16)
+        return self.weight.to(torch.bfloat16) * (s.unsqueeze(1) if s.dim() == 1 else s)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        w = self.widened()
+        return torch.nn.functional.linear(x, w if x.dtype == w.dtype else w.to(x.dtype), self.bias)
+
+    @classmethod
+    def from_linear(cls, linear: nn.Linear, scaling: str = "tensor") -> "W8Linear":
+        w = linear.weight.data
+        q = cls(linear.in_features, linear.out_features, bias=linear.bias is not None, device=w.device,
+                dtype=w.dtype if linear.bias is None else linear.bias.dtype, scaling=scaling)
+        wf = w.float()
+        amax = wf.abs().amax(dim=1) if scaling == "row" else wf.abs().amax()
+        recip = pow2_scale_reciprocal(amax, torch.finfo(torch.float8_e4m3fn).max)
+        scaled = wf / (recip.unsqueeze(1) if scaling == "row" else recip)      # a division by a power of two: exact
+        q.weight = nn.Parameter(scaled.to(torch.float8_e4m3fn), requires_grad=False)
+        q.scale_reciprocal = recip
+        if linear.bias is not None:
+            q.bias = nn.Parameter(linear.bias.data, requires_grad=False)
+        return q
+
+
 @torch.inference_mode()
 def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
                            input_float8_dtype=torch.float8_e4m3fn, parent_name: Optional[str] = None,
@@ -270,12 +334,18 @@ def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
     image MLP (child ``"2"`` of an ``nn.Sequential`` named ``img_mlp``) while ``mlp.is_enabled``: the sparse step's
     GEMM2 gathers bf16 rows of ``fc2.weight.T``.  With ``mlp.fp8_fc2`` on (and e4m3 weights asked for) that ``fc2`` is swapped too:
     the sparse step's GEMM2 then gathers e4m3 rows (``csp_mlp_mm2_w8``).  ``scaling`` (default: the config key ``mlp.fp8_scaling``) is the
-    layers' scale granularity; that ``fc2`` of a sparse image MLP is built per tensor whatever it says (GEMM2's gather takes one scale)."""
+    layers' scale granularity; that ``fc2`` of a sparse image MLP is built per tensor whatever it says (GEMM2's gather takes one scale).
+    With ``mlp.fp8_weight_only`` on, every layer that would become an ``F8Linear`` becomes a ``W8Linear`` instead (e4m3 weights with
+    power-of-two scales, bf16 activations; ``input_float8_dtype`` is then not used): same exclusions, same rule for that ``fc2``."""
     from ..util.config import GLOBAL_CONFIG
     if scaling is None:
         scaling = amd_key("mlp", "fp8_scaling")
     if scaling not in SCALINGS:
         raise ValueError(f"recursive_swap_linears: mlp.fp8_scaling must be one of {', '.join(SCALINGS)} (got {scaling!r})")
+    # mlp.fp8_weight_only: W8Linear in F8Linear's place -- same exclusions, same rule for fc2 of a sparse image MLP
+    weight_only = bool(amd_key("mlp", "fp8_weight_only"))
+    if weight_only and float8_dtype != torch.float8_e4m3fn:
+        raise ValueError(f"recursive_swap_linears: mlp.fp8_weight_only builds float8_e4m3fn weights only (got float8_dtype {float8_dtype})")
     for name, child in list(model.named_children()):
         if name in ignore_keys or "mod" in name:
             continue
@@ -285,6 +355,9 @@ def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
             print("skipping fc2 of sparse img mlp")
             continue
         if isinstance(child, nn.Linear) and not isinstance(child, F8Linear):
+            if weight_only:      # e4m3 weights with power-of-two scales, bf16 activations
+                setattr(model, name, W8Linear.from_linear(child, scaling="tensor" if sparse_fc2 else scaling))
+                continue
             setattr(model, name, F8Linear.from_linear(child, float8_dtype, input_float8_dtype,
                                                       scaling="tensor" if sparse_fc2 else scaling))
         else:

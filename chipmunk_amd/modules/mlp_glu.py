@@ -69,6 +69,9 @@ class SparseDiffGatedMlp:
                              f"{tuple(up[0].shape)})")
         if fc2.weight.shape[1] != gate[0].shape[0]:
             raise ValueError(f"SparseDiffGatedMlp: fc2 takes {fc2.weight.shape[1]} features, the projections give {gate[0].shape[0]}")
+        if any(getattr(p, "weight_only", False) for p in projs):
+            raise ValueError("SparseDiffGatedMlp: a W8Linear projection (weight-only fp8, mlp.fp8_weight_only) is refused: only the ungated "
+                             "GEMM1 has a weight-only form (csp_mlp_mm1_w8); keep the gate and up projections in bf16, or build them as F8Linear")
         f8 = [p.weight.dtype in _F8 for p in projs]
         if any(f8) != all(f8):
             raise ValueError("SparseDiffGatedMlp: a mixed pair -- one projection is fp8, the other is not; the gated GEMM1 takes both "

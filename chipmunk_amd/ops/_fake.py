@@ -289,5 +289,18 @@ def _register():
                      lambda: "shape mismatch (mma_b must be [F, N2], mma_c [M, N2], or [B, M, N2] with the batch size of mma_a)")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm1_w8")
+    def _(a, b, scale_b, c, bias, pa_cache, indices, counts, act, update_cache):
+        # as csp_mlp_mm1_act, with an e4m3 b and its float32 reciprocal scale: one element, or [F]
+        torch._check(a.dtype == torch.bfloat16 and b.dtype == torch.float8_e4m3fn, lambda: "a must be bfloat16 and b float8_e4m3fn")
+        torch._check(c.dtype == torch.bfloat16 and pa_cache.dtype == torch.bfloat16, lambda: "c and pa_cache must be bfloat16")
+        torch._check(a.ndim in (2, 3) and b.ndim == 2 and a.shape[-1] == b.shape[1], lambda: "a and b must share the K dimension")
+        torch._check(c.shape == a.shape[:-1] + (b.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        torch._check(bias is None or bias.numel() == b.shape[0], lambda: "bias must have F entries")
+        torch._check(scale_b.dtype == torch.float32 and (scale_b.numel() == 1 or scale_b.shape == (b.shape[0],)),
+                     lambda: "scale_b must be float32 with one element, or [F]")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_w8: unknown activation '{act}'")
+        return None
+
 
 _register()

@@ -67,9 +67,50 @@ def scatter_add_gm(packed: torch.Tensor, unpacked_groups: torch.Tensor, indices:
     torch.ops.chipmunk.csp_scatter_add_gm(packed, unpacked_groups, indices, counts)
 
 
+def _check_fc1_scale(who: str, x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, scale_a, scale_b,
+                     names=("scale_a", "scale_b")) -> None:
+    """The rules of ``fc1_scale`` (weight-only fp8 ``fc1``): an e4m3 ``fc1w``, a bf16 ``x``, no activation / weight scale pair, and one
+    number or one per row of ``fc1w``.  Every violation raises ``ValueError`` and names the argument."""
+    if fc1w.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"{who}: fc1_scale is the reciprocal scale of a float8_e4m3fn fc1w (weight-only fp8); fc1w is {fc1w.dtype}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{who}: with fc1_scale (weight-only fp8) x must be bfloat16 (got {x.dtype}): the activations are not quantised")
+    for name, t in zip(names, (scale_a, scale_b)):
+        if t is not None:
+            raise ValueError(f"{who}: {name} must be None with fc1_scale: a weight-only fc1 has no activation scale, and its weight scale "
+                             "is fc1_scale")
+    if fc1_scale.numel() != 1 and tuple(fc1_scale.shape) != (fc1w.shape[0],):
+        raise ValueError(f"{who}: fc1_scale must hold one number, or one per row of fc1w ({fc1w.shape[0]},); got {tuple(fc1_scale.shape)}")
+
+
+def _positional_act(fc1_scale, act):
+    """``fc1_scale`` sits in front of ``act``, which stays the last parameter of ``mm1`` / ``mm1_scatter`` / ``run_e2e``: a caller that
+    passed the activation's name by position still means the activation."""
+    return (None, fc1_scale) if isinstance(fc1_scale, str) else (fc1_scale, act)
+
+
+def mm1_w8(x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
+           sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, act: str = "gelu_tanh", update_cache: bool = False) -> None:
+    """Weight-only fp8 GEMM1: ``packed = bf16(act((x f(fc1w)^T) * fc1_scale + fc1b) - cache)`` on the kept columns with bf16 ``x``, e4m3
+    ``fc1w`` ``[F, K]`` and ``fc1_scale`` its RECIPROCAL scale (``W8Linear.scale_reciprocal``: one number, or ``[F]``); ``update_cache``
+    also applies the scatter-add of the packed deltas to ``sparse_act_T``.  Every cache layout and batch form of ``csp_mlp_mm1_act``."""
+    if act not in GLU_ACTS:
+        raise ValueError(f"mm1_w8: unknown activation {act!r} (one of {', '.join(GLU_ACTS)})")
+    _check_fc1_scale("mm1_w8", x, fc1w, fc1_scale, None, None)
+    assert sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
+    scale = fc1_scale.float().reshape(1) if fc1_scale.numel() == 1 else fc1_scale.float().contiguous()
+    torch.ops.chipmunk.csp_mlp_mm1_w8(x, fc1w.contiguous(), scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act,
+                                      bool(update_cache))
+
+
 def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
         sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
-        scale_a: Optional[torch.Tensor] = None, scale_b: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
+        scale_a: Optional[torch.Tensor] = None, scale_b: Optional[torch.Tensor] = None, fc1_scale: Optional[torch.Tensor] = None,
+        act: str = "gelu_tanh") -> None:
+    fc1_scale, act = _positional_act(fc1_scale, act)
+    if fc1_scale is not None:      # weight-only fp8 fc1: bf16 x, e4m3 fc1w (csp_mlp_mm1_w8); the cache is left to the scatter-add
+        _check_fc1_scale("mm1", x, fc1w, fc1_scale, scale_a, scale_b)
+        return mm1_w8(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache=False)
     # (the reference asserts x is bf16 even on its fp8 branch, one of the reasons that branch cannot run as shipped)
     assert x.dtype == (torch.float8_e4m3fn if fc1w.dtype == torch.float8_e4m3fn else torch.bfloat16)
     assert sparse_act_packed.dtype == torch.bfloat16
@@ -90,8 +131,14 @@ def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc
 
 
 def mm1_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
-                sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, act: str = "gelu_tanh") -> None:
-    """GEMM1 + ``csp_scatter_add`` of its output into ``sparse_act_T`` in one kernel (bf16 only)."""
+                sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, fc1_scale: Optional[torch.Tensor] = None,
+                act: str = "gelu_tanh") -> None:
+    """GEMM1 + ``csp_scatter_add`` of its output into ``sparse_act_T`` in one kernel (bf16, or -- with ``fc1_scale`` -- a weight-only
+    e4m3 ``fc1w`` under a bf16 ``x``)."""
+    fc1_scale, act = _positional_act(fc1_scale, act)
+    if fc1_scale is not None:
+        _check_fc1_scale("mm1_scatter", x, fc1w, fc1_scale, None, None)
+        return mm1_w8(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache=True)
     assert x.dtype == torch.bfloat16 and sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
     if _default_form("mm1_scatter", act, fc1b) and not group_major(x, sparse_act_T):
         torch.ops.chipmunk.csp_mlp_mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
@@ -229,7 +276,9 @@ def _after_gemm1(cache_updated: bool, sparse_act_packed: torch.Tensor, fc2w_T: t
 def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], fc2w_T: torch.Tensor, indices: torch.Tensor,
             counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
             mm1_scale_a: Optional[torch.Tensor] = None, mm1_scale_b: Optional[torch.Tensor] = None,
-            fc2_scale: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
+            fc2_scale: Optional[torch.Tensor] = None, fc1_scale: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
+    # fc1_scale (W8Linear.scale_reciprocal; the sibling of fc2_scale): fc1w is e4m3 under a bf16 x, weight-only -- GEMM1 is csp_mlp_mm1_w8, with
+    # its own scatter-add or (mlp.fused_scatter off) the scatter-add behind it; mm1_scale_a / mm1_scale_b must then be None.
     # sparse_act_T of one dimension more than x ([G, F, 128] / [B, G, F, 128]) is the group-major cache: see group_major.  Otherwise:
     # M is any positive row count (ceil(M / 128) groups, the last one short); sparse_act_T is [F, M], contiguous or -- required when
     # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers.
@@ -241,6 +290,7 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
     # per fc1 column (csp_mlp_mm1_fp8_act_rs in GEMM1's place); a mixed pair raises.
     # act (one of GLU_ACTS) names fc1's activation and fc1b may be None: anything but tanh-GELU with a bias takes csp_mlp_mm1_act /
     # csp_mlp_mm1_fp8_act in GEMM1's place, everything behind GEMM1 is unchanged.
+    fc1_scale, act = _positional_act(fc1_scale, act)
     _check_batch(x, indices, counts, sparse_act_T, cached_out)
     M, K1 = x.shape[-2:]
     K2, K1_ = fc1w.shape
@@ -249,6 +299,11 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
     assert K2 == K2_, "K2 must match"
     sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)  # bf16 also when x is fp8
     tail = (sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
+    if fc1_scale is not None:
+        _check_fc1_scale("run_e2e", x, fc1w, fc1_scale, mm1_scale_a, mm1_scale_b, ("mm1_scale_a", "mm1_scale_b"))
+        fused = bool(x.is_cuda and amd_key("mlp", "fused_scatter"))
+        (mm1_scatter if fused else mm1)(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act=act, fc1_scale=fc1_scale)
+        return _after_gemm1(fused, *tail)
     if (x.is_cuda and fc1w.dtype == torch.bfloat16
             and amd_key("mlp", "fused_scatter")):
         mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act)
@@ -335,5 +390,5 @@ def run_e2e_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b
                    x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
 
 
-__all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
+__all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_w8", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
            "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8"]

@@ -122,6 +122,11 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # F8Linear fc2 with e4m3 weights -- the sparse steps' GEMM2 then gathers e4m3 rows of fc2.weight^T (csp_mlp_mm2_w8: 1 byte per weight
     # in HBM and through the gather instead of 2 + 2).  Off by default: fc2 stays bf16, as in the reference.
     "mlp.fp8_fc2": False,
+    # weight-only fp8 (not in the reference): recursive_swap_linears / quantize_fp8 build W8Linear where they build F8Linear -- e4m3 weights
+    # with power-of-two scales, bf16 activations, no activation quantisation.  A W8Linear fc1 runs its sparse steps through csp_mlp_mm1_w8
+    # (GEMM1 gathers e4m3 rows of fc1.weight: half the bytes of the bf16 gather); fc2 of a sparse image MLP follows the mlp.fp8_fc2 rule.
+    # Off by default: nothing changes.
+    "mlp.fp8_weight_only": False,
     # mask step with a key count per (batch, head, 192-query group) (not in the reference; should_compress_indices only): a sparse group keeps
     # the smallest top set of keys that carries this share of its column-sum mass (the group's summed softmax probabilities), never more
     # than the top_keys count -- a head whose mass sits on few keys stores and gathers fewer.  0.0 = off: exactly top_keys keys per group.
@@ -165,6 +170,7 @@ BASE_CONFIG["attn"]["keep_unpacked_indices_offloaded"] = AMD_EXTRA_KEYS["attn.ke
 BASE_CONFIG["attn"]["kept_indices_offloaded_budget_gb"] = AMD_EXTRA_KEYS["attn.kept_indices_offloaded_budget_gb"]
 BASE_CONFIG["attn"]["ragged_mask_to_indices"] = AMD_EXTRA_KEYS["attn.ragged_mask_to_indices"]
 BASE_CONFIG["mlp"]["fp8_fc2"] = AMD_EXTRA_KEYS["mlp.fp8_fc2"]
+BASE_CONFIG["mlp"]["fp8_weight_only"] = AMD_EXTRA_KEYS["mlp.fp8_weight_only"]
 BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
 BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]

@@ -342,6 +342,24 @@ int chipmunk_csp_mlp_mm2_w8(const void *mma_a, const void *mma_b, const float *s
 int chipmunk_csp_mlp_mm2_w8_batched(const void *mma_a, const void *mma_b, const float *scale_b, void *mma_c, const int32_t *indices,
                                     const int32_t *counts, int M, int F, int N2, int B, void *stream);
 
+/* fp8 fc1, weight-only: chipmunk_csp_mlp_mm1_act[_batched|_gm] over an e4m3 weight with bf16 activations (no reference counterpart).
+ * a [M,K] bf16; b [F,K] OCP e4m3 bytes (float8_e4m3fn), plain row-major; scale_b fp32 on the device, the weight's RECIPROCAL
+ * quantisation scale: one number (scale_n == 1) or one per row of b (scale_n == F, read at the GATHERED column i = idx[g,j]):
+ *   c[m,j] = bf16( act( (sum_k a[m,k] * f(b[i,k])) * scale_b[i] + bias[i] ) - pa_cache[i, m] )
+ * f widens e4m3 to bf16 (exact); the sum is chipmunk_csp_mlp_mm1_act's, in fp32 from zero, on the widened weight; the scale and then the
+ * bias are applied in fp32, each rounded (no fma); act and the subtraction are one rounding.  With a power-of-two scale and no bias the
+ * result has the bits of chipmunk_csp_mlp_mm1_act on bf16(f(b) * scale_b).  bias is bf16 [F] or NULL (= zero); update_cache 0 leaves
+ * the cache, 1 also applies the scatter-add of c.  Contract of chipmunk_csp_mlp_mm1_act and its *_batched / *_gm forms: any M >= 1,
+ * ldc >= M, ldc % 8 == 0, F % 64 == 0, K % 64 == 0, F*K, M*K and F*ldc below 2^31.  A null a / b / scale_b / c / pa_cache, a scale_n
+ * other than 1 or F, a scale_b off 4-byte alignment, a K off its multiple, an update_cache outside 0 / 1 or an unknown act returns
+ * CHIPMUNK_ERR_INVALID with a message, before anything is enqueued.  No element of scale_b at or past scale_n is read. */
+int chipmunk_csp_mlp_mm1_w8(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias, void *pa_cache,
+                            const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache,
+                            void *stream);
+int chipmunk_csp_mlp_mm1_w8_batched(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias,
+                                    void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
+                                    int update_cache, int B, int64_t cache_batch_stride, void *stream);
+
 /* Group-major cache: the activation cache of one sequence as [G, F, 128] bf16, contiguous, G = ceil(M / 128) -- element (g, i, r) is
  * activation column i of token row g * 128 + r -- instead of the column-major [F, ldc] (no reference counterpart).  The 256-byte pieces of
  * a group's kept columns then lie on a 256-byte grid inside one F * 256-byte window.  Rows of the last group at or past M are never
@@ -367,6 +385,9 @@ int chipmunk_csp_mlp_mm1_glu_fp8_gm(const void *a, const void *b_gate, const voi
                                     const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts,
                                     const float *scale_a, const float *scale_b_gate, const float *scale_b_up, int M, int K, int F,
                                     int act, int update_cache, int B, int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_w8_gm(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias, void *pa_cache,
+                               const int32_t *indices, const int32_t *counts, int M, int K, int F, int act, int update_cache, int B,
+                               int64_t cache_batch_stride, void *stream);
 /* chipmunk_csp_scatter_add_batched on the group-major cache: unpacked_groups[b][g, idx[b,g,j], r] += packed[b, g * 128 + r, j] */
 int chipmunk_csp_scatter_add_gm(const void *packed, void *unpacked_groups, const int32_t *indices, const int32_t *counts, int M,
                                 int F, int B, int64_t cache_batch_stride, void *stream);

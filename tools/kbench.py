@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -297,6 +297,68 @@ def bench_mm2_w8(M=4352, F=12288, N2=3072, keep=3840):
     print(f"mm2_w8  e4m3 rows: {med['w8']:8.1f} us  [{min(t['w8']):.1f} .. {max(t['w8']):.1f}]  {flops/med['w8']/1e6:7.1f} TFLOP/s   {tag}")
     print(f"mm2     bf16 rows: {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]  {flops/med['bf16']/1e6:7.1f} TFLOP/s")
     print(f"mm2_w8 / mm2     : {med['w8'] / med['bf16']:8.3f}")
+
+
+def bench_mm1_w8(M=4352, K=3072, F=12288, keep=3840):
+    """The weight-only fp8 GEMM1 with its scatter-add (csp_mlp_mm1_w8: e4m3 rows of fc1, bf16 activations) against the bf16
+    csp_mlp_mm1_scatter (`mm1s`) on the same activations, index lists and shape.  Same process, the two alternating (KB_ROUNDS pairs,
+    default 5); per launch the median bracket of `timeit` (20 launches, clocks warmed), then the median and the range over the rounds.
+    KB_LAYERS=n rotates n sets of weights / caches / outputs (n = 8: the weight rows come from HBM).  KB_W8_SCALES=row: one scale per fc1
+    row instead of one number.  Also times the selecting step's block-mean probe fc1(block_mean(x)) through W8Linear.forward (the whole
+    weight widened per call) against the bf16 nn.Linear."""
+    from chipmunk_amd.modules import W8Linear
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    rows = os.environ.get("KB_W8_SCALES", "tensor") == "row"
+    G = (M + 127) // 128
+    ldc = (M + 7) // 8 * 8
+    sets = []
+    for _ in range(L):
+        w = torch.randn(F, K, device=dev, generator=g) * 0.02
+        w8 = (w * 512).clamp(-448, 448).to(torch.float8_e4m3fn)
+        x = torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g) * 0.5
+        bias = torch.randn(F, device=dev, dtype=torch.bfloat16, generator=g) * 0.1
+        cache = torch.zeros(F, ldc, device=dev, dtype=torch.bfloat16)[:, :M]
+        sets.append((w.to(torch.bfloat16), w8, x, bias, cache, torch.empty(M, F, device=dev, dtype=torch.bfloat16)))
+    sb = torch.full((F,) if rows else (1,), 1 / 512.0, device=dev)
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_w8():
+        _, w8, x, bias, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_w8(x, w8, sb, out, bias, cache, inds, counts, "gelu_tanh", True)
+
+    def run_bf16():
+        w16, _, x, bias, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_scatter(x, w16, out, bias, cache, inds, counts)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {"w8": [], "bf16": []}
+    for _ in range(rounds):
+        t["w8"].append(timeit(run_w8) * 1e3)
+        t["bf16"].append(timeit(run_bf16) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * K * keep
+    tag = f"(M={M} K={K} F={F} keep={keep} layers={L} scales={'row' if rows else 'tensor'}, {rounds} alternating rounds)"
+    print(f"mm1_w8  e4m3 rows: {med['w8']:8.1f} us  [{min(t['w8']):.1f} .. {max(t['w8']):.1f}]  {flops/med['w8']/1e6:7.1f} TFLOP/s   {tag}")
+    print(f"mm1s    bf16 rows: {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]  {flops/med['bf16']/1e6:7.1f} TFLOP/s")
+    print(f"mm1_w8 / mm1s    : {med['w8'] / med['bf16']:8.3f}")
+    # the block-mean probe of a selecting step: [G, K] rows through fc1
+    lin = torch.nn.Linear(K, F, device=dev, dtype=torch.bfloat16)
+    q = W8Linear.from_linear(lin, scaling="row" if rows else "tensor")
+    xm = torch.randn(1, G, K, device=dev, dtype=torch.bfloat16, generator=g)
+    tp = {"w8": [], "bf16": []}
+    with torch.no_grad():
+        for _ in range(rounds):
+            tp["w8"].append(timeit(lambda: q(xm)) * 1e3)
+            tp["bf16"].append(timeit(lambda: lin(xm)) * 1e3)
+    mp = {k: sorted(v)[len(v) // 2] for k, v in tp.items()}
+    print(f"probe fc1(block_mean(x)) [{G} x {K}] -> {F}: W8Linear {mp['w8']:8.1f} us  [{min(tp['w8']):.1f} .. {max(tp['w8']):.1f}]   "
+          f"nn.Linear {mp['bf16']:8.1f} us  [{min(tp['bf16']):.1f} .. {max(tp['bf16']):.1f}]   ratio {mp['w8'] / mp['bf16']:.2f}")
 
 
 def bench_fp8_wan(M=32768, ldc=None):
@@ -633,6 +695,10 @@ def main():
             bench_mm1_glu_fp8(act=os.environ.get("KB_GLU_ACT", "silu"))
         elif w == "mm2_w8":           # weight-only fp8 GEMM2 against the bf16 GEMM2 at the FLUX shape, 30 % of 12 288 columns kept
             bench_mm2_w8()
+        elif w == "mm1_w8":           # weight-only fp8 GEMM1 (+ scatter-add) against mm1s at the FLUX shape, 3 840 of 12 288 columns kept
+            bench_mm1_w8()
+        elif w == "mm1_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), K = 1 536, F = 8 960, 2 816 kept
+            bench_mm1_w8(M=32760, K=1536, F=8960, keep=2816)
         elif w == "mm2_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), N2 = 1 536, F = 8 960, 2 816 kept
             bench_mm2_w8(M=32760, F=8960, N2=1536, keep=2816)
         elif w == "fp8_wan":
