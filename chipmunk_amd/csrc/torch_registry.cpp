@@ -712,6 +712,30 @@ void csp_mlp_mm1_w8(at::Tensor a, at::Tensor b, at::Tensor scale_b, at::Tensor c
                                       upd, cur_stream(a)), who);
 }
 
+// addition: the weight-only fp8 linear layer for few rows (chipmunk_w8_linear): y = bf16(bf16((x f(w)^T) * scale_b) + bias), x [M, K] bf16 with
+// contiguous rows (any row pitch), w [F, K] e4m3, scale_b float32 with one element or [F], y [M, F] bf16 (any row pitch), written in place
+void w8_linear(at::Tensor x, at::Tensor w, at::Tensor scale_b, const c10::optional<at::Tensor> &bias, at::Tensor y) {
+    const char *who = "w8_linear";
+    CHECK_DEV(x); CHECK_DEV(w); CHECK_DEV(scale_b); CHECK_DEV(y);
+    CHECK_BF16(x); CHECK_BF16(y);
+    TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn, who, ": w must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+    CHECK_CONTIG(w);
+    TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2 && x.size(1) == w.size(1) && y.size(0) == x.size(0) && y.size(1) == w.size(0),
+                who, ": x must be [M, K], w [F, K] and y [M, F]");
+    TORCH_CHECK(x.size(0) >= 1 && x.stride(1) == 1 && y.stride(1) == 1, who, ": x and y need at least one row and contiguous rows");
+    TORCH_CHECK(w.device() == x.device() && y.device() == x.device(), who, ": w and y must be on the device of x");
+    const int64_t M = x.size(0), K = x.size(1), F = w.size(0);
+    TORCH_CHECK(M <= CHIPMUNK_W8_LINEAR_MAX_M && K < (int64_t(1) << 31) && F < (int64_t(1) << 31), who, ": M, K or F too large");
+    TORCH_CHECK(scale_b.scalar_type() == at::kFloat && scale_b.is_contiguous() && scale_b.device() == x.device() &&
+                    (scale_b.numel() == 1 || (scale_b.dim() == 1 && scale_b.size(0) == F)),
+                who, ": scale_b must be a contiguous float32 tensor on the device of x with one element, or [F] with one reciprocal scale per row of w");
+    const void *bp = optional_bias(bias, "bias", F);
+    c10::DeviceGuard guard(x.device());
+    const int64_t ldx = M > 1 ? x.stride(0) : K, ldy = M > 1 ? y.stride(0) : F;
+    check(chipmunk_w8_linear(x.data_ptr(), ldx, w.data_ptr(), scale_b.data_ptr<float>(), (int)scale_b.numel(), bp, y.data_ptr(), ldy, (int)M,
+                             (int)K, (int)F, cur_stream(x)), who);
+}
+
 int64_t check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, const at::Tensor &inds,
                            const at::Tensor &counts, int64_t *cache_bs) {   // returns the cache pitch; *cache_bs: the cache's batch stride
     // reference csrc/indexed_io/scatter_add.cu:111-142 (B is hard-wired to 1, :58-59,138)
@@ -1544,6 +1568,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_glu_fp8(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b_gate, Tensor scale_b_up, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_w8(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
+    m.def("w8_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
     m.def("csp_mlp_mm1_fp8_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, Tensor scale_a, Tensor scale_b, str act, int update_cache) -> ()");
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
     m.def("topk_indices_p(Tensor activation, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
@@ -1623,6 +1648,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_glu_fp8", &csp_mlp_mm1_glu_fp8);
     m.impl("csp_mlp_mm1_act", &csp_mlp_mm1_act);
     m.impl("csp_mlp_mm1_w8", &csp_mlp_mm1_w8);
+    m.impl("w8_linear", &w8_linear);
     m.impl("csp_mlp_mm1_fp8_act", &csp_mlp_mm1_fp8_act);
     m.impl("topk_delta_indices", &topk_delta_indices);
     m.impl("topk_indices_p", &topk_indices_p);

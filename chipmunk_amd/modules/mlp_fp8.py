@@ -277,7 +277,8 @@ class W8Linear(nn.Module):
     ``scale_reciprocal`` fp32 -- ``[]`` (``scaling="tensor"``) or ``[out]`` (``scaling="row"``: one per output feature) --, an optional bias,
     bf16 activations.  The scales are POWERS OF TWO (``pow2_scale_reciprocal``), so ``weight.to(bf16) * scale_reciprocal`` is exact in bf16:
     the layer IS the bf16 linear layer over that widened weight, and ``forward`` computes it as such -- widening on every call, so that
-    the weight costs one byte per element; no widened copy is kept.  As ``fc1`` of a ``SparseDiffMlp`` its sparse steps gather the e4m3
+    the weight costs one byte per element; no widened copy is kept.  With ``mlp.w8_stream_rows`` > 0 a bf16 GPU input of at most that many
+    rows does not widen at all: ``ops.w8_linear`` streams the e4m3 weight once (``bf16(bf16(S * scale) + bias)``, fp32 sums).  As ``fc1`` of a ``SparseDiffMlp`` its sparse steps gather the e4m3
     rows themselves (``csp_mlp_mm1_w8``); as ``fc2`` under ``mlp.fp8_fc2`` (per tensor only) GEMM2 does (``csp_mlp_mm2_w8``)."""
     weight_only = True
 
@@ -305,6 +306,13 @@ class W8Linear(nn.Module):
         return self.weight.to(torch.bfloat16) * (s.unsqueeze(1) if s.dim() == 1 else s)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        # few rows (mlp.w8_stream_rows): the e4m3 weight streamed once through ops.w8_linear, nothing widened in memory
+        cap = int(amd_key("mlp", "w8_stream_rows"))
+        if (cap > 0 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() >= 1 and x.shape[-1] == self.in_features and x.stride(-1) == 1
+                and self.in_features % 64 == 0 and self.out_features % 8 == 0 and 0 < x.numel() // self.in_features <= cap
+                and (self.bias is None or self.bias.dtype == torch.bfloat16)):
+            from .. import ops
+            return ops.w8_linear(x, self.weight, self.scale_reciprocal, self.bias)
         w = self.widened()
         return torch.nn.functional.linear(x, w if x.dtype == w.dtype else w.to(x.dtype), self.bias)
 

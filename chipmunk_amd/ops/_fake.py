@@ -302,5 +302,17 @@ def _register():
         torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_w8: unknown activation '{act}'")
         return None
 
+    @lib.register_fake("chipmunk::w8_linear")
+    def _(x, w, scale_b, bias, y):
+        # writes y [M, F] in place and returns nothing
+        torch._check(x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and w.dtype == torch.float8_e4m3fn,
+                     lambda: "x and y must be bfloat16 and w float8_e4m3fn")
+        torch._check(x.ndim == 2 and w.ndim == 2 and x.shape[1] == w.shape[1] and y.shape == (x.shape[0], w.shape[0]),
+                     lambda: "x must be [M, K], w [F, K] and y [M, F]")
+        torch._check(bias is None or bias.numel() == w.shape[0], lambda: "bias must have F entries")
+        torch._check(scale_b.dtype == torch.float32 and (scale_b.numel() == 1 or scale_b.shape == (w.shape[0],)),
+                     lambda: "scale_b must be float32 with one element, or [F]")
+        return None
+
 
 _register()

@@ -127,6 +127,11 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # (GEMM1 gathers e4m3 rows of fc1.weight: half the bytes of the bf16 gather); fc2 of a sparse image MLP follows the mlp.fp8_fc2 rule.
     # Off by default: nothing changes.
     "mlp.fp8_weight_only": False,
+    # W8Linear.forward for few rows (not in the reference): a bf16 GPU input of at most this many rows (all leading dimensions flattened)
+    # runs ops.w8_linear -- the e4m3 weight is read once and widened in registers, with the scale and the bias in the epilogue -- instead
+    # of widening the whole weight to bf16 for F.linear; what SparseDiffMlp's block-mean probe fc1(block_mean(x)) needs on every selecting
+    # step.  More rows, other dtypes, in_features % 64 != 0 or out_features % 8 != 0 take the widened path.  0 = off: the widened path always.
+    "mlp.w8_stream_rows": 0,
     # mask step with a key count per (batch, head, 192-query group) (not in the reference; should_compress_indices only): a sparse group keeps
     # the smallest top set of keys that carries this share of its column-sum mass (the group's summed softmax probabilities), never more
     # than the top_keys count -- a head whose mass sits on few keys stores and gathers fewer.  0.0 = off: exactly top_keys keys per group.
@@ -171,6 +176,7 @@ BASE_CONFIG["attn"]["kept_indices_offloaded_budget_gb"] = AMD_EXTRA_KEYS["attn.k
 BASE_CONFIG["attn"]["ragged_mask_to_indices"] = AMD_EXTRA_KEYS["attn.ragged_mask_to_indices"]
 BASE_CONFIG["mlp"]["fp8_fc2"] = AMD_EXTRA_KEYS["mlp.fp8_fc2"]
 BASE_CONFIG["mlp"]["fp8_weight_only"] = AMD_EXTRA_KEYS["mlp.fp8_weight_only"]
+BASE_CONFIG["mlp"]["w8_stream_rows"] = AMD_EXTRA_KEYS["mlp.w8_stream_rows"]
 BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
 BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]

@@ -360,6 +360,25 @@ int chipmunk_csp_mlp_mm1_w8_batched(const void *a, const void *b, const float *s
                                     void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
                                     int update_cache, int B, int64_t cache_batch_stride, void *stream);
 
+/* Weight-only fp8 linear layer for few rows (W8Linear.forward under mlp.w8_stream_rows; no reference counterpart): the weight is read
+ * once as e4m3 and widened in registers, no widened copy exists.
+ *   x [M, K] bf16, rows ldx elements apart; w [F, K] OCP e4m3 bytes (float8_e4m3fn), plain row-major; scale_b fp32 on the device, the
+ *   weight's RECIPROCAL quantisation scale: one number (scale_n == 1) or one per row of w (scale_n == F); bias bf16 [F] or NULL;
+ *   y [M, F] bf16, rows ldy elements apart.
+ *   S[m,i] = sum_k x[m,k] * f(w[i,k])     f widens e4m3 to bf16 (exact); fp32, from zero, in an order that depends on K and F only
+ *   y[m,i] = bf16( bf16( S[m,i] * scale_b[i] ) + bias[i] )      the product and the sum each rounded, never an fma
+ *   y[m,i] = bf16( S[m,i] * scale_b[i] )                        without a bias
+ * Row independence: the bits of output row m depend on input row m, w, scale_b and bias and on nothing else -- not on M, not on the other
+ * rows, not on the row block row m falls in.  K is not split over workgroups, nothing is accumulated with atomics, two launches give
+ * the same bits.  Rows of x at and past M are never read; of y only [0, M) x [0, F) is written.
+ * Refused with CHIPMUNK_ERR_INVALID and a message, before anything is enqueued: a null x / w / scale_b / y; M < 1, K < 64, F < 8;
+ * K % 64 != 0 or F % 8 != 0; M > CHIPMUNK_W8_LINEAR_MAX_M (the grid carries 128 rows per block of its y dimension); a scale_n other than
+ * 1 or F; a scale_b off 4-byte alignment; x, w, y or bias off 16-byte alignment; ldx or ldy no multiple of 8 elements; ldx < K or
+ * ldy < F.  No element of scale_b at or past scale_n is read. */
+#define CHIPMUNK_W8_LINEAR_MAX_M (1 << 20)
+int chipmunk_w8_linear(const void *x, int64_t ldx, const void *w, const float *scale_b, int scale_n, const void *bias, void *y,
+                       int64_t ldy, int M, int K, int F, void *stream);
+
 /* Group-major cache: the activation cache of one sequence as [G, F, 128] bf16, contiguous, G = ceil(M / 128) -- element (g, i, r) is
  * activation column i of token row g * 128 + r -- instead of the column-major [F, ldc] (no reference counterpart).  The 256-byte pieces of
  * a group's kept columns then lie on a 256-byte grid inside one F * 256-byte window.  Rows of the last group at or past M are never

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan w8_probe w8_probe_wan w8_probe_hunyuan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -361,6 +361,60 @@ def bench_mm1_w8(M=4352, K=3072, F=12288, keep=3840):
           f"nn.Linear {mp['bf16']:8.1f} us  [{min(tp['bf16']):.1f} .. {max(tp['bf16']):.1f}]   ratio {mp['w8'] / mp['bf16']:.2f}")
 
 
+def bench_w8_probe(M=34, K=3072, F=12288):
+    """The few-row weight-only forward (ops.w8_linear: the e4m3 weight streamed once, widened in registers) against W8Linear.forward with
+    mlp.w8_stream_rows off (the whole weight widened to bf16 per call, then F.linear) and the bf16 nn.Linear over the widened weight, on the
+    same rows: the block-mean probe fc1(block_mean(x)) of a selecting sparse step.  Same process, the three alternating (KB_ROUNDS rounds,
+    default 5); per launch the median bracket of `timeit`, then the median and the range over the rounds.  KB_LAYERS=n rotates n layers
+    (weights, inputs) per launch (n = 8 at the FLUX shape: 0.3 GB of e4m3 and 0.6 GB of bf16 weights, beyond the Infinity Cache: cold
+    weights); KB_W8_SCALES=row: one scale per output feature."""
+    from chipmunk_amd import ops
+    from chipmunk_amd.modules import W8Linear
+    from chipmunk_amd.util.config import GLOBAL_CONFIG
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    rows = os.environ.get("KB_W8_SCALES", "tensor") == "row"
+    sets = []
+    for _ in range(L):
+        lin = torch.nn.Linear(K, F, device=dev, dtype=torch.bfloat16)
+        q = W8Linear.from_linear(lin, scaling="row" if rows else "tensor")
+        with torch.no_grad():
+            lin.weight.copy_(q.widened())
+        sets.append((q, lin, torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g)))
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_kernel():
+        q, _, x = nxt()
+        ops.w8_linear(x, q.weight, q.scale_reciprocal, q.bias)
+
+    def run_widened():
+        q, _, x = nxt()
+        q(x)
+
+    def run_bf16():
+        _, lin, x = nxt()
+        lin(x)
+    GLOBAL_CONFIG["mlp"]["w8_stream_rows"] = 0
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {"kernel": [], "widened": [], "bf16": []}
+    with torch.no_grad():
+        for _ in range(rounds):
+            t["kernel"].append(timeit(run_kernel) * 1e3)
+            t["widened"].append(timeit(run_widened) * 1e3)
+            t["bf16"].append(timeit(run_bf16) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    tag = f"(M={M} K={K} F={F} layers={L} scales={'row' if rows else 'tensor'}, {rounds} alternating rounds)"
+    print(f"w8_probe  w8_linear kernel : {med['kernel']:8.1f} us  [{min(t['kernel']):.1f} .. {max(t['kernel']):.1f}]  "
+          f"{F * K / med['kernel'] / 1e6:6.2f} TB/s on the weight stream   {tag}")
+    print(f"w8_probe  W8Linear widened : {med['widened']:8.1f} us  [{min(t['widened']):.1f} .. {max(t['widened']):.1f}]")
+    print(f"w8_probe  bf16 nn.Linear   : {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]")
+    print(f"w8_probe  kernel / widened : {med['kernel'] / med['widened']:8.3f}    kernel / nn.Linear: {med['kernel'] / med['bf16']:8.3f}")
+
+
 def bench_fp8_wan(M=32768, ldc=None):
     """BASELINE config C5 (Wan2.1-1.3B, 832x480x81 -> 32 760 tokens padded to 32 768): fp8 e4m3 GEMM1, M = 32768, K = 1536,
     F = 8960, keep 0.3 (2688 columns); bf16 GEMM1 at the same shape beside it.  M = 32760: the ragged launch on the tokens as they are
@@ -699,6 +753,12 @@ def main():
             bench_mm1_w8()
         elif w == "mm1_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), K = 1 536, F = 8 960, 2 816 kept
             bench_mm1_w8(M=32760, K=1536, F=8960, keep=2816)
+        elif w == "w8_probe":         # few-row weight-only forward at the FLUX probe shape [34, 3072] -> 12288: kernel / widened W8Linear / nn.Linear
+            bench_w8_probe()
+        elif w == "w8_probe_wan":     # ... at the Wan2.1 1.3B probe shape [256, 1536] -> 8960
+            bench_w8_probe(M=256, K=1536, F=8960)
+        elif w == "w8_probe_hunyuan": # ... at the HunyuanVideo probe shape [931, 3072] -> 12288
+            bench_w8_probe(M=931, K=3072, F=12288)
         elif w == "mm2_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), N2 = 1 536, F = 8 960, 2 816 kept
             bench_mm2_w8(M=32760, F=8960, N2=1536, keep=2816)
         elif w == "fp8_wan":
