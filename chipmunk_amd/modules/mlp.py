@@ -1,4 +1,5 @@
-"""Sparse-delta MLP layer state machine (mirror of reference ``src/chipmunk/modules/mlp.py:11-123``).
+"""Sparse-delta MLP layer state machine (mirror of reference ``src/chipmunk/modules/mlp.py:11-123``): ``SparseDeltaMlp``, once, for
+``SparseDiffMlp`` below and for the gated ``SparseDiffGatedMlp`` of ``modules/mlp_glu.py``, with the column selection (``select_columns``).
 
 Full step: dense ``fc2(act(fc1(x)))``; cache the transposed activations (column-major ``[F, M]``), the output and the
 128-row block means of the fc1 output.  Sparse step: pick, per 128-row group, the fc1 columns whose block mean moved
@@ -152,12 +153,142 @@ def activation_code(activation: torch.nn.Module, who: str = "SparseDiffGatedMlp"
                      "nn.GELU(approximate='tanh') and nn.GELU() only")
 
 
-class SparseDiffMlp:
+def select_route(is_cuda: bool, contiguous: bool, R: int, fused_single: bool, fused_group: bool) -> str:
+    """How a sparse step selects its columns from ``R`` block-mean rows per 128-row group: ``"single"`` -- one kernel for
+    ``|pre - cache|`` -> top-k indices -> copy of the selected columns into the cache (``R == 1``, ``mlp.fused_topk_delta``) -- ``"group"`` --
+    the same over the ``R`` rows of a group (``R > 1``, ``mlp.fused_group_topk_delta``) -- or ``"chain"``, those steps as separate
+    operators.  The kernels take contiguous GPU tensors; everything else, every CPU tensor included, is the chain."""
+    if is_cuda and contiguous and (fused_single if R == 1 else fused_group):
+        return "single" if R == 1 else "group"
+    return "chain"
+
+
+def _topk(plain, with_top_p, operands: tuple, cfg, top_p: float, min_keys: float) -> None:
+    """``plain`` with the ``top_keys`` selection or, when ``mlp.top_p`` is set, its ``_p`` sibling with ``top_keys`` as the cap"""
+    if top_p > 0.0:
+        with_top_p(*operands, 1 - cfg["top_keys"], top_p, min_keys, cfg["counts_multiple_of"], cfg["random_keys"])
+    else:
+        plain(*operands, 1 - cfg["top_keys"], cfg["counts_multiple_of"], cfg["random_keys"])
+
+
+def select_columns(pre: torch.Tensor, cache: torch.Tensor, R: int, cfg, top_p: float, min_keys: float) -> tuple:
+    """(indices ``[B, G, F]``, counts ``[B, G]``) of the columns whose block means ``pre`` ``[B, rows, F]`` moved most against ``cache``,
+    summed over the ``R`` rows of each of the ``G = ceil(rows / R)`` groups; the listed columns of ``cache`` are refreshed in place.  A
+    ragged last group sums and refreshes the rows it has."""
+    b, rows, f = pre.shape
+    groups = (rows + R - 1) // R
+    route = select_route(pre.is_cuda, pre.is_contiguous(), R, amd_key("mlp", "fused_topk_delta"), amd_key("mlp", "fused_group_topk_delta"))
+    inds = torch.empty((b, groups, f), dtype=torch.int32, device=pre.device)
+    counts = torch.empty((b, groups), dtype=torch.int32, device=pre.device)
+    if route == "single":
+        _topk(torch.ops.chipmunk.topk_delta_indices, ops.topk_delta_indices_p, (pre, cache, inds, counts), cfg, top_p, min_keys)
+    elif route == "group":
+        _topk(ops.topk_group_delta_indices, ops.topk_group_delta_indices_p, (pre, cache, inds, counts, R), cfg, top_p, min_keys)
+    else:
+        mdiff = (pre - cache).abs()
+        if rows % R:   # ragged last group: it sums the blocks it has
+            mdiff = torch.nn.functional.pad(mdiff, (0, 0, 0, R - rows % R))
+        mdiff = mdiff.reshape(b, groups, R, f).sum(dim=2)
+        _topk(ops.topk_indices, ops.topk_indices_p, (mdiff, inds, counts), cfg, top_p, min_keys)
+        ops.copy_indices(pre, cache, inds, counts)       # rows [R g, R (g + 1)) take group g's list
+    return inds, counts
+
+
+def _host_copy_follows(holder) -> None:
+    """The LOADED tensor of ``holder`` was updated in place.  When it lives in host memory (offloading on, not kept resident) the host copy
+    has to follow, or the next load brings back the tensor of the last full step: the next selection is then made against stale block
+    means, the next deltas are taken against activations the output cache has long moved on from."""
+    if holder is not None and not holder.is_resident():
+        holder.offload_cur_value()
+
+
+class SparseDeltaMlp:
+    """The state machine of both sparse MLP layers: dense layers, full steps, sparse steps and the cached selection.  A layer is this
+    class plus what differs between ``fc2(act(fc1(x)))`` and the gated ``fc2(act(gate(x)) * up(x))``: ``_pre`` (the pre-activations of
+    ``x``, a tuple), ``_act`` (the activation they become), ``_layout`` (their block means as the selection and the cache take them, and
+    the rows ``R`` a 128-row group owns there), ``_sparse`` (the operator call of a sparse step) and ``_check_config``.  It reads
+    ``fc2`` (a one-element list), ``layer_counter`` and ``storage`` of the layer, and ``_who``, its name in messages."""
+    _who = ""
+
+    def _check_config(self, cfg) -> None:
+        """what the layer asserts of ``GLOBAL_CONFIG["mlp"]`` at every call with the method enabled (here: nothing)"""
+
+    def _dense(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fc2[0](self._act(*self._pre(x)))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        cfg = GLOBAL_CONFIG["mlp"]
+        if not cfg["is_enabled"]:
+            return self._dense(x)
+
+        top_p, min_keys = top_p_of(self._who, cfg)     # (0.0, 0.0) unless mlp.top_p is set: top_keys is then only the cap
+        do_full = self.layer_counter.should_do_full_mlp_step()
+        inference_step, layer, _submodule = self.layer_counter.increment()
+        assert x.ndim == 3 and x.shape[0] >= 1, "x must be (B, N, C)"
+        mbm = cfg["mbm"]
+        self._check_config(cfg)
+
+        if layer < cfg["first_n_dense_layers"]:
+            return self._dense(x)
+
+        n = x.shape[1]
+        if do_full:
+            pre = self._pre(x)
+            act = self._act(*pre)
+            out = self.fc2[0](act)
+            # the module owns the activation cache: [B, F, ld] with ld = ceil8(N) and zeroed padding, stored (and offloaded) whole; the
+            # operators get its [F, N] view ([B, F, N] for a batch).  ld == N for every N % 8 == 0: the contiguous cache of the reference.
+            # (mlp.cache_layout "group": [B, ceil(N/128), F, 128] instead, handed to the operators whole)
+            self.storage.set_sparse_act_T(activation_cache_of(self._who, act))
+            self.storage.set_out_cache(out)
+            self.storage.set_blockmean_mid_cache(self._layout([block_mean(p, mbm) for p in pre], n, cfg)[0])
+            return out
+
+        # the stored state (activation cache [B, F, ld], output cache [B, N, C], block means, indices [B, G, F], counts [B, G]) is per
+        # sequence: a sparse step continues the B sequences of the last full step and nothing else
+        stored = self.storage.get_out_cache()
+        if stored is None or stored.shape[0] != x.shape[0] or stored.shape[1] != n:
+            raise RuntimeError(
+                f"{self._who}: a sparse step got x of shape {tuple(x.shape)} but the state of the last full step is for "
+                f"{'no input at all' if stored is None else f'batch size {stored.shape[0]} with {stored.shape[1]} tokens'}: the batch size "
+                "and token count may only change on a full step")
+
+        reuse_mask = (inference_step % cfg["block_mask_cache"] != 0 and inference_step >= 10
+                      and self.storage.get_indices() is not None)
+        if not reuse_mask:
+            pre, R = self._layout(self._pre(block_mean(x, mbm)), n, cfg)
+            inds, counts = select_columns(pre, self.storage.get_blockmean_mid_cache(), R, cfg, top_p, min_keys)
+            _host_copy_follows(self.storage.blockmean_mid_cache)
+            self.storage.set_indices(inds)
+            self.storage.set_counts(counts)
+        else:
+            inds, counts = self.storage.get_indices(), self.storage.get_counts()
+
+        # (a step that made the selection uses it as it made it: read back through the storage, a selection that was just sent to the host
+        # -- offloading["mlp.indices"] -- is not what the getter shows, which is the pipeline slot as last loaded)
+        batched = x.shape[0] > 1     # B == 1 passes the 2-D operands it always passed
+        out_cache = stored if batched else stored[0]
+        # (the [F, N] view of the pitched cache, or the group-major cache whole: the stored tensor's rank decides, not the config key)
+        sparse_act_T = activation_cache_view(self.storage.get_sparse_act_T(), n, batched)
+        self._sparse(x, batched, inds if batched else inds[0], counts if batched else counts[0], sparse_act_T, out_cache)
+        _host_copy_follows(self.storage.sparse_act_T)
+
+        if not batched:
+            out_cache = out_cache.unsqueeze(0)
+        self.storage.set_out_cache(out_cache)
+        return out_cache
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+
+class SparseDiffMlp(SparseDeltaMlp):
     """``fc2(activation(fc1(x)))``.  The sparse steps recompute ``activation`` inside GEMM1, so it has to be one the kernel knows:
     ``nn.GELU(approximate="tanh")`` (the reference's), ``nn.GELU()`` (exact, erf) or ``nn.SiLU()``, subclasses included; for any other
     callable that computes one of the three, ``act`` names it (``"gelu_tanh"``, ``"gelu"``, ``"silu"``).  Everything else raises at
     construction: its sparse steps would subtract another function from the activation cache than the full steps put there.
     ``fc1`` may have no bias (``nn.Linear(..., bias=False)``, or an e4m3 ``F8Linear`` without one)."""
+    _who = "SparseDiffMlp"
 
     def __init__(self, layer_num: int, layer_counter: LayerCounter, fc1: torch.nn.Linear,
                  activation: torch.nn.Module, fc2: torch.nn.Linear, heuristic_sms_scatter_add: int = 6, act: Optional[str] = None):
@@ -180,104 +311,17 @@ class SparseDiffMlp:
         self.storage = MlpStorage(layer_num)
         self.num_sms_scatter_add = heuristic_sms_scatter_add
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _pre(self, x: torch.Tensor) -> tuple:
+        return (self.fc1[0](x),)
+
+    def _act(self, mid: torch.Tensor) -> torch.Tensor:
+        return self.activation(mid)
+
+    def _layout(self, means, n: int, cfg) -> tuple:
+        return means[0], cfg["bm"] // cfg["mbm"]
+
+    def _sparse(self, x, batched, indices, counts, sparse_act_T, out_cache) -> None:
         fc1, fc2 = self.fc1[0], self.fc2[0]
-        cfg = GLOBAL_CONFIG["mlp"]
-        if not cfg["is_enabled"]:
-            return fc2(self.activation(fc1(x)))
-
-        top_p, min_keys = top_p_of("SparseDiffMlp", cfg)     # (0.0, 0.0) unless mlp.top_p is set: top_keys is then only the cap
-        do_full = self.layer_counter.should_do_full_mlp_step()
-        inference_step, layer, _submodule = self.layer_counter.increment()
-        assert x.ndim == 3 and x.shape[0] >= 1, "x must be (B, N, C)"
-        mbm, bm = cfg["mbm"], cfg["bm"]
-
-        if layer < cfg["first_n_dense_layers"]:
-            return fc2(self.activation(fc1(x)))
-
-        if do_full:
-            mid = fc1(x)
-            act = self.activation(mid)
-            out = fc2(act)
-            # the module owns the activation cache: [B, F, ld] with ld = ceil8(N) and zeroed padding, stored (and offloaded) whole; the
-            # operators get its [F, N] view ([B, F, N] for a batch).  ld == N for every N % 8 == 0: the contiguous cache of the reference.
-            # (mlp.cache_layout "group": [B, ceil(N/128), F, 128] instead, handed to the operators whole)
-            self.storage.set_sparse_act_T(activation_cache_of("SparseDiffMlp", act))
-            self.storage.set_out_cache(out)
-            self.storage.set_blockmean_mid_cache(block_mean(mid, mbm))
-            return out
-
-        # the stored state (activation cache [B, F, ld], output cache [B, N, C], block means, indices [B, G, F], counts [B, G]) is per
-        # sequence: a sparse step continues the B sequences of the last full step and nothing else
-        stored = self.storage.get_out_cache()
-        if stored is None or stored.shape[0] != x.shape[0] or stored.shape[1] != x.shape[1]:
-            raise RuntimeError(
-                f"SparseDiffMlp: a sparse step got x of shape {tuple(x.shape)} but the state of the last full step is for "
-                f"{'no input at all' if stored is None else f'batch size {stored.shape[0]} with {stored.shape[1]} tokens'}: the batch size "
-                "and token count may only change on a full step")
-
-        reuse_mask = (inference_step % cfg["block_mask_cache"] != 0 and inference_step >= 10
-                      and self.storage.get_indices() is not None)
-        if not reuse_mask:
-            bmfc1 = fc1(block_mean(x, mbm))
-            r = bm // mbm
-            cache = self.storage.get_blockmean_mid_cache()
-            if r == 1 and bmfc1.is_cuda and amd_key("mlp", "fused_topk_delta") and bmfc1.is_contiguous():
-                # one kernel for |bmfc1 - cache| -> top-k indices -> copy of the selected columns into the cache
-                inds = torch.empty_like(bmfc1, dtype=torch.int32)
-                counts = torch.empty((bmfc1.size(0), bmfc1.size(1)), dtype=torch.int32, device=x.device)
-                if top_p > 0.0:
-                    ops.topk_delta_indices_p(bmfc1, cache, inds, counts, 1 - cfg["top_keys"], top_p, min_keys,
-                                             cfg["counts_multiple_of"], cfg["random_keys"])
-                else:
-                    torch.ops.chipmunk.topk_delta_indices(bmfc1, cache, inds, counts, 1 - cfg["top_keys"],
-                                                          cfg["counts_multiple_of"], cfg["random_keys"])
-            elif r > 1 and bmfc1.is_cuda and amd_key("mlp", "fused_group_topk_delta") and bmfc1.is_contiguous():
-                # the same over the r block-mean rows of a group (a ragged last group sums and refreshes the rows it has)
-                b, rows, f = bmfc1.shape
-                inds = torch.empty((b, (rows + r - 1) // r, f), dtype=torch.int32, device=x.device)
-                counts = torch.empty((b, (rows + r - 1) // r), dtype=torch.int32, device=x.device)
-                if top_p > 0.0:
-                    ops.topk_group_delta_indices_p(bmfc1, cache, inds, counts, r, 1 - cfg["top_keys"], top_p, min_keys,
-                                                   cfg["counts_multiple_of"], cfg["random_keys"])
-                else:
-                    ops.topk_group_delta_indices(bmfc1, cache, inds, counts, r, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
-                                                 cfg["random_keys"])
-            else:
-                mdiff = (bmfc1 - cache).abs()
-                b, rows, f = mdiff.shape
-                if rows % r:   # ragged last group: it sums the blocks it has
-                    mdiff = torch.nn.functional.pad(mdiff, (0, 0, 0, r - rows % r))
-                mdiff = mdiff.reshape(b, -1, r, f).sum(dim=2)
-                inds = torch.empty_like(mdiff, dtype=torch.int32, device=x.device)
-                counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=x.device)
-                if top_p > 0.0:
-                    ops.topk_indices_p(mdiff, inds, counts, 1 - cfg["top_keys"], top_p, min_keys, cfg["counts_multiple_of"],
-                                       cfg["random_keys"])
-                else:
-                    ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
-                                     cfg["random_keys"])
-                ops.copy_indices(bmfc1, cache, inds, counts)
-            # the selected columns of the block means were refreshed in the LOADED tensor; a host copy has to follow (as for the activation
-            # cache below), or the next selection is made against the block means of the last full step
-            holder = self.storage.blockmean_mid_cache
-            if holder is not None and not holder.is_resident():
-                holder.offload_cur_value()
-            self.storage.set_indices(inds)
-            self.storage.set_counts(counts)
-
-        else:
-            inds, counts = self.storage.get_indices(), self.storage.get_counts()
-
-        # (a step that made the selection uses it as it made it: read back through the storage, a selection that was just sent to the host
-        # -- offloading["mlp.indices"] -- is not what the getter shows, which is the pipeline slot as last loaded)
-        batched = x.shape[0] > 1     # B == 1 passes the 2-D operands it always passed
-        indices = inds if batched else inds[0]
-        counts = counts if batched else counts[0]
-        out_cache = stored if batched else stored[0]
-        # (the [F, N] view of the pitched cache, or the group-major cache whole: the stored tensor's rank decides, not the config key)
-        sparse_act_T = activation_cache_view(self.storage.get_sparse_act_T(), x.shape[1], batched)
-
         scale_a = scale_b = fc1_scale = None
         if getattr(fc1, "weight_only", False):                  # W8Linear: x stays bf16, GEMM1 gathers e4m3 rows of fc1.weight
             fc1_scale = fc1.scale_reciprocal                    # one number, or one per fc1 column: [F]
@@ -293,18 +337,3 @@ class SparseDiffMlp:
                 fc2w_T=self.fc2w_T[0], indices=indices, counts=counts, sparse_act_T=sparse_act_T, cached_out=out_cache,
                 num_sms_scatter_add=self.num_sms_scatter_add, mm1_scale_a=scale_a, mm1_scale_b=scale_b, fc2_scale=fc2_scale_of(fc2),
                 act=self.act_code, **({} if fc1_scale is None else {"fc1_scale": fc1_scale}))
-
-        # the operators updated the LOADED activation cache in place.  When it lives in host memory (offloading on, not kept resident) the
-        # host copy has to follow, or the next step's load brings back the cache of the last full step and that step's deltas are taken
-        # against activations the output cache has long moved on from
-        holder = self.storage.sparse_act_T
-        if holder is not None and not holder.is_resident():
-            holder.offload_cur_value()
-
-        if not batched:
-            out_cache = out_cache.unsqueeze(0)
-        self.storage.set_out_cache(out_cache)
-        return out_cache
-
-    def __call__(self, *args, **kwargs):
-        return self.forward(*args, **kwargs)

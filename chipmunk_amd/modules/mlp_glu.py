@@ -1,12 +1,12 @@
-"""Sparse-delta state machine for gated feed-forwards, ``fc2(act(gate_proj(x)) * up_proj(x))`` (SwiGLU / GEGLU; no reference counterpart:
-the reference's ``SparseDiffMlp`` knows ``fc2(act(fc1(x)))`` only).
+"""Sparse-delta layer for gated feed-forwards, ``fc2(act(gate_proj(x)) * up_proj(x))`` (SwiGLU / GEGLU; no reference counterpart: the
+reference's ``SparseDiffMlp`` knows ``fc2(act(fc1(x)))`` only).  The state machine is ``SparseDeltaMlp`` of ``modules/mlp.py``; this file
+holds what the gated layer adds to it.
 
 The method carries over unchanged: a hidden column ``j`` is recomputed or kept as a whole, its activation-cache entry is the gated product,
 and GEMM2 and the scatter-add see the same packed deltas as in ``SparseDiffMlp``.  Only GEMM1 differs (``csp_mlp_mm1_glu``: two gathered
 weight rows per kept column) and the movement of a column is the movement of its two inputs: the block means of BOTH pre-activations are
 cached as one ``[B, 2 Gm, F]`` tensor (rows ``2i`` / ``2i + 1`` = gate / up means of block ``i``) and the score of a column in a group is
-the sum of ``|delta block mean|`` over the group's rows of that tensor -- the ``r > 1`` branch of ``SparseDiffMlp`` with ``r = 2 bm / mbm``.
-State, storage (``MlpStorage``), schedule and offload handling are those of ``SparseDiffMlp``.
+the sum of ``|delta block mean|`` over the group's rows of that tensor -- ``select_columns`` with ``R = 2 bm / mbm`` rows per group.
 
 fp8 projections (``F8Linear``: two layers, or one fused ``[2F, K]`` layer) take ``csp_mlp_mm1_glu_fp8`` on the sparse steps: ``x`` is quantised
 ONCE, with the gate projection's (or the fused projection's) ``quantize_input``, and the kernel multiplies both sums by that layer's
@@ -21,12 +21,9 @@ from typing import Optional, Tuple
 import torch
 
 from .. import ops
-from ..util.config import GLOBAL_CONFIG, amd_key
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
-from .mlp import activation_cache_of, activation_cache_view, activation_code, block_mean, check_fc2, fc2_scale_of, top_p_of
-
-_F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
+from .mlp import _F8, SparseDeltaMlp, activation_code, check_fc2, fc2_scale_of
 
 
 def _params(lin: torch.nn.Linear, rows: Optional[slice] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -35,13 +32,14 @@ def _params(lin: torch.nn.Linear, rows: Optional[slice] = None) -> Tuple[torch.T
     return (w, b) if rows is None else (w[rows], None if b is None else b[rows])
 
 
-class SparseDiffGatedMlp:
+class SparseDiffGatedMlp(SparseDeltaMlp):
     """``gate_proj`` / ``up_proj`` / ``fc2``: ``nn.Linear`` with or without bias, bf16 for the sparse steps; or ``gate_proj`` / ``up_proj``
     (or the fused ``fc1``) BOTH ``F8Linear`` with e4m3 weights and e4m3 inputs (``input_float8_dtype=torch.float8_e4m3fn``;
     ``F8Linear.from_linear`` defaults to e5m2, which the kernel does not read).  ``fc2`` is bf16 (GEMM2 gathers bf16 rows) or, with
     ``mlp.fp8_fc2`` on, an ``F8Linear`` with e4m3 weights (GEMM2 gathers e4m3 rows, ``fc2.scale_reciprocal`` on its sums).
     Their parameters are read at every call, so the model may be moved or cast after wrapping.  The sparse steps select columns with
     ``topk_indices``, which takes rows of 1024 columns or more: the hidden width ``F`` must be at least 1024."""
+    _who = "SparseDiffGatedMlp"
 
     def __init__(self, layer_num: int, layer_counter: LayerCounter, gate_proj: torch.nn.Linear, up_proj: torch.nn.Linear,
                  activation: torch.nn.Module, fc2: torch.nn.Linear, heuristic_sms_scatter_add: int = 6):
@@ -126,10 +124,6 @@ class SparseDiffGatedMlp:
             return (first, second) if self.gate_first else (second, first)
         return torch.nn.functional.linear(x, *self.gate), torch.nn.functional.linear(x, *self.up)
 
-    def _dense(self, x: torch.Tensor) -> torch.Tensor:
-        g, u = self._pre(x)
-        return self.fc2[0](self.activation(g) * u)
-
     @staticmethod
     def _paired_block_means(g: torch.Tensor, u: torch.Tensor, rows: int) -> torch.Tensor:
         """[B, Gm, F] gate and up block means -> [B, 2 * rows, F], rows 2i / 2i + 1 = gate / up of block i (zero rows behind the Gm blocks
@@ -139,87 +133,18 @@ class SparseDiffGatedMlp:
             pair = torch.nn.functional.pad(pair, (0, 0, 0, 0, 0, rows - pair.shape[1]))
         return pair.reshape(pair.shape[0], 2 * rows, pair.shape[-1]).contiguous()
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        cfg = GLOBAL_CONFIG["mlp"]
-        if not cfg["is_enabled"]:
-            return self._dense(x)
+    def _act(self, g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+        return self.activation(g) * u
 
-        top_p, min_keys = top_p_of("SparseDiffGatedMlp", cfg)     # (0.0, 0.0) unless mlp.top_p is set: top_keys is then only the cap
-        do_full = self.layer_counter.should_do_full_mlp_step()
-        inference_step, layer, _submodule = self.layer_counter.increment()
-        assert x.ndim == 3 and x.shape[0] >= 1, "x must be (B, N, C)"
-        mbm, bm = cfg["mbm"], cfg["bm"]
-        assert bm % mbm == 0, "mlp.bm must be a multiple of mlp.mbm"
+    def _check_config(self, cfg) -> None:
+        assert cfg["bm"] % cfg["mbm"] == 0, "mlp.bm must be a multiple of mlp.mbm"
 
-        if layer < cfg["first_n_dense_layers"]:
-            return self._dense(x)
+    def _layout(self, means, n: int, cfg) -> Tuple[torch.Tensor, int]:
+        # a column's movement is the movement of its two inputs: |delta| summed over the group's 2 r rows (gate and up means)
+        bm, r = cfg["bm"], cfg["bm"] // cfg["mbm"]         # r: block means per 128-row group and branch
+        return self._paired_block_means(*means, (n + bm - 1) // bm * r), 2 * r
 
-        n = x.shape[1]
-        r = bm // mbm                              # block means per 128-row group and branch
-        bm_rows = (n + bm - 1) // bm * r           # ... over all groups (a ragged last group has zero rows for the blocks it lacks)
-        if do_full:
-            g, u = self._pre(x)
-            act = self.activation(g) * u
-            out = self.fc2[0](act)
-            # the module owns the activation cache: [B, F, ld] with ld = ceil8(N) and zeroed padding, or -- mlp.cache_layout "group" --
-            # [B, ceil(N/128), F, 128] (see SparseDiffMlp)
-            self.storage.set_sparse_act_T(activation_cache_of("SparseDiffGatedMlp", act))
-            self.storage.set_out_cache(out)
-            self.storage.set_blockmean_mid_cache(self._paired_block_means(block_mean(g, mbm), block_mean(u, mbm), bm_rows))
-            return out
-
-        stored = self.storage.get_out_cache()
-        if stored is None or stored.shape[0] != x.shape[0] or stored.shape[1] != x.shape[1]:
-            raise RuntimeError(
-                f"SparseDiffGatedMlp: a sparse step got x of shape {tuple(x.shape)} but the state of the last full step is for "
-                f"{'no input at all' if stored is None else f'batch size {stored.shape[0]} with {stored.shape[1]} tokens'}: the batch size "
-                "and token count may only change on a full step")
-
-        reuse_mask = (inference_step % cfg["block_mask_cache"] != 0 and inference_step >= 10
-                      and self.storage.get_indices() is not None)
-        if not reuse_mask:
-            bmx = block_mean(x, mbm)
-            bmpre = self._paired_block_means(*self._pre(bmx), bm_rows)
-            cache = self.storage.get_blockmean_mid_cache()
-            # a column's movement is the movement of its two inputs: |delta| summed over the group's 2 r rows (gate and up means)
-            if bmpre.is_cuda and amd_key("mlp", "fused_group_topk_delta"):
-                # one kernel for that sum -> top-k indices -> copy of the listed columns into the group's 2 r rows of the cache
-                b, rows, f = bmpre.shape
-                inds = torch.empty((b, rows // (2 * r), f), dtype=torch.int32, device=x.device)
-                counts = torch.empty((b, rows // (2 * r)), dtype=torch.int32, device=x.device)
-                if top_p > 0.0:
-                    ops.topk_group_delta_indices_p(bmpre, cache, inds, counts, 2 * r, 1 - cfg["top_keys"], top_p, min_keys,
-                                                   cfg["counts_multiple_of"], cfg["random_keys"])
-                else:
-                    ops.topk_group_delta_indices(bmpre, cache, inds, counts, 2 * r, 1 - cfg["top_keys"], cfg["counts_multiple_of"],
-                                                 cfg["random_keys"])
-            else:
-                mdiff = (bmpre - cache).abs()
-                b, _rows, f = mdiff.shape
-                mdiff = mdiff.reshape(b, -1, 2 * r, f).sum(dim=2)
-                inds = torch.empty_like(mdiff, dtype=torch.int32, device=x.device)
-                counts = torch.empty((mdiff.size(0), mdiff.size(1)), dtype=torch.int32, device=x.device)
-                if top_p > 0.0:
-                    ops.topk_indices_p(mdiff, inds, counts, 1 - cfg["top_keys"], top_p, min_keys, cfg["counts_multiple_of"],
-                                       cfg["random_keys"])
-                else:
-                    ops.topk_indices(mdiff, inds, counts, 1 - cfg["top_keys"], cfg["counts_multiple_of"], cfg["random_keys"])
-                ops.copy_indices(bmpre, cache, inds, counts)     # rows [2 r g, 2 r (g + 1)) take group g's list
-            # the selected columns of the block means were refreshed in the LOADED tensor; a host copy has to follow
-            holder = self.storage.blockmean_mid_cache
-            if holder is not None and not holder.is_resident():
-                holder.offload_cur_value()
-            self.storage.set_indices(inds)
-            self.storage.set_counts(counts)
-        else:
-            inds, counts = self.storage.get_indices(), self.storage.get_counts()
-
-        batched = x.shape[0] > 1     # B == 1 passes 2-D operands
-        indices = inds if batched else inds[0]
-        counts = counts if batched else counts[0]
-        out_cache = stored if batched else stored[0]
-        sparse_act_T = activation_cache_view(self.storage.get_sparse_act_T(), n, batched)   # by the stored tensor's rank
-
+    def _sparse(self, x, batched, indices, counts, sparse_act_T, out_cache) -> None:
         gate, up = self.gate, self.up
         if self.fp8:
             qgate, qup = self.projs[0], self.projs[-1]     # (the same layer twice for a fused projection)
@@ -233,16 +158,3 @@ class SparseDiffGatedMlp:
             ops.mlp_glu(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], b_gate=gate[1], b_up=up[1],
                         act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
                         cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add, fc2_scale=fc2_scale_of(self.fc2[0]))
-
-        # the operators updated the LOADED activation cache in place: its host copy has to follow (see SparseDiffMlp)
-        holder = self.storage.sparse_act_T
-        if holder is not None and not holder.is_resident():
-            holder.offload_cur_value()
-
-        if not batched:
-            out_cache = out_cache.unsqueeze(0)
-        self.storage.set_out_cache(out_cache)
-        return out_cache
-
-    def __call__(self, *args, **kwargs):
-        return self.forward(*args, **kwargs)
