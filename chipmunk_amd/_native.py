@@ -23,6 +23,7 @@ SYMBOLS = [
     "chipmunk_csp_mlp_mm1_act", "chipmunk_csp_mlp_mm1_act_batched", "chipmunk_csp_mlp_mm1_fp8_act", "chipmunk_csp_mlp_mm1_fp8_act_batched",
     "chipmunk_csp_mlp_mm2_w8", "chipmunk_csp_mlp_mm2_w8_batched",
     "chipmunk_csp_mlp_mm1_w8", "chipmunk_csp_mlp_mm1_w8_batched", "chipmunk_csp_mlp_mm1_w8_gm", "chipmunk_w8_linear",
+    "chipmunk_csp_mlp_mm1_glu_w8", "chipmunk_csp_mlp_mm1_glu_w8_batched", "chipmunk_csp_mlp_mm1_glu_w8_gm",
     "chipmunk_csp_mlp_mm1_fp8_act_rs", "chipmunk_csp_mlp_mm1_fp8_act_rs_batched", "chipmunk_quantize_fp8_rowwise",
     "chipmunk_csp_mlp_mm1_act_gm", "chipmunk_csp_mlp_mm1_fp8_act_gm", "chipmunk_csp_mlp_mm1_fp8_act_rs_gm", "chipmunk_csp_mlp_mm1_glu_gm",
     "chipmunk_csp_mlp_mm1_glu_fp8_gm", "chipmunk_csp_scatter_add_gm", "chipmunk_transpose16_groups",

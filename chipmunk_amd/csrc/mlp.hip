@@ -220,6 +220,12 @@ struct Mm1GluF8Params : Mm1Params {
 struct Mm1W8Params : Mm1Params {
     int scale_n;
 };
+// The gated weight-only form (mm1_glu_w8_kernel): b / b_up are the e4m3 gate / up weights [F, K] (b_up / bias_up in the union slots as in the
+// gated bf16 form: the shared block keeps its size), each with a reciprocal scale of its own -- one number (_n == 1) or one per row (_n == F).
+struct Mm1GluW8Params : Mm1Params {
+    const float *scale_gate, *scale_up;
+    int scale_gate_n, scale_up_n;
+};
 
 // One TM x TN output tile (TM rows of group g starting at m_off, packed columns n0 .. n0+TN-1): 4 waves as 2 x 2, each a
 // (TM/2) x (TN/2) accumulator of 32x32x16 MFMA tiles; NST-deep LDS ring of [A tile | B tile] stages.
@@ -257,11 +263,23 @@ struct Mm1W8Params : Mm1Params {
 // ends 8 bytes behind its KiB, so every PAIR of pieces (one 32-row fragment) owns 2 KiB + 16 bytes: an even piece at the pair's start, the odd
 // one 1 KiB + 8 behind it (a pair's start moves all its 32 rows by the same number of banks).  The sum starts from zero, is multiplied by the gathered column's reciprocal scale (p.scale_n == 1:
 // one number for all) and then biased, two roundings, never an fma; act and the subtraction are the bf16 form's, one rounding.
+// GLU && W8 (mm1_glu_w8_kernel; P = Mm1GluW8Params): the two composed.  The B tile is W8's: TN = 128 rows of BK = 64 bytes, KTile<32>, 16 rows per
+// DMA instruction, so instruction I of the tile's 8 covers tile rows [16 I, 16 I + 16) and wave w issues I = 2 w and 2 w + 1 -- the even and the
+// odd piece of PAIR w, tile rows [32 w, 32 w + 32).  The gated form assigns tile rows [64 wn + 32 half, +32) to the gate (half 0) or the up (half 1)
+// rows of packed columns n0 + 32 wn + (lane & 31); a pair's 32 rows start at a multiple of 32, so they lie inside one such range: pair w holds
+// half w & 1 of wave column wn = w >> 1, whole.  Both pieces of a pair therefore gather from ONE weight, (16 I >> 5) & 1 = w & 1 is wave-uniform
+// per instruction (here: per wave), and nothing of the LDS image moves: the row a lane reads for (wn, n4) is 64 wn + 32 n4 + (lane & 31) in the
+// gated and in the ungated form alike, pair (row >> 5), piece (row >> 4) & 1, so swizzle, 8-byte shift and the bank argument above hold
+// unchanged -- only the SOURCE of rows 32 .. 63 and 96 .. 127 differs.  k loop: W8's (sums from zero, k where the bf16 gated form puts it).
+// Epilogue: g = (sum_g * scale_gate[i]) + bias_gate[i], u = (sum_u * scale_up[i]) + bias_up[i], each a rounded multiply and a rounded add
+// (scale_then_bias2), then the gated form's fma(act(g), u, -cache), one rounding.  EPI = TM * 64 * 2 = 16 KiB fits a 24 640-byte stage: the plain
+// staged epilogue, cache block and output image in one stage each.
 template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params, bool NULLB = false,
           bool RS = false, bool W8 = false>
 __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
     static_assert(!RS || (FP8 && !GLU && NULLB), "row / column scale vectors: the ungated fp8 form with a nullable bias (mm1_form_kernel) only");
-    static_assert(!W8 || (!FP8 && !GLU && !RS && NULLB && NW == 4 && BK == 64), "the weight-only form: ungated, bf16 a, 4 waves, 64-byte B row pieces");
+    static_assert(!W8 || (!FP8 && !RS && (GLU || NULLB) && NW == 4 && BK == 64), "the weight-only form: bf16 a, 4 waves, 64-byte B row pieces");
+    static_assert(!(W8 && GLU) || std::is_base_of<Mm1GluW8Params, P>::value, "the gated weight-only form reads its scales from Mm1GluW8Params");
     using KT = KTile<BK>;
     using KTB = KTile<W8 ? BK / 2 : BK>;     // the B tile's geometry
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
@@ -275,7 +293,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     static_assert(A_INST >= 1 && B_INST >= 1, "tile too small for one DMA instruction per wave");
     constexpr int PW = GLU ? TN / 2 : TN;                           // packed columns of the tile
     constexpr int NP4 = GLU ? 1 : NT4;                              // 32-wide tiles of packed columns per wave
-    static_assert(!GLU || (NW == 4 && NT4 == 2 && 32 % KT::RPI == 0), "the gated form: 4 waves, a 64-row B slab per wave");
+    static_assert(!GLU || (NW == 4 && NT4 == 2 && 32 % KTB::RPI == 0), "the gated form: 4 waves, a 64-row B slab per wave");
     static_assert(!(FP8 && GLU) || std::is_base_of<Mm1GluF8Params, P>::value, "the gated fp8 form reads its scales from Mm1GluF8Params");
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -308,7 +326,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         for (int i = 0; i < A_INST; ++i) blds16(ra, aoff[i], kb * BK * 2, st + (w * A_INST + i) * 1024);
 #pragma unroll
         for (int i = 0; i < B_INST; ++i) {
-            if constexpr (GLU) {
+            if constexpr (GLU && W8) {   // pair (w * B_INST + i) >> 1 is wholly gate or wholly up (see above); W8's piece placement
+                const bool up = (((w * B_INST + i) * KTB::RPI) >> 5) & 1;
+                blds16(up ? rb_up : rb, boff[i], kb * BK, st + A_TILE + ((w * B_INST + i) >> 1) * B_PAIR + ((w * B_INST + i) & 1) * (1024 + 8));
+            } else if constexpr (GLU) {
                 const bool up = (((w * B_INST + i) * KT::RPI) >> 5) & 1;   // wave-uniform: the instruction's rows lie in one half
                 blds16(up ? rb_up : rb, boff[i], kb * BK * 2, st + A_TILE + (w * B_INST + i) * 1024);
             } else if constexpr (W8) {   // BK bytes of a row per k step; the odd pieces land 8 bytes up
@@ -373,6 +394,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         if constexpr (GLU) {   // n4 = 0: the gate's bias, 1: the up projection's; a null vector is zero
             const uint16_t *bp = n4 ? p.bias_up : p.bias;
             bias_v[n4] = bp ? bf16_bits_to_f32(bp[idxg[j < cnt ? j : n0]]) : 0.f;
+            if constexpr (W8) {   // the branch's reciprocal scale: one per weight row, gathered like the bias, or one number
+                const float *sp = n4 ? p.scale_up : p.scale_gate;
+                sb_col[n4] = sp[(n4 ? p.scale_up_n : p.scale_gate_n) > 1 ? idxg[j < cnt ? j : n0] : 0];
+            }
         } else if constexpr (NULLB) {
             bias_v[n4] = p.bias ? bf16_bits_to_f32(p.bias[idxg[j < cnt ? j : n0]]) : 0.f;
             if constexpr (RS) sb_col[n4] = p.scale_b[idxg[j < cnt ? j : n0]];
@@ -578,6 +603,12 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                             const uint32_t t23 = pack_bf16x2_v(glu_act2<ACT>((a23 * sav23) * sbv + bv));
                             d01 = pack_bf16x2_v(unpack_bf16x2(t01) - c01), d23 = pack_bf16x2_v(unpack_bf16x2(t23) - c23);
                             if constexpr (UPD == 2) n01 = t01, n23 = t23;   // 2: cache = new activation, what the reference's Triton kernel does (csp_mlp_mm1.py:140)
+                        } else if constexpr (GLU && W8) {
+                            // each branch: sum * scale, then + bias, two roundings each (scale_then_bias2); then the gated form's one rounding
+                            const f32x2 u01 = {acc[mt][1][q4 * 4 + 0], acc[mt][1][q4 * 4 + 1]}, u23 = {acc[mt][1][q4 * 4 + 2], acc[mt][1][q4 * 4 + 3]};
+                            const f32x2 sgv = {sb_col[0], sb_col[0]}, suv = {sb_col[1], sb_col[1]}, bgv = {bia, bia}, buv = {bias_v[1], bias_v[1]};
+                            d01 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>(scale_then_bias2(a01, sgv, bgv)), scale_then_bias2(u01, suv, buv), -c01));
+                            d23 = pack_bf16x2_v(__builtin_elementwise_fma(glu_act2<ACT>(scale_then_bias2(a23, sgv, bgv)), scale_then_bias2(u23, suv, buv), -c23));
                         } else if constexpr (GLU) {
                             // act(gate) * up - cache in fp32, one rounding (both biases are already in the sums); a01 / a23 are the gate's
                             const f32x2 u01 = {acc[mt][1][q4 * 4 + 0], acc[mt][1][q4 * 4 + 1]}, u23 = {acc[mt][1][q4 * 4 + 2], acc[mt][1][q4 * 4 + 3]};
@@ -849,6 +880,43 @@ __global__ __launch_bounds__(256, WPS) void mm1_w8_kernel(const typename std::co
             if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
             mm1_tile<64, 64, BK, SUB_NST, false, 4, false, ACT, P, true, false, true>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
         }
+        __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
+    }
+}
+
+// Gated weight-only e4m3 gate / up (mm1_tile's GLU && W8 form): c = bf16(fma(act(g), u, -cache[i, m])), g = (a . f(b[i, :])) * scale_gate[i] +
+// bias[i], u the same over b_up / scale_up / bias_up.  mm1_form_kernel's walk for a gated form -- a whole tile is BN / 2 packed columns, no tail
+// split, tiles past counts[g] skipped before the batch advance, the single sequence on the kernel's own block -- under a name of its own.
+struct Mm1GluW8Batch : Mm1GluW8Params {
+    int B;
+    int64_t cache_bs;   // as Mm1Batch
+};
+template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED>
+__global__ __launch_bounds__(256, WPS) void mm1_glu_w8_kernel(const typename std::conditional<BATCHED, Mm1GluW8Batch, Mm1GluW8Params>::type p) {
+    using P = Mm1GluW8Params;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int PBN = BN / 2;           // packed columns of a whole tile: the B tile's BN rows are {gate, up} pairs
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
+    const TilePlan pl = plan_tiles<PBN>(p.counts, G, p.NT, p.NR, 0, 1);   // (no tail split)
+    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+        const TileMap tm = tile_at(pl, slot);
+        if (!tm.live) continue;
+        const int cnt = p.counts[tm.g];
+        if (tm.nt * PBN >= cnt) continue;  // tiles past counts[g] are skipped
+        int g = tm.g;
+        typename std::conditional<BATCHED, P, const P &>::type q = p;   // the tile sees its sequence's operands (one sequence: the kernel's own block)
+        if constexpr (BATCHED) {
+            const int seq = tm.g / Gs;
+            g = tm.g - seq * Gs;                      // group inside sequence seq
+            q.a = p.a + (int64_t)seq * p.M * p.K;
+            q.c = p.c + (int64_t)seq * p.M * p.F;
+            q.cache = p.cache + (int64_t)seq * p.cache_bs;
+            q.indices = p.indices + (int64_t)seq * Gs * p.F;
+        }
+        mm1_tile<BM, BN, BK, NST, false, 4, true, ACT, P, false, false, true>(q, smem, g, 0, tm.nt * PBN, cnt);
         __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
     }
 }
@@ -2022,7 +2090,100 @@ int mm1_w8_entry(const void *a, const void *b, const float *scale_b, int scale_n
     return B > 0 ? launch_mm1_w8<true>(p, act, stream, B, cache_bs) : launch_mm1_w8<false>(p, act, stream, 1, 0);
 #endif
 }
+
+// Gated weight-only e4m3 gate / up: mm1_glu_w8_kernel at its one tile shape -- <128 B rows = 64 packed columns, k step 64, 3 stages, 2 workgroups
+// per CU> --, the grid as launch_mm1_variant sets it for the gated forms (no tail split)
+#ifndef CHIPMUNK_MM1_PROBES
+template <int ACT, bool BATCHED>
+int launch_mm1_glu_w8_kernel(Mm1GluW8Params p, hipStream_t s, int B, int64_t cache_bs) {
+    constexpr int BN = 128, BK = 64, NST = 3, WPS = 2;
+    constexpr int PBN = BN / 2;   // packed columns per whole tile
+    constexpr int LDS = NST * (BM * BK * 2 + BN * BK + BN / 32 * 16);
+    static_assert(LDS <= 80 * 1024, "two workgroups share a CU's 160 KiB");
+    static_assert(BM * PBN * 2 <= LDS / NST, "the staged epilogue: cache block and output image fit one stage each");
+    auto kern = mm1_glu_w8_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+    static uint64_t lds_set = 0;
+    ensure_dynamic_lds((const void *)kern, LDS, lds_set);
+    p.NT = (p.F + PBN - 1) / PBN;
+    const int nr_option = chipmunk_get_option("mm1_nr");   // column tiles per walk: launch_mm1_variant's
+    p.NR = nr_option > 0 ? nr_option : 4;
+    if (p.NR > p.NT) p.NR = p.NT;
+    p.slots_per_xcd = 0;   // (the gated form has no tail split)
+    const int resident_per_xcd = WPS * device_cu_count() / 8;
+    const int tiles_per_xcd = (B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8;
+    const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
+    if constexpr (BATCHED) {
+        Mm1GluW8Batch q;
+        static_cast<Mm1GluW8Params &>(q) = p;
+        q.B = B, q.cache_bs = cache_bs;
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(256), LDS, s, q);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(256), LDS, s, p);
+    }
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+template <bool BATCHED>
+int launch_mm1_glu_w8(const Mm1GluW8Params &p, int act, hipStream_t s, int B, int64_t cache_bs) {
+    switch (act) {
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_glu_w8_kernel<0, BATCHED>(p, s, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_glu_w8_kernel<1, BATCHED>(p, s, B, cache_bs);
+        default: return launch_mm1_glu_w8_kernel<2, BATCHED>(p, s, B, cache_bs);
+    }
+}
+#endif
+
+// B > 0: the *_batched entry; gm: the *_gm entry, as mm1_w8_entry
+int mm1_glu_w8_entry(const void *a, const void *b_gate, const void *b_up, const float *scale_gate, int scale_gate_n, const float *scale_up,
+                     int scale_up_n, void *c, const void *bias_gate, const void *bias_up, void *pa_cache, const int32_t *indices,
+                     const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, hipStream_t stream, int B = 0,
+                     int64_t cache_bs = 0, bool gm = false) {
+#ifdef CHIPMUNK_MM1_PROBES
+    CM_CHECK(false, "csp_mlp_mm1_glu_w8: not part of the probe-forms build");
+#else
+    CM_CHECK(a && b_gate && b_up && scale_gate && scale_up && c && pa_cache, "csp_mlp_mm1_glu_w8: null tensor or scale pointer");
+    CM_CHECK(scale_gate_n == 1 || scale_gate_n == F,
+             "csp_mlp_mm1_glu_w8: scale_gate_n must be 1 (one reciprocal scale) or F = %d (one per gate row), got %d", F, scale_gate_n);
+    CM_CHECK(scale_up_n == 1 || scale_up_n == F,
+             "csp_mlp_mm1_glu_w8: scale_up_n must be 1 (one reciprocal scale) or F = %d (one per up row), got %d", F, scale_up_n);
+    CM_CHECK((((uintptr_t)scale_gate | (uintptr_t)scale_up) & 3) == 0, "csp_mlp_mm1_glu_w8: scale_gate and scale_up must be 4-byte aligned");
+    if (int e = check_mm1("csp_mlp_mm1_glu_w8", true, indices, counts, M, K, F, ldc, B, cache_bs, 64, true, act, update_cache, 1, gm)) return e;
+    Mm1GluW8Params p;
+    static_cast<Mm1Params &>(p) = {(const uint16_t *)a, (const uint16_t *)b_gate, (const uint16_t *)bias_gate, (uint16_t *)pa_cache,
+                                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
+    p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
+    p.scale_gate = scale_gate, p.scale_up = scale_up, p.scale_gate_n = scale_gate_n, p.scale_up_n = scale_up_n;
+    if (gm) p.gs = F * BM, B = B == 1 ? 0 : B;
+    return B > 0 ? launch_mm1_glu_w8<true>(p, act, stream, B, cache_bs) : launch_mm1_glu_w8<false>(p, act, stream, 1, 0);
+#endif
+}
 }  // namespace
+
+// ---- gated weight-only e4m3 gate / up (include/chipmunk_hip.h, "gated fp8, weight-only")
+extern "C" int chipmunk_csp_mlp_mm1_glu_w8(const void *a, const void *b_gate, const void *b_up, const float *scale_gate, int scale_gate_n,
+                                           const float *scale_up, int scale_up_n, void *c, const void *bias_gate, const void *bias_up,
+                                           void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
+                                           int update_cache, void *stream) {
+    return mm1_glu_w8_entry(a, b_gate, b_up, scale_gate, scale_gate_n, scale_up, scale_up_n, c, bias_gate, bias_up, pa_cache, indices, counts, M,
+                            K, F, ldc, act, update_cache, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_glu_w8_batched(const void *a, const void *b_gate, const void *b_up, const float *scale_gate,
+                                                   int scale_gate_n, const float *scale_up, int scale_up_n, void *c, const void *bias_gate,
+                                                   const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M,
+                                                   int K, int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride,
+                                                   void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_glu_w8_entry(a, b_gate, b_up, scale_gate, scale_gate_n, scale_up, scale_up_n, c, bias_gate, bias_up, pa_cache, indices, counts, M,
+                            K, F, ldc, act, update_cache, (hipStream_t)stream, B, cache_batch_stride);
+}
+extern "C" int chipmunk_csp_mlp_mm1_glu_w8_gm(const void *a, const void *b_gate, const void *b_up, const float *scale_gate, int scale_gate_n,
+                                              const float *scale_up, int scale_up_n, void *c, const void *bias_gate, const void *bias_up,
+                                              void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int act,
+                                              int update_cache, int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_glu_w8_entry(a, b_gate, b_up, scale_gate, scale_gate_n, scale_up, scale_up_n, c, bias_gate, bias_up, pa_cache, indices, counts, M,
+                            K, F, BM, act, update_cache, (hipStream_t)stream, B, cache_batch_stride, true);
+}
 
 // ---- weight-only e4m3 fc1 (include/chipmunk_hip.h, "fp8 fc1, weight-only")
 extern "C" int chipmunk_csp_mlp_mm1_w8(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias,

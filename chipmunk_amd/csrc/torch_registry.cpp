@@ -712,6 +712,47 @@ void csp_mlp_mm1_w8(at::Tensor a, at::Tensor b, at::Tensor scale_b, at::Tensor c
                                       upd, cur_stream(a)), who);
 }
 
+// addition: csp_mlp_mm1_glu over e4m3 gate / up weights with bf16 activations (gated weight-only fp8, chipmunk_csp_mlp_mm1_glu_w8): scale_gate /
+// scale_up are the weights' float32 reciprocal scales -- one element, or [F] with one per row --,
+// c = bf16(fma(act((a f(b_gate)^T) * scale_gate + bias_gate), (a f(b_up)^T) * scale_up + bias_up, -cache))
+void csp_mlp_mm1_glu_w8(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor scale_gate, at::Tensor scale_up, at::Tensor c,
+                        const c10::optional<at::Tensor> &bias_gate, const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache,
+                        at::Tensor indices, at::Tensor counts, std::string act, bool update_cache) {
+    const char *who = "csp_mlp_mm1_glu_w8";
+    CHECK_DEV(a); CHECK_DEV(b_gate); CHECK_DEV(b_up); CHECK_DEV(scale_gate); CHECK_DEV(scale_up); CHECK_DEV(c); CHECK_DEV(pa_cache);
+    CHECK_DEV(indices); CHECK_DEV(counts);
+    CHECK_BF16(a);
+    TORCH_CHECK(b_gate.scalar_type() == at::kFloat8_e4m3fn && b_up.scalar_type() == at::kFloat8_e4m3fn, who,
+                ": b_gate and b_up must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+    CHECK_BF16(c); CHECK_BF16(pa_cache);
+    CHECK_I32(indices); CHECK_I32(counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(b_gate); CHECK_CONTIG(b_up); CHECK_CONTIG(c); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
+    const Mm1Shape sh = mm1_shape(a, b_gate, c, nullptr, pa_cache, indices, counts, true);
+    TORCH_CHECK(b_up.dim() == 2 && b_up.size(0) == sh.F && b_up.size(1) == sh.K, "b_up must have the shape of b_gate ([F, K])");
+    for (const at::Tensor *s : {&scale_gate, &scale_up})
+        TORCH_CHECK(s->scalar_type() == at::kFloat && s->is_contiguous() && s->device() == a.device() &&
+                        (s->numel() == 1 || (s->dim() == 1 && s->size(0) == sh.F)),
+                    who, ": scale_gate and scale_up must be contiguous float32 tensors on the device of a with one element, or [F] with one "
+                         "reciprocal scale per weight row");
+    const void *bg = optional_bias(bias_gate, "bias_gate", sh.F), *bu = optional_bias(bias_up, "bias_up", sh.F);
+    const int code = act_code(who, act);
+    c10::DeviceGuard guard(a.device());
+    int *ip = indices.data_ptr<int>(), *cp = counts.data_ptr<int>();
+    const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc, upd = update_cache ? 1 : 0;
+    const int gn = (int)scale_gate.numel(), un = (int)scale_up.numel();
+    const float *gp = scale_gate.data_ptr<float>(), *up = scale_up.data_ptr<float>();
+    if (sh.gm)
+        check(chipmunk_csp_mlp_mm1_glu_w8_gm(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), gp, gn, up, un, c.data_ptr(), bg, bu,
+                                             pa_cache.data_ptr(), ip, cp, M, K, F, code, upd, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_glu_w8_batched(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), gp, gn, up, un, c.data_ptr(), bg, bu,
+                                                  pa_cache.data_ptr(), ip, cp, M, K, F, ldc, code, upd, (int)sh.B, sh.cache_bs, cur_stream(a)),
+              who);
+    else
+        check(chipmunk_csp_mlp_mm1_glu_w8(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), gp, gn, up, un, c.data_ptr(), bg, bu,
+                                          pa_cache.data_ptr(), ip, cp, M, K, F, ldc, code, upd, cur_stream(a)), who);
+}
+
 // addition: the weight-only fp8 linear layer for few rows (chipmunk_w8_linear): y = bf16(bf16((x f(w)^T) * scale_b) + bias), x [M, K] bf16 with
 // contiguous rows (any row pitch), w [F, K] e4m3, scale_b float32 with one element or [F], y [M, F] bf16 (any row pitch), written in place
 void w8_linear(at::Tensor x, at::Tensor w, at::Tensor scale_b, const c10::optional<at::Tensor> &bias, at::Tensor y) {
@@ -1568,6 +1609,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_glu_fp8(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b_gate, Tensor scale_b_up, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_w8(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
+    m.def("csp_mlp_mm1_glu_w8(Tensor a, Tensor b_gate, Tensor b_up, Tensor scale_gate, Tensor scale_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("w8_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
     m.def("csp_mlp_mm1_fp8_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, Tensor scale_a, Tensor scale_b, str act, int update_cache) -> ()");
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
@@ -1648,6 +1690,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_glu_fp8", &csp_mlp_mm1_glu_fp8);
     m.impl("csp_mlp_mm1_act", &csp_mlp_mm1_act);
     m.impl("csp_mlp_mm1_w8", &csp_mlp_mm1_w8);
+    m.impl("csp_mlp_mm1_glu_w8", &csp_mlp_mm1_glu_w8);
     m.impl("w8_linear", &w8_linear);
     m.impl("csp_mlp_mm1_fp8_act", &csp_mlp_mm1_fp8_act);
     m.impl("topk_delta_indices", &topk_delta_indices);

@@ -13,6 +13,12 @@ ONCE, with the gate projection's (or the fused projection's) ``quantize_input``,
 ``input_scale_reciprocal`` and each by its own layer's ``scale_reciprocal``.  Dequantising with the gate's input scale is exact arithmetic for
 both products -- the e4m3 values ARE ``x * input_scale`` rounded, whichever weight they meet -- so the up layer's own input scale is used only
 by its dense forward (full steps, the block means of the selection), which is also what calibrates it.
+
+Weight-only fp8 projections (``W8Linear``: two layers, or one fused ``[2F, K]`` layer; per-tensor or per-row scales) are taken with
+``mlp.w8_gated`` on and run ``csp_mlp_mm1_glu_w8`` on the sparse steps: ``x`` stays bf16, GEMM1 gathers e4m3 rows of both weights and
+multiplies each branch's sum by its layer's ``scale_reciprocal`` (a fused layer's ``[2F]`` scale is split like its weight, a ``[]`` scale
+serves both halves).  Dense and full steps and the block-mean probe call the layers' own forward -- the bf16 linear layer over the widened
+weight, or ``ops.w8_linear`` for few rows under ``mlp.w8_stream_rows`` --, a fused layer once, its output split.
 """
 from __future__ import annotations
 
@@ -21,6 +27,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import ops
+from ..util.config import amd_key
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
 from .mlp import _F8, SparseDeltaMlp, activation_code, check_fc2, fc2_scale_of
@@ -35,7 +42,8 @@ def _params(lin: torch.nn.Linear, rows: Optional[slice] = None) -> Tuple[torch.T
 class SparseDiffGatedMlp(SparseDeltaMlp):
     """``gate_proj`` / ``up_proj`` / ``fc2``: ``nn.Linear`` with or without bias, bf16 for the sparse steps; or ``gate_proj`` / ``up_proj``
     (or the fused ``fc1``) BOTH ``F8Linear`` with e4m3 weights and e4m3 inputs (``input_float8_dtype=torch.float8_e4m3fn``;
-    ``F8Linear.from_linear`` defaults to e5m2, which the kernel does not read).  ``fc2`` is bf16 (GEMM2 gathers bf16 rows) or, with
+    ``F8Linear.from_linear`` defaults to e5m2, which the kernel does not read); or, with ``mlp.w8_gated`` on, BOTH ``W8Linear`` (weight-only
+    e4m3, bf16 inputs; a fused ``W8Linear`` likewise).  ``fc2`` is bf16 (GEMM2 gathers bf16 rows) or, with
     ``mlp.fp8_fc2`` on, an ``F8Linear`` with e4m3 weights (GEMM2 gathers e4m3 rows, ``fc2.scale_reciprocal`` on its sums).
     Their parameters are read at every call, so the model may be moved or cast after wrapping.  The sparse steps select columns with
     ``topk_indices``, which takes rows of 1024 columns or more: the hidden width ``F`` must be at least 1024."""
@@ -67,10 +75,19 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
                              f"{tuple(up[0].shape)})")
         if fc2.weight.shape[1] != gate[0].shape[0]:
             raise ValueError(f"SparseDiffGatedMlp: fc2 takes {fc2.weight.shape[1]} features, the projections give {gate[0].shape[0]}")
-        if any(getattr(p, "weight_only", False) for p in projs):
+        w8 = [bool(getattr(p, "weight_only", False)) for p in projs]
+        if any(w8) and not amd_key("mlp", "w8_gated"):
             raise ValueError("SparseDiffGatedMlp: a W8Linear projection (weight-only fp8, mlp.fp8_weight_only) is refused: only the ungated "
-                             "GEMM1 has a weight-only form (csp_mlp_mm1_w8); keep the gate and up projections in bf16, or build them as F8Linear")
-        f8 = [p.weight.dtype in _F8 for p in projs]
+                             "GEMM1 has a weight-only form (csp_mlp_mm1_w8) unless mlp.w8_gated is on -- set it to run the gated weight-only "
+                             "GEMM1 (csp_mlp_mm1_glu_w8), or keep the gate and up projections in bf16, or build them as F8Linear")
+        if any(w8) != all(w8):
+            raise ValueError("SparseDiffGatedMlp: a mixed pair -- one projection is a W8Linear (weight-only fp8), the other is not; the "
+                             "gated weight-only GEMM1 takes both projections as W8Linear")
+        self.w8 = all(w8)               # weight-only e4m3 projections: x stays bf16 (csp_mlp_mm1_glu_w8)
+        for p in projs if self.w8 else ():
+            if p.weight.dtype != torch.float8_e4m3fn:
+                raise ValueError(f"SparseDiffGatedMlp: the gated weight-only GEMM1 reads float8_e4m3fn weights only (got {p.weight.dtype})")
+        f8 = [p.weight.dtype in _F8 and not self.w8 for p in projs]
         if any(f8) != all(f8):
             raise ValueError("SparseDiffGatedMlp: a mixed pair -- one projection is fp8, the other is not; the gated GEMM1 takes both "
                              "projections in bf16 or both as F8Linear")
@@ -108,6 +125,19 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
         return self._half(1)
 
     @property
+    def w8_scales(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(gate, up) ``scale_reciprocal`` of ``W8Linear`` projections as they are NOW: each layer's own, or -- a fused layer -- the halves
+        of its ``[2F]`` scale as views, split like the weight; a ``[]`` scale serves both halves"""
+        if self.gate_first is None:
+            return self.projs[0].scale_reciprocal, self.projs[1].scale_reciprocal
+        s = self.projs[0].scale_reciprocal
+        if s.dim() == 0:
+            return s, s
+        f = s.shape[0] // 2
+        first, second = s[:f], s[f:]
+        return (first, second) if self.gate_first else (second, first)
+
+    @property
     def fc2w_T(self) -> torch.Tensor:
         """fc2.weight^T, contiguous ``[F, C]``: made once per weight tensor (again after the module was moved or cast)"""
         w = self.fc2[0].weight.data
@@ -117,7 +147,7 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
         return self._fc2w_T[1]
 
     def _pre(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        if self.fp8:   # the projections' own forward (torch._scaled_mm), which also feeds their input-scale calibration
+        if self.fp8 or self.w8:   # the projections' own forward (F8Linear: torch._scaled_mm, which also feeds their input-scale calibration)
             if self.gate_first is None:
                 return self.projs[0](x), self.projs[1](x)
             first, second = self.projs[0](x).chunk(2, dim=-1)   # one call of the fused projection, its output split
@@ -154,6 +184,11 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
                             cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add,
                             scale_a=qgate.input_scale_reciprocal, scale_b_gate=qgate.scale_reciprocal, scale_b_up=qup.scale_reciprocal,
                             fc2_scale=fc2_scale_of(self.fc2[0]))
+        elif self.w8:
+            scale_gate, scale_up = self.w8_scales
+            ops.mlp_glu_w8(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], scale_gate=scale_gate, scale_up=scale_up, b_gate=gate[1],
+                           b_up=up[1], act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
+                           cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add, fc2_scale=fc2_scale_of(self.fc2[0]))
         else:
             ops.mlp_glu(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], b_gate=gate[1], b_up=up[1],
                         act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,

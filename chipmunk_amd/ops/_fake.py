@@ -302,6 +302,24 @@ def _register():
         torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_w8: unknown activation '{act}'")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm1_glu_w8")
+    def _(a, b_gate, b_up, scale_gate, scale_up, c, bias_gate, bias_up, pa_cache, indices, counts, act, update_cache):
+        # as csp_mlp_mm1_glu, with e4m3 b_gate / b_up and their float32 reciprocal scales: one element each, or [F]
+        f8 = torch.float8_e4m3fn
+        torch._check(a.dtype == torch.bfloat16 and b_gate.dtype == f8 and b_up.dtype == f8,
+                     lambda: "a must be bfloat16, b_gate and b_up float8_e4m3fn")
+        torch._check(c.dtype == torch.bfloat16 and pa_cache.dtype == torch.bfloat16, lambda: "c and pa_cache must be bfloat16")
+        torch._check(a.ndim in (2, 3) and b_gate.ndim == 2 and a.shape[-1] == b_gate.shape[1] and b_gate.shape == b_up.shape,
+                     lambda: "a, b_gate and b_up must share K; b_up the shape of b_gate")
+        torch._check(c.shape == a.shape[:-1] + (b_gate.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        for bias in (bias_gate, bias_up):
+            torch._check(bias is None or bias.numel() == b_gate.shape[0], lambda: "bias_gate and bias_up must have F entries")
+        for s in (scale_gate, scale_up):
+            torch._check(s.dtype == torch.float32 and (s.numel() == 1 or s.shape == (b_gate.shape[0],)),
+                         lambda: "scale_gate and scale_up must be float32 with one element, or [F]")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_glu_w8: unknown activation '{act}'")
+        return None
+
     @lib.register_fake("chipmunk::w8_linear")
     def _(x, w, scale_b, bias, y):
         # writes y [M, F] in place and returns nothing

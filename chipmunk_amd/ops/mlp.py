@@ -390,5 +390,40 @@ def run_e2e_glu_fp8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, b
                    x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
 
 
+def mm1_glu_w8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, scale_gate: torch.Tensor, scale_up: torch.Tensor,
+               sparse_act_packed: torch.Tensor, b_gate: Optional[torch.Tensor], b_up: Optional[torch.Tensor], act: str,
+               sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, update_cache: bool = False) -> None:
+    """``mm1_glu`` over weight-only fp8 projections: bf16 ``x``, e4m3 ``w_gate`` / ``w_up`` ``[F, K]`` (two weights or the halves of one
+    fused ``[2F, K]`` tensor) and ``scale_gate`` / ``scale_up`` their RECIPROCAL scales (``W8Linear.scale_reciprocal``: one number, or
+    ``[F]``).  ``packed = bf16(act((x f(Wg)^T) * scale_gate + bg) * ((x f(Wu)^T) * scale_up + bu) - cache)`` on the kept columns.  Every
+    violation of these rules raises ``ValueError`` and names the argument."""
+    if act not in GLU_ACTS:
+        raise ValueError(f"mm1_glu_w8: unknown activation {act!r} (one of {', '.join(GLU_ACTS)})")
+    for name, w in (("w_gate", w_gate), ("w_up", w_up)):
+        if w.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"mm1_glu_w8: {name} must be float8_e4m3fn (weight-only fp8); got {w.dtype}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"mm1_glu_w8: x must be bfloat16 (got {x.dtype}): the activations are not quantised")
+    for name, s, w in (("scale_gate", scale_gate, w_gate), ("scale_up", scale_up, w_up)):
+        if s.numel() != 1 and tuple(s.shape) != (w.shape[0],):
+            raise ValueError(f"mm1_glu_w8: {name} must hold one number, or one per weight row ({w.shape[0]},); got {tuple(s.shape)}")
+    assert sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
+    sg, su = (s.float().reshape(1) if s.numel() == 1 else s.float().contiguous() for s in (scale_gate, scale_up))
+    torch.ops.chipmunk.csp_mlp_mm1_glu_w8(x, w_gate, w_up, sg, su, sparse_act_packed, b_gate, b_up, sparse_act_T, indices, counts, act,
+                                          bool(update_cache))
+
+
+@torch.compiler.disable
+def run_e2e_glu_w8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, scale_gate: torch.Tensor, scale_up: torch.Tensor,
+                   b_gate: Optional[torch.Tensor], b_up: Optional[torch.Tensor], act: str, fc2w_T: torch.Tensor, indices: torch.Tensor,
+                   counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
+                   fc2_scale: Optional[torch.Tensor] = None) -> None:
+    """``run_e2e_glu`` with the gated weight-only fp8 GEMM1 (bf16 ``x``, e4m3 gate / up weights): the packed deltas are bf16, so GEMM2
+    (``fc2w_T`` bf16, or e4m3 with ``fc2_scale``) and the scatter-add are the operators of the bf16 route."""
+    _run_e2e_gated(lambda packed, upd: mm1_glu_w8(x, w_gate, w_up, scale_gate, scale_up, packed, b_gate, b_up, act, sparse_act_T, indices,
+                                                  counts, update_cache=upd),
+                   x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
+
+
 __all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_w8", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
-           "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8"]
+           "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8", "mm1_glu_w8", "run_e2e_glu_w8"]

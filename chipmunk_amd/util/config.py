@@ -132,6 +132,11 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # of widening the whole weight to bf16 for F.linear; what SparseDiffMlp's block-mean probe fc1(block_mean(x)) needs on every selecting
     # step.  More rows, other dtypes, in_features % 64 != 0 or out_features % 8 != 0 take the widened path.  0 = off: the widened path always.
     "mlp.w8_stream_rows": 0,
+    # gated weight-only fp8 (not in the reference): SparseDiffGatedMlp accepts W8Linear gate / up projections -- two layers, or one fused
+    # [2F, K] layer through from_fused, per-tensor or per-row scales -- and runs its sparse steps through csp_mlp_mm1_glu_w8 (GEMM1 gathers
+    # e4m3 rows of both weights; bf16 activations, nothing is quantised).  Dense and full steps and the block-mean probe call the layers'
+    # own forward.  Off by default: the constructor refuses a W8Linear projection, as it always did.
+    "mlp.w8_gated": False,
     # mask step with a key count per (batch, head, 192-query group) (not in the reference; should_compress_indices only): a sparse group keeps
     # the smallest top set of keys that carries this share of its column-sum mass (the group's summed softmax probabilities), never more
     # than the top_keys count -- a head whose mass sits on few keys stores and gathers fewer.  0.0 = off: exactly top_keys keys per group.
@@ -177,6 +182,7 @@ BASE_CONFIG["attn"]["ragged_mask_to_indices"] = AMD_EXTRA_KEYS["attn.ragged_mask
 BASE_CONFIG["mlp"]["fp8_fc2"] = AMD_EXTRA_KEYS["mlp.fp8_fc2"]
 BASE_CONFIG["mlp"]["fp8_weight_only"] = AMD_EXTRA_KEYS["mlp.fp8_weight_only"]
 BASE_CONFIG["mlp"]["w8_stream_rows"] = AMD_EXTRA_KEYS["mlp.w8_stream_rows"]
+BASE_CONFIG["mlp"]["w8_gated"] = AMD_EXTRA_KEYS["mlp.w8_gated"]
 BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
 BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]

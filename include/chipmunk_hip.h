@@ -360,6 +360,29 @@ int chipmunk_csp_mlp_mm1_w8_batched(const void *a, const void *b, const float *s
                                     void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
                                     int update_cache, int B, int64_t cache_batch_stride, void *stream);
 
+/* gated fp8, weight-only: chipmunk_csp_mlp_mm1_glu[_batched|_gm] over e4m3 gate / up weights with bf16 activations (no reference
+ * counterpart).  a [M,K] bf16; b_gate / b_up [F,K] OCP e4m3 bytes (float8_e4m3fn), row stride K: two weights, or the halves of one
+ * fused [2F,K] projection in either order; scale_gate / scale_up fp32 on the device, each weight's RECIPROCAL quantisation scale: one
+ * number (its _n == 1) or one per row (its _n == F, read at the GATHERED column i = idx[g,j]).  In fp32:
+ *   g = (sum_k a[m,k] * f(b_gate[i,k])) * scale_gate[i] + bias_gate[i],   u = (sum_k a[m,k] * f(b_up[i,k])) * scale_up[i] + bias_up[i]
+ *   c[m,j] = bf16( fma(act(g), u, -pa_cache[i, m]) )
+ * f widens e4m3 to bf16 (exact); the sums are chipmunk_csp_mlp_mm1_glu's, from zero, on the widened weights; each scale and then each
+ * bias is applied in fp32, each rounded (no fma); act, the product and the subtraction are one rounding.  With power-of-two scales and
+ * no biases the result has the bits of chipmunk_csp_mlp_mm1_glu on bf16(f(b_gate) * scale_gate), bf16(f(b_up) * scale_up).  Biases are
+ * bf16 [F] or NULL (= zero); update_cache 0 leaves the cache, 1 also applies the scatter-add of c.  Contract of
+ * chipmunk_csp_mlp_mm1_glu and its *_batched / *_gm forms: any M >= 1, ldc >= M, ldc % 8 == 0, F % 64 == 0, K % 64 == 0, F*K, M*K and
+ * F*ldc below 2^31.  A null a / b_gate / b_up / scale_gate / scale_up / c / pa_cache, a scale_gate_n or scale_up_n other than 1 or F, a
+ * scale off 4-byte alignment, a K off its multiple, an update_cache outside 0 / 1 or an unknown act returns CHIPMUNK_ERR_INVALID with a
+ * message, before anything is enqueued.  No element of a scale at or past its _n is read. */
+int chipmunk_csp_mlp_mm1_glu_w8(const void *a, const void *b_gate, const void *b_up, const float *scale_gate, int scale_gate_n,
+                                const float *scale_up, int scale_up_n, void *c, const void *bias_gate, const void *bias_up,
+                                void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
+                                int update_cache, void *stream);
+int chipmunk_csp_mlp_mm1_glu_w8_batched(const void *a, const void *b_gate, const void *b_up, const float *scale_gate, int scale_gate_n,
+                                        const float *scale_up, int scale_up_n, void *c, const void *bias_gate, const void *bias_up,
+                                        void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc,
+                                        int act, int update_cache, int B, int64_t cache_batch_stride, void *stream);
+
 /* Weight-only fp8 linear layer for few rows (W8Linear.forward under mlp.w8_stream_rows; no reference counterpart): the weight is read
  * once as e4m3 and widened in registers, no widened copy exists.
  *   x [M, K] bf16, rows ldx elements apart; w [F, K] OCP e4m3 bytes (float8_e4m3fn), plain row-major; scale_b fp32 on the device, the
@@ -407,6 +430,10 @@ int chipmunk_csp_mlp_mm1_glu_fp8_gm(const void *a, const void *b_gate, const voi
 int chipmunk_csp_mlp_mm1_w8_gm(const void *a, const void *b, const float *scale_b, int scale_n, void *c, const void *bias, void *pa_cache,
                                const int32_t *indices, const int32_t *counts, int M, int K, int F, int act, int update_cache, int B,
                                int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_glu_w8_gm(const void *a, const void *b_gate, const void *b_up, const float *scale_gate, int scale_gate_n,
+                                   const float *scale_up, int scale_up_n, void *c, const void *bias_gate, const void *bias_up,
+                                   void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int act,
+                                   int update_cache, int B, int64_t cache_batch_stride, void *stream);
 /* chipmunk_csp_scatter_add_batched on the group-major cache: unpacked_groups[b][g, idx[b,g,j], r] += packed[b, g * 128 + r, j] */
 int chipmunk_csp_scatter_add_gm(const void *packed, void *unpacked_groups, const int32_t *indices, const int32_t *counts, int M,
                                 int F, int B, int64_t cache_batch_stride, void *stream);

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan w8_probe w8_probe_wan w8_probe_hunyuan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan mm1_glu_w8 w8_probe w8_probe_wan w8_probe_hunyuan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -359,6 +359,55 @@ def bench_mm1_w8(M=4352, K=3072, F=12288, keep=3840):
     mp = {k: sorted(v)[len(v) // 2] for k, v in tp.items()}
     print(f"probe fc1(block_mean(x)) [{G} x {K}] -> {F}: W8Linear {mp['w8']:8.1f} us  [{min(tp['w8']):.1f} .. {max(tp['w8']):.1f}]   "
           f"nn.Linear {mp['bf16']:8.1f} us  [{min(tp['bf16']):.1f} .. {max(tp['bf16']):.1f}]   ratio {mp['w8'] / mp['bf16']:.2f}")
+
+
+def bench_mm1_glu_w8(M=4352, K=3072, F=12288, keep=3840, act="silu"):
+    """The gated weight-only fp8 GEMM1 (csp_mlp_mm1_glu_w8: e4m3 rows of the gate / up weights, bf16 activations) against the bf16
+    csp_mlp_mm1_glu on the widened weights, at the FLUX gated shape of bench_mm1_glu, same activations and index lists.  Same process, the
+    two alternating (KB_ROUNDS pairs, default 5); per launch the median bracket of `timeit` (20 launches, clocks warmed), then the median
+    and the range over the rounds.  KB_LAYERS=n rotates n sets of weights / caches / outputs (n = 8: the weight rows come from HBM).
+    KB_W8_SCALES=row: one scale per weight row instead of one number; KB_GLU_UPDATE=0 times the forms without the scatter-add."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    rows = os.environ.get("KB_W8_SCALES", "tensor") == "row"
+    upd = os.environ.get("KB_GLU_UPDATE", "1") == "1"
+    G = (M + 127) // 128
+    sets = []
+    for _ in range(L):
+        w = torch.randn(2 * F, K, device=dev, generator=g) * 0.02      # the halves of one fused projection
+        w8 = (w * 512).clamp(-448, 448).to(torch.float8_e4m3fn)
+        w16 = (w8.to(torch.bfloat16) * (1 / 512.0)).contiguous()      # the widened weight: exact
+        x = torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g) * 0.5
+        cache = torch.zeros(F, M, device=dev, dtype=torch.bfloat16)
+        sets.append((w16, w8, x, cache, torch.empty(M, F, device=dev, dtype=torch.bfloat16)))
+    sg, su = (torch.full((F,) if rows else (1,), 1 / 512.0, device=dev) for _ in range(2))
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_w8():
+        _, w8, x, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_glu_w8(x, w8[:F], w8[F:], sg, su, out, None, None, cache, inds, counts, act, upd)
+
+    def run_bf16():
+        w16, _, x, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_glu(x, w16[:F], w16[F:], out, None, None, cache, inds, counts, act, upd)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {"w8": [], "bf16": []}
+    for _ in range(rounds):
+        t["w8"].append(timeit(run_w8) * 1e3)
+        t["bf16"].append(timeit(run_bf16) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * K * 2 * keep
+    tag = (f"(M={M} K={K} F={F} keep={keep} {act} layers={L} scales={'row' if rows else 'tensor'} {'scatter' if upd else 'update off'}, "
+           f"{rounds} alternating rounds)")
+    print(f"mm1_glu_w8 e4m3 rows: {med['w8']:8.1f} us  [{min(t['w8']):.1f} .. {max(t['w8']):.1f}]  {flops/med['w8']/1e6:7.1f} TFLOP/s   {tag}")
+    print(f"mm1_glu    bf16 rows: {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]  {flops/med['bf16']/1e6:7.1f} TFLOP/s")
+    print(f"mm1_glu_w8 / mm1_glu: {med['w8'] / med['bf16']:8.3f}")
 
 
 def bench_w8_probe(M=34, K=3072, F=12288):
@@ -753,6 +802,8 @@ def main():
             bench_mm1_w8()
         elif w == "mm1_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), K = 1 536, F = 8 960, 2 816 kept
             bench_mm1_w8(M=32760, K=1536, F=8960, keep=2816)
+        elif w == "mm1_glu_w8":       # gated weight-only fp8 GEMM1 against the bf16 gated GEMM1 on the widened weights, FLUX gated shape (KB_GLU_ACT)
+            bench_mm1_glu_w8(act=os.environ.get("KB_GLU_ACT", "silu"))
         elif w == "w8_probe":         # few-row weight-only forward at the FLUX probe shape [34, 3072] -> 12288: kernel / widened W8Linear / nn.Linear
             bench_w8_probe()
         elif w == "w8_probe_wan":     # ... at the Wan2.1 1.3B probe shape [256, 1536] -> 8960
