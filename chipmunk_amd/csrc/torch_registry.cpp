@@ -372,13 +372,14 @@ struct Mm1Shape {
 };
 // (bias: null for the gated operator, which checks its two optional vectors itself)
 Mm1Shape mm1_shape(const at::Tensor &a, const at::Tensor &b, const at::Tensor &c, const at::Tensor *bias, const at::Tensor &cache,
-                   const at::Tensor &indices, const at::Tensor &counts, bool allow_gm = false) {
+                   const at::Tensor &indices, const at::Tensor &counts, bool allow_gm = false, int64_t k_per_b_col = 1) {
+    // k_per_b_col: k elements one column of b holds (2 for the packed MXFP4 weight [F, K / 2])
     TORCH_CHECK((a.dim() == 2 || a.dim() == 3) && b.dim() == 2 && c.dim() == a.dim(), "a and c must both be 2D ([M, .]) or 3D ([B, M, .]), b 2D");
     Mm1Shape s;
     s.B = a.dim() == 3 ? a.size(0) : 1;
     s.M = a.size(-2), s.K = a.size(-1), s.F = b.size(0);
     TORCH_CHECK(s.B >= 1, "the batch size must be at least 1");
-    TORCH_CHECK(b.size(1) == s.K, "a and b must share the K dimension");
+    TORCH_CHECK(b.size(1) * k_per_b_col == s.K, "a and b must share the K dimension");
     TORCH_CHECK(c.size(-2) == s.M && c.size(-1) == s.F && c.numel() == s.B * s.M * s.F, "c must be [M, F] ([B, M, F] with the batch size of a)");
     if (bias) TORCH_CHECK(bias->numel() == s.F, "bias must have F entries");
     const int64_t G = groups_of(s.M);
@@ -710,6 +711,40 @@ void csp_mlp_mm1_w8(at::Tensor a, at::Tensor b, at::Tensor scale_b, at::Tensor c
     else
         check(chipmunk_csp_mlp_mm1_w8(a.data_ptr(), b.data_ptr(), sp, sn, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, M, K, F, ldc, code,
                                       upd, cur_stream(a)), who);
+}
+
+// addition: csp_mlp_mm1_act over an MXFP4 weight with bf16 activations (chipmunk_csp_mlp_mm1_w4): b uint8 [F, K / 2], two e2m1 elements a
+// byte; scale_b uint8 [F, K / 32], one e8m0 byte per 32 k.  The bits of csp_mlp_mm1_act on the widened weight.
+void csp_mlp_mm1_w4(at::Tensor a, at::Tensor b, at::Tensor scale_b, at::Tensor c, const c10::optional<at::Tensor> &bias, at::Tensor pa_cache,
+                    at::Tensor indices, at::Tensor counts, std::string act, bool update_cache) {
+    const char *who = "csp_mlp_mm1_w4";
+    CHECK_DEV(a); CHECK_DEV(b); CHECK_DEV(scale_b); CHECK_DEV(c); CHECK_DEV(pa_cache); CHECK_DEV(indices); CHECK_DEV(counts);
+    CHECK_BF16(a); CHECK_BF16(c); CHECK_BF16(pa_cache);
+    CHECK_I32(indices); CHECK_I32(counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(c); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
+    const int64_t Kw = a.size(-1);
+    TORCH_CHECK(Kw % 128 == 0, who, ": K must be a multiple of 128 (got ", Kw, ")");
+    TORCH_CHECK(b.scalar_type() == at::kByte && b.dim() == 2 && b.size(1) * 2 == Kw && b.is_contiguous() && b.device() == a.device(), who,
+                ": b must be a contiguous uint8 tensor [F, K / 2] on the device of a (two e2m1 elements a byte)");
+    TORCH_CHECK(scale_b.scalar_type() == at::kByte && scale_b.dim() == 2 && scale_b.size(0) == b.size(0) && scale_b.size(1) * 32 == Kw &&
+                    scale_b.is_contiguous() && scale_b.device() == a.device(),
+                who, ": scale_b must be a contiguous uint8 tensor [F, K / 32] on the device of a (one e8m0 byte per 32 k)");
+    const Mm1Shape sh = mm1_shape(a, b, c, nullptr, pa_cache, indices, counts, true, 2);
+    const void *bp = optional_bias(bias, "bias", sh.F);
+    const int code = act_code(who, act);
+    c10::DeviceGuard guard(a.device());
+    int *ip = indices.data_ptr<int>(), *cp = counts.data_ptr<int>();
+    const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc, upd = update_cache ? 1 : 0;
+    const uint8_t *sp = scale_b.data_ptr<uint8_t>();
+    if (sh.gm)
+        check(chipmunk_csp_mlp_mm1_w4_gm(a.data_ptr(), b.data_ptr(), sp, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, M, K, F, code, upd,
+                                         (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_w4_batched(a.data_ptr(), b.data_ptr(), sp, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, M, K, F, ldc, code,
+                                              upd, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else
+        check(chipmunk_csp_mlp_mm1_w4(a.data_ptr(), b.data_ptr(), sp, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, M, K, F, ldc, code, upd,
+                                      cur_stream(a)), who);
 }
 
 // addition: csp_mlp_mm1_glu over e4m3 gate / up weights with bf16 activations (gated weight-only fp8, chipmunk_csp_mlp_mm1_glu_w8): scale_gate /
@@ -1608,6 +1643,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_glu(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_fp8(Tensor a, Tensor b_gate, Tensor b_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa_cache_colmajor!) pa_cache_colmajor, Tensor indices, Tensor indices_counts, Tensor scale_a, Tensor scale_b_gate, Tensor scale_b_up, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
+    m.def("csp_mlp_mm1_w4(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_w8(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_w8(Tensor a, Tensor b_gate, Tensor b_up, Tensor scale_gate, Tensor scale_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("w8_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
@@ -1690,6 +1726,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_glu_fp8", &csp_mlp_mm1_glu_fp8);
     m.impl("csp_mlp_mm1_act", &csp_mlp_mm1_act);
     m.impl("csp_mlp_mm1_w8", &csp_mlp_mm1_w8);
+    m.impl("csp_mlp_mm1_w4", &csp_mlp_mm1_w4);
     m.impl("csp_mlp_mm1_glu_w8", &csp_mlp_mm1_glu_w8);
     m.impl("w8_linear", &w8_linear);
     m.impl("csp_mlp_mm1_fp8_act", &csp_mlp_mm1_fp8_act);

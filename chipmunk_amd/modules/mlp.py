@@ -17,6 +17,10 @@ one dynamic scale per token (``fc1.quantize_input_rowwise``) and hands GEMM1 the
 A weight-only ``fc1`` (``W8Linear``, ``mlp.fp8_weight_only``: e4m3 weight, power-of-two scales, bf16 activations) keeps ``x`` in bf16: dense and
 full steps and the block-mean probe call its forward (the bf16 linear layer over the widened weight), the sparse steps gather e4m3 rows of
 ``fc1.weight`` (``csp_mlp_mm1_w8``) with ``fc1.scale_reciprocal``.  A ``W8Linear`` ``fc2`` (per tensor) is taken under ``mlp.fp8_fc2`` like an ``F8Linear``.
+
+An MXFP4 ``fc1`` (``W4Linear``, ``mlp.mxfp4_fc1``: packed e2m1 weight with one e8m0 scale per 32 ``k``, ``in_features % 128 == 0``) is the same
+route one format down: forward on dense and full steps and for the probe, ``csp_mlp_mm1_w4`` with ``fc1.weight`` / ``fc1.block_scale`` on the
+sparse steps -- the bits of the bf16 layer over ``fc1.widened()``.  A ``W4Linear`` ``fc2`` is refused.
 """
 from __future__ import annotations
 
@@ -108,7 +112,11 @@ _F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 def check_fc2(who: str, fc2: torch.nn.Module) -> None:
     """An fp8 ``fc2`` is taken with ``mlp.fp8_fc2`` on, as an ``F8Linear`` with e4m3 weights: the sparse steps' GEMM2 then gathers e4m3
     rows of ``fc2.weight^T`` and multiplies its sums by ``fc2.scale_reciprocal``.  A ``W8Linear`` (weight-only, per tensor) carries the
-    same attributes and is taken the same way.  Everything else raises at construction."""
+    same attributes and is taken the same way.  Everything else raises at construction, a ``W4Linear`` (MXFP4) included: GEMM2 has no
+    form over packed e2m1 rows."""
+    if getattr(fc2, "weight_format", None) == "mxfp4":
+        raise ValueError(f"{who}: a W4Linear fc2 (MXFP4) is refused: GEMM2 gathers bf16 or e4m3 rows of fc2.weight^T and has no form over "
+                         "packed e2m1 rows; only fc1 of a SparseDiffMlp takes the format (csp_mlp_mm1_w4)")
     if fc2.weight.dtype not in _F8:
         return
     if not amd_key("mlp", "fp8_fc2"):
@@ -294,6 +302,9 @@ class SparseDiffMlp(SparseDeltaMlp):
                  activation: torch.nn.Module, fc2: torch.nn.Linear, heuristic_sms_scatter_add: int = 6, act: Optional[str] = None):
         # lists keep the Linear modules out of any parent nn.Module's parameter registry (reference mlp.py:21-23)
         check_fc2("SparseDiffMlp", fc2)
+        if getattr(fc1, "weight_format", None) == "mxfp4" and fc1.in_features % 128:
+            raise ValueError(f"SparseDiffMlp: a W4Linear fc1 (MXFP4) needs in_features % 128 == 0 (got {fc1.in_features}): the sparse steps' "
+                             "GEMM1 (csp_mlp_mm1_w4) moves a row's scale bytes in whole dwords, one per 128 k")
         if act is not None:
             if act not in ops.GLU_ACTS:
                 raise ValueError(f"SparseDiffMlp: unknown act {act!r} (one of {', '.join(ops.GLU_ACTS)})")
@@ -323,7 +334,9 @@ class SparseDiffMlp(SparseDeltaMlp):
     def _sparse(self, x, batched, indices, counts, sparse_act_T, out_cache) -> None:
         fc1, fc2 = self.fc1[0], self.fc2[0]
         scale_a = scale_b = fc1_scale = None
-        if getattr(fc1, "weight_only", False):                  # W8Linear: x stays bf16, GEMM1 gathers e4m3 rows of fc1.weight
+        if getattr(fc1, "weight_format", None) == "mxfp4":      # W4Linear: x stays bf16, GEMM1 gathers packed e2m1 rows of fc1.weight
+            fc1_scale = fc1.block_scale                         # ... and their e8m0 block scales [F, K / 32]
+        elif getattr(fc1, "weight_only", False):                # W8Linear: x stays bf16, GEMM1 gathers e4m3 rows of fc1.weight
             fc1_scale = fc1.scale_reciprocal                    # one number, or one per fc1 column: [F]
         elif fc1.weight.dtype == torch.float8_e4m3fn and getattr(fc1, "scaling", "tensor") == "row":
             x, scale_a = fc1.quantize_input_rowwise(x)          # one reciprocal scale per token: [B, N]

@@ -332,6 +332,89 @@ class W8Linear(nn.Module):
         return q
 
 
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)     # the magnitudes of an e2m1 nibble's low three bits; bit 3 is the sign
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """OCP MXFP4 of ``w`` ``[out, in]`` (``in % 32 == 0``): ``(packed uint8 [out, in / 2], block_scale uint8 [out, in / 32])``.  Per block
+    of 32 consecutive ``k``: ``e = floor(log2(amax)) - 2`` (2 = e2m1's largest exponent) clamped to e8m0's finite range [-127, 127],
+    ``amax == 0`` gives ``e = 0``; the byte is ``e + 127``.  The elements are ``w / 2^e`` rounded to nearest, ties to even, onto e2m1,
+    saturating at +-6.  ``floor(log2)`` is ``frexp``'s exponent and the rounding a count of exact thresholds (the midpoints of the e2m1
+    grid, each open or closed as the even neighbour asks): no logarithm is rounded anywhere.  Element ``2j`` of a row sits in bits 0 .. 3
+    of byte ``j``, element ``2j + 1`` in bits 4 .. 7 (torch's ``float4_e2m1fn_x2`` order)."""
+    out_f, in_f = w.shape
+    if in_f % 32:
+        raise ValueError(f"quantize_mxfp4: in_features must be a multiple of 32, one e8m0 scale per 32 k (got {in_f})")
+    blocks = w.float().reshape(out_f, in_f // 32, 32)
+    amax = blocks.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)                                    # amax = m * 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1, exact
+    e = torch.where(amax > 0, ex - 3, torch.zeros_like(ex)).clamp(-127, 127)
+    v = torch.ldexp(blocks.abs(), -e.unsqueeze(2))               # a power of two: exact
+    code = ((v > 0.25).to(torch.uint8) + (v >= 0.75) + (v > 1.25) + (v >= 1.75) + (v > 2.5) + (v >= 3.5) + (v > 5.0)).to(torch.uint8)
+    code = (code | (torch.signbit(blocks).to(torch.uint8) << 3)).reshape(out_f, in_f // 2, 2)
+    return code[..., 0] | (code[..., 1] << 4), (e + 127).to(torch.uint8)
+
+
+class W4Linear(nn.Module):
+    """Weight-only MXFP4 linear layer (``mlp.mxfp4_fc1``; not in the reference): ``weight`` uint8 ``[out, in / 2]`` -- two e2m1 elements a
+    byte, the even one in bits 0 .. 3 --, ``block_scale`` uint8 ``[out, in / 32]`` -- one e8m0 byte per 32 consecutive ``k`` --, an optional
+    bias, bf16 activations: 4.25 bits a weight.  An e2m1 value times a power of two is exact in bf16 (wherever the product is a normal bf16
+    number or zero), so the layer IS the bf16 linear layer over ``widened()``, and ``forward`` computes it as such, widening on every call;
+    no widened copy is kept.  As ``fc1`` of a ``SparseDiffMlp`` its sparse steps gather the packed rows and their scale bytes themselves
+    (``csp_mlp_mm1_w4``: the bits of the bf16 GEMM1 on ``widened()``).  A scale byte 255 (e8m0's NaN) is outside the format's use here."""
+    weight_only = True
+    weight_format = "mxfp4"
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=torch.bfloat16) -> None:
+        super().__init__()
+        if in_features % 32:
+            raise ValueError(f"W4Linear: in_features must be a multiple of 32, one e8m0 scale per 32 k (got {in_features})")
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = nn.Parameter(torch.zeros((out_features, in_features // 2), dtype=torch.uint8, device=device), requires_grad=False)
+        self.register_buffer("block_scale", torch.full((out_features, in_features // 32), 127, dtype=torch.uint8, device=device))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_features, dtype=dtype, device=device), requires_grad=False)
+        else:
+            self.register_parameter("bias", None)
+
+    def widened(self) -> torch.Tensor:
+        """The exact bf16 weight ``[out, in]``: a 16-entry table lookup and ``ldexp`` by the block's ``scale - 127``.  A new tensor per call."""
+        table = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=self.weight.device)
+        w = self.weight.data
+        nib = torch.stack((w & 15, w >> 4), dim=2).reshape(self.out_features, self.in_features)
+        e = (self.block_scale.to(torch.int32) - 127).repeat_interleave(32, dim=1)
+        return torch.ldexp(table[nib.long()], e).to(torch.bfloat16)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        w = self.widened()
+        return torch.nn.functional.linear(x, w if x.dtype == w.dtype else w.to(x.dtype), self.bias)
+
+    @classmethod
+    def from_mx(cls, weight: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor] = None) -> "W4Linear":
+        """A layer over tensors already in the format: ``weight`` ``[out, in / 2]`` uint8 or ``float4_e2m1fn_x2``, ``scales``
+        ``[out, in / 32]`` uint8 or ``float8_e8m0fnu`` (viewed as bytes, not copied), ``bias`` ``[out]`` or None."""
+        from ..ops.mlp import MXFP4_SCALES, MXFP4_WEIGHTS
+        if weight.dtype not in MXFP4_WEIGHTS or weight.ndim != 2:
+            raise ValueError(f"W4Linear.from_mx: weight must be uint8 or float4_e2m1fn_x2 [out, in / 2] (got {weight.dtype} {tuple(weight.shape)})")
+        out_f, in_f = weight.shape[0], weight.shape[1] * 2
+        if scales.dtype not in MXFP4_SCALES or in_f % 32 or tuple(scales.shape) != (out_f, in_f // 32):
+            raise ValueError(f"W4Linear.from_mx: scales must be uint8 or float8_e8m0fnu [out, in / 32] = {(out_f, in_f // 32)} "
+                             f"(got {scales.dtype} {tuple(scales.shape)})")
+        if bias is not None and tuple(bias.shape) != (out_f,):
+            raise ValueError(f"W4Linear.from_mx: bias must be [{out_f}] (got {tuple(bias.shape)})")
+        q = cls(in_f, out_f, bias=bias is not None, device=weight.device, dtype=torch.bfloat16 if bias is None else bias.dtype)
+        q.weight = nn.Parameter(weight.view(torch.uint8), requires_grad=False)
+        q.block_scale = scales.view(torch.uint8)
+        if bias is not None:
+            q.bias = nn.Parameter(bias, requires_grad=False)
+        return q
+
+    @classmethod
+    def from_linear(cls, linear: nn.Linear) -> "W4Linear":
+        packed, scales = quantize_mxfp4(linear.weight.data)
+        return cls.from_mx(packed, scales, None if linear.bias is None else linear.bias.data)
+
+
 @torch.inference_mode()
 def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
                            input_float8_dtype=torch.float8_e4m3fn, parent_name: Optional[str] = None,
@@ -344,7 +427,9 @@ def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
     the sparse step's GEMM2 then gathers e4m3 rows (``csp_mlp_mm2_w8``).  ``scaling`` (default: the config key ``mlp.fp8_scaling``) is the
     layers' scale granularity; that ``fc2`` of a sparse image MLP is built per tensor whatever it says (GEMM2's gather takes one scale).
     With ``mlp.fp8_weight_only`` on, every layer that would become an ``F8Linear`` becomes a ``W8Linear`` instead (e4m3 weights with
-    power-of-two scales, bf16 activations; ``input_float8_dtype`` is then not used): same exclusions, same rule for that ``fc2``."""
+    power-of-two scales, bf16 activations; ``input_float8_dtype`` is then not used): same exclusions, same rule for that ``fc2``.
+    With ``mlp.mxfp4_fc1`` on as well, ``fc1`` of a sparse image MLP (child ``"0"`` of an ``nn.Sequential`` named ``img_mlp``, while
+    ``mlp.is_enabled``, ``in_features % 128 == 0``) becomes a ``W4Linear`` (MXFP4); every other layer gets what it gets without the key."""
     from ..util.config import GLOBAL_CONFIG
     if scaling is None:
         scaling = amd_key("mlp", "fp8_scaling")
@@ -363,6 +448,10 @@ def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
             print("skipping fc2 of sparse img mlp")
             continue
         if isinstance(child, nn.Linear) and not isinstance(child, F8Linear):
+            if (weight_only and amd_key("mlp", "mxfp4_fc1") and isinstance(model, nn.Sequential) and str(name) == "0"
+                    and parent_name == "img_mlp" and GLOBAL_CONFIG["mlp"]["is_enabled"] and child.in_features % 128 == 0):
+                setattr(model, name, W4Linear.from_linear(child))      # fc1 of a sparse image MLP: MXFP4 rows for csp_mlp_mm1_w4
+                continue
             if weight_only:      # e4m3 weights with power-of-two scales, bf16 activations
                 setattr(model, name, W8Linear.from_linear(child, scaling="tensor" if sparse_fc2 else scaling))
                 continue

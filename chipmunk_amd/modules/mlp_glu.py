@@ -69,6 +69,10 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
         self.act_code = activation_code(activation)      # raises for an activation the sparse steps could not honour
         self.projs = projs              # (lists keep the Linear modules out of any parent nn.Module's parameter registry)
         self.gate_first = gate_first    # None: two projections; True / False: the halves of projs[0], and which of them is the gate
+        if any(getattr(p, "weight_format", None) == "mxfp4" for p in projs):
+            raise ValueError("SparseDiffGatedMlp: a W4Linear projection (MXFP4) is refused: only the ungated GEMM1 has an MXFP4 form "
+                             "(csp_mlp_mm1_w4, fc1 of a SparseDiffMlp); keep the gate and up projections in bf16, or build them as F8Linear "
+                             "or W8Linear")
         gate, up = self.gate, self.up
         if gate[0].shape != up[0].shape or gate[0].ndim != 2:
             raise ValueError(f"SparseDiffGatedMlp: gate and up projections must have one shape [F, K] (got {tuple(gate[0].shape)} and "

@@ -103,14 +103,76 @@ def mm1_w8(x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, sparse_
                                       bool(update_cache))
 
 
+# the packed e2m1 weight [F, K / 2] -- bytes, or torch's two-elements-a-byte dtype -- and its e8m0 block scales [F, K / 32]; a torch build
+# without the two dtypes takes the byte tensors alone
+MXFP4_WEIGHTS = tuple(t for t in (torch.uint8, getattr(torch, "float4_e2m1fn_x2", None)) if t is not None)
+MXFP4_SCALES = tuple(t for t in (torch.uint8, getattr(torch, "float8_e8m0fnu", None)) if t is not None)
+
+
+def _check_mxfp4(who: str, x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, scale_a, scale_b,
+                 names=("scale_a", "scale_b")) -> None:
+    """The rules of an MXFP4 ``fc1`` (weight-only, ``W4Linear``): ``fc1w`` uint8 / ``float4_e2m1fn_x2`` ``[F, K / 2]`` with ``fc1_scale`` uint8 /
+    ``float8_e8m0fnu`` ``[F, K / 32]``, a bf16 ``x`` with ``K % 128 == 0``, no activation / weight scale pair.  Every violation raises
+    ``ValueError`` and names the argument."""
+    if fc1_scale.dtype not in MXFP4_SCALES:
+        raise ValueError(f"{who}: fc1_scale of a {fc1w.dtype} fc1w (MXFP4) must be its e8m0 block scales, uint8 or float8_e8m0fnu; got {fc1_scale.dtype}")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"{who}: with an MXFP4 fc1w x must be bfloat16 (got {x.dtype}): the activations are not quantised")
+    for name, t in zip(names, (scale_a, scale_b)):
+        if t is not None:
+            raise ValueError(f"{who}: {name} must be None with an MXFP4 fc1w: a weight-only fc1 has no activation scale, and its block "
+                             "scales are fc1_scale")
+    K = x.shape[-1]
+    if K % 128:
+        raise ValueError(f"{who}: x must have K % 128 == 0 columns for an MXFP4 fc1w (got K = {K})")
+    if fc1w.ndim != 2 or fc1w.shape[1] * 2 != K:
+        raise ValueError(f"{who}: an MXFP4 fc1w must be [F, K / 2] = [F, {K // 2}], two e2m1 elements a byte; got {tuple(fc1w.shape)}")
+    if tuple(fc1_scale.shape) != (fc1w.shape[0], K // 32):
+        raise ValueError(f"{who}: fc1_scale must be [F, K / 32] = {(fc1w.shape[0], K // 32)}, one e8m0 byte per 32 k; got {tuple(fc1_scale.shape)}")
+    if fc1_scale.device != x.device or fc1w.device != x.device:
+        raise ValueError(f"{who}: fc1w and fc1_scale must be on the device of x ({x.device}); got {fc1w.device} and {fc1_scale.device}")
+
+
+def mm1_w4(x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
+           sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, act: str = "gelu_tanh", update_cache: bool = False) -> None:
+    """Weight-only MXFP4 GEMM1: ``packed = bf16(act(x W^T + fc1b) - cache)`` on the kept columns with bf16 ``x`` and
+    ``W = e2m1(fc1w) * 2^(fc1_scale - 127)`` per block of 32 k (``W4Linear.weight`` / ``.block_scale``) -- the bits of ``csp_mlp_mm1_act`` on
+    the widened weight; ``update_cache`` also applies the scatter-add of the packed deltas to ``sparse_act_T``.  Every cache layout and
+    batch form of ``csp_mlp_mm1_act``."""
+    if act not in GLU_ACTS:
+        raise ValueError(f"mm1_w4: unknown activation {act!r} (one of {', '.join(GLU_ACTS)})")
+    if fc1w.dtype not in MXFP4_WEIGHTS:
+        raise ValueError(f"mm1_w4: fc1w must be uint8 or float4_e2m1fn_x2 (MXFP4, two e2m1 elements a byte); got {fc1w.dtype}")
+    _check_mxfp4("mm1_w4", x, fc1w, fc1_scale, None, None)
+    _launch_mm1_w4(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache)
+
+
+def _launch_mm1_w4(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache) -> None:
+    """``mm1_w4`` behind its argument rules: the byte views and the operator"""
+    assert sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
+    torch.ops.chipmunk.csp_mlp_mm1_w4(x, fc1w.view(torch.uint8).contiguous(), fc1_scale.view(torch.uint8).contiguous(), sparse_act_packed,
+                                      fc1b, sparse_act_T, indices, counts, act, bool(update_cache))
+
+
+def _weight_only_gemm1(who: str, x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, scale_a, scale_b,
+                       names=("scale_a", "scale_b")):
+    """The GEMM1 of a weight-only ``fc1`` after its argument rules, reported under the caller's name: the MXFP4 launch for a uint8 /
+    ``float4_e2m1fn_x2`` ``fc1w``, ``mm1_w8`` for everything else ``fc1_scale`` comes with."""
+    if fc1w.dtype in MXFP4_WEIGHTS:
+        _check_mxfp4(who, x, fc1w, fc1_scale, scale_a, scale_b, names)
+        return _launch_mm1_w4
+    _check_fc1_scale(who, x, fc1w, fc1_scale, scale_a, scale_b, names)
+    return mm1_w8
+
+
 def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
         sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor,
         scale_a: Optional[torch.Tensor] = None, scale_b: Optional[torch.Tensor] = None, fc1_scale: Optional[torch.Tensor] = None,
         act: str = "gelu_tanh") -> None:
     fc1_scale, act = _positional_act(fc1_scale, act)
-    if fc1_scale is not None:      # weight-only fp8 fc1: bf16 x, e4m3 fc1w (csp_mlp_mm1_w8); the cache is left to the scatter-add
-        _check_fc1_scale("mm1", x, fc1w, fc1_scale, scale_a, scale_b)
-        return mm1_w8(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache=False)
+    if fc1_scale is not None:      # weight-only fc1 under a bf16 x: e4m3 fc1w (csp_mlp_mm1_w8) or MXFP4 (csp_mlp_mm1_w4); the cache is left to the scatter-add
+        gemm1 = _weight_only_gemm1("mm1", x, fc1w, fc1_scale, scale_a, scale_b)
+        return gemm1(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache=False)
     # (the reference asserts x is bf16 even on its fp8 branch, one of the reasons that branch cannot run as shipped)
     assert x.dtype == (torch.float8_e4m3fn if fc1w.dtype == torch.float8_e4m3fn else torch.bfloat16)
     assert sparse_act_packed.dtype == torch.bfloat16
@@ -137,8 +199,8 @@ def mm1_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Te
     e4m3 ``fc1w`` under a bf16 ``x``)."""
     fc1_scale, act = _positional_act(fc1_scale, act)
     if fc1_scale is not None:
-        _check_fc1_scale("mm1_scatter", x, fc1w, fc1_scale, None, None)
-        return mm1_w8(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache=True)
+        gemm1 = _weight_only_gemm1("mm1_scatter", x, fc1w, fc1_scale, None, None)
+        return gemm1(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache=True)
     assert x.dtype == torch.bfloat16 and sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
     if _default_form("mm1_scatter", act, fc1b) and not group_major(x, sparse_act_T):
         torch.ops.chipmunk.csp_mlp_mm1_scatter(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts)
@@ -279,6 +341,8 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
             fc2_scale: Optional[torch.Tensor] = None, fc1_scale: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
     # fc1_scale (W8Linear.scale_reciprocal; the sibling of fc2_scale): fc1w is e4m3 under a bf16 x, weight-only -- GEMM1 is csp_mlp_mm1_w8, with
     # its own scatter-add or (mlp.fused_scatter off) the scatter-add behind it; mm1_scale_a / mm1_scale_b must then be None.
+    # fc1w uint8 / float4_e2m1fn_x2 [F, K1 / 2] with fc1_scale uint8 / float8_e8m0fnu [F, K1 / 32] (W4Linear.weight / .block_scale): MXFP4,
+    # GEMM1 is csp_mlp_mm1_w4 in the same place.
     # sparse_act_T of one dimension more than x ([G, F, 128] / [B, G, F, 128]) is the group-major cache: see group_major.  Otherwise:
     # M is any positive row count (ceil(M / 128) groups, the last one short); sparse_act_T is [F, M], contiguous or -- required when
     # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers.
@@ -294,13 +358,15 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
     _check_batch(x, indices, counts, sparse_act_T, cached_out)
     M, K1 = x.shape[-2:]
     K2, K1_ = fc1w.shape
+    if fc1_scale is not None and fc1w.dtype in MXFP4_WEIGHTS:
+        K1_ *= 2      # an MXFP4 fc1w (with fc1_scale its e8m0 block scales) holds two e2m1 elements a byte
     assert K1 == K1_, "K1 must match"
     K2_, _N = fc2w_T.shape
     assert K2 == K2_, "K2 must match"
     sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)  # bf16 also when x is fp8
     tail = (sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
     if fc1_scale is not None:
-        _check_fc1_scale("run_e2e", x, fc1w, fc1_scale, mm1_scale_a, mm1_scale_b, ("mm1_scale_a", "mm1_scale_b"))
+        _weight_only_gemm1("run_e2e", x, fc1w, fc1_scale, mm1_scale_a, mm1_scale_b, ("mm1_scale_a", "mm1_scale_b"))
         fused = bool(x.is_cuda and amd_key("mlp", "fused_scatter"))
         (mm1_scatter if fused else mm1)(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act=act, fc1_scale=fc1_scale)
         return _after_gemm1(fused, *tail)
@@ -425,5 +491,5 @@ def run_e2e_glu_w8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sc
                    x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
 
 
-__all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_w8", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
+__all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_w8", "mm1_w4", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
            "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8", "mm1_glu_w8", "run_e2e_glu_w8"]

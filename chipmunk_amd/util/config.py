@@ -137,6 +137,11 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # e4m3 rows of both weights; bf16 activations, nothing is quantised).  Dense and full steps and the block-mean probe call the layers'
     # own forward.  Off by default: the constructor refuses a W8Linear projection, as it always did.
     "mlp.w8_gated": False,
+    # MXFP4 fc1 (not in the reference): with mlp.fp8_weight_only on as well, recursive_swap_linears builds fc1 of a sparse image MLP (child
+    # "0" of an nn.Sequential named img_mlp, while mlp.is_enabled, in_features % 128 == 0) as a W4Linear -- packed e2m1 weights with one e8m0
+    # scale per 32 k, 4.25 bits a weight, bf16 activations -- and SparseDiffMlp's sparse steps gather those rows (csp_mlp_mm1_w4: the bits of
+    # the bf16 GEMM1 on the widened weight).  Every other layer gets what it gets without the key.  Off by default: nothing changes.
+    "mlp.mxfp4_fc1": False,
     # mask step with a key count per (batch, head, 192-query group) (not in the reference; should_compress_indices only): a sparse group keeps
     # the smallest top set of keys that carries this share of its column-sum mass (the group's summed softmax probabilities), never more
     # than the top_keys count -- a head whose mass sits on few keys stores and gathers fewer.  0.0 = off: exactly top_keys keys per group.
@@ -183,6 +188,7 @@ BASE_CONFIG["mlp"]["fp8_fc2"] = AMD_EXTRA_KEYS["mlp.fp8_fc2"]
 BASE_CONFIG["mlp"]["fp8_weight_only"] = AMD_EXTRA_KEYS["mlp.fp8_weight_only"]
 BASE_CONFIG["mlp"]["w8_stream_rows"] = AMD_EXTRA_KEYS["mlp.w8_stream_rows"]
 BASE_CONFIG["mlp"]["w8_gated"] = AMD_EXTRA_KEYS["mlp.w8_gated"]
+BASE_CONFIG["mlp"]["mxfp4_fc1"] = AMD_EXTRA_KEYS["mlp.mxfp4_fc1"]
 BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
 BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]

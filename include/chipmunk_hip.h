@@ -360,6 +360,27 @@ int chipmunk_csp_mlp_mm1_w8_batched(const void *a, const void *b, const float *s
                                     void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
                                     int update_cache, int B, int64_t cache_batch_stride, void *stream);
 
+/* MXFP4 fc1, weight-only: chipmunk_csp_mlp_mm1_act[_batched|_gm] over an OCP MXFP4 weight with bf16 activations (no reference counterpart).
+ * a [M,K] bf16.  b [F, K/2] bytes, row-major along k: element 2j of a row in bits 0..3 of byte j, element 2j+1 in bits 4..7 (torch's
+ * float4_e2m1fn_x2 order); a nibble is e2m1 -- sign, 2 exponent bits, 1 mantissa bit: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}.  scale_b [F, K/32]
+ * bytes, e8m0: block j of row i scales elements 32j .. 32j+31 by 2^(scale_b[i,j] - 127).  With W[i,k] = e2m1(b[i,k]) * 2^(scale_b[i,k/32] - 127):
+ *   c[m,j] = bf16( act( sum_k a[m,k] * W[i,k] + bias[i] ) - pa_cache[i, m] ),   i = idx[g,j]
+ * The scale is applied where the nibbles are widened, so the kernel's weight operand IS bf16(W) and sum, bias, act and subtraction are
+ * chipmunk_csp_mlp_mm1_act's own (fp32 accumulators seeded with the bias, its k order, one rounding at the end): wherever every W[i,k] is
+ * a normal bf16 number or zero -- block bytes 1 .. 254 with 2^(s-127) * 0.5 normal, i.e. s >= 2 -- the result has the bits of
+ * chipmunk_csp_mlp_mm1_act on that widened weight, with or without a bias.  Scale byte 255 (NaN) is outside the contract and not looked
+ * for; byte 0 is read as a zero scale.  bias is bf16 [F] or NULL (= zero); update_cache 0 leaves the cache, 1 also applies the
+ * scatter-add of c.  Contract of chipmunk_csp_mlp_mm1_act and its *_batched / *_gm forms except K % 128 == 0 (a row's scale bytes are
+ * whole dwords): any M >= 1, ldc >= M, ldc % 8 == 0, F % 64 == 0, F*K, M*K and F*ldc below 2^31.  A null a / b / scale_b / c / pa_cache
+ * (named in the message), b or scale_b off 4-byte alignment, a K off its multiple, an update_cache outside 0 / 1 or an unknown act
+ * returns CHIPMUNK_ERR_INVALID with a message, before anything is enqueued.  Not part of the probe-forms build. */
+int chipmunk_csp_mlp_mm1_w4(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
+                            const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache,
+                            void *stream);
+int chipmunk_csp_mlp_mm1_w4_batched(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
+                                    const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
+                                    int update_cache, int B, int64_t cache_batch_stride, void *stream);
+
 /* gated fp8, weight-only: chipmunk_csp_mlp_mm1_glu[_batched|_gm] over e4m3 gate / up weights with bf16 activations (no reference
  * counterpart).  a [M,K] bf16; b_gate / b_up [F,K] OCP e4m3 bytes (float8_e4m3fn), row stride K: two weights, or the halves of one
  * fused [2F,K] projection in either order; scale_gate / scale_up fp32 on the device, each weight's RECIPROCAL quantisation scale: one
@@ -434,6 +455,9 @@ int chipmunk_csp_mlp_mm1_glu_w8_gm(const void *a, const void *b_gate, const void
                                    const float *scale_up, int scale_up_n, void *c, const void *bias_gate, const void *bias_up,
                                    void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int act,
                                    int update_cache, int B, int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_w4_gm(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
+                               const int32_t *indices, const int32_t *counts, int M, int K, int F, int act, int update_cache, int B,
+                               int64_t cache_batch_stride, void *stream);
 /* chipmunk_csp_scatter_add_batched on the group-major cache: unpacked_groups[b][g, idx[b,g,j], r] += packed[b, g * 128 + r, j] */
 int chipmunk_csp_scatter_add_gm(const void *packed, void *unpacked_groups, const int32_t *indices, const int32_t *counts, int M,
                                 int F, int B, int64_t cache_batch_stride, void *stream);

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan mm1_glu_w8 w8_probe w8_probe_wan w8_probe_hunyuan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_glu_w8 w8_probe w8_probe_wan w8_probe_hunyuan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -297,6 +297,50 @@ def bench_mm2_w8(M=4352, F=12288, N2=3072, keep=3840):
     print(f"mm2_w8  e4m3 rows: {med['w8']:8.1f} us  [{min(t['w8']):.1f} .. {max(t['w8']):.1f}]  {flops/med['w8']/1e6:7.1f} TFLOP/s   {tag}")
     print(f"mm2     bf16 rows: {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]  {flops/med['bf16']/1e6:7.1f} TFLOP/s")
     print(f"mm2_w8 / mm2     : {med['w8'] / med['bf16']:8.3f}")
+
+
+def bench_mm1_w4(M=4352, K=3072, F=12288, keep=3840):
+    """The MXFP4 GEMM1 with its scatter-add (csp_mlp_mm1_w4: packed e2m1 rows of fc1 + e8m0 block scales, bf16 activations) against the bf16
+    csp_mlp_mm1_scatter (`mm1s`) on the WIDENED weight, same activations, index lists and shape; alternating as bench_mm1_w8 (KB_ROUNDS,
+    KB_LAYERS)."""
+    from chipmunk_amd.modules import W4Linear
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    G = (M + 127) // 128
+    ldc = (M + 7) // 8 * 8
+    sets = []
+    for _ in range(L):
+        q = W4Linear.from_linear(torch.nn.Linear(K, F, bias=False, device=dev, dtype=torch.bfloat16))
+        x = torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g) * 0.5
+        bias = torch.randn(F, device=dev, dtype=torch.bfloat16, generator=g) * 0.1
+        cache = torch.zeros(F, ldc, device=dev, dtype=torch.bfloat16)[:, :M]
+        sets.append((q.widened(), q.weight.data, q.block_scale, x, bias, cache, torch.empty(M, F, device=dev, dtype=torch.bfloat16)))
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_w4():
+        _, w4, sc, x, bias, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_w4(x, w4, sc, out, bias, cache, inds, counts, "gelu_tanh", True)
+
+    def run_bf16():
+        w16, _, _, x, bias, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_scatter(x, w16, out, bias, cache, inds, counts)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {"w4": [], "bf16": []}
+    for _ in range(rounds):
+        t["w4"].append(timeit(run_w4) * 1e3)
+        t["bf16"].append(timeit(run_bf16) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * K * keep
+    tag = f"(M={M} K={K} F={F} keep={keep} layers={L}, {rounds} alternating rounds)"
+    print(f"mm1_w4  mxfp4 rows: {med['w4']:8.1f} us  [{min(t['w4']):.1f} .. {max(t['w4']):.1f}]  {flops/med['w4']/1e6:7.1f} TFLOP/s   {tag}")
+    print(f"mm1s    bf16 rows : {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]  {flops/med['bf16']/1e6:7.1f} TFLOP/s")
+    print(f"mm1_w4 / mm1s     : {med['w4'] / med['bf16']:8.3f}")
 
 
 def bench_mm1_w8(M=4352, K=3072, F=12288, keep=3840):
@@ -798,6 +842,10 @@ def main():
             bench_mm1_glu_fp8(act=os.environ.get("KB_GLU_ACT", "silu"))
         elif w == "mm2_w8":           # weight-only fp8 GEMM2 against the bf16 GEMM2 at the FLUX shape, 30 % of 12 288 columns kept
             bench_mm2_w8()
+        elif w == "mm1_w4":           # MXFP4 GEMM1 (+ scatter-add) against mm1s on the widened weight at the FLUX shape
+            bench_mm1_w4()
+        elif w == "mm1_w4_wan":       # ... at the Wan2.1 1.3B shape (K = 1 536: 12 scale dwords a row)
+            bench_mm1_w4(M=32760, K=1536, F=8960, keep=2816)
         elif w == "mm1_w8":           # weight-only fp8 GEMM1 (+ scatter-add) against mm1s at the FLUX shape, 3 840 of 12 288 columns kept
             bench_mm1_w8()
         elif w == "mm1_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), K = 1 536, F = 8 960, 2 816 kept
