@@ -812,6 +812,31 @@ void w8_linear(at::Tensor x, at::Tensor w, at::Tensor scale_b, const c10::option
                              (int)K, (int)F, cur_stream(x)), who);
 }
 
+// addition: the weight-only MXFP4 linear layer for few rows (chipmunk_w4_linear): y = bf16(x wide(w)^T + bias), x [M, K] bf16 with contiguous
+// rows (any row pitch), w uint8 [F, K / 2] (two e2m1 elements a byte), scale_b uint8 [F, K / 32] (one e8m0 byte per 32 k), y [M, F] bf16
+// (any row pitch), written in place
+void w4_linear(at::Tensor x, at::Tensor w, at::Tensor scale_b, const c10::optional<at::Tensor> &bias, at::Tensor y) {
+    const char *who = "w4_linear";
+    CHECK_DEV(x); CHECK_DEV(w); CHECK_DEV(scale_b); CHECK_DEV(y);
+    CHECK_BF16(x); CHECK_BF16(y);
+    TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && y.size(0) == x.size(0), who, ": x must be [M, K] and y [M, F]");
+    const int64_t M = x.size(0), K = x.size(1), F = y.size(1);
+    TORCH_CHECK(w.scalar_type() == at::kByte && w.dim() == 2 && w.size(0) == F && w.size(1) * 2 == K && w.is_contiguous() &&
+                    w.device() == x.device(),
+                who, ": w must be a contiguous uint8 tensor [F, K / 2] on the device of x (two e2m1 elements a byte)");
+    TORCH_CHECK(scale_b.scalar_type() == at::kByte && scale_b.dim() == 2 && scale_b.size(0) == F && scale_b.size(1) * 32 == K &&
+                    scale_b.is_contiguous() && scale_b.device() == x.device(),
+                who, ": scale_b must be a contiguous uint8 tensor [F, K / 32] on the device of x (one e8m0 byte per 32 k)");
+    TORCH_CHECK(M >= 1 && x.stride(1) == 1 && y.stride(1) == 1, who, ": x and y need at least one row and contiguous rows");
+    TORCH_CHECK(y.device() == x.device(), who, ": y must be on the device of x");
+    TORCH_CHECK(M <= CHIPMUNK_W4_LINEAR_MAX_M && K < (int64_t(1) << 31) && F < (int64_t(1) << 31), who, ": M, K or F too large");
+    const void *bp = optional_bias(bias, "bias", F);
+    c10::DeviceGuard guard(x.device());
+    const int64_t ldx = M > 1 ? x.stride(0) : K, ldy = M > 1 ? y.stride(0) : F;
+    check(chipmunk_w4_linear(x.data_ptr(), ldx, w.data_ptr(), scale_b.data_ptr<uint8_t>(), bp, y.data_ptr(), ldy, (int)M, (int)K, (int)F,
+                             cur_stream(x)), who);
+}
+
 int64_t check_scatter_args(const at::Tensor &packed, const at::Tensor &unpacked, const at::Tensor &inds,
                            const at::Tensor &counts, int64_t *cache_bs) {   // returns the cache pitch; *cache_bs: the cache's batch stride
     // reference csrc/indexed_io/scatter_add.cu:111-142 (B is hard-wired to 1, :58-59,138)
@@ -1647,6 +1672,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_w8(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_w8(Tensor a, Tensor b_gate, Tensor b_up, Tensor scale_gate, Tensor scale_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("w8_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
+    m.def("w4_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
     m.def("csp_mlp_mm1_fp8_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, Tensor scale_a, Tensor scale_b, str act, int update_cache) -> ()");
     m.def("topk_delta_indices(Tensor activation, Tensor(cache!) cache, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, int multiple_of, float random_amount) -> ()");
     m.def("topk_indices_p(Tensor activation, Tensor(indices!) indices, Tensor(counts!) counts, float sparsity_amount, float top_p, float min_keys, int multiple_of, float random_amount) -> ()");
@@ -1729,6 +1755,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_w4", &csp_mlp_mm1_w4);
     m.impl("csp_mlp_mm1_glu_w8", &csp_mlp_mm1_glu_w8);
     m.impl("w8_linear", &w8_linear);
+    m.impl("w4_linear", &w4_linear);
     m.impl("csp_mlp_mm1_fp8_act", &csp_mlp_mm1_fp8_act);
     m.impl("topk_delta_indices", &topk_delta_indices);
     m.impl("topk_indices_p", &topk_indices_p);

@@ -360,7 +360,8 @@ class W4Linear(nn.Module):
     byte, the even one in bits 0 .. 3 --, ``block_scale`` uint8 ``[out, in / 32]`` -- one e8m0 byte per 32 consecutive ``k`` --, an optional
     bias, bf16 activations: 4.25 bits a weight.  An e2m1 value times a power of two is exact in bf16 (wherever the product is a normal bf16
     number or zero), so the layer IS the bf16 linear layer over ``widened()``, and ``forward`` computes it as such, widening on every call;
-    no widened copy is kept.  As ``fc1`` of a ``SparseDiffMlp`` its sparse steps gather the packed rows and their scale bytes themselves
+    no widened copy is kept.  With ``mlp.w4_stream_rows`` > 0 a bf16 GPU input of at most that many rows does not widen at all:
+    ``ops.w4_linear`` streams the packed weight once (``bf16(S + bias)``, fp32 sums over the widened values).  As ``fc1`` of a ``SparseDiffMlp`` its sparse steps gather the packed rows and their scale bytes themselves
     (``csp_mlp_mm1_w4``: the bits of the bf16 GEMM1 on ``widened()``).  A scale byte 255 (e8m0's NaN) is outside the format's use here."""
     weight_only = True
     weight_format = "mxfp4"
@@ -386,6 +387,13 @@ class W4Linear(nn.Module):
         return torch.ldexp(table[nib.long()], e).to(torch.bfloat16)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        # few rows (mlp.w4_stream_rows): the packed weight streamed once through ops.w4_linear, nothing widened in memory
+        cap = int(amd_key("mlp", "w4_stream_rows"))
+        if (cap > 0 and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() >= 1 and x.shape[-1] == self.in_features and x.stride(-1) == 1
+                and self.in_features % 128 == 0 and self.out_features % 8 == 0 and 0 < x.numel() // self.in_features <= cap
+                and (self.bias is None or self.bias.dtype == torch.bfloat16)):
+            from .. import ops
+            return ops.w4_linear(x, self.weight, self.block_scale, self.bias)
         w = self.widened()
         return torch.nn.functional.linear(x, w if x.dtype == w.dtype else w.to(x.dtype), self.bias)
 
@@ -429,7 +437,8 @@ def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
     With ``mlp.fp8_weight_only`` on, every layer that would become an ``F8Linear`` becomes a ``W8Linear`` instead (e4m3 weights with
     power-of-two scales, bf16 activations; ``input_float8_dtype`` is then not used): same exclusions, same rule for that ``fc2``.
     With ``mlp.mxfp4_fc1`` on as well, ``fc1`` of a sparse image MLP (child ``"0"`` of an ``nn.Sequential`` named ``img_mlp``, while
-    ``mlp.is_enabled``, ``in_features % 128 == 0``) becomes a ``W4Linear`` (MXFP4); every other layer gets what it gets without the key."""
+    ``mlp.is_enabled``, ``in_features % 128 == 0``) becomes a ``W4Linear`` (MXFP4; its ``forward`` widens on every call unless
+    ``mlp.w4_stream_rows`` sends few rows through ``ops.w4_linear``); every other layer gets what it gets without the key."""
     from ..util.config import GLOBAL_CONFIG
     if scaling is None:
         scaling = amd_key("mlp", "fp8_scaling")

@@ -346,5 +346,17 @@ def _register():
                      lambda: "scale_b must be float32 with one element, or [F]")
         return None
 
+    @lib.register_fake("chipmunk::w4_linear")
+    def _(x, w, scale_b, bias, y):
+        # writes y [M, F] in place and returns nothing; w uint8 [F, K / 2] (two e2m1 elements a byte), scale_b uint8 [F, K / 32] (e8m0)
+        torch._check(x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and w.dtype == torch.uint8 and scale_b.dtype == torch.uint8,
+                     lambda: "x and y must be bfloat16, w and scale_b uint8")
+        torch._check(x.ndim == 2 and w.ndim == 2 and x.shape[1] == 2 * w.shape[1] and y.shape == (x.shape[0], w.shape[0]),
+                     lambda: "x must be [M, K], w [F, K / 2] and y [M, F]")
+        torch._check(x.shape[1] % 128 == 0, lambda: "K must be a multiple of 128")
+        torch._check(scale_b.shape == (w.shape[0], x.shape[1] // 32), lambda: "scale_b must be [F, K / 32]")
+        torch._check(bias is None or bias.numel() == w.shape[0], lambda: "bias must have F entries")
+        return None
+
 
 _register()

@@ -142,6 +142,12 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # scale per 32 k, 4.25 bits a weight, bf16 activations -- and SparseDiffMlp's sparse steps gather those rows (csp_mlp_mm1_w4: the bits of
     # the bf16 GEMM1 on the widened weight).  Every other layer gets what it gets without the key.  Off by default: nothing changes.
     "mlp.mxfp4_fc1": False,
+    # W4Linear.forward for few rows (not in the reference): a bf16 GPU input of at most this many rows (all leading dimensions flattened)
+    # runs ops.w4_linear -- the packed e2m1 weight and its e8m0 bytes are read once and widened in registers, the block scale applied at the
+    # conversion -- instead of building the whole bf16 weight for F.linear; what SparseDiffMlp's block-mean probe fc1(block_mean(x)) needs on
+    # every selecting step.  More rows, other dtypes, in_features % 128 != 0 or out_features % 8 != 0 take the widened path.  0 = off: the
+    # widened path always.
+    "mlp.w4_stream_rows": 0,
     # mask step with a key count per (batch, head, 192-query group) (not in the reference; should_compress_indices only): a sparse group keeps
     # the smallest top set of keys that carries this share of its column-sum mass (the group's summed softmax probabilities), never more
     # than the top_keys count -- a head whose mass sits on few keys stores and gathers fewer.  0.0 = off: exactly top_keys keys per group.
@@ -189,6 +195,7 @@ BASE_CONFIG["mlp"]["fp8_weight_only"] = AMD_EXTRA_KEYS["mlp.fp8_weight_only"]
 BASE_CONFIG["mlp"]["w8_stream_rows"] = AMD_EXTRA_KEYS["mlp.w8_stream_rows"]
 BASE_CONFIG["mlp"]["w8_gated"] = AMD_EXTRA_KEYS["mlp.w8_gated"]
 BASE_CONFIG["mlp"]["mxfp4_fc1"] = AMD_EXTRA_KEYS["mlp.mxfp4_fc1"]
+BASE_CONFIG["mlp"]["w4_stream_rows"] = AMD_EXTRA_KEYS["mlp.w4_stream_rows"]
 BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]
 BASE_CONFIG["mlp"]["top_p"] = AMD_EXTRA_KEYS["mlp.top_p"]

@@ -423,6 +423,25 @@ int chipmunk_csp_mlp_mm1_glu_w8_batched(const void *a, const void *b_gate, const
 int chipmunk_w8_linear(const void *x, int64_t ldx, const void *w, const float *scale_b, int scale_n, const void *bias, void *y,
                        int64_t ldy, int M, int K, int F, void *stream);
 
+/* Weight-only MXFP4 linear layer for few rows (W4Linear.forward under mlp.w4_stream_rows; no reference counterpart): the weight is read
+ * once as packed e2m1 with its e8m0 block scales and widened in registers, no widened copy exists.
+ *   x [M, K] bf16, rows ldx elements apart; w uint8 [F, K / 2], element 2j of a row in bits 0 .. 3 of byte j, element 2j + 1 in bits
+ *   4 .. 7; scale_b uint8 [F, K / 32] on the device, e8m0: block j of row i scales elements 32j .. 32j + 31 by 2^(s - 127); bias bf16 [F]
+ *   or NULL; y [M, F] bf16, rows ldy elements apart.
+ *   S[m,i] = sum_k x[m,k] * wide(w)[i,k]     wide(w) = W4Linear.widened(), exact in bf16; fp32, from zero, in an order that depends on K only
+ *   y[m,i] = bf16( S[m,i] + float(bias[i]) )     one rounding; without a bias bf16( S[m,i] )
+ * The block scale is applied where the nibbles are widened, so the matrix operand is the widened bf16 weight and nothing is scaled
+ * afterwards.  Scale byte 255 (e8m0's NaN) and widened values that are subnormal in bf16 are outside the contract.
+ * Row independence: the bits of output row m depend on input row m, w, scale_b and bias and on nothing else -- not on M, not on the other
+ * rows, not on the row block row m falls in.  K is not split over workgroups, nothing is accumulated with atomics, two launches give
+ * the same bits.  Rows of x at and past M are never read; of y only [0, M) x [0, F) is written.
+ * Refused with CHIPMUNK_ERR_INVALID and a message, before anything is enqueued: a null x / w / scale_b / y; M < 1, K < 128, F < 8;
+ * K % 128 != 0 or F % 8 != 0; M > CHIPMUNK_W4_LINEAR_MAX_M (the grid carries 128 rows per block of its y dimension); a scale_b off 4-byte
+ * alignment; x, w, y or bias off 16-byte alignment; ldx or ldy no multiple of 8 elements; ldx < K or ldy < F. */
+#define CHIPMUNK_W4_LINEAR_MAX_M (1 << 20)
+int chipmunk_w4_linear(const void *x, int64_t ldx, const void *w, const uint8_t *scale_b, const void *bias, void *y, int64_t ldy, int M,
+                       int K, int F, void *stream);
+
 /* Group-major cache: the activation cache of one sequence as [G, F, 128] bf16, contiguous, G = ceil(M / 128) -- element (g, i, r) is
  * activation column i of token row g * 128 + r -- instead of the column-major [F, ldc] (no reference counterpart).  The 256-byte pieces of
  * a group's kept columns then lie on a 256-byte grid inside one F * 256-byte window.  Rows of the last group at or past M are never

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_glu_w8 w8_probe w8_probe_wan w8_probe_hunyuan scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_glu_w8 w8_probe w8_probe_wan w8_probe_hunyuan w4_probe w4_probe_wan w4_probe_hv scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -508,6 +508,68 @@ def bench_w8_probe(M=34, K=3072, F=12288):
     print(f"w8_probe  kernel / widened : {med['kernel'] / med['widened']:8.3f}    kernel / nn.Linear: {med['kernel'] / med['bf16']:8.3f}")
 
 
+def bench_w4_probe(M=34, K=3072, F=12288):
+    """The few-row MXFP4 forward (ops.w4_linear: packed e2m1 + e8m0 bytes streamed once, widened in registers) against W4Linear.forward with
+    mlp.w4_stream_rows off (the whole bf16 weight built per call, then F.linear), the bf16 nn.Linear over the widened weight and ops.w8_linear
+    on the same weight requantised to e4m3, on the same rows: the block-mean probe fc1(block_mean(x)) of a selecting sparse step.  Same
+    process, the four alternating (KB_ROUNDS rounds, default 5); per launch the median bracket of `timeit`, then the median and the range
+    over the rounds.  KB_LAYERS=n (default 16) rotates n layers (weights, inputs) per launch: at the FLUX shape 16 x 20 MB of MXFP4, 16 x
+    38 MB of e4m3 and 16 x 75 MB of bf16 weights, each beyond the Infinity Cache: cold weights."""
+    from chipmunk_amd import ops
+    from chipmunk_amd.modules import W4Linear, W8Linear
+    from chipmunk_amd.util.config import GLOBAL_CONFIG
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "16"))
+    sets = []
+    for _ in range(L):
+        q = W4Linear.from_mx(torch.randint(0, 256, (F, K // 2), device=dev, dtype=torch.uint8, generator=g),
+                             torch.randint(120, 128, (F, K // 32), device=dev, dtype=torch.uint8, generator=g),
+                             torch.randn(F, device=dev, dtype=torch.bfloat16, generator=g))
+        lin = torch.nn.Linear(K, F, device=dev, dtype=torch.bfloat16)
+        with torch.no_grad():
+            lin.weight.copy_(q.widened())
+            lin.bias.copy_(q.bias)
+        sets.append((q, lin, W8Linear.from_linear(lin, scaling="row"), torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g)))
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_kernel():
+        q, _, _, x = nxt()
+        ops.w4_linear(x, q.weight, q.block_scale, q.bias)
+
+    def run_widened():
+        q, _, _, x = nxt()
+        q(x)
+
+    def run_bf16():
+        _, lin, _, x = nxt()
+        lin(x)
+
+    def run_w8():
+        _, _, q8, x = nxt()
+        ops.w8_linear(x, q8.weight, q8.scale_reciprocal, q8.bias)
+    GLOBAL_CONFIG["mlp"]["w4_stream_rows"] = 0
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    runs = {"kernel": run_kernel, "widened": run_widened, "bf16": run_bf16, "w8": run_w8}
+    t = {k: [] for k in runs}
+    with torch.no_grad():
+        for _ in range(rounds):
+            for k, fn in runs.items():
+                t[k].append(timeit(fn) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    stream = F * K // 2 + F * K // 32      # bytes of the weight-plus-scale stream
+    print(f"w4_probe  w4_linear kernel : {med['kernel']:8.1f} us  [{min(t['kernel']):.1f} .. {max(t['kernel']):.1f}]  "
+          f"{stream / med['kernel'] / 1e6:6.2f} TB/s on the weight + scale stream   (M={M} K={K} F={F} layers={L}, {rounds} alternating rounds)")
+    print(f"w4_probe  W4Linear key off : {med['widened']:8.1f} us  [{min(t['widened']):.1f} .. {max(t['widened']):.1f}]")
+    print(f"w4_probe  bf16 nn.Linear   : {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]")
+    print(f"w4_probe  w8_linear (e4m3) : {med['w8']:8.1f} us  [{min(t['w8']):.1f} .. {max(t['w8']):.1f}]")
+    print(f"w4_probe  kernel / key off : {med['kernel'] / med['widened']:8.3f}    kernel / nn.Linear: {med['kernel'] / med['bf16']:8.3f}"
+          f"    kernel / w8_linear: {med['kernel'] / med['w8']:8.3f}")
+
+
 def bench_fp8_wan(M=32768, ldc=None):
     """BASELINE config C5 (Wan2.1-1.3B, 832x480x81 -> 32 760 tokens padded to 32 768): fp8 e4m3 GEMM1, M = 32768, K = 1536,
     F = 8960, keep 0.3 (2688 columns); bf16 GEMM1 at the same shape beside it.  M = 32760: the ragged launch on the tokens as they are
@@ -858,6 +920,12 @@ def main():
             bench_w8_probe(M=256, K=1536, F=8960)
         elif w == "w8_probe_hunyuan": # ... at the HunyuanVideo probe shape [931, 3072] -> 12288
             bench_w8_probe(M=931, K=3072, F=12288)
+        elif w == "w4_probe":         # few-row MXFP4 forward at the FLUX probe shape: kernel / key-off W4Linear / nn.Linear / w8_linear
+            bench_w4_probe()
+        elif w == "w4_probe_wan":     # ... at the Wan2.1 1.3B probe shape [256, 1536] -> 8960
+            bench_w4_probe(M=256, K=1536, F=8960)
+        elif w == "w4_probe_hv":      # ... at the HunyuanVideo probe shape [931, 3072] -> 12288
+            bench_w4_probe(M=931, K=3072, F=12288)
         elif w == "mm2_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), N2 = 1 536, F = 8 960, 2 816 kept
             bench_mm2_w8(M=32760, F=8960, N2=1536, keep=2816)
         elif w == "fp8_wan":
