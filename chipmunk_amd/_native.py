@@ -21,7 +21,7 @@ SYMBOLS = [
     "chipmunk_csp_mlp_mm2_and_scatter_add_batched", "chipmunk_csp_scatter_add_batched",
     "chipmunk_csp_mlp_mm1_glu", "chipmunk_csp_mlp_mm1_glu_batched", "chipmunk_csp_mlp_mm1_glu_fp8", "chipmunk_csp_mlp_mm1_glu_fp8_batched",
     "chipmunk_csp_mlp_mm1_act", "chipmunk_csp_mlp_mm1_act_batched", "chipmunk_csp_mlp_mm1_fp8_act", "chipmunk_csp_mlp_mm1_fp8_act_batched",
-    "chipmunk_csp_mlp_mm2_w8", "chipmunk_csp_mlp_mm2_w8_batched",
+    "chipmunk_csp_mlp_mm2_w8", "chipmunk_csp_mlp_mm2_w8_batched", "chipmunk_csp_mlp_mm2_w4", "chipmunk_csp_mlp_mm2_w4_batched",
     "chipmunk_csp_mlp_mm1_w8", "chipmunk_csp_mlp_mm1_w8_batched", "chipmunk_csp_mlp_mm1_w8_gm", "chipmunk_w8_linear",
     "chipmunk_csp_mlp_mm1_w4", "chipmunk_csp_mlp_mm1_w4_batched", "chipmunk_csp_mlp_mm1_w4_gm", "chipmunk_w4_linear",
     "chipmunk_csp_mlp_mm1_glu_w8", "chipmunk_csp_mlp_mm1_glu_w8_batched", "chipmunk_csp_mlp_mm1_glu_w8_gm",

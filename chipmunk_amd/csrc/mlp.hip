@@ -19,6 +19,8 @@
 // ... and over OCP MXFP4 rows (mm1_w4_kernel, mm1_tile's W4): 32 BYTES of e2m1 nibbles a row and k step plus the row's e8m0 block-scale bytes, both
 // by LDS-DMA; a fragment is one ds_read_b32 widened by v_cvt_scalef32_pk_bf16_fp4 with the block's power-of-two scale, so the B operand is the
 // widened bf16 weight and the result the bf16 form's, bit for bit; three stages of 16 + 4 + 1 KiB (22 KiB) under the FLAT epilogue.
+// GEMM2 over MXFP4 rows of fc2^T (mm2_w4_kernel), the scale blocks along N2: 128-byte row slices, the transpose read with FOUR columns as its
+// 16-bit element, v_cvt_scalef32_pk_bf16_fp4 with the row's scale + v_perm_b32 in front of the same bf16 MFMA <256, 32, 5, 2, 4 waves of 64x128>.
 #include "common.h"
 #include "attn64_util.h"
 #include <type_traits>
@@ -1668,6 +1670,305 @@ __global__ __launch_bounds__(NW == 8 ? 512 : 256, WPS) void mm2_w8_kernel(const 
         *(u32x4 *)cp = out;
     }
 }
+
+// ------------------------------------------------------------------------------------------------ mm2, MXFP4 weights
+// GEMM2 over MXFP4 rows of fc2^T (weight-only): C = bf16(bf16(A_packed x wide(fc2^T[idx])) + C), wide() = e2m1 value * 2^(e8m0 - 127), exact in
+// bf16 -- mm2_kernel on the widened weight, bit for bit.  b is [F, N2 / 2] (element 2 j of a row in bits 0 .. 3 of byte j), scale_e8 [F, N2 / 32]:
+// the 32-element scale blocks run along N2, so the two elements of a byte share a scale.  Tile map, placement, scalar keys one tile ahead, ring
+// with a counted vmcnt, ragged rows, batch advance, dead-k masking and the staged read-modify-write epilogue are mm2_w8_kernel's.  Its own:
+//   * shape <256 columns, k step 32, 5 stages, 2 workgroups per CU, 4 waves (2 x 2, wave tile 64 x 128)>.  A gathered row slice is 128 bytes, a
+//     B tile 4 KiB = 4 DMA instructions of 8 rows: one per wave with 4 waves (with 8, half the waves would issue none and the vmcnt a wave
+//     counts would depend on the wave).  A stage is 8 + 4 + 1 KiB; the staged epilogue needs 64 KiB, which is 5 stages, so the ring is that deep;
+//   * chunk c of row r lies at chunk c ^ (((r >> 1) & 1) << 2).  A transpose read's 32-lane pass covers 4 consecutive rows x 64 bytes; a row is
+//     128 bytes = 32 banks, so rows r and r + 1 fall into different bank halves by themselves and the XOR sends r and r + 2 to different 64-byte
+//     halves: the 256 bytes of a pass cover the 64 banks once (derived, not measured);
+//   * ds_read_b64_tr_b16 over the byte image: one 16-bit element is FOUR columns, so lane l & 31 of a read pair receives 8 k-consecutive
+//     16-bit elements of columns 4 (l & 31) .. + 3 of the wave's 128 -- one pair of reads per k slice feeds four MFMA fragments, whose accumulator
+//     row i is column 4 i + fragment.  v_cvt_scalef32_pk_bf16_fp4 widens one byte (two columns of one k) with the scale of that k's row;
+//     v_perm_b32 then pairs the k's of one column.  k sits where mm2_kernel puts it (lane half = k half, 8 consecutive k per lane);
+//   * scale image: every wave fetches, with ONE dword LDS-DMA, the 8 scale bytes of each of the 8 rows it gathers (lane = row + 8 * dword; the
+//     lanes above 15 repeat those addresses), into 256 bytes of its own.  A lane's 32-column block lies in dword wn for the whole loop, so the
+//     scales of its 8 k rows are 32 contiguous bytes: two ds_read_b128, then v_bfe_u32 + v_lshlrev_b32 put byte (l & 31) >> 3 into the exponent.
+// Per k slice and lane: 16 conversions, 16 perms and 16 scale operations (48 VALU) in front of 8 MFMAs.
+struct Mm2W4Params {
+    const uint16_t *a;        // packed [M,F] bf16
+    const uint8_t *b;         // fc2^T [F,N2/2] e2m1 pairs
+    const uint8_t *scale_e8;  // [F,N2/32] e8m0
+    uint16_t *c;              // [M,N2] bf16, accumulated in place
+    const int32_t *indices, *counts;
+    int M, F, N2, NT, NR;
+    int cus_per_xcd;          // as Mm2Params
+};
+struct Mm2W4Batch : Mm2W4Params {
+    int B;
+};
+
+// (without the packed fp32 VALU forms, as mm1_w4_kernel: see there.  A function of the HIP headers is compiled with them and would stay a CALL from
+// this kernel, with a stack in scratch: the barrier is written out, and shuffles, ballots and bit casts are the compiler's builtins)
+__device__ __forceinline__ void mm2_w4_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int BN, int BK, int NST, int WPS, bool BATCHED>
+__global__ __launch_bounds__(256, WPS) __attribute__((target("no-packed-fp32-ops"))) void mm2_w4_kernel(const typename std::conditional<BATCHED, Mm2W4Batch, Mm2W4Params>::type p) {
+    constexpr int NW = 4, WNG = 2;              // 2 x 2 waves; wave tile = 64 rows x 128 columns
+    using KT = KTile<BK>;
+    constexpr int BROWB = BN / 2;               // bytes per gathered fc2^T row slice
+    constexpr int A_TILE = BM * BK * 2, B_TILE = BK * BROWB, S_TILE = NW * 256, STAGE = A_TILE + B_TILE + S_TILE;
+    constexpr int A_INST = A_TILE / (1024 * NW), PER = A_INST + 2;   // DMA instructions per wave and tile: A pieces, one B piece, the scale dwords
+    constexpr int BCPR = BROWB / 16;            // 16-byte chunks per row
+    constexpr int BRPI = 1024 / BROWB;          // rows per DMA instruction
+    static_assert(BN == 256 && BK == 32 && BCPR == 8 && BRPI == 8 && B_TILE == 1024 * NW,
+                  "one B instruction per wave; the swizzle, the key select and the scale image are written for 128-byte row slices");
+    static_assert(BM * BN * 2 <= NST * STAGE, "the epilogue stages the bf16 output tile in the ring");
+    static_assert((NST - 2) * PER < 64, "vmcnt immediate");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = w / WNG, wn = w % WNG;
+
+    // (every lambda of this kernel is always_inline: a lambda does not inherit the kernel's target attribute and would stay a call)
+    // tile map and length-aware placement: mm2_kernel's
+    const int Gs = (p.M + BM - 1) / BM;
+    int G = Gs;
+    if constexpr (BATCHED) G = Gs * p.B;
+    const int xcdq = (G * p.NT) >> 3, xcdr = (G * p.NT) & 7;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    if (slot >= xcdq + (xcd < xcdr ? 1 : 0)) return;
+    const int NR = p.NR;
+    const int mine = xcdq + (xcd < xcdr ? 1 : 0);
+    const int tbase = xcd < xcdr ? xcd * (xcdq + 1) : xcdr * (xcdq + 1) + (xcd - xcdr) * xcdq;
+    auto group_of = [&](int tt) __attribute__((always_inline)) {
+        const int nb_ = tt / (G * NR), rem_ = tt - nb_ * (G * NR);
+        return rem_ / min(NR, p.NT - nb_ * NR);
+    };
+    int t = tbase + slot;
+    const int cap = p.cus_per_xcd;
+    if (cap > 0 && mine > cap && mine <= 64 && mine <= 2 * cap) {
+        const int nl = 2 * cap - mine;
+        const int want = slot < mine - cap ? nl + slot : slot < cap ? slot - (mine - cap) : mine - 1 - (slot - cap);
+        const int len = lane < mine ? p.counts[group_of(tbase + lane)] : -1;
+        int rank = 0;
+        for (int j = 0; j < mine; ++j) {
+            const int lj = __builtin_amdgcn_ds_bpermute(j * 4, len);   // (the builtins, not the header's __shfl / __ballot: see mm2_w4_sync)
+            rank += (lj > len || (lj == len && j < lane)) ? 1 : 0;
+        }
+        const unsigned long long hit = __builtin_amdgcn_ballot_w64(lane < mine && rank == want);
+        t = tbase + (int)__builtin_ctzll(hit);
+    }
+    const int nb = t / (G * NR), rem = t - nb * (G * NR);
+    const int nr = min(NR, p.NT - nb * NR);
+    const int gi = rem / nr, nt = nb * NR + rem - gi * nr;
+    const int cnt = p.counts[gi];
+    int g = gi, bseq = 0;
+    if constexpr (BATCHED) {
+        bseq = gi / Gs;
+        g = gi - bseq * Gs;
+    }
+    auto seq_a = [&]() __attribute__((always_inline)) -> const uint16_t * {
+        if constexpr (BATCHED) return p.a + (int64_t)bseq * p.M * p.F;
+        else return p.a;
+    };
+    auto seq_c = [&]() __attribute__((always_inline)) -> uint16_t * {
+        if constexpr (BATCHED) return p.c + (int64_t)bseq * p.M * p.N2;
+        else return p.c;
+    };
+    const int n0 = nt * BN;
+    const int ncols = min(BN, p.N2 - n0);  // N2 is a multiple of 128 (checked on the host): 128 or 256, whole scale dwords and whole 64-column pieces
+    const int32_t *idxg = p.indices + (int64_t)gi * p.F;
+    const int nkb = (cnt + BK - 1) / BK;
+    if (nkb == 0) return;
+
+    const int rows = min(BM, p.M - g * BM);   // ragged last group, as mm2_kernel
+    const __amdgpu_buffer_rsrc_t ra = make_rsrc(seq_a(), (uint32_t)p.M * p.F * 2u), rb = make_rsrc(p.b, (uint32_t)p.F * (uint32_t)(p.N2 >> 1)),
+                                 rs = make_rsrc(p.scale_e8, (uint32_t)p.F * (uint32_t)(p.N2 >> 5));
+    uint32_t aoff[A_INST];  // byte offsets
+#pragma unroll
+    for (int i = 0; i < A_INST; ++i) {
+        const int row = KT::lane_row(w * A_INST + i, lane);
+        aoff[i] = ((uint32_t)(g * BM + min(row, rows - 1)) * p.F + KT::src_chunk_elems(row, lane)) * 2u;
+    }
+    constexpr int NKEY = BRPI;                   // keys per wave per tile (8): consecutive entries of the index list, scalar loads
+    int keys[NKEY];
+    auto load_keys = [&](int kb) __attribute__((always_inline)) {
+        // counts are multiples of 8 and so is the block start: the block is live or dead as a whole
+        const int base = kb * BK + w * NKEY;
+        const __attribute__((address_space(4))) int32_t *kp =
+            (const __attribute__((address_space(4))) int32_t *)(idxg + __builtin_amdgcn_readfirstlane(base < cnt ? base : 0));
+#pragma unroll
+        for (int j = 0; j < NKEY; ++j) keys[j] = kp[j];
+    };
+    // (selects on the bits of the row: a chain over eight keys is compiled into an indexed load from a scratch copy of the keys)
+    auto key_of = [&](int r) __attribute__((always_inline)) {
+        const int k01 = (r & 1) ? keys[1] : keys[0], k23 = (r & 1) ? keys[3] : keys[2];
+        const int k45 = (r & 1) ? keys[5] : keys[4], k67 = (r & 1) ? keys[7] : keys[6];
+        const int k03 = (r & 2) ? k23 : k01, k47 = (r & 2) ? k67 : k45;
+        return (r & 4) ? k47 : k03;
+    };
+    const int rsel = lane / BCPR;                  // which of the instruction's 8 rows this lane stages
+    // this lane's piece of its row: chunk (lane % 8) ^ swizzle of the 128 bytes, 32 columns; a partial last column tile stays inside the row
+    int bchunk = (lane % BCPR) ^ ((((w * BRPI + rsel) >> 1) & 1) << 2);
+    bchunk = bchunk * 32 < ncols ? bchunk : 0;
+    const uint32_t bcol = (uint32_t)(n0 >> 1) + bchunk * 16;
+    // the scale dword of this lane: row lane & 7 of the wave's 8, dword (lane >> 3) & 1 (columns [128 dword, + 128) of the tile)
+    const int sdw = ((lane >> 3) & 1) * 128 < ncols ? (lane >> 3) & 1 : 0;
+    const uint32_t scol = (uint32_t)(n0 >> 5) + sdw * 4;
+    auto issue = [&](int kb, int buf) __attribute__((always_inline)) {
+        unsigned char *st = smem + buf * STAGE;
+#pragma unroll
+        for (int i = 0; i < A_INST; ++i) blds16(ra, aoff[i], kb * BK * 2, st + (w * A_INST + i) * 1024);
+        blds16(rb, (uint32_t)key_of(rsel) * (uint32_t)(p.N2 >> 1) + bcol, 0, st + A_TILE + w * 1024);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(st + A_TILE + B_TILE + w * 256), 4,
+                                                 (int)((uint32_t)key_of(lane & 7) * (uint32_t)(p.N2 >> 5) + scol), 0, 0, 0);
+    };
+
+    f32x16 acc[4][2];  // [column 4 i + f of the wave's 128: fragment f][m tile]: MFMA rows = n, MFMA cols = m
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[f][mt][r] = 0.f;
+
+#pragma unroll
+    for (int s = 0; s < NST - 1; ++s)
+        if (s < nkb) {
+            load_keys(s);
+            issue(s, s);
+        }
+    if (NST - 1 < nkb) load_keys(NST - 1);
+    const int li = lane & 15, grp = lane >> 4;
+    const uint32_t sbit = ((lane & 31) >> 3) * 8;   // the lane's 32-column block inside its wave's scale dword
+    int buf = 0, nbuf = NST - 1;
+    for (int kb = 0; kb < nkb; ++kb) {
+        if (kb + NST - 1 <= nkb) wait_vmcnt<(NST - 2) * PER>();
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        if (kb + NST - 1 < nkb) {
+            issue(kb + NST - 1, nbuf);
+            if (kb + NST < nkb) load_keys(kb + NST);
+        }
+        // every LDS read of the loop in inline asm with hand-counted lgkmcnt (see mm2_kernel)
+        constexpr int KK = BK / 16;
+        constexpr int RD = 6;   // LDS reads per k slice: two A fragments, the transpose pair, the scale pair
+        const uint32_t stage_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem + buf * STAGE;
+        u32x4 pf[KK][2], sc[KK][2];
+        u32x2 wlo[KK], whi[KK];
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                const int row = wm * 64 + mt * 32 + (lane & 31);
+                const uint32_t ad = stage_lds + row * KT::ROWB + (((kk * 2 + (lane >> 5)) ^ KT::swz(row)) << 4);
+                asm volatile("ds_read_b128 %0, %1" : "=&v"(pf[kk][mt]) : "v"(ad) : "memory");
+            }
+            // lane group grp: column half = grp&1 (64 columns = 32 bytes), k half = grp>>1; lane li addresses block row li>>2, bytes (li&3)*8
+            const int row = kk * 16 + (grp >> 1) * 8 + (li >> 2);
+            const int chunk = (wn * 4 + (grp & 1) * 2 + ((li & 3) >> 1)) ^ (((row >> 1) & 1) << 2);
+            const uint32_t ad = stage_lds + A_TILE + row * BROWB + chunk * 16 + (li & 1) * 8;
+            asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%c3"
+                         : "=&v"(wlo[kk]), "=&v"(whi[kk]) : "v"(ad), "i"(4 * BROWB) : "memory");
+            // the 8 rows of this lane's k half were gathered by wave kk * 2 + k half: their scale dwords wn, 32 contiguous bytes
+            const uint32_t sad = stage_lds + A_TILE + B_TILE + (kk * 2 + (lane >> 5)) * 256 + wn * 32;
+            asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16" : "=&v"(sc[kk][0]), "=&v"(sc[kk][1]) : "v"(sad) : "memory");
+        }
+        if (kb == nkb - 1) {   // packed columns past the count hold garbage: only the last k step can see them (counts are multiples of 8)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) {
+                const bool kdead = kb * BK + kk * 16 + (lane >> 5) * 8 >= cnt;
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    asm volatile("" : "+v"(pf[kk][mt]));
+                    if (kdead) pf[kk][mt] = (u32x4){0u, 0u, 0u, 0u};
+                }
+            }
+        }
+        static_for<0, KK>([&](auto kc) __attribute__((always_inline)) {
+            constexpr int kk = decltype(kc)::value;
+            constexpr int YOUNGER = RD * (KK - 1 - kk);
+            asm volatile("s_waitcnt lgkmcnt(%c0)" ::"i"(YOUNGER > 15 ? 15 : YOUNGER) : "memory");
+#pragma unroll
+            for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(pf[kk][i]), "+v"(sc[kk][i]));
+            asm volatile("" : "+v"(wlo[kk]), "+v"(whi[kk]));
+            // wlo = {k0 | k1 << 16, k2 | k3 << 16}, each 16 bits = the nibbles of columns 4 i .. 4 i + 3; whi: k4 .. k7.  cv[j][k]: columns
+            // (2 j, 2 j + 1) of row k as a bf16 pair, scaled by 2^(e8m0 of row k - 127) -- the byte shifted into a float's exponent field
+            uint32_t cv[2][8];
+            static_for<0, 8>([&](auto ki) __attribute__((always_inline)) {
+                constexpr int k = decltype(ki)::value;
+                const uint32_t d = k < 4 ? wlo[kk][k >> 1] : whi[kk][(k >> 1) & 1];
+                const float s = __builtin_bit_cast(float, __builtin_amdgcn_ubfe(sc[kk][k >> 2][k & 3], sbit, 8u) << 23);
+                cv[0][k] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, (k & 1) * 2));
+                cv[1][k] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, s, (k & 1) * 2 + 1));
+            });
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {   // fragment f = column 4 i + f: the low (f even) or high halves of cv[f >> 1], k pairs in order
+                const uint32_t sel = (f & 1) ? 0x07060302u : 0x05040100u;
+                u32x4 fr;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) fr[q] = __builtin_amdgcn_perm(cv[f >> 1][2 * q + 1], cv[f >> 1][2 * q], sel);
+                const bf16x8 wfr = __builtin_bit_cast(bf16x8, fr);
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) acc[f][mt] = mfma32(wfr, __builtin_bit_cast(bf16x8, pf[kk][mt]), acc[f][mt]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        buf = buf + 1 == NST ? 0 : buf + 1;
+        nbuf = nbuf + 1 == NST ? 0 : nbuf + 1;
+    }
+
+    // ---- epilogue: lane owns row m = lane&31 of each tile; accumulator register q4*4 + j of fragment f is column 4 (q4*8 + (lane>>5)*4 + j) + f
+    //      of the wave's 128, so j = 0, 1 (2, 3) of the four fragments are 8 consecutive columns, a whole 16-byte chunk.  C = bf16(acc) + C in
+    //      bf16, staged through the ring as in mm2_kernel (row-major [128][BN] bf16, chunk c of row m at chunk c ^ (m & 31))
+    constexpr int CPRO = BN / 8;  // 16-byte chunks per output row
+    mm2_w4_sync();                // every wave is done reading the last operand stage
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+        const int ml = wm * 64 + mt * 32 + (lane & 31);
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int ch = (wn * 128 + q4 * 32 + (lane >> 5) * 16) / 8 + h;
+                u32x4 v;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    v[2 * j] = pack_bf16x2(acc[0][mt][q4 * 4 + 2 * h + j], acc[1][mt][q4 * 4 + 2 * h + j]);
+                    v[2 * j + 1] = pack_bf16x2(acc[2][mt][q4 * 4 + 2 * h + j], acc[3][mt][q4 * 4 + 2 * h + j]);
+                }
+                *(u32x4 *)(smem + ml * (BN * 2) + ((ch ^ (ml & (CPRO - 1) & 31)) << 4)) = v;
+            }
+        }
+    }
+    mm2_w4_sync();
+    constexpr int ITEMS = BM * CPRO / (NW * 64);  // 16-byte pieces per thread; all requested before the first is used (see mm2_kernel)
+    u32x4 olds[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        const int item = it * (NW * 64) + tid;
+        const int r = item / CPRO, ch = item % CPRO;
+        const int n = n0 + ch * 8;
+        olds[it] = (n < p.N2 && r < rows) ? *(const u32x4 *)(seq_c() + (int64_t)(g * BM + r) * p.N2 + n) : (u32x4){0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+        const int item = it * (NW * 64) + tid;
+        const int r = item / CPRO, ch = item % CPRO;
+        const int n = n0 + ch * 8;
+        if (n >= p.N2 || r >= rows) continue;  // N2 is a multiple of 128: a chunk is live or dead as a whole
+        const u32x4 a = *(const u32x4 *)(smem + r * (BN * 2) + ((ch ^ (r & (CPRO - 1) & 31)) << 4));
+        uint16_t *cp = seq_c() + (int64_t)(g * BM + r) * p.N2 + n;
+        const u32x4 old = olds[it];
+        u32x4 out;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            out[e] = pack_bf16x2(__builtin_bit_cast(float, a[e] << 16) + __builtin_bit_cast(float, old[e] << 16),
+                                 __builtin_bit_cast(float, a[e] & 0xffff0000u) + __builtin_bit_cast(float, old[e] & 0xffff0000u));
+        *(u32x4 *)cp = out;
+    }
+}
 #endif   // CHIPMUNK_MM1_PROBES
 
 // ------------------------------------------------------------------------------------------------ scatter-add
@@ -1937,9 +2238,58 @@ int launch_mm2_w8(const void *a, const void *b, const float *scale_b, void *c, c
     Mm2W8Params p = {(const uint16_t *)a, (const uint8_t *)b, scale_b, (uint16_t *)c, indices, counts, M, F, N2, 0, 0, 0};
     return B > 0 ? launch_mm2_w8_variant<true>(p, s, B) : launch_mm2_w8_variant<false>(p, s, 1);
 }
+
+// GEMM2 over MXFP4 weights: mm2_w4_kernel at its one shape, launch_mm2_w8_variant's grid, walk and placement; B > 0: the batched form
+template <bool BATCHED>
+int launch_mm2_w4_variant(Mm2W4Params p, hipStream_t s, int B) {
+    constexpr int BN = 256, BK = 32, NST = 5, WPS = 2;
+    constexpr int LDS = NST * (BM * BK * 2 + BK * BN / 2 + 1024);
+    auto kern = mm2_w4_kernel<BN, BK, NST, WPS, BATCHED>;
+    static uint64_t lds_set = 0;
+    ensure_dynamic_lds((const void *)kern, LDS, lds_set);
+    p.NT = (p.N2 + BN - 1) / BN;
+    const int nr_option = chipmunk_get_option("mm2_nr");
+    p.NR = nr_option > 0 ? nr_option : 4;
+    if (p.NR > p.NT) p.NR = p.NT;
+    p.cus_per_xcd = !chipmunk_get_option("mm2_order") ? device_cu_count() / 8 : 0;
+    const dim3 grid(((B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8) * 8);
+    if constexpr (BATCHED) {
+        Mm2W4Batch q;
+        static_cast<Mm2W4Params &>(q) = p;
+        q.B = B;
+        hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, q);
+    } else {
+        hipLaunchKernelGGL(kern, grid, dim3(256), LDS, s, p);
+    }
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+
+int launch_mm2_w4(const void *a, const void *b, const uint8_t *scale_b, void *c, const int32_t *indices, const int32_t *counts, int M, int F,
+                  int N2, hipStream_t s, int B = 0) {
+    CM_CHECK(a, "csp_mlp_mm2_w4: mma_a is null");
+    CM_CHECK(b, "csp_mlp_mm2_w4: mma_b is null");
+    CM_CHECK(scale_b, "csp_mlp_mm2_w4: scale_b is null");
+    CM_CHECK(c, "csp_mlp_mm2_w4: mma_c is null");
+    if (int e = check_mlp_ragged(M, F, indices, counts)) return e;
+    if (B > 0) {
+        if (int e = check_mlp_batch(B, M)) return e;
+    }
+    CM_CHECK(N2 >= 128 && N2 % 128 == 0,
+             "csp_mlp_mm2_w4: N2 must be a positive multiple of 128 (got %d): a row's scale bytes are fetched as whole dwords of 4 x 32 columns", N2);
+    CM_CHECK(((uintptr_t)b & 15) == 0, "csp_mlp_mm2_w4: mma_b must be 16-byte aligned");
+    CM_CHECK(((uintptr_t)scale_b & 3) == 0, "csp_mlp_mm2_w4: scale_b must be 4-byte aligned");
+    CM_CHECK((int64_t)M * F < (1ll << 31) && (int64_t)F * N2 < (1ll << 31) && (int64_t)M * N2 < (1ll << 31),
+             "csp_mlp_mm2_w4: M*F, F*N2 or M*N2 too large for 32-bit offsets");
+    Mm2W4Params p = {(const uint16_t *)a, (const uint8_t *)b, scale_b, (uint16_t *)c, indices, counts, M, F, N2, 0, 0, 0};
+    return B > 0 ? launch_mm2_w4_variant<true>(p, s, B) : launch_mm2_w4_variant<false>(p, s, 1);
+}
 #else
 int launch_mm2_w8(const void *, const void *, const float *, void *, const int32_t *, const int32_t *, int, int, int, hipStream_t, int = 0) {
     CM_CHECK(false, "csp_mlp_mm2_w8: not part of the probe-forms build");
+}
+int launch_mm2_w4(const void *, const void *, const uint8_t *, void *, const int32_t *, const int32_t *, int, int, int, hipStream_t, int = 0) {
+    CM_CHECK(false, "csp_mlp_mm2_w4: not part of the probe-forms build");
 }
 #endif   // CHIPMUNK_MM1_PROBES
 
@@ -2637,6 +2987,17 @@ extern "C" int chipmunk_csp_mlp_mm2_w8_batched(const void *mma_a, const void *mm
                                                const int32_t *indices, const int32_t *counts, int M, int F, int N2, int B, void *stream) {
     CM_CHECK(B >= 1, "mlp: the batch size B must be at least 1 (got %d)", B);
     return launch_mm2_w8(mma_a, mma_b, scale_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream, B);
+}
+
+// GEMM2 over MXFP4 fc2^T (packed e2m1 [F, N2/2] + e8m0 [F, N2/32]); ragged M
+extern "C" int chipmunk_csp_mlp_mm2_w4(const void *mma_a, const void *mma_b, const uint8_t *scale_b, void *mma_c, const int32_t *indices,
+                                       const int32_t *counts, int M, int F, int N2, void *stream) {
+    return launch_mm2_w4(mma_a, mma_b, scale_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm2_w4_batched(const void *mma_a, const void *mma_b, const uint8_t *scale_b, void *mma_c,
+                                               const int32_t *indices, const int32_t *counts, int M, int F, int N2, int B, void *stream) {
+    CM_CHECK(B >= 1, "mlp: the batch size B must be at least 1 (got %d)", B);
+    return launch_mm2_w4(mma_a, mma_b, scale_b, mma_c, indices, counts, M, F, N2, (hipStream_t)stream, B);
 }
 
 // ---- group-major activation cache (include/chipmunk_hip.h, "Group-major cache"): the *_gm entries.  The cache of sequence b is the

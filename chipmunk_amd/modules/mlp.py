@@ -21,6 +21,10 @@ full steps and the block-mean probe call its forward (the bf16 linear layer over
 An MXFP4 ``fc1`` (``W4Linear``, ``mlp.mxfp4_fc1``: packed e2m1 weight with one e8m0 scale per 32 ``k``, ``in_features % 128 == 0``) is the same
 route one format down: forward on dense and full steps and for the probe, ``csp_mlp_mm1_w4`` with ``fc1.weight`` / ``fc1.block_scale`` on the
 sparse steps -- the bits of the bf16 layer over ``fc1.widened()``.  A ``W4Linear`` ``fc2`` is refused.
+
+An MXFP4 ``fc2`` (``W4LinearT``, ``mlp.mxfp4_fc2``: ``fc2.weight^T`` packed, one e8m0 scale per 32 output features, ``out_features % 128 == 0``)
+is stored once, in the orientation GEMM2 gathers: ``fc2w_T`` IS ``fc2.weight_t``, the sparse steps run ``csp_mlp_mm2_w4`` with
+``fc2.block_scale_t`` -- the bits of the bf16 GEMM2 over ``fc2.widened()^T`` --, dense and full steps call ``fc2.forward``.
 """
 from __future__ import annotations
 
@@ -112,11 +116,20 @@ _F8 = (torch.float8_e4m3fn, torch.float8_e5m2)
 def check_fc2(who: str, fc2: torch.nn.Module) -> None:
     """An fp8 ``fc2`` is taken with ``mlp.fp8_fc2`` on, as an ``F8Linear`` with e4m3 weights: the sparse steps' GEMM2 then gathers e4m3
     rows of ``fc2.weight^T`` and multiplies its sums by ``fc2.scale_reciprocal``.  A ``W8Linear`` (weight-only, per tensor) carries the
-    same attributes and is taken the same way.  Everything else raises at construction, a ``W4Linear`` (MXFP4) included: GEMM2 has no
-    form over packed e2m1 rows."""
+    same attributes and is taken the same way.  With ``mlp.mxfp4_fc2`` on a ``W4LinearT`` (MXFP4 of ``fc2.weight^T``, scale blocks along
+    ``out_features``, ``out_features % 128 == 0``) is taken: GEMM2 gathers its packed rows (``csp_mlp_mm2_w4``).  Everything else raises at
+    construction, a ``W4Linear`` (blocks along ``in_features``) included."""
     if getattr(fc2, "weight_format", None) == "mxfp4":
-        raise ValueError(f"{who}: a W4Linear fc2 (MXFP4) is refused: GEMM2 gathers bf16 or e4m3 rows of fc2.weight^T and has no form over "
-                         "packed e2m1 rows; only fc1 of a SparseDiffMlp takes the format (csp_mlp_mm1_w4)")
+        raise ValueError(f"{who}: a W4Linear fc2 (MXFP4 with the scale blocks along in_features) is refused: GEMM2 reduces over the "
+                         "gathered rows of fc2.weight^T, so every element of a row would have a scale of its own; build fc2 as a W4LinearT "
+                         "(W4LinearT.from_linear: blocks along out_features, csp_mlp_mm2_w4) with mlp.mxfp4_fc2 on")
+    if is_mxfp4_t(fc2):
+        if not amd_key("mlp", "mxfp4_fc2"):
+            raise ValueError(f"{who}: a W4LinearT fc2 (MXFP4) is refused unless the config key mlp.mxfp4_fc2 is on")
+        if fc2.out_features % 128:
+            raise ValueError(f"{who}: a W4LinearT fc2 needs out_features % 128 == 0 (got {fc2.out_features}): GEMM2 (csp_mlp_mm2_w4) moves "
+                             "a gathered row's scale bytes in whole dwords, one per 128 output features")
+        return
     if fc2.weight.dtype not in _F8:
         return
     if not amd_key("mlp", "fp8_fc2"):
@@ -131,8 +144,19 @@ def check_fc2(who: str, fc2: torch.nn.Module) -> None:
                          "mlp.fp8_scaling says)")
 
 
+def is_mxfp4_t(fc2: torch.nn.Module) -> bool:
+    return getattr(fc2, "weight_format", None) == "mxfp4_t"
+
+
+def fc2w_T_of(fc2: torch.nn.Module) -> torch.Tensor:
+    """What GEMM2 gathers from: a ``W4LinearT``'s own ``weight_t`` (no copy), the contiguous transpose of every other ``fc2.weight``"""
+    return fc2.weight_t.data if is_mxfp4_t(fc2) else fc2.weight.data.transpose(0, 1).contiguous()
+
+
 def fc2_scale_of(fc2: torch.nn.Module):
-    """``fc2.scale_reciprocal`` for an e4m3 ``fc2``, ``None`` for a bf16 one"""
+    """``fc2.scale_reciprocal`` for an e4m3 ``fc2``, ``fc2.block_scale_t`` for a ``W4LinearT``, ``None`` for a bf16 one"""
+    if is_mxfp4_t(fc2):
+        return fc2.block_scale_t
     return fc2.scale_reciprocal if fc2.weight.dtype == torch.float8_e4m3fn else None
 
 
@@ -316,7 +340,7 @@ class SparseDiffMlp(SparseDeltaMlp):
                 raise ValueError(f"{e}; for another callable that computes one of them pass act='gelu_tanh', 'gelu' or 'silu'") from None
         self.fc1 = [fc1]
         self.fc2 = [fc2]
-        self.fc2w_T = [fc2.weight.data.transpose(0, 1).contiguous()]
+        self.fc2w_T = [fc2w_T_of(fc2)]
         self.layer_counter = layer_counter
         self.activation = activation
         self.storage = MlpStorage(layer_num)

@@ -423,6 +423,69 @@ class W4Linear(nn.Module):
         return cls.from_mx(packed, scales, None if linear.bias is None else linear.bias.data)
 
 
+class W4LinearT(nn.Module):
+    """Weight-only MXFP4 linear layer stored TRANSPOSED, for ``fc2`` of a sparse MLP (``mlp.mxfp4_fc2``; not in the reference):
+    ``weight_t`` uint8 ``[in, out / 2]`` -- row ``f`` is column ``f`` of the ``[out, in]`` weight, two e2m1 elements a byte, the even one in
+    bits 0 .. 3 --, ``block_scale_t`` uint8 ``[in, out / 32]`` -- one e8m0 byte per 32 consecutive OUTPUT features of that column --, an
+    optional bias.  Both are ``quantize_mxfp4(weight.t())``: the orientation the sparse steps' GEMM2 gathers (``csp_mlp_mm2_w4``, the bits
+    of the bf16 GEMM2 on ``widened()^T``), stored once -- no transposed copy exists.  ``forward`` is the bf16 linear layer over
+    ``widened()``, widening on every call.  The scale blocks run along ``out_features``, the reduction index of GEMM2 being the gathered
+    row: that is NOT the orientation of ``fc2`` in an OCP MXFP4 checkpoint (blocks along ``in_features``), which has to be requantised
+    through ``from_linear``.  A scale byte 255 is outside the format's use here."""
+    weight_only = True
+    weight_format = "mxfp4_t"
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=torch.bfloat16) -> None:
+        super().__init__()
+        if out_features % 32:
+            raise ValueError(f"W4LinearT: out_features must be a multiple of 32, one e8m0 scale per 32 output features (got {out_features})")
+        self.in_features, self.out_features = in_features, out_features
+        self.weight_t = nn.Parameter(torch.zeros((in_features, out_features // 2), dtype=torch.uint8, device=device), requires_grad=False)
+        self.register_buffer("block_scale_t", torch.full((in_features, out_features // 32), 127, dtype=torch.uint8, device=device))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_features, dtype=dtype, device=device), requires_grad=False)
+        else:
+            self.register_parameter("bias", None)
+
+    def widened(self) -> torch.Tensor:
+        """The exact bf16 weight ``[out, in]``: ``W4Linear``'s lookup over the stored rows, transposed.  A new tensor per call."""
+        table = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=self.weight_t.device)
+        w = self.weight_t.data
+        nib = torch.stack((w & 15, w >> 4), dim=2).reshape(self.in_features, self.out_features)
+        e = (self.block_scale_t.to(torch.int32) - 127).repeat_interleave(32, dim=1)
+        return torch.ldexp(table[nib.long()], e).to(torch.bfloat16).t().contiguous()
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        w = self.widened()
+        return torch.nn.functional.linear(x, w if x.dtype == w.dtype else w.to(x.dtype), self.bias)
+
+    @classmethod
+    def from_mx_t(cls, weight_t: torch.Tensor, scales_t: torch.Tensor, bias: Optional[torch.Tensor] = None) -> "W4LinearT":
+        """A layer over tensors already in this orientation: ``weight_t`` ``[in, out / 2]`` uint8 or ``float4_e2m1fn_x2``, ``scales_t``
+        ``[in, out / 32]`` uint8 or ``float8_e8m0fnu`` (viewed as bytes, not copied), ``bias`` ``[out]`` or None."""
+        from ..ops.mlp import MXFP4_SCALES, MXFP4_WEIGHTS
+        if weight_t.dtype not in MXFP4_WEIGHTS or weight_t.ndim != 2:
+            raise ValueError(f"W4LinearT.from_mx_t: weight_t must be uint8 or float4_e2m1fn_x2 [in, out / 2] (got {weight_t.dtype} "
+                             f"{tuple(weight_t.shape)})")
+        in_f, out_f = weight_t.shape[0], weight_t.shape[1] * 2
+        if scales_t.dtype not in MXFP4_SCALES or out_f % 32 or tuple(scales_t.shape) != (in_f, out_f // 32):
+            raise ValueError(f"W4LinearT.from_mx_t: scales_t must be uint8 or float8_e8m0fnu [in, out / 32] = {(in_f, out_f // 32)} "
+                             f"(got {scales_t.dtype} {tuple(scales_t.shape)})")
+        if bias is not None and tuple(bias.shape) != (out_f,):
+            raise ValueError(f"W4LinearT.from_mx_t: bias must be [{out_f}] (got {tuple(bias.shape)})")
+        q = cls(in_f, out_f, bias=bias is not None, device=weight_t.device, dtype=torch.bfloat16 if bias is None else bias.dtype)
+        q.weight_t = nn.Parameter(weight_t.view(torch.uint8), requires_grad=False)
+        q.block_scale_t = scales_t.view(torch.uint8)
+        if bias is not None:
+            q.bias = nn.Parameter(bias, requires_grad=False)
+        return q
+
+    @classmethod
+    def from_linear(cls, linear: nn.Linear) -> "W4LinearT":
+        packed, scales = quantize_mxfp4(linear.weight.data.t().contiguous())
+        return cls.from_mx_t(packed, scales, None if linear.bias is None else linear.bias.data)
+
+
 @torch.inference_mode()
 def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
                            input_float8_dtype=torch.float8_e4m3fn, parent_name: Optional[str] = None,
@@ -438,7 +501,10 @@ def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
     power-of-two scales, bf16 activations; ``input_float8_dtype`` is then not used): same exclusions, same rule for that ``fc2``.
     With ``mlp.mxfp4_fc1`` on as well, ``fc1`` of a sparse image MLP (child ``"0"`` of an ``nn.Sequential`` named ``img_mlp``, while
     ``mlp.is_enabled``, ``in_features % 128 == 0``) becomes a ``W4Linear`` (MXFP4; its ``forward`` widens on every call unless
-    ``mlp.w4_stream_rows`` sends few rows through ``ops.w4_linear``); every other layer gets what it gets without the key."""
+    ``mlp.w4_stream_rows`` sends few rows through ``ops.w4_linear``); every other layer gets what it gets without the key.
+    With ``mlp.fp8_weight_only`` and ``mlp.mxfp4_fc2`` on, that ``fc2`` of a sparse image MLP (``out_features % 128 == 0``) becomes a
+    ``W4LinearT`` -- MXFP4 of ``fc2.weight^T``, stored once, gathered by ``csp_mlp_mm2_w4`` --, whatever ``mlp.fp8_fc2`` says; every other
+    layer gets what it gets without the key."""
     from ..util.config import GLOBAL_CONFIG
     if scaling is None:
         scaling = amd_key("mlp", "fp8_scaling")
@@ -453,6 +519,10 @@ def recursive_swap_linears(model: nn.Module, float8_dtype=torch.float8_e4m3fn,
             continue
         sparse_fc2 = (isinstance(model, nn.Sequential) and str(name) == "2" and isinstance(child, nn.Linear)
                       and parent_name == "img_mlp" and GLOBAL_CONFIG["mlp"]["is_enabled"])
+        if (sparse_fc2 and weight_only and amd_key("mlp", "mxfp4_fc2") and child.out_features % 128 == 0
+                and not isinstance(child, F8Linear)):
+            setattr(model, name, W4LinearT.from_linear(child))         # fc2 of a sparse image MLP: MXFP4 rows of fc2.weight^T for csp_mlp_mm2_w4
+            continue
         if sparse_fc2 and not (amd_key("mlp", "fp8_fc2") and float8_dtype == torch.float8_e4m3fn):
             print("skipping fc2 of sparse img mlp")
             continue

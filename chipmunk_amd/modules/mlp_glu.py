@@ -30,7 +30,7 @@ from .. import ops
 from ..util.config import amd_key
 from ..util.layer_counter import LayerCounter
 from ..util.storage import MlpStorage
-from .mlp import _F8, SparseDeltaMlp, activation_code, check_fc2, fc2_scale_of
+from .mlp import _F8, SparseDeltaMlp, activation_code, check_fc2, fc2_scale_of, is_mxfp4_t
 
 
 def _params(lin: torch.nn.Linear, rows: Optional[slice] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -45,6 +45,7 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
     ``F8Linear.from_linear`` defaults to e5m2, which the kernel does not read); or, with ``mlp.w8_gated`` on, BOTH ``W8Linear`` (weight-only
     e4m3, bf16 inputs; a fused ``W8Linear`` likewise).  ``fc2`` is bf16 (GEMM2 gathers bf16 rows) or, with
     ``mlp.fp8_fc2`` on, an ``F8Linear`` with e4m3 weights (GEMM2 gathers e4m3 rows, ``fc2.scale_reciprocal`` on its sums).
+    With ``mlp.mxfp4_fc2`` on, a ``W4LinearT`` (``out_features % 128 == 0``): GEMM2 gathers packed e2m1 rows of ``fc2.weight_t`` itself.
     Their parameters are read at every call, so the model may be moved or cast after wrapping.  The sparse steps select columns with
     ``topk_indices``, which takes rows of 1024 columns or more: the hidden width ``F`` must be at least 1024."""
     _who = "SparseDiffGatedMlp"
@@ -77,8 +78,9 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
         if gate[0].shape != up[0].shape or gate[0].ndim != 2:
             raise ValueError(f"SparseDiffGatedMlp: gate and up projections must have one shape [F, K] (got {tuple(gate[0].shape)} and "
                              f"{tuple(up[0].shape)})")
-        if fc2.weight.shape[1] != gate[0].shape[0]:
-            raise ValueError(f"SparseDiffGatedMlp: fc2 takes {fc2.weight.shape[1]} features, the projections give {gate[0].shape[0]}")
+        fc2_in = fc2.in_features if is_mxfp4_t(fc2) else fc2.weight.shape[1]
+        if fc2_in != gate[0].shape[0]:
+            raise ValueError(f"SparseDiffGatedMlp: fc2 takes {fc2_in} features, the projections give {gate[0].shape[0]}")
         w8 = [bool(getattr(p, "weight_only", False)) for p in projs]
         if any(w8) and not amd_key("mlp", "w8_gated"):
             raise ValueError("SparseDiffGatedMlp: a W8Linear projection (weight-only fp8, mlp.fp8_weight_only) is refused: only the ungated "
@@ -144,6 +146,8 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
     @property
     def fc2w_T(self) -> torch.Tensor:
         """fc2.weight^T, contiguous ``[F, C]``: made once per weight tensor (again after the module was moved or cast)"""
+        if is_mxfp4_t(self.fc2[0]):      # W4LinearT: stored in GEMM2's orientation, no copy
+            return self.fc2[0].weight_t.data
         w = self.fc2[0].weight.data
         key = (w.data_ptr(), w.dtype, w.device)
         if self._fc2w_T is None or self._fc2w_T[0] != key:

@@ -289,6 +289,18 @@ def _register():
                      lambda: "shape mismatch (mma_b must be [F, N2], mma_c [M, N2], or [B, M, N2] with the batch size of mma_a)")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm2_w4")
+    def _(mma_a, mma_b, scale_b, indices, counts, mma_c):
+        # accumulates into mma_c in place and returns nothing; mma_b uint8 [F, N2 / 2] (two e2m1 elements a byte), scale_b uint8 [F, N2 / 32]
+        torch._check(mma_a.dtype == torch.bfloat16 and mma_c.dtype == torch.bfloat16, lambda: "mma_a and mma_c must be bfloat16")
+        torch._check(mma_b.dtype == torch.uint8 and scale_b.dtype == torch.uint8, lambda: "mma_b and scale_b must be uint8 (MXFP4 bytes)")
+        torch._check(mma_b.ndim == 2 and mma_b.shape[0] == mma_a.shape[-1] and (mma_b.shape[1] * 2) % 128 == 0,
+                     lambda: "mma_b must be [F, N2 / 2] with N2 % 128 == 0")
+        torch._check(scale_b.shape == (mma_b.shape[0], mma_b.shape[1] // 16), lambda: "scale_b must be [F, N2 / 32]")
+        torch._check(mma_c.shape == mma_a.shape[:-1] + (mma_b.shape[1] * 2,),
+                     lambda: "shape mismatch (mma_c must be [M, N2], or [B, M, N2] with the batch size of mma_a)")
+        return None
+
     @lib.register_fake("chipmunk::csp_mlp_mm1_w8")
     def _(a, b, scale_b, c, bias, pa_cache, indices, counts, act, update_cache):
         # as csp_mlp_mm1_act, with an e4m3 b and its float32 reciprocal scale: one element, or [F]

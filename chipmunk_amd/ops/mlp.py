@@ -274,9 +274,18 @@ def csp_mlp_mm2(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, indices: t
     ``float8_e4m3fn``, plain row-major) takes the weight-only fp8 GEMM2 and needs ``fc2_scale``, the weight's RECIPROCAL quantisation scale
     (``F8Linear.scale_reciprocal``), which multiplies the fp32 sums before they are rounded to bf16.
 
-    ``counts`` must be multiples of 8: both GEMM2 kernels mask the packed columns past a count in whole 16-byte pieces (the reference's
+    An MXFP4 ``fc2wT`` -- uint8 or ``float4_e2m1fn_x2`` ``[F, N / 2]`` with ``fc2_scale`` uint8 or ``float8_e8m0fnu`` ``[F, N / 32]``, the e8m0
+    scales of 32-COLUMN blocks (``W4LinearT.weight_t`` / ``.block_scale_t``), ``N % 128 == 0`` -- takes ``csp_mlp_mm2_w4``: the bits of the
+    bf16 form on the widened weight.  Every violation of these rules raises ``ValueError`` and names the argument.
+
+    ``counts`` must be multiples of 8: all GEMM2 kernels mask the packed columns past a count in whole 16-byte pieces (the reference's
     Triton kernel reads whole k blocks), so a count of 154 would take columns 154 .. 159 of ``sparse_act_packed`` into the sum.
     ``topk_indices`` emits multiples of ``counts_multiple_of`` (256 / 128 as shipped).  GEMM1 and the scatter-add take any count."""
+    if fc2wT.dtype in MXFP4_WEIGHTS:
+        _check_mxfp4_fc2(sparse_act_packed, fc2wT, fc2_scale, cached_out)
+        torch.ops.chipmunk.csp_mlp_mm2_w4(sparse_act_packed, fc2wT.view(torch.uint8).contiguous(), fc2_scale.view(torch.uint8).contiguous(),
+                                          indices, counts, cached_out)
+        return
     if fc2wT.dtype == torch.float8_e4m3fn:
         if fc2_scale is None:
             raise ValueError("csp_mlp_mm2: an e4m3 fc2wT needs fc2_scale, the weight's reciprocal quantisation scale (F8Linear.scale_reciprocal)")
@@ -285,10 +294,33 @@ def csp_mlp_mm2(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, indices: t
     torch.ops.chipmunk.csp_mlp_mm2(sparse_act_packed, fc2wT, indices, counts, cached_out)
 
 
+def _check_mxfp4_fc2(sparse_act_packed: torch.Tensor, fc2wT: torch.Tensor, fc2_scale: Optional[torch.Tensor], cached_out: torch.Tensor) -> None:
+    """The rules of an MXFP4 ``fc2wT`` (``W4LinearT``); every violation raises ``ValueError`` and names the argument"""
+    who = "csp_mlp_mm2"
+    if fc2_scale is None:
+        raise ValueError(f"{who}: a {fc2wT.dtype} fc2wT (MXFP4) needs fc2_scale, its e8m0 block scales [F, N / 32] (W4LinearT.block_scale_t)")
+    if fc2_scale.dtype not in MXFP4_SCALES:
+        raise ValueError(f"{who}: fc2_scale of a {fc2wT.dtype} fc2wT (MXFP4) must be its e8m0 block scales, uint8 or float8_e8m0fnu; got "
+                         f"{fc2_scale.dtype}")
+    if sparse_act_packed.dtype != torch.bfloat16 or cached_out.dtype != torch.bfloat16:
+        raise ValueError(f"{who}: with an MXFP4 fc2wT sparse_act_packed and cached_out must be bfloat16 (got {sparse_act_packed.dtype} and "
+                         f"{cached_out.dtype})")
+    F, N = sparse_act_packed.shape[-1], cached_out.shape[-1]
+    if N % 128:
+        raise ValueError(f"{who}: cached_out must have N % 128 == 0 columns for an MXFP4 fc2wT (got N = {N})")
+    if fc2wT.ndim != 2 or tuple(fc2wT.shape) != (F, N // 2):
+        raise ValueError(f"{who}: an MXFP4 fc2wT must be [F, N / 2] = {(F, N // 2)}, two e2m1 elements a byte; got {tuple(fc2wT.shape)}")
+    if tuple(fc2_scale.shape) != (F, N // 32):
+        raise ValueError(f"{who}: fc2_scale must be [F, N / 32] = {(F, N // 32)}, one e8m0 byte per 32 columns; got {tuple(fc2_scale.shape)}")
+    if fc2wT.device != sparse_act_packed.device or fc2_scale.device != sparse_act_packed.device:
+        raise ValueError(f"{who}: fc2wT and fc2_scale must be on the device of sparse_act_packed ({sparse_act_packed.device}); got "
+                         f"{fc2wT.device} and {fc2_scale.device}")
+
+
 def _mm2_w8_after_gemm1(sparse_act_packed: torch.Tensor, fc2w_T: torch.Tensor, fc2_scale: Optional[torch.Tensor], indices: torch.Tensor,
                         counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int) -> None:
-    """The tail of a sparse step with an e4m3 ``fc2w_T`` whose GEMM1 left the cache alone: the scatter-add of the packed deltas, then the
-    weight-only fp8 GEMM2 (``csp_mlp_mm2_and_scatter_add`` is bf16-only)."""
+    """The tail of a sparse step with an e4m3 or MXFP4 ``fc2w_T`` whose GEMM1 left the cache alone: the scatter-add of the packed deltas,
+    then the weight-only GEMM2 (``csp_mlp_mm2_and_scatter_add`` is bf16-only)."""
     scatter_add(sparse_act_packed, sparse_act_T, indices, counts, num_sms_scatter_add)
     csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
 
@@ -326,7 +358,7 @@ def _after_gemm1(cache_updated: bool, sparse_act_packed: torch.Tensor, fc2w_T: t
     elif group_major(sparse_act_packed, sparse_act_T):   # csp_mlp_mm2_and_scatter_add knows the column-major cache only
         scatter_add_gm(sparse_act_packed, sparse_act_T, indices, counts)
         csp_mlp_mm2(sparse_act_packed, fc2w_T, indices, counts, cached_out, fc2_scale=fc2_scale)
-    elif fc2w_T.dtype == torch.float8_e4m3fn:
+    elif fc2w_T.dtype == torch.float8_e4m3fn or fc2w_T.dtype in MXFP4_WEIGHTS:
         _mm2_w8_after_gemm1(sparse_act_packed, fc2w_T, fc2_scale, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add)
     elif USE_FUSED_MLP_MATMUL_2:
         mm2_fused(sparse_act_packed, sparse_act_T, indices, counts, sparse_act_packed, fc2w_T, cached_out, num_sms_scatter_add)
@@ -350,6 +382,8 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
     # cached_out [B, M, N] -- one launch per kernel for all B sequences, the bits of B calls on the slices.
     # fc2w_T float8_e4m3fn with fc2_scale (F8Linear.scale_reciprocal): the scatter-add is GEMM1's own (or csp_scatter_add with
     # mlp.fused_scatter off) and GEMM2 gathers e4m3 rows.
+    # fc2w_T uint8 / float4_e2m1fn_x2 [F, N / 2] with fc2_scale uint8 / float8_e8m0fnu [F, N / 32] (W4LinearT.weight_t / .block_scale_t): MXFP4,
+    # GEMM2 is csp_mlp_mm2_w4 in the same place.
     # mm1_scale_a / mm1_scale_b (fp8 fc1): one number each, or mm1_scale_a [M] ([B, M]) -- one per token row -- with mm1_scale_b [F] -- one
     # per fc1 column (csp_mlp_mm1_fp8_act_rs in GEMM1's place); a mixed pair raises.
     # act (one of GLU_ACTS) names fc1's activation and fc1b may be None: anything but tanh-GELU with a bias takes csp_mlp_mm1_act /

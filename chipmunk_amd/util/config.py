@@ -148,6 +148,12 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # every selecting step.  More rows, other dtypes, in_features % 128 != 0 or out_features % 8 != 0 take the widened path.  0 = off: the
     # widened path always.
     "mlp.w4_stream_rows": 0,
+    # MXFP4 fc2 (not in the reference): SparseDiffMlp / SparseDiffGatedMlp accept a W4LinearT fc2 -- fc2.weight^T [F, N2 / 2] packed e2m1 with
+    # one e8m0 scale per 32 OUTPUT features [F, N2 / 32], out_features % 128 == 0, stored once: the sparse steps' GEMM2 gathers those rows
+    # (csp_mlp_mm2_w4: the bits of the bf16 GEMM2 on the widened weight) and no transposed copy is kept.  With mlp.fp8_weight_only on as well,
+    # recursive_swap_linears builds fc2 of a sparse image MLP as a W4LinearT.  The blocks run along out_features, which is NOT the orientation
+    # of an OCP MXFP4 checkpoint's fc2: such a weight has to be requantised (W4LinearT.from_linear).  Off by default: nothing changes.
+    "mlp.mxfp4_fc2": False,
     # mask step with a key count per (batch, head, 192-query group) (not in the reference; should_compress_indices only): a sparse group keeps
     # the smallest top set of keys that carries this share of its column-sum mass (the group's summed softmax probabilities), never more
     # than the top_keys count -- a head whose mass sits on few keys stores and gathers fewer.  0.0 = off: exactly top_keys keys per group.

@@ -342,6 +342,21 @@ int chipmunk_csp_mlp_mm2_w8(const void *mma_a, const void *mma_b, const float *s
 int chipmunk_csp_mlp_mm2_w8_batched(const void *mma_a, const void *mma_b, const float *scale_b, void *mma_c, const int32_t *indices,
                                     const int32_t *counts, int M, int F, int N2, int B, void *stream);
 
+/* MXFP4 fc2: GEMM (ii) over MXFP4 rows of fc2^T (weight-only, no reference counterpart).  mma_a [M,F] bf16 packed deltas; mma_b [F,N2/2]
+ * bytes, row f = column f of fc2.weight, element 2j of the row in bits 0..3 of byte j and element 2j+1 in bits 4..7 (OCP e2m1); scale_b
+ * [F,N2/32] bytes (OCP e8m0): byte j of row f scales elements 32j .. 32j+31 of that row by 2^(s - 127) -- the scale blocks run along N2,
+ * NOT along the reduction; mma_c [M,N2] bf16:
+ *   mma_c[m,:] = bf16( bf16( sum_{c < counts[g]} mma_a[m,c] * wide(mma_b)[indices[g,c],:] ) + mma_c[m,:] ),  wide = e2m1 * 2^(s - 127)
+ * wide() is exact in bf16 and the sum is chipmunk_csp_mlp_mm2's, in fp32: the result has the bits of chipmunk_csp_mlp_mm2 on the widened
+ * weight.  A scale byte 255 (e8m0's NaN) and widened values that are subnormal in bf16 are outside the contract.  Any M > 0, indices /
+ * counts / groups as for chipmunk_csp_mlp_mm2[_ragged|_batched]; N2 a positive multiple of 128; mma_b 16-byte and scale_b 4-byte aligned;
+ * M*F, F*N2 and M*N2 below 2^31 per sequence; *_batched: B sequences, B * ceil(M/128) <= 65535.  Violations return CHIPMUNK_ERR_INVALID
+ * before any launch. */
+int chipmunk_csp_mlp_mm2_w4(const void *mma_a, const void *mma_b, const uint8_t *scale_b, void *mma_c, const int32_t *indices,
+                            const int32_t *counts, int M, int F, int N2, void *stream);
+int chipmunk_csp_mlp_mm2_w4_batched(const void *mma_a, const void *mma_b, const uint8_t *scale_b, void *mma_c, const int32_t *indices,
+                                    const int32_t *counts, int M, int F, int N2, int B, void *stream);
+
 /* fp8 fc1, weight-only: chipmunk_csp_mlp_mm1_act[_batched|_gm] over an e4m3 weight with bf16 activations (no reference counterpart).
  * a [M,K] bf16; b [F,K] OCP e4m3 bytes (float8_e4m3fn), plain row-major; scale_b fp32 on the device, the weight's RECIPROCAL
  * quantisation scale: one number (scale_n == 1) or one per row of b (scale_n == F, read at the GATHERED column i = idx[g,j]):

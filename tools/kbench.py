@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_glu_w8 w8_probe w8_probe_wan w8_probe_hunyuan w4_probe w4_probe_wan w4_probe_hv scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm2_w4 mm2_w4_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_glu_w8 w8_probe w8_probe_wan w8_probe_hunyuan w4_probe w4_probe_wan w4_probe_hv scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -297,6 +297,58 @@ def bench_mm2_w8(M=4352, F=12288, N2=3072, keep=3840):
     print(f"mm2_w8  e4m3 rows: {med['w8']:8.1f} us  [{min(t['w8']):.1f} .. {max(t['w8']):.1f}]  {flops/med['w8']/1e6:7.1f} TFLOP/s   {tag}")
     print(f"mm2     bf16 rows: {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]  {flops/med['bf16']/1e6:7.1f} TFLOP/s")
     print(f"mm2_w8 / mm2     : {med['w8'] / med['bf16']:8.3f}")
+
+
+def bench_mm2_w4(M=4352, F=12288, N2=3072, keep=3840):
+    """The MXFP4 GEMM2 (csp_mlp_mm2_w4: packed e2m1 rows of fc2^T with the e8m0 scales of their 32-column blocks) against the bf16
+    csp_mlp_mm2 on the widened weight (the same bits) and against csp_mlp_mm2_w8, on the same packed deltas and index lists.  Same
+    process, the three alternating (KB_ROUNDS rounds, default 5); per launch the median bracket of `timeit`, then the median and the range
+    over the rounds.  KB_LAYERS=n rotates n sets of weights / deltas / outputs (n = 8: the weight rows come from HBM)."""
+    from chipmunk_amd.modules.mlp_fp8 import W4LinearT, quantize_mxfp4
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    sets = []
+    for _ in range(L):
+        w = torch.randn(F, N2, device=dev, generator=g) * 0.02
+        q = W4LinearT.from_mx_t(*quantize_mxfp4(w))
+        w8 = (w * 512).clamp(-448, 448).to(torch.float8_e4m3fn)
+        packed = torch.randn(M, F, device=dev, dtype=torch.bfloat16, generator=g) * 0.1
+        sets.append((q.widened().t().contiguous(), w8, q.weight_t.data, q.block_scale_t, packed,
+                     torch.zeros(M, N2, device=dev, dtype=torch.bfloat16)))
+    sb = torch.tensor([1 / 512.0], device=dev)
+    G = (M + 127) // 128
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_w4():
+        _, _, w4, s4, packed, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm2_w4(packed, w4, s4, inds, counts, out)
+
+    def run_w8():
+        _, w8, _, _, packed, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm2_w8(packed, w8, sb, inds, counts, out)
+
+    def run_bf16():
+        w16, _, _, _, packed, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm2(packed, w16, inds, counts, out)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    runs = {"w4": run_w4, "bf16": run_bf16, "w8": run_w8}
+    t = {k: [] for k in runs}
+    for _ in range(rounds):
+        for k, fn in runs.items():
+            t[k].append(timeit(fn) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * N2 * keep
+    tag = f"(M={M} F={F} N2={N2} keep={keep} layers={L}, {rounds} alternating rounds)"
+    for k, name in (("w4", "mm2_w4  MXFP4 rows"), ("bf16", "mm2     widened   "), ("w8", "mm2_w8  e4m3 rows ")):
+        print(f"{name}: {med[k]:8.1f} us  [{min(t[k]):.1f} .. {max(t[k]):.1f}]  {flops/med[k]/1e6:7.1f} TFLOP/s   {tag if k == 'w4' else ''}")
+    print(f"mm2_w4 / mm2      : {med['w4'] / med['bf16']:8.3f}")
+    print(f"mm2_w8 / mm2      : {med['w8'] / med['bf16']:8.3f}")
 
 
 def bench_mm1_w4(M=4352, K=3072, F=12288, keep=3840):
@@ -926,6 +978,10 @@ def main():
             bench_w4_probe(M=256, K=1536, F=8960)
         elif w == "w4_probe_hv":      # ... at the HunyuanVideo probe shape [931, 3072] -> 12288
             bench_w4_probe(M=931, K=3072, F=12288)
+        elif w == "mm2_w4":           # MXFP4 GEMM2 against the bf16 GEMM2 on the widened weight and the e4m3 GEMM2, FLUX shape
+            bench_mm2_w4()
+        elif w == "mm2_w4_wan":       # ... at the Wan2.1 1.3B shape
+            bench_mm2_w4(M=32760, F=8960, N2=1536, keep=2816)
         elif w == "mm2_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), N2 = 1 536, F = 8 960, 2 816 kept
             bench_mm2_w8(M=32760, F=8960, N2=1536, keep=2816)
         elif w == "fp8_wan":
