@@ -238,6 +238,11 @@ struct Mm1W4Params : Mm1Params {
 };
 // LDS bytes of one ring stage of the MXFP4 form: the A tile, TN row pieces of BK / 2 bytes (+ 16 bytes per 64 rows for the odd pieces' shift),
 // 256 bytes of scale dwords per 32-row fragment, rounded up to 1 KiB (the full tile's 22 KiB stage is then 88 whole output rows: FLAT below)
+// The gated MXFP4 form (mm1_glu_w4_kernel): b / b_up are the packed e2m1 gate / up weights [F, K / 2] (b_up / bias_up in the union slots as in the
+// gated bf16 form: the shared block keeps its size), each with e8m0 block scales [F, K / 32] of its own.
+struct Mm1GluW4Params : Mm1Params {
+    const uint8_t *scale_gate_e8, *scale_up_e8;
+};
 constexpr int mm1_w4_stage(int TM, int TN, int BK) { return (TM * BK * 2 + TN * BK / 2 + TN / 64 * 16 + TN / 32 * 256 + 1023) & ~1023; }
 
 // One TM x TN output tile (TM rows of group g starting at m_off, packed columns n0 .. n0+TN-1): 4 waves as 2 x 2, each a
@@ -305,14 +310,26 @@ constexpr int mm1_w4_stage(int TM, int TN, int BK) { return (TM * BK * 2 + TN * 
 //   need no address of their own.  The byte of slice kk is (kb & 1) * 2 + (kk >> 1); shifted into a float's exponent field it is 2^(s - 127).
 //   A 64 x 64 sub-tile has two pieces and two fragments: waves 2 / 3 issue the pieces of waves 0 / 1 again (the same bytes to the same place), so
 //   that every wave counts the same vmcnt.  Full tile: 3 stages of 22 KiB, FLAT epilogue (EPI = 32 KiB; FLAT_SKIP = EPI exactly).
+// GLU && W4 (mm1_glu_w4_kernel; P = Mm1GluW4Params): the two composed -- W4's B image, scale image and convert-at-load k loop under GLU's row split
+// and two-accumulator epilogue (bias seeds, fma(act(g), u, -cache)): csp_mlp_mm1_glu on the two widened weights, bit for bit.  Unlike W8's, a W4 DMA
+// piece spans BOTH fragments of its pair (lane >> 5), and in the gated form pair wn is {gate fragment, up fragment}: lanes 0 .. 31 of every piece
+// gather from b_gate, lanes 32 .. 63 from b_up, and a buffer instruction has one descriptor.  The image stays where it is (the reader's row 64 wn +
+// 32 n4 + (lane & 31) is the same expression in both forms, so placement, 8-byte shift and the bank argument hold); the piece is ISSUED as two
+// half-wave LDS-DMAs to the same wave base, lane half i alone in EXEC under descriptor i, each writing its lanes' 512 bytes of the lane-linear KiB.
+// B_INST = 2: a stage is 4 + 2 + 1 = 7 instructions a wave, which is what the counted vmcnt is made of.  Supposed from the ISA document and proven
+// by the bit tests (tests/test_gpu_mlp_glu_w4.py): a lane masked off in EXEC leaves its LDS bytes alone, and the instruction still counts once.
+// The scale dwords of fragment w (pair w >> 1, half w & 1) come under the wave-uniform gate or up scale descriptor.  EPI = 16 KiB <= the 22 KiB
+// stage: the plain staged epilogue, the cache block in stage (last + 2) % 3, free since the barrier of the last k step.
 template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params, bool NULLB = false,
           bool RS = false, bool W8 = false, bool W4 = false>
 __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
     static_assert(!RS || (FP8 && !GLU && NULLB), "row / column scale vectors: the ungated fp8 form with a nullable bias (mm1_form_kernel) only");
     static_assert(!W8 || (!FP8 && !RS && (GLU || NULLB) && NW == 4 && BK == 64), "the weight-only form: bf16 a, 4 waves, 64-byte B row pieces");
     static_assert(!(W8 && GLU) || std::is_base_of<Mm1GluW8Params, P>::value, "the gated weight-only form reads its scales from Mm1GluW8Params");
-    static_assert(!W4 || (!FP8 && !RS && !GLU && !W8 && NULLB && NW == 4 && BK == 64 && (TN == 128 || TN == 64) && std::is_base_of<Mm1W4Params, P>::value),
-                  "the MXFP4 form: bf16 a, ungated, 4 waves, 32-byte B row pieces, one or two pairs of pieces");
+    static_assert(!W4 || (!FP8 && !RS && (GLU ? TN == 128 : NULLB) && !W8 && NW == 4 && BK == 64 && (TN == 128 || TN == 64) &&
+                          (GLU || std::is_base_of<Mm1W4Params, P>::value)),
+                  "the MXFP4 form: bf16 a, 4 waves, 32-byte B row pieces, one or two pairs of pieces (gated: two)");
+    static_assert(!(W4 && GLU) || std::is_base_of<Mm1GluW4Params, P>::value, "the gated MXFP4 form reads its scales from Mm1GluW4Params");
     using KT = KTile<BK>;
     using KTB = KTile<W8 ? BK / 2 : BK>;     // the B tile's geometry
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
@@ -321,7 +338,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     constexpr int B_PAIR = 2048 + 16;              // (W8, W4: bytes a pair of pieces owns)
     constexpr int A_TILE = TM * BK * 2, B_TILE = W4 ? TN * BK / 2 + B_PAD : TN * BK * (int)(W8 ? 1 : 2) + B_PAD;
     constexpr int STAGE = W4 ? mm1_w4_stage(TM, TN, BK) : A_TILE + B_TILE;
-    constexpr int A_INST = A_TILE / (1024 * NW), B_INST = W4 ? 1 : (B_TILE - B_PAD) / (1024 * NW);  // DMA instructions per wave per tile
+    constexpr int A_INST = A_TILE / (1024 * NW), B_INST = W4 ? (GLU ? 2 : 1) : (B_TILE - B_PAD) / (1024 * NW);  // DMA instructions per wave per tile (GLU && W4: one piece as two half-wave instructions)
     constexpr int S_INST = W4 ? 1 : 0;             // (W4: and one dword instruction for the scale bytes)
     constexpr int NFR = TN / 32;                   // (W4: DMA pieces of the B tile = its 32-row fragments)
     constexpr int WNC = NW / 2;                                     // waves across the tile's columns (2 down its rows)
@@ -353,7 +370,9 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     for (int i = 0; i < B_INST; ++i) {
         if constexpr (W4) {   // piece w % NFR: rows [16 odd, + 16) of both fragments of its pair, lane = (fragment, k chunk, row16)
             const int pc = w % NFR, row = (pc >> 1) * 64 + (lane >> 5) * 32 + (pc & 1) * 16 + (lane & 15);
-            const int j = n0 + row;
+            // gated: fragment lane >> 5 of pair pc >> 1 is the gate (0) or the up (1) rows of packed columns n0 + 32 (pc >> 1) + (row & 31); both of
+            // the piece's instructions carry the lane's one offset
+            const int j = GLU ? n0 + (pc >> 1) * 32 + (row & 31) : n0 + row;
             boff[i] = (uint32_t)idxg[j < cnt ? j : n0] * (uint32_t)(p.K >> 1) + ((lane >> 4) & 1) * 16u;
         } else {
         const int row = KTB::lane_row(w * B_INST + i, lane);
@@ -364,7 +383,11 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     }
     [[maybe_unused]] uint32_t soff = 0;   // (W4: byte offset of the scale bytes of the lane's row of fragment w % NFR; lanes l and l + 32 the same row)
     [[maybe_unused]] __amdgpu_buffer_rsrc_t rs = rb;
-    if constexpr (W4) {
+    if constexpr (W4 && GLU) {   // fragment w = pair w >> 1, half w & 1: the gate's or the up projection's scales, wave-uniform
+        const int j = n0 + (w >> 1) * 32 + (lane & 31);
+        soff = (uint32_t)idxg[j < cnt ? j : n0] * (uint32_t)(p.K >> 5);
+        rs = make_rsrc((w & 1) ? p.scale_up_e8 : p.scale_gate_e8);
+    } else if constexpr (W4) {
         const int j = n0 + (w % NFR) * 32 + (lane & 31);
         soff = (uint32_t)idxg[j < cnt ? j : n0] * (uint32_t)(p.K >> 5);
         rs = make_rsrc(p.scale_e8);
@@ -375,7 +398,13 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         for (int i = 0; i < A_INST; ++i) blds16(ra, aoff[i], kb * BK * 2, st + (w * A_INST + i) * 1024);
 #pragma unroll
         for (int i = 0; i < B_INST; ++i) {
-            if constexpr (W4) {   // 32 bytes of a row per k step; the odd piece of a pair lands 8 bytes up.  Then the dword of scale bytes of this
+            if constexpr (GLU && W4) {   // W4's piece w, but its lanes 0 .. 31 (fragment 0 of the pair: gate rows) and 32 .. 63 (fragment 1: up rows)
+                                         // gather under different descriptors: instruction i runs with lane half i alone in EXEC and writes that
+                                         // half's 512 bytes of the lane-linear KiB (a masked lane's LDS bytes are left alone; each instruction
+                                         // counts once in vmcnt).  The scale dword follows the piece's second half.
+                if ((lane >> 5) == i) blds16(i ? rb_up : rb, boff[i], kb * (BK / 2), st + A_TILE + (w >> 1) * B_PAIR + (w & 1) * (1024 + 8));
+                if (i == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(st + A_TILE + B_TILE + w * 256), 4, (int)soff, (kb >> 1) * 4, 0, 0);
+            } else if constexpr (W4) {   // 32 bytes of a row per k step; the odd piece of a pair lands 8 bytes up.  Then the dword of scale bytes of this
                                   // step's 128-k block: the same DMA path as the weights, no register load in the loop
                 const int pc = w % NFR;
                 blds16(rb, boff[i], kb * (BK / 2), st + A_TILE + (pc >> 1) * B_PAIR + (pc & 1) * (1024 + 8));
@@ -1048,6 +1077,48 @@ __global__ __launch_bounds__(256, WPS) void mm1_glu_w8_kernel(const typename std
         }
         mm1_tile<BM, BN, BK, NST, false, 4, true, ACT, P, false, false, true>(q, smem, g, 0, tm.nt * PBN, cnt);
         __syncthreads();   // the next tile's DMA lands where this tile's epilogue was reading
+    }
+}
+
+// Gated MXFP4 gate / up (mm1_tile's GLU && W4 form): c = bf16(fma(act(g), u, -cache[i, m])), g = a . Wg[i, :] + bias[i] with Wg[i, k] =
+// e2m1(b[i, k]) * 2^(scale_gate_e8[i, k / 32] - 127), u the same over b_up / scale_up_e8 / bias_up -- csp_mlp_mm1_glu on the two widened weights,
+// bit for bit.  mm1_glu_w8_kernel's walk (a whole tile is BN / 2 packed columns, no tail split, ragged last group, batch advance) over 3 stages
+// of mm1_w4_stage bytes; the plain staged epilogue (16 KiB of cache block and of outputs, one 22 KiB stage each).  Built without the packed
+// fp32 forms like mm1_w4_kernel (see there): the barrier of the walk is written out.
+struct Mm1GluW4Batch : Mm1GluW4Params {
+    int B;
+    int64_t cache_bs;   // as Mm1Batch
+};
+template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED>
+__global__ __launch_bounds__(256, WPS) __attribute__((target("no-packed-fp32-ops"))) void mm1_glu_w4_kernel(const typename std::conditional<BATCHED, Mm1GluW4Batch, Mm1GluW4Params>::type p) {
+    using P = Mm1GluW4Params;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int PBN = BN / 2;           // packed columns of a whole tile: the B tile's BN rows are {gate, up} pairs
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
+    const TilePlan pl = plan_tiles<PBN>(p.counts, G, p.NT, p.NR, 0, 1);   // (no tail split)
+    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+        const TileMap tm = tile_at(pl, slot);
+        if (!tm.live) continue;
+        const int cnt = p.counts[tm.g];
+        if (tm.nt * PBN >= cnt) continue;  // tiles past counts[g] are skipped
+        int g = tm.g;
+        typename std::conditional<BATCHED, P, const P &>::type q = p;   // the tile sees its sequence's operands (one sequence: the kernel's own block)
+        if constexpr (BATCHED) {
+            const int seq = tm.g / Gs;
+            g = tm.g - seq * Gs;                      // group inside sequence seq
+            q.a = p.a + (int64_t)seq * p.M * p.K;
+            q.c = p.c + (int64_t)seq * p.M * p.F;
+            q.cache = p.cache + (int64_t)seq * p.cache_bs;
+            q.indices = p.indices + (int64_t)seq * Gs * p.F;
+        }
+        mm1_tile<BM, BN, BK, NST, false, 4, true, ACT, P, false, false, false, true>(q, smem, g, 0, tm.nt * PBN, cnt);
+        // (the next tile's DMA lands where this tile's epilogue was reading; written out as in mm1_w4_kernel)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
 }
 #endif   // CHIPMUNK_MM1_PROBES
@@ -2700,7 +2771,100 @@ int mm1_w4_entry(const void *a, const void *b, const uint8_t *scale_b, void *c, 
     return B > 0 ? launch_mm1_w4<true>(p, act, stream, B, cache_bs) : launch_mm1_w4<false>(p, act, stream, 1, 0);
 #endif
 }
+
+// Gated MXFP4 gate / up: mm1_glu_w4_kernel at its one tile shape -- <128 B rows = 64 packed columns, k step 64, 3 stages, 2 workgroups per CU> --,
+// the grid as launch_mm1_glu_w8_kernel sets it (no tail split)
+#ifndef CHIPMUNK_MM1_PROBES
+template <int ACT, bool BATCHED>
+int launch_mm1_glu_w4_kernel(Mm1GluW4Params p, hipStream_t s, int B, int64_t cache_bs) {
+    constexpr int BN = 128, BK = 64, NST = 3, WPS = 2;
+    constexpr int PBN = BN / 2;   // packed columns per whole tile
+    constexpr int LDS = NST * mm1_w4_stage(BM, BN, BK);
+    static_assert(LDS <= 80 * 1024, "two workgroups share a CU's 160 KiB");
+    static_assert(BM * PBN * 2 <= LDS / NST, "the staged epilogue: cache block and output image fit one stage each");
+    auto kern = mm1_glu_w4_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+    static uint64_t lds_set = 0;
+    ensure_dynamic_lds((const void *)kern, LDS, lds_set);
+    p.NT = (p.F + PBN - 1) / PBN;
+    const int nr_option = chipmunk_get_option("mm1_nr");   // column tiles per walk: launch_mm1_variant's
+    p.NR = nr_option > 0 ? nr_option : 4;
+    if (p.NR > p.NT) p.NR = p.NT;
+    p.slots_per_xcd = 0;   // (the gated form has no tail split)
+    const int resident_per_xcd = WPS * device_cu_count() / 8;
+    const int tiles_per_xcd = (B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8;
+    const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
+    if constexpr (BATCHED) {
+        Mm1GluW4Batch q;
+        static_cast<Mm1GluW4Params &>(q) = p;
+        q.B = B, q.cache_bs = cache_bs;
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(256), LDS, s, q);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(256), LDS, s, p);
+    }
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+template <bool BATCHED>
+int launch_mm1_glu_w4(const Mm1GluW4Params &p, int act, hipStream_t s, int B, int64_t cache_bs) {
+    switch (act) {
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_glu_w4_kernel<0, BATCHED>(p, s, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_glu_w4_kernel<1, BATCHED>(p, s, B, cache_bs);
+        default: return launch_mm1_glu_w4_kernel<2, BATCHED>(p, s, B, cache_bs);
+    }
+}
+#endif
+
+// B > 0: the *_batched entry; gm: the *_gm entry, as mm1_w8_entry
+int mm1_glu_w4_entry(const void *a, const void *b_gate, const void *b_up, const uint8_t *scale_gate, const uint8_t *scale_up, void *c,
+                     const void *bias_gate, const void *bias_up, void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K,
+                     int F, int ldc, int act, int update_cache, hipStream_t stream, int B = 0, int64_t cache_bs = 0, bool gm = false) {
+#ifdef CHIPMUNK_MM1_PROBES
+    CM_CHECK(false, "csp_mlp_mm1_glu_w4: not part of the probe-forms build");
+#else
+    CM_CHECK(a, "csp_mlp_mm1_glu_w4: a is null");
+    CM_CHECK(b_gate && b_up, "csp_mlp_mm1_glu_w4: b_gate or b_up is null");
+    CM_CHECK(scale_gate && scale_up, "csp_mlp_mm1_glu_w4: scale_gate or scale_up is null");
+    CM_CHECK(c, "csp_mlp_mm1_glu_w4: c is null");
+    CM_CHECK(pa_cache, "csp_mlp_mm1_glu_w4: pa_cache is null");
+    CM_CHECK((((uintptr_t)b_gate | (uintptr_t)b_up | (uintptr_t)scale_gate | (uintptr_t)scale_up) & 3) == 0,
+             "csp_mlp_mm1_glu_w4: b_gate, b_up, scale_gate and scale_up must be 4-byte aligned");
+    // (K % 128: a row's e8m0 bytes are whole dwords, the unit they travel in)
+    if (int e = check_mm1("csp_mlp_mm1_glu_w4", true, indices, counts, M, K, F, ldc, B, cache_bs, 128, true, act, update_cache, 1, gm)) return e;
+    Mm1GluW4Params p;
+    static_cast<Mm1Params &>(p) = {(const uint16_t *)a, (const uint16_t *)b_gate, (const uint16_t *)bias_gate, (uint16_t *)pa_cache,
+                                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
+    p.b_up = (const uint16_t *)b_up, p.bias_up = (const uint16_t *)bias_up;
+    p.scale_gate_e8 = scale_gate, p.scale_up_e8 = scale_up;
+    if (gm) p.gs = F * BM, B = B == 1 ? 0 : B;
+    return B > 0 ? launch_mm1_glu_w4<true>(p, act, stream, B, cache_bs) : launch_mm1_glu_w4<false>(p, act, stream, 1, 0);
+#endif
+}
 }  // namespace
+
+// ---- gated MXFP4 gate / up (include/chipmunk_hip.h, "gated MXFP4, weight-only")
+extern "C" int chipmunk_csp_mlp_mm1_glu_w4(const void *a, const void *b_gate, const void *b_up, const uint8_t *scale_gate,
+                                           const uint8_t *scale_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
+                                           const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
+                                           int update_cache, void *stream) {
+    return mm1_glu_w4_entry(a, b_gate, b_up, scale_gate, scale_up, c, bias_gate, bias_up, pa_cache, indices, counts, M, K, F, ldc, act,
+                            update_cache, (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_glu_w4_batched(const void *a, const void *b_gate, const void *b_up, const uint8_t *scale_gate,
+                                                   const uint8_t *scale_up, void *c, const void *bias_gate, const void *bias_up,
+                                                   void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc,
+                                                   int act, int update_cache, int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_glu_w4_entry(a, b_gate, b_up, scale_gate, scale_up, c, bias_gate, bias_up, pa_cache, indices, counts, M, K, F, ldc, act,
+                            update_cache, (hipStream_t)stream, B, cache_batch_stride);
+}
+extern "C" int chipmunk_csp_mlp_mm1_glu_w4_gm(const void *a, const void *b_gate, const void *b_up, const uint8_t *scale_gate,
+                                              const uint8_t *scale_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
+                                              const int32_t *indices, const int32_t *counts, int M, int K, int F, int act, int update_cache,
+                                              int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_glu_w4_entry(a, b_gate, b_up, scale_gate, scale_up, c, bias_gate, bias_up, pa_cache, indices, counts, M, K, F, BM, act,
+                            update_cache, (hipStream_t)stream, B, cache_batch_stride, true);
+}
 
 // ---- weight-only MXFP4 fc1 (include/chipmunk_hip.h, "MXFP4 fc1, weight-only")
 extern "C" int chipmunk_csp_mlp_mm1_w4(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,

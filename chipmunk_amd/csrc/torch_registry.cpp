@@ -788,6 +788,46 @@ void csp_mlp_mm1_glu_w8(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Te
                                           pa_cache.data_ptr(), ip, cp, M, K, F, ldc, code, upd, cur_stream(a)), who);
 }
 
+// addition: csp_mlp_mm1_glu over MXFP4 gate / up weights with bf16 activations (chipmunk_csp_mlp_mm1_glu_w4): b_gate / b_up uint8 [F, K / 2], two
+// e2m1 elements a byte; scale_gate / scale_up uint8 [F, K / 32], one e8m0 byte per 32 k.  The bits of csp_mlp_mm1_glu on the widened weights.
+void csp_mlp_mm1_glu_w4(at::Tensor a, at::Tensor b_gate, at::Tensor b_up, at::Tensor scale_gate, at::Tensor scale_up, at::Tensor c,
+                        const c10::optional<at::Tensor> &bias_gate, const c10::optional<at::Tensor> &bias_up, at::Tensor pa_cache,
+                        at::Tensor indices, at::Tensor counts, std::string act, bool update_cache) {
+    const char *who = "csp_mlp_mm1_glu_w4";
+    CHECK_DEV(a); CHECK_DEV(b_gate); CHECK_DEV(b_up); CHECK_DEV(scale_gate); CHECK_DEV(scale_up); CHECK_DEV(c); CHECK_DEV(pa_cache);
+    CHECK_DEV(indices); CHECK_DEV(counts);
+    CHECK_BF16(a); CHECK_BF16(c); CHECK_BF16(pa_cache);
+    CHECK_I32(indices); CHECK_I32(counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(c); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
+    const int64_t Kw = a.size(-1);
+    TORCH_CHECK(Kw % 128 == 0, who, ": K must be a multiple of 128 (got ", Kw, ")");
+    for (const at::Tensor *b : {&b_gate, &b_up})
+        TORCH_CHECK(b->scalar_type() == at::kByte && b->dim() == 2 && b->size(0) == b_gate.size(0) && b->size(1) * 2 == Kw && b->is_contiguous() &&
+                        b->device() == a.device(),
+                    who, ": b_gate and b_up must be contiguous uint8 tensors [F, K / 2] on the device of a (two e2m1 elements a byte)");
+    for (const at::Tensor *s : {&scale_gate, &scale_up})
+        TORCH_CHECK(s->scalar_type() == at::kByte && s->dim() == 2 && s->size(0) == b_gate.size(0) && s->size(1) * 32 == Kw && s->is_contiguous() &&
+                        s->device() == a.device(),
+                    who, ": scale_gate and scale_up must be contiguous uint8 tensors [F, K / 32] on the device of a (one e8m0 byte per 32 k)");
+    const Mm1Shape sh = mm1_shape(a, b_gate, c, nullptr, pa_cache, indices, counts, true, 2);
+    const void *bg = optional_bias(bias_gate, "bias_gate", sh.F), *bu = optional_bias(bias_up, "bias_up", sh.F);
+    const int code = act_code(who, act);
+    c10::DeviceGuard guard(a.device());
+    int *ip = indices.data_ptr<int>(), *cp = counts.data_ptr<int>();
+    const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc, upd = update_cache ? 1 : 0;
+    const uint8_t *gp = scale_gate.data_ptr<uint8_t>(), *up = scale_up.data_ptr<uint8_t>();
+    if (sh.gm)
+        check(chipmunk_csp_mlp_mm1_glu_w4_gm(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), gp, up, c.data_ptr(), bg, bu, pa_cache.data_ptr(),
+                                             ip, cp, M, K, F, code, upd, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_glu_w4_batched(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), gp, up, c.data_ptr(), bg, bu,
+                                                  pa_cache.data_ptr(), ip, cp, M, K, F, ldc, code, upd, (int)sh.B, sh.cache_bs, cur_stream(a)),
+              who);
+    else
+        check(chipmunk_csp_mlp_mm1_glu_w4(a.data_ptr(), b_gate.data_ptr(), b_up.data_ptr(), gp, up, c.data_ptr(), bg, bu, pa_cache.data_ptr(),
+                                          ip, cp, M, K, F, ldc, code, upd, cur_stream(a)), who);
+}
+
 // addition: the weight-only fp8 linear layer for few rows (chipmunk_w8_linear): y = bf16(bf16((x f(w)^T) * scale_b) + bias), x [M, K] bf16 with
 // contiguous rows (any row pitch), w [F, K] e4m3, scale_b float32 with one element or [F], y [M, F] bf16 (any row pitch), written in place
 void w8_linear(at::Tensor x, at::Tensor w, at::Tensor scale_b, const c10::optional<at::Tensor> &bias, at::Tensor y) {
@@ -1704,6 +1744,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_w4(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_w8(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_w8(Tensor a, Tensor b_gate, Tensor b_up, Tensor scale_gate, Tensor scale_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
+    m.def("csp_mlp_mm1_glu_w4(Tensor a, Tensor b_gate, Tensor b_up, Tensor scale_gate, Tensor scale_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("w8_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
     m.def("w4_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
     m.def("csp_mlp_mm1_fp8_act(Tensor a, Tensor b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, Tensor scale_a, Tensor scale_b, str act, int update_cache) -> ()");
@@ -1788,6 +1829,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_w8", &csp_mlp_mm1_w8);
     m.impl("csp_mlp_mm1_w4", &csp_mlp_mm1_w4);
     m.impl("csp_mlp_mm1_glu_w8", &csp_mlp_mm1_glu_w8);
+    m.impl("csp_mlp_mm1_glu_w4", &csp_mlp_mm1_glu_w4);
     m.impl("w8_linear", &w8_linear);
     m.impl("w4_linear", &w4_linear);
     m.impl("csp_mlp_mm1_fp8_act", &csp_mlp_mm1_fp8_act);

@@ -19,6 +19,13 @@ Weight-only fp8 projections (``W8Linear``: two layers, or one fused ``[2F, K]`` 
 multiplies each branch's sum by its layer's ``scale_reciprocal`` (a fused layer's ``[2F]`` scale is split like its weight, a ``[]`` scale
 serves both halves).  Dense and full steps and the block-mean probe call the layers' own forward -- the bf16 linear layer over the widened
 weight, or ``ops.w8_linear`` for few rows under ``mlp.w8_stream_rows`` --, a fused layer once, its output split.
+
+MXFP4 projections (``W4Linear``: two layers, or one fused ``[2F, K / 2]`` layer; ``in_features % 128 == 0``) are taken with
+``mlp.mxfp4_gated`` on and run ``csp_mlp_mm1_glu_w4`` on the sparse steps: ``x`` stays bf16, GEMM1 gathers the packed e2m1 rows of both
+weights and their e8m0 block scales (a fused layer's weight, ``block_scale`` and bias are split into row views) -- the bits of the bf16
+gated GEMM1 on the two widened weights, no widened copy kept.  Dense and full steps and the probe call ``W4Linear.forward`` (which streams
+few rows under ``mlp.w4_stream_rows``), a fused layer once.  ``recursive_swap_linears`` / ``quantize_fp8`` build no gated MXFP4 layers:
+they know no gated module layout.
 """
 from __future__ import annotations
 
@@ -43,7 +50,8 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
     """``gate_proj`` / ``up_proj`` / ``fc2``: ``nn.Linear`` with or without bias, bf16 for the sparse steps; or ``gate_proj`` / ``up_proj``
     (or the fused ``fc1``) BOTH ``F8Linear`` with e4m3 weights and e4m3 inputs (``input_float8_dtype=torch.float8_e4m3fn``;
     ``F8Linear.from_linear`` defaults to e5m2, which the kernel does not read); or, with ``mlp.w8_gated`` on, BOTH ``W8Linear`` (weight-only
-    e4m3, bf16 inputs; a fused ``W8Linear`` likewise).  ``fc2`` is bf16 (GEMM2 gathers bf16 rows) or, with
+    e4m3, bf16 inputs; a fused ``W8Linear`` likewise); or, with ``mlp.mxfp4_gated`` on, BOTH ``W4Linear`` (MXFP4, bf16 inputs,
+    ``in_features % 128 == 0``; a fused ``W4Linear`` likewise).  ``fc2`` is bf16 (GEMM2 gathers bf16 rows) or, with
     ``mlp.fp8_fc2`` on, an ``F8Linear`` with e4m3 weights (GEMM2 gathers e4m3 rows, ``fc2.scale_reciprocal`` on its sums).
     With ``mlp.mxfp4_fc2`` on, a ``W4LinearT`` (``out_features % 128 == 0``): GEMM2 gathers packed e2m1 rows of ``fc2.weight_t`` itself.
     Their parameters are read at every call, so the model may be moved or cast after wrapping.  The sparse steps select columns with
@@ -70,10 +78,19 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
         self.act_code = activation_code(activation)      # raises for an activation the sparse steps could not honour
         self.projs = projs              # (lists keep the Linear modules out of any parent nn.Module's parameter registry)
         self.gate_first = gate_first    # None: two projections; True / False: the halves of projs[0], and which of them is the gate
-        if any(getattr(p, "weight_format", None) == "mxfp4" for p in projs):
-            raise ValueError("SparseDiffGatedMlp: a W4Linear projection (MXFP4) is refused: only the ungated GEMM1 has an MXFP4 form "
-                             "(csp_mlp_mm1_w4, fc1 of a SparseDiffMlp); keep the gate and up projections in bf16, or build them as F8Linear "
+        w4 = [getattr(p, "weight_format", None) == "mxfp4" for p in projs]
+        if any(w4) != all(w4):
+            raise ValueError("SparseDiffGatedMlp: a mixed pair -- one projection is a W4Linear (MXFP4), the other is not; the gated MXFP4 "
+                             "GEMM1 takes both projections as W4Linear")
+        if any(w4) and not amd_key("mlp", "mxfp4_gated"):
+            raise ValueError("SparseDiffGatedMlp: a W4Linear projection (MXFP4) is refused unless mlp.mxfp4_gated is on -- set it to run the "
+                             "gated MXFP4 GEMM1 (csp_mlp_mm1_glu_w4), or keep the gate and up projections in bf16, or build them as F8Linear "
                              "or W8Linear")
+        self.w4 = all(w4)               # MXFP4 projections: x stays bf16 (csp_mlp_mm1_glu_w4); checked in front of w8, W4Linear.weight_only is true
+        for p in projs if self.w4 else ():
+            if p.in_features % 128:
+                raise ValueError(f"SparseDiffGatedMlp: a W4Linear projection needs in_features % 128 == 0 (got {p.in_features}): the gated "
+                                 "MXFP4 GEMM1 moves a row's block-scale bytes as whole dwords, one per 128 k")
         gate, up = self.gate, self.up
         if gate[0].shape != up[0].shape or gate[0].ndim != 2:
             raise ValueError(f"SparseDiffGatedMlp: gate and up projections must have one shape [F, K] (got {tuple(gate[0].shape)} and "
@@ -81,7 +98,7 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
         fc2_in = fc2.in_features if is_mxfp4_t(fc2) else fc2.weight.shape[1]
         if fc2_in != gate[0].shape[0]:
             raise ValueError(f"SparseDiffGatedMlp: fc2 takes {fc2_in} features, the projections give {gate[0].shape[0]}")
-        w8 = [bool(getattr(p, "weight_only", False)) for p in projs]
+        w8 = [bool(getattr(p, "weight_only", False)) and not self.w4 for p in projs]
         if any(w8) and not amd_key("mlp", "w8_gated"):
             raise ValueError("SparseDiffGatedMlp: a W8Linear projection (weight-only fp8, mlp.fp8_weight_only) is refused: only the ungated "
                              "GEMM1 has a weight-only form (csp_mlp_mm1_w8) unless mlp.w8_gated is on -- set it to run the gated weight-only "
@@ -144,6 +161,16 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
         return (first, second) if self.gate_first else (second, first)
 
     @property
+    def w4_scales(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(gate, up) ``block_scale`` of ``W4Linear`` projections as they are NOW: each layer's own, or -- a fused layer -- the row halves
+        of its ``[2F, K / 32]`` scales as views, split like the weight"""
+        if self.gate_first is None:
+            return self.projs[0].block_scale, self.projs[1].block_scale
+        s = self.projs[0].block_scale
+        f = s.shape[0] // 2
+        return (s[:f], s[f:]) if self.gate_first else (s[f:], s[:f])
+
+    @property
     def fc2w_T(self) -> torch.Tensor:
         """fc2.weight^T, contiguous ``[F, C]``: made once per weight tensor (again after the module was moved or cast)"""
         if is_mxfp4_t(self.fc2[0]):      # W4LinearT: stored in GEMM2's orientation, no copy
@@ -155,7 +182,7 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
         return self._fc2w_T[1]
 
     def _pre(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        if self.fp8 or self.w8:   # the projections' own forward (F8Linear: torch._scaled_mm, which also feeds their input-scale calibration)
+        if self.fp8 or self.w8 or self.w4:   # the projections' own forward (F8Linear: torch._scaled_mm, which also feeds their input-scale calibration)
             if self.gate_first is None:
                 return self.projs[0](x), self.projs[1](x)
             first, second = self.projs[0](x).chunk(2, dim=-1)   # one call of the fused projection, its output split
@@ -192,6 +219,11 @@ class SparseDiffGatedMlp(SparseDeltaMlp):
                             cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add,
                             scale_a=qgate.input_scale_reciprocal, scale_b_gate=qgate.scale_reciprocal, scale_b_up=qup.scale_reciprocal,
                             fc2_scale=fc2_scale_of(self.fc2[0]))
+        elif self.w4:
+            scale_gate, scale_up = self.w4_scales
+            ops.mlp_glu_w4(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], scale_gate=scale_gate, scale_up=scale_up, b_gate=gate[1],
+                           b_up=up[1], act=self.act_code, fc2w_T=self.fc2w_T, indices=indices, counts=counts, sparse_act_T=sparse_act_T,
+                           cached_out=out_cache, num_sms_scatter_add=self.num_sms_scatter_add, fc2_scale=fc2_scale_of(self.fc2[0]))
         elif self.w8:
             scale_gate, scale_up = self.w8_scales
             ops.mlp_glu_w8(x=x if batched else x[0], w_gate=gate[0], w_up=up[0], scale_gate=scale_gate, scale_up=scale_up, b_gate=gate[1],

@@ -346,6 +346,23 @@ def _register():
         torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_glu_w8: unknown activation '{act}'")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm1_glu_w4")
+    def _(a, b_gate, b_up, scale_gate, scale_up, c, bias_gate, bias_up, pa_cache, indices, counts, act, update_cache):
+        # as csp_mlp_mm1_glu, with MXFP4 b_gate / b_up: uint8 [F, K / 2] (two e2m1 elements a byte) and their e8m0 block scales uint8 [F, K / 32]
+        torch._check(a.dtype == torch.bfloat16 and all(t.dtype == torch.uint8 for t in (b_gate, b_up, scale_gate, scale_up)),
+                     lambda: "a must be bfloat16, b_gate, b_up, scale_gate and scale_up uint8")
+        torch._check(c.dtype == torch.bfloat16 and pa_cache.dtype == torch.bfloat16, lambda: "c and pa_cache must be bfloat16")
+        torch._check(a.ndim in (2, 3) and a.shape[-1] % 128 == 0, lambda: "K must be a multiple of 128")
+        torch._check(b_gate.ndim == 2 and b_gate.shape[1] * 2 == a.shape[-1] and b_up.shape == b_gate.shape,
+                     lambda: "b_gate and b_up must be [F, K / 2]")
+        for s in (scale_gate, scale_up):
+            torch._check(s.shape == (b_gate.shape[0], a.shape[-1] // 32), lambda: "scale_gate and scale_up must be [F, K / 32]")
+        torch._check(c.shape == a.shape[:-1] + (b_gate.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        for bias in (bias_gate, bias_up):
+            torch._check(bias is None or bias.numel() == b_gate.shape[0], lambda: "bias_gate and bias_up must have F entries")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_glu_w4: unknown activation '{act}'")
+        return None
+
     @lib.register_fake("chipmunk::w8_linear")
     def _(x, w, scale_b, bias, y):
         # writes y [M, F] in place and returns nothing

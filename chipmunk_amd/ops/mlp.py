@@ -425,7 +425,9 @@ def _run_e2e_gated(gemm1, x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Ten
     _check_batch(x, indices, counts, sparse_act_T, cached_out)
     K1 = x.shape[-1]
     K2, K1_ = w_gate.shape
-    assert K1 == K1_ and tuple(w_up.shape) == (K2, K1), "K1 must match, w_up must have the shape of w_gate"
+    if w_gate.dtype in MXFP4_WEIGHTS:
+        K1_ *= 2      # MXFP4 gate / up weights (run_e2e_glu_w4) hold two e2m1 elements a byte
+    assert K1 == K1_ and tuple(w_up.shape) == tuple(w_gate.shape), "K1 must match, w_up must have the shape of w_gate"
     assert fc2w_T.shape[0] == K2, "K2 must match"
     sparse_act_packed = torch.empty(x.shape[:-1] + (K2,), device=x.device, dtype=sparse_act_T.dtype)   # bf16 also when x is fp8
     fused = bool(amd_key("mlp", "fused_scatter"))
@@ -525,5 +527,51 @@ def run_e2e_glu_w8(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sc
                    x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
 
 
+def mm1_glu_w4(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, scale_gate: torch.Tensor, scale_up: torch.Tensor,
+               sparse_act_packed: torch.Tensor, b_gate: Optional[torch.Tensor], b_up: Optional[torch.Tensor], act: str,
+               sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, update_cache: bool = False) -> None:
+    """``mm1_glu`` over MXFP4 projections: bf16 ``x`` (``K % 128 == 0``), ``w_gate`` / ``w_up`` uint8 / ``float4_e2m1fn_x2`` ``[F, K / 2]``
+    (two weights or the halves of one fused ``[2F, K / 2]`` tensor) and ``scale_gate`` / ``scale_up`` their e8m0 block scales, uint8 /
+    ``float8_e8m0fnu`` ``[F, K / 32]`` (``W4Linear.weight`` / ``.block_scale``).  The bits of ``mm1_glu`` on the two widened weights.  Every
+    violation of these rules raises ``ValueError`` and names the argument."""
+    if act not in GLU_ACTS:
+        raise ValueError(f"mm1_glu_w4: unknown activation {act!r} (one of {', '.join(GLU_ACTS)})")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"mm1_glu_w4: x must be bfloat16 (got {x.dtype}): the activations are not quantised")
+    K = x.shape[-1]
+    if K % 128:
+        raise ValueError(f"mm1_glu_w4: x must have K % 128 == 0 columns (got K = {K})")
+    F = w_gate.shape[0]
+    for name, w in (("w_gate", w_gate), ("w_up", w_up)):
+        if w.dtype not in MXFP4_WEIGHTS:
+            raise ValueError(f"mm1_glu_w4: {name} must be uint8 or float4_e2m1fn_x2 (MXFP4, two e2m1 elements a byte); got {w.dtype}")
+        if tuple(w.shape) != (F, K // 2):
+            raise ValueError(f"mm1_glu_w4: {name} must be [F, K / 2] = {(F, K // 2)}, two e2m1 elements a byte; got {tuple(w.shape)}")
+    for name, s in (("scale_gate", scale_gate), ("scale_up", scale_up)):
+        if s.dtype not in MXFP4_SCALES:
+            raise ValueError(f"mm1_glu_w4: {name} must be e8m0 block scales, uint8 or float8_e8m0fnu; got {s.dtype}")
+        if tuple(s.shape) != (F, K // 32):
+            raise ValueError(f"mm1_glu_w4: {name} must be [F, K / 32] = {(F, K // 32)}, one e8m0 byte per 32 k; got {tuple(s.shape)}")
+    for name, t in (("w_gate", w_gate), ("w_up", w_up), ("scale_gate", scale_gate), ("scale_up", scale_up)):
+        if t.device != x.device:
+            raise ValueError(f"mm1_glu_w4: {name} must be on the device of x ({x.device}); got {t.device}")
+    assert sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
+    wg, wu, sg, su = (t.view(torch.uint8).contiguous() for t in (w_gate, w_up, scale_gate, scale_up))
+    torch.ops.chipmunk.csp_mlp_mm1_glu_w4(x, wg, wu, sg, su, sparse_act_packed, b_gate, b_up, sparse_act_T, indices, counts, act,
+                                          bool(update_cache))
+
+
+@torch.compiler.disable
+def run_e2e_glu_w4(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, scale_gate: torch.Tensor, scale_up: torch.Tensor,
+                   b_gate: Optional[torch.Tensor], b_up: Optional[torch.Tensor], act: str, fc2w_T: torch.Tensor, indices: torch.Tensor,
+                   counts: torch.Tensor, sparse_act_T: torch.Tensor, cached_out: torch.Tensor, num_sms_scatter_add: int,
+                   fc2_scale: Optional[torch.Tensor] = None) -> None:
+    """``run_e2e_glu`` with the gated MXFP4 GEMM1 (bf16 ``x``, MXFP4 gate / up weights): the packed deltas are bf16, so GEMM2 (``fc2w_T``
+    bf16, or e4m3 / MXFP4 with ``fc2_scale``) and the scatter-add are the operators of the bf16 route."""
+    _run_e2e_gated(lambda packed, upd: mm1_glu_w4(x, w_gate, w_up, scale_gate, scale_up, packed, b_gate, b_up, act, sparse_act_T, indices,
+                                                  counts, update_cache=upd),
+                   x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
+
+
 __all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_w8", "mm1_w4", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
-           "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8", "mm1_glu_w8", "run_e2e_glu_w8"]
+           "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8", "mm1_glu_w8", "run_e2e_glu_w8", "mm1_glu_w4", "run_e2e_glu_w4"]

@@ -137,6 +137,12 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # e4m3 rows of both weights; bf16 activations, nothing is quantised).  Dense and full steps and the block-mean probe call the layers'
     # own forward.  Off by default: the constructor refuses a W8Linear projection, as it always did.
     "mlp.w8_gated": False,
+    # gated MXFP4 (not in the reference): SparseDiffGatedMlp accepts W4Linear gate / up projections -- two layers, or one fused [2F, K / 2]
+    # layer through from_fused, in_features % 128 == 0 -- and runs its sparse steps through csp_mlp_mm1_glu_w4 (GEMM1 gathers the packed e2m1
+    # rows of both weights and their e8m0 block scales: the bits of the bf16 gated GEMM1 on the widened weights, no widened copy kept).
+    # Dense and full steps and the block-mean probe call the layers' own forward.  recursive_swap_linears / quantize_fp8 build no such
+    # layers.  Off by default: the constructor refuses a W4Linear projection, as it always did.
+    "mlp.mxfp4_gated": False,
     # MXFP4 fc1 (not in the reference): with mlp.fp8_weight_only on as well, recursive_swap_linears builds fc1 of a sparse image MLP (child
     # "0" of an nn.Sequential named img_mlp, while mlp.is_enabled, in_features % 128 == 0) as a W4Linear -- packed e2m1 weights with one e8m0
     # scale per 32 k, 4.25 bits a weight, bf16 activations -- and SparseDiffMlp's sparse steps gather those rows (csp_mlp_mm1_w4: the bits of
@@ -200,7 +206,8 @@ BASE_CONFIG["mlp"]["fp8_fc2"] = AMD_EXTRA_KEYS["mlp.fp8_fc2"]
 BASE_CONFIG["mlp"]["fp8_weight_only"] = AMD_EXTRA_KEYS["mlp.fp8_weight_only"]
 BASE_CONFIG["mlp"]["w8_stream_rows"] = AMD_EXTRA_KEYS["mlp.w8_stream_rows"]
 BASE_CONFIG["mlp"]["w8_gated"] = AMD_EXTRA_KEYS["mlp.w8_gated"]
-BASE_CONFIG["mlp"]["mxfp4_fc1"] = AMD_EXTRA_KEYS["mlp.mxfp4_fc1"]
+BASE_CONFIG["mlp"]["mxfp4_gated"] = AMD_EXTRA_KEYS["mlp.mxfp4_gated"]
+BASE_CONFIG["mlp"]["mxfp4_fc1"] =AMD_EXTRA_KEYS["mlp.mxfp4_fc1"]
 BASE_CONFIG["mlp"]["w4_stream_rows"] = AMD_EXTRA_KEYS["mlp.w4_stream_rows"]
 BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]

@@ -419,6 +419,28 @@ int chipmunk_csp_mlp_mm1_glu_w8_batched(const void *a, const void *b_gate, const
                                         void *pa_cache, const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc,
                                         int act, int update_cache, int B, int64_t cache_batch_stride, void *stream);
 
+/* gated MXFP4, weight-only: chipmunk_csp_mlp_mm1_glu[_batched|_gm] over OCP MXFP4 gate / up weights with bf16 activations (no reference
+ * counterpart).  a [M,K] bf16; b_gate / b_up [F, K/2] bytes and scale_gate / scale_up [F, K/32] e8m0 bytes, each in the layout of
+ * chipmunk_csp_mlp_mm1_w4's b / scale_b: two weights, or the halves of one fused [2F, K/2] projection in either order.  With
+ * Wg[i,k] = e2m1(b_gate[i,k]) * 2^(scale_gate[i,k/32] - 127), Wu the same over b_up / scale_up, and i = idx[g,j], in fp32:
+ *   g = bias_gate[i] + sum_k a[m,k] * Wg[i,k],   u = bias_up[i] + sum_k a[m,k] * Wu[i,k]
+ *   c[m,j] = bf16( fma(act(g), u, -pa_cache[i, m]) )
+ * The block scales are applied where the nibbles are widened, so the kernel's weight operands ARE bf16(Wg) / bf16(Wu) and sums (seeded
+ * with the biases), act, product and subtraction are chipmunk_csp_mlp_mm1_glu's own: wherever every widened value is a normal bf16
+ * number or zero the result has the bits of chipmunk_csp_mlp_mm1_glu on the two widened weights, with or without biases.  Scale byte
+ * 255 (NaN) is outside the contract; byte 0 is read as a zero scale.  Biases are bf16 [F] or NULL (= zero); update_cache 0 leaves the
+ * cache, 1 also applies the scatter-add of c.  Contract of chipmunk_csp_mlp_mm1_glu and its *_batched / *_gm forms except K % 128 == 0 (a
+ * row's scale bytes are whole dwords).  A null a / b_gate / b_up / scale_gate / scale_up / c / pa_cache, a weight or scale off 4-byte
+ * alignment, a K off its multiple, an update_cache outside 0 / 1 or an unknown act returns CHIPMUNK_ERR_INVALID with a message, before
+ * anything is enqueued.  Not part of the probe-forms build. */
+int chipmunk_csp_mlp_mm1_glu_w4(const void *a, const void *b_gate, const void *b_up, const uint8_t *scale_gate, const uint8_t *scale_up,
+                                void *c, const void *bias_gate, const void *bias_up, void *pa_cache, const int32_t *indices,
+                                const int32_t *counts, int M, int K, int F, int ldc, int act, int update_cache, void *stream);
+int chipmunk_csp_mlp_mm1_glu_w4_batched(const void *a, const void *b_gate, const void *b_up, const uint8_t *scale_gate,
+                                        const uint8_t *scale_up, void *c, const void *bias_gate, const void *bias_up, void *pa_cache,
+                                        const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
+                                        int update_cache, int B, int64_t cache_batch_stride, void *stream);
+
 /* Weight-only fp8 linear layer for few rows (W8Linear.forward under mlp.w8_stream_rows; no reference counterpart): the weight is read
  * once as e4m3 and widened in registers, no widened copy exists.
  *   x [M, K] bf16, rows ldx elements apart; w [F, K] OCP e4m3 bytes (float8_e4m3fn), plain row-major; scale_b fp32 on the device, the
@@ -492,6 +514,10 @@ int chipmunk_csp_mlp_mm1_glu_w8_gm(const void *a, const void *b_gate, const void
 int chipmunk_csp_mlp_mm1_w4_gm(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
                                const int32_t *indices, const int32_t *counts, int M, int K, int F, int act, int update_cache, int B,
                                int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_glu_w4_gm(const void *a, const void *b_gate, const void *b_up, const uint8_t *scale_gate, const uint8_t *scale_up,
+                                   void *c, const void *bias_gate, const void *bias_up, void *pa_cache, const int32_t *indices,
+                                   const int32_t *counts, int M, int K, int F, int act, int update_cache, int B,
+                                   int64_t cache_batch_stride, void *stream);
 /* chipmunk_csp_scatter_add_batched on the group-major cache: unpacked_groups[b][g, idx[b,g,j], r] += packed[b, g * 128 + r, j] */
 int chipmunk_csp_scatter_add_gm(const void *packed, void *unpacked_groups, const int32_t *indices, const int32_t *counts, int M,
                                 int F, int B, int64_t cache_batch_stride, void *stream);

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm2_w4 mm2_w4_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_glu_w8 w8_probe w8_probe_wan w8_probe_hunyuan w4_probe w4_probe_wan w4_probe_hv scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm2_w4 mm2_w4_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_glu_w8 mm1_glu_w4 w8_probe w8_probe_wan w8_probe_hunyuan w4_probe w4_probe_wan w4_probe_hv scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -506,6 +506,61 @@ def bench_mm1_glu_w8(M=4352, K=3072, F=12288, keep=3840, act="silu"):
     print(f"mm1_glu_w8 / mm1_glu: {med['w8'] / med['bf16']:8.3f}")
 
 
+def bench_mm1_glu_w4(M=4352, K=3072, F=12288, keep=3840, act="silu"):
+    """The gated MXFP4 GEMM1 (csp_mlp_mm1_glu_w4: packed e2m1 rows of the gate / up weights + e8m0 block scales, bf16 activations) against
+    the bf16 csp_mlp_mm1_glu on the WIDENED weights and against csp_mlp_mm1_glu_w8 on an e4m3 quantisation of the same fused projection, at
+    the FLUX gated shape of bench_mm1_glu_w8: same activations and index lists, scatter-add on (KB_GLU_UPDATE=0: off).  Same process, the
+    three alternating (KB_ROUNDS rounds, default 5); per launch the median bracket of `timeit`, then the median and the range over the
+    rounds.  KB_LAYERS=n rotates n sets of weights / caches / outputs (n = 8: the weight rows come from HBM)."""
+    from chipmunk_amd.modules import W4Linear
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    upd = os.environ.get("KB_GLU_UPDATE", "1") == "1"
+    G = (M + 127) // 128
+    sets = []
+    for _ in range(L):
+        lin = torch.nn.Linear(K, 2 * F, bias=False, device=dev, dtype=torch.bfloat16)      # the halves of one fused projection
+        lin.weight.data = (torch.randn(2 * F, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
+        q = W4Linear.from_linear(lin)
+        w8 = (lin.weight.data.float() * 512).clamp(-448, 448).to(torch.float8_e4m3fn)
+        x = torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g) * 0.5
+        cache = torch.zeros(F, M, device=dev, dtype=torch.bfloat16)
+        sets.append((q.widened(), q.weight.data, q.block_scale, w8, x, cache, torch.empty(M, F, device=dev, dtype=torch.bfloat16)))
+        del lin
+    s8 = torch.full((1,), 1 / 512.0, device=dev)
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_w4():
+        _, w4, sc, _, x, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_glu_w4(x, w4[:F], w4[F:], sc[:F], sc[F:], out, None, None, cache, inds, counts, act, upd)
+
+    def run_bf16():
+        w16, _, _, _, x, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_glu(x, w16[:F], w16[F:], out, None, None, cache, inds, counts, act, upd)
+
+    def run_w8():
+        _, _, _, w8, x, cache, out = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_glu_w8(x, w8[:F], w8[F:], s8, s8, out, None, None, cache, inds, counts, act, upd)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    t = {"w4": [], "bf16": [], "w8": []}
+    for _ in range(rounds):
+        t["w4"].append(timeit(run_w4) * 1e3)
+        t["bf16"].append(timeit(run_bf16) * 1e3)
+        t["w8"].append(timeit(run_w8) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * K * 2 * keep
+    tag = f"(M={M} K={K} F={F} keep={keep} {act} layers={L} {'scatter' if upd else 'update off'}, {rounds} alternating rounds)"
+    for key, name in (("w4", "mm1_glu_w4 mxfp4 rows"), ("bf16", "mm1_glu    bf16 rows "), ("w8", "mm1_glu_w8 e4m3 rows ")):
+        print(f"{name}: {med[key]:8.1f} us  [{min(t[key]):.1f} .. {max(t[key]):.1f}]  {flops/med[key]/1e6:7.1f} TFLOP/s   {tag if key == 'w4' else ''}")
+    print(f"mm1_glu_w4 / mm1_glu: {med['w4'] / med['bf16']:8.3f}    mm1_glu_w4 / mm1_glu_w8: {med['w4'] / med['w8']:8.3f}")
+
+
 def bench_w8_probe(M=34, K=3072, F=12288):
     """The few-row weight-only forward (ops.w8_linear: the e4m3 weight streamed once, widened in registers) against W8Linear.forward with
     mlp.w8_stream_rows off (the whole weight widened to bf16 per call, then F.linear) and the bf16 nn.Linear over the widened weight, on the
@@ -966,6 +1021,8 @@ def main():
             bench_mm1_w8(M=32760, K=1536, F=8960, keep=2816)
         elif w == "mm1_glu_w8":       # gated weight-only fp8 GEMM1 against the bf16 gated GEMM1 on the widened weights, FLUX gated shape (KB_GLU_ACT)
             bench_mm1_glu_w8(act=os.environ.get("KB_GLU_ACT", "silu"))
+        elif w == "mm1_glu_w4":       # gated MXFP4 GEMM1 against the bf16 gated GEMM1 on the widened weights and the gated e4m3 form (KB_GLU_ACT)
+            bench_mm1_glu_w4(act=os.environ.get("KB_GLU_ACT", "silu"))
         elif w == "w8_probe":         # few-row weight-only forward at the FLUX probe shape [34, 3072] -> 12288: kernel / widened W8Linear / nn.Linear
             bench_w8_probe()
         elif w == "w8_probe_wan":     # ... at the Wan2.1 1.3B probe shape [256, 1536] -> 8960
