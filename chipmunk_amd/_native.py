@@ -24,6 +24,7 @@ SYMBOLS = [
     "chipmunk_csp_mlp_mm2_w8", "chipmunk_csp_mlp_mm2_w8_batched", "chipmunk_csp_mlp_mm2_w4", "chipmunk_csp_mlp_mm2_w4_batched",
     "chipmunk_csp_mlp_mm1_w8", "chipmunk_csp_mlp_mm1_w8_batched", "chipmunk_csp_mlp_mm1_w8_gm", "chipmunk_w8_linear",
     "chipmunk_csp_mlp_mm1_w4", "chipmunk_csp_mlp_mm1_w4_batched", "chipmunk_csp_mlp_mm1_w4_gm", "chipmunk_w4_linear",
+    "chipmunk_csp_mlp_mm1_fp8_w4", "chipmunk_csp_mlp_mm1_fp8_w4_batched", "chipmunk_csp_mlp_mm1_fp8_w4_gm",
     "chipmunk_csp_mlp_mm1_glu_w8", "chipmunk_csp_mlp_mm1_glu_w8_batched", "chipmunk_csp_mlp_mm1_glu_w8_gm",
     "chipmunk_csp_mlp_mm1_glu_w4", "chipmunk_csp_mlp_mm1_glu_w4_batched", "chipmunk_csp_mlp_mm1_glu_w4_gm",
     "chipmunk_csp_mlp_mm1_fp8_act_rs", "chipmunk_csp_mlp_mm1_fp8_act_rs_batched", "chipmunk_quantize_fp8_rowwise",

@@ -19,6 +19,9 @@
 // ... and over OCP MXFP4 rows (mm1_w4_kernel, mm1_tile's W4): 32 BYTES of e2m1 nibbles a row and k step plus the row's e8m0 block-scale bytes, both
 // by LDS-DMA; a fragment is one ds_read_b32 widened by v_cvt_scalef32_pk_bf16_fp4 with the block's power-of-two scale, so the B operand is the
 // widened bf16 weight and the result the bf16 form's, bit for bit; three stages of 16 + 4 + 1 KiB (22 KiB) under the FLAT epilogue.
+// ... and over the same MXFP4 rows under e4m3 ACTIVATIONS (mm1_fp8_w4_kernel, mm1_tile's F8W4): v_mfma_scale_f32_32x32x64_f8f6f4 with an fp8 A and
+// an fp4 B operand, the nibbles packed all the way into the instruction and the e8m0 bytes in its scale operand -- no convert, no bf16 B image;
+// 128 k a stage: one 64-byte piece a row (chunk-major, one ds_read_b128 a fragment) and one scale dword; three stages of 16 + 8 + 1 KiB (25 KiB).
 // GEMM2 over MXFP4 rows of fc2^T (mm2_w4_kernel), the scale blocks along N2: 128-byte row slices, the transpose read with FOUR columns as its
 // 16-bit element, v_cvt_scalef32_pk_bf16_fp4 with the row's scale + v_perm_b32 in front of the same bf16 MFMA <256, 32, 5, 2, 4 waves of 64x128>.
 #include "common.h"
@@ -244,6 +247,15 @@ struct Mm1GluW4Params : Mm1Params {
     const uint8_t *scale_gate_e8, *scale_up_e8;
 };
 constexpr int mm1_w4_stage(int TM, int TN, int BK) { return (TM * BK * 2 + TN * BK / 2 + TN / 64 * 16 + TN / 32 * 256 + 1023) & ~1023; }
+// The e4m3 x MXFP4 form (mm1_fp8_w4_kernel): a is e4m3 bytes [M, K], b / scale_e8 the packed e2m1 weight and its e8m0 block scales as in
+// Mm1W4Params, scale_a (the shared block's slot) the reciprocal activation scale -- one number (scale_n == 1) or one per token row (scale_n == M).
+struct Mm1F8W4Params : Mm1Params {
+    const uint8_t *scale_e8;
+    int scale_n;
+};
+// LDS bytes of one ring stage of that form: TM rows of 128 e4m3 bytes, TN rows of 64 nibble bytes, 256 bytes of scale dwords per 32-row
+// fragment, rounded up to 1 KiB (full tile: 16 + 8 + 1 = 25 KiB, 100 whole output rows: FLAT below; 64 x 64 sub-tile: 13 KiB)
+constexpr int mm1_f8w4_stage(int TM, int TN) { return (TM * 128 + TN * 64 + TN / 32 * 256 + 1023) & ~1023; }
 
 // One TM x TN output tile (TM rows of group g starting at m_off, packed columns n0 .. n0+TN-1): 4 waves as 2 x 2, each a
 // (TM/2) x (TN/2) accumulator of 32x32x16 MFMA tiles; NST-deep LDS ring of [A tile | B tile] stages.
@@ -320,8 +332,30 @@ constexpr int mm1_w4_stage(int TM, int TN, int BK) { return (TM * BK * 2 + TN * 
 // by the bit tests (tests/test_gpu_mlp_glu_w4.py): a lane masked off in EXEC leaves its LDS bytes alone, and the instruction still counts once.
 // The scale dwords of fragment w (pair w >> 1, half w & 1) come under the wave-uniform gate or up scale descriptor.  EPI = 16 KiB <= the 22 KiB
 // stage: the plain staged epilogue, the cache block in stage (last + 2) % 3, free since the barrier of the last k step.
+// F8W4 (mm1_fp8_w4_kernel; FP8 is set with it; P = Mm1F8W4Params): e4m3 a x MXFP4 weight rows on v_mfma_scale_f32_32x32x64_f8f6f4, A format
+// e4m3, B format fp4, the e8m0 block scales in the instruction's B scale operand -- no conversion and no bf16 B image.  The A tile and its DMA
+// are the fp8 form's (128 k = 128 bytes a row and stage).  k order inside the instruction, measured with one-hot rows: lane half
+// h = lane >> 5 of an fp4 operand (4 dwords, 32 nibbles, low nibble first) holds k = 32 h .. 32 h + 31 of the 64-k slice -- 32 consecutive k of
+// weight row lane & 31, exactly one MX block, so the lane's one scale byte is that block's --, while the 8-dword fp8 operand holds k = 16 h ..
+// 16 h + 15 in dwords 0 .. 3 and k = 32 + 16 h .. + 15 in dwords 4 .. 7.  Between two fp8 operands that order cancels (the fp8 form reads chunks
+// 2 h and 2 h + 1 on both sides); against fp4 it does not, so this form's A fragment is the 16-byte chunks kk * 4 + h and kk * 4 + 2 + h of its
+// row, same swizzle, same bank argument.  The fp4 operand is an 8-dword vector whose first four dwords are used.
+//   B image.  A row piece of a stage is 128 k = 64 bytes = FOUR 16-byte DMA lanes, one 64-byte piece of the gathered row (the W4 form: two 32-byte
+//   pieces in two steps).  The fragment read of slice kk is one ds_read_b128 a lane, chunk c = kk * 2 + (lane >> 5) of row lane & 31.  A b128 read
+//   is served 16 lanes = 256 bytes = 64 banks at a time, and the 16 lanes of a pass hold 16 consecutive rows at one chunk c.  Row-major (row * 64 +
+//   c * 16) those 16 addresses are 64 bytes apart: 4 distinct 16-byte slots of the 256-byte bank row, 4-way.  The DMA piece's lane -> (row, chunk)
+//   map is free (per-lane source offset), so piece I = tile rows [16 I, + 16) is stored chunk-major: lane p = (chunk p >> 4, row16 p & 15) at
+//   I * 1024 + c * 256 + row16 * 16.  A pass then reads the 256 CONTIGUOUS bytes [c * 256, + 256) of its piece: bank = 4 row16 + dword, 16 x 4
+//   dwords on 64 different banks, once each -- derived from the addresses, not counted on hardware.  No shift, no padding: B tile = TN * 64 bytes.
+//   Scale image.  A stage's 128 k are 4 blocks = the ONE aligned dword kb of the row's scale bytes (K % 128 == 0), fetched once: one
+//   buffer_load_dword ... lds per wave and stage, lanes l and l + 32 the row l & 31 of fragment w, read back lane-linear (lane l at dword l).  Lane
+//   half h needs block kk * 2 + h but the instruction's byte selector is an immediate, the same for all lanes: the lanes >= 32 shift their dword
+//   down 8 bits once per stage, so that selector 2 kk picks byte 2 kk + h on either half.  The A-side scale is the constant byte 127 (1.0).
+//   A stage is 4 + 2 + 1 = 7 DMA instructions a wave (sub-tile: 2 + 1 + 1, waves 2 / 3 re-issue the scale dwords of waves 0 / 1).  Full tile: 3
+//   stages of 25 KiB under the FLAT epilogue; the epilogue is W8's with the ROW's reciprocal scale: act((S * scale_a[m]) + bias) - cache, the
+//   multiply and the add each rounded, then one rounding to bf16.  The row scales are fetched behind the k loop as RS does.
 template <int TM, int TN, int BK, int NST, bool FP8 = false, int NW = 4, bool GLU = false, int ACT = 0, class P = Mm1Params, bool NULLB = false,
-          bool RS = false, bool W8 = false, bool W4 = false>
+          bool RS = false, bool W8 = false, bool W4 = false, bool F8W4 = false>
 __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g, int m_off, int n0, int cnt) {
     static_assert(!RS || (FP8 && !GLU && NULLB), "row / column scale vectors: the ungated fp8 form with a nullable bias (mm1_form_kernel) only");
     static_assert(!W8 || (!FP8 && !RS && (GLU || NULLB) && NW == 4 && BK == 64), "the weight-only form: bf16 a, 4 waves, 64-byte B row pieces");
@@ -330,16 +364,20 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                           (GLU || std::is_base_of<Mm1W4Params, P>::value)),
                   "the MXFP4 form: bf16 a, 4 waves, 32-byte B row pieces, one or two pairs of pieces (gated: two)");
     static_assert(!(W4 && GLU) || std::is_base_of<Mm1GluW4Params, P>::value, "the gated MXFP4 form reads its scales from Mm1GluW4Params");
+    static_assert(!F8W4 || (FP8 && !GLU && NULLB && !RS && !W8 && !W4 && NW == 4 && BK == 64 && (TN == 128 || TN == 64) &&
+                            std::is_base_of<Mm1F8W4Params, P>::value),
+                  "the e4m3 x MXFP4 form: ungated, 4 waves, 128 k a stage, 64-byte B row pieces");
     using KT = KTile<BK>;
     using KTB = KTile<W8 ? BK / 2 : BK>;     // the B tile's geometry
     constexpr uint32_t ESZ = FP8 ? 1u : 2u;  // operand element size in bytes
     constexpr uint32_t BSZ = W8 ? 1u : ESZ;  // ... of the weight
     constexpr int B_PAD = W8 ? TN / 32 * 16 : W4 ? TN / 64 * 16 : 0;   // (W8, W4: 16 bytes per pair of DMA pieces, room for the odd piece's 8-byte shift)
     constexpr int B_PAIR = 2048 + 16;              // (W8, W4: bytes a pair of pieces owns)
-    constexpr int A_TILE = TM * BK * 2, B_TILE = W4 ? TN * BK / 2 + B_PAD : TN * BK * (int)(W8 ? 1 : 2) + B_PAD;
-    constexpr int STAGE = W4 ? mm1_w4_stage(TM, TN, BK) : A_TILE + B_TILE;
+    constexpr int A_TILE = TM * BK * 2, B_TILE = F8W4 ? TN * BK : W4 ? TN * BK / 2 + B_PAD : TN * BK * (int)(W8 ? 1 : 2) + B_PAD;
+    constexpr int STAGE = F8W4 ? mm1_f8w4_stage(TM, TN) : W4 ? mm1_w4_stage(TM, TN, BK) : A_TILE + B_TILE;
     constexpr int A_INST = A_TILE / (1024 * NW), B_INST = W4 ? (GLU ? 2 : 1) : (B_TILE - B_PAD) / (1024 * NW);  // DMA instructions per wave per tile (GLU && W4: one piece as two half-wave instructions)
-    constexpr int S_INST = W4 ? 1 : 0;             // (W4: and one dword instruction for the scale bytes)
+    constexpr int S_INST = W4 || F8W4 ? 1 : 0;     // (W4, F8W4: and one dword instruction for the scale bytes)
+    constexpr bool NOPROBE = W4 || F8W4;           // (no timing probes: their entries pass none)
     constexpr int NFR = TN / 32;                   // (W4: DMA pieces of the B tile = its 32-row fragments)
     constexpr int WNC = NW / 2;                                     // waves across the tile's columns (2 down its rows)
     constexpr int MT = TM / 64, NT4 = TN / (32 * WNC);              // 32-wide m / n tiles per wave
@@ -368,7 +406,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     }
 #pragma unroll
     for (int i = 0; i < B_INST; ++i) {
-        if constexpr (W4) {   // piece w % NFR: rows [16 odd, + 16) of both fragments of its pair, lane = (fragment, k chunk, row16)
+        if constexpr (F8W4) {   // piece w * B_INST + i: tile rows [16 piece, + 16), lane = (k chunk lane >> 4, row16 lane & 15)
+            const int j = n0 + (w * B_INST + i) * 16 + (lane & 15);
+            boff[i] = (uint32_t)idxg[j < cnt ? j : n0] * (uint32_t)(p.K >> 1) + (uint32_t)(lane >> 4) * 16u;
+        } else if constexpr (W4) {   // piece w % NFR: rows [16 odd, + 16) of both fragments of its pair, lane = (fragment, k chunk, row16)
             const int pc = w % NFR, row = (pc >> 1) * 64 + (lane >> 5) * 32 + (pc & 1) * 16 + (lane & 15);
             // gated: fragment lane >> 5 of pair pc >> 1 is the gate (0) or the up (1) rows of packed columns n0 + 32 (pc >> 1) + (row & 31); both of
             // the piece's instructions carry the lane's one offset
@@ -387,7 +428,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         const int j = n0 + (w >> 1) * 32 + (lane & 31);
         soff = (uint32_t)idxg[j < cnt ? j : n0] * (uint32_t)(p.K >> 5);
         rs = make_rsrc((w & 1) ? p.scale_up_e8 : p.scale_gate_e8);
-    } else if constexpr (W4) {
+    } else if constexpr (W4 || F8W4) {
         const int j = n0 + (w % NFR) * 32 + (lane & 31);
         soff = (uint32_t)idxg[j < cnt ? j : n0] * (uint32_t)(p.K >> 5);
         rs = make_rsrc(p.scale_e8);
@@ -404,6 +445,11 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                                          // counts once in vmcnt).  The scale dword follows the piece's second half.
                 if ((lane >> 5) == i) blds16(i ? rb_up : rb, boff[i], kb * (BK / 2), st + A_TILE + (w >> 1) * B_PAIR + (w & 1) * (1024 + 8));
                 if (i == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(st + A_TILE + B_TILE + w * 256), 4, (int)soff, (kb >> 1) * 4, 0, 0);
+            } else if constexpr (F8W4) {   // 64 bytes of a row per stage, chunk-major pieces; behind the wave's last piece the stage's ONE dword of scale
+                                           // bytes a row (blocks 4 kb .. 4 kb + 3): the same DMA path, no register load in the loop
+                blds16(rb, boff[i], kb * BK, st + A_TILE + (w * B_INST + i) * 1024);
+                if (i == B_INST - 1)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(st + A_TILE + B_TILE + (w % NFR) * 256), 4, (int)soff, kb * 4, 0, 0);
             } else if constexpr (W4) {   // 32 bytes of a row per k step; the odd piece of a pair lands 8 bytes up.  Then the dword of scale bytes of this
                                   // step's 128-k block: the same DMA path as the weights, no register load in the loop
                 const int pc = w % NFR;
@@ -432,7 +478,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     constexpr int EPI = TM * PW * 2;   // (gated form: half the columns -- cache block PW columns x TM rows, output image TM x PW)
     // (W8: a stage is no whole number of output rows -- the rows behind the cache block start FLAT_SKIP behind their place in a contiguous image)
     constexpr int FLAT_ROWS = STAGE / (TN * 2), FLAT_SKIP = EPI + STAGE - FLAT_ROWS * TN * 2;
-    constexpr bool FLAT = (NW == 8 || W8 || W4) && EPI > STAGE && EPI <= (NST - 1) * STAGE && EPI + FLAT_SKIP <= NST * STAGE &&
+    constexpr bool FLAT = (NW == 8 || W8 || W4 || F8W4) && EPI > STAGE && EPI <= (NST - 1) * STAGE && EPI + FLAT_SKIP <= NST * STAGE &&
                           (W8 ? FLAT_ROWS % 4 == 0 : STAGE % (TN * 2) == 0);
     constexpr bool STAGED = EPI <= STAGE || FLAT;
     static_assert(!FP8 || STAGED, "the fp8 form is only built for tile shapes with the staged epilogue");
@@ -469,7 +515,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     float sb_up = 1.f;                       // (gated fp8 form: sb is the gate weight's scale, sb_up the up weight's)
     float sb_col[RS || W8 ? NT4 : 1];        // (RS, W8: the weight scale of the lane's column of every 32-wide tile)
     if constexpr (FP8 && GLU) sa = p.scale_x[0], sb = p.scale_gate[0], sb_up = p.scale_up[0];
-    else if constexpr (FP8 && !RS) sa = p.scale_a[0], sb = p.scale_b[0];
+    else if constexpr (FP8 && !RS && !F8W4) sa = p.scale_a[0], sb = p.scale_b[0];
     f32x16 acc[MT][NT4];
 #pragma unroll
     for (int n4 = 0; n4 < NT4; ++n4) {
@@ -500,7 +546,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     // W8: every register load of the tile -- gather indices, bias, scale -- has landed before the first LDS-DMA is issued, so none of them is
     // consumed under a counted vmcnt with LDS-DMAs behind it (an LDS-DMA may retire ahead of an older register load).  The counted
     // waits the compiler still puts in front of their uses then wait for nothing; the loop and the epilogue issue no register load of their own.
-    if constexpr (W8 || W4) wait_vmcnt<0>();
+    if constexpr (W8 || W4 || F8W4) wait_vmcnt<0>();
 #pragma unroll
     for (int s = 0; s < NST - 1; ++s)
         if (s < nkb) issue(s, (buf + s) % NST);
@@ -515,10 +561,10 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         MPROF_MARK(0);
         __builtin_amdgcn_s_barrier();
         MPROF_MARK(1);
-        if (kb + NST - 1 < nkb && (W4 || p.probe != 1)) issue(kb + NST - 1, nbuf);   // (W4: no timing probes, its entry passes none)
+        if (kb + NST - 1 < nkb && (NOPROBE || p.probe != 1)) issue(kb + NST - 1, nbuf);
         if (kb == nkb - 1) issue_cache(nbuf);  // the stage tile kb-1 occupied is free for good
         MPROF_MARK(2);
-        if (!W4 && p.probe == 2) {
+        if (!NOPROBE && p.probe == 2) {
             buf = buf + 1 == NST ? 0 : buf + 1;
             nbuf = nbuf + 1 == NST ? 0 : nbuf + 1;
             continue;
@@ -538,13 +584,25 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         Frag af[2][MT], bfr[2][NT4];
         u32x2 bw8[2][W8 ? NT4 : 1];   // (W8: the fragments' e4m3 bytes, widened in front of their MFMAs)
         uint32_t bw4[2][W4 ? NT4 : 1], scw[W4 ? NT4 : 1];   // (W4: the fragments' e2m1 nibbles; the scale bytes of this k step's two 32-k blocks)
+        u32x4 bq[2][F8W4 ? NT4 : 1];   // (F8W4: the fragments' 32 nibbles a lane, as they go into the MFMA)
+        uint32_t scq[F8W4 ? NT4 : 1];  // (F8W4: the stage's four scale bytes of the lane's row; lanes >= 32 one byte down)
+        if constexpr (F8W4) {
+#pragma unroll
+            for (int n4 = 0; n4 < NT4; ++n4)
+                scq[n4] = *(const uint32_t *)(Bt + B_TILE + (wn * (TN / WNC / 32) + n4) * 256 + lane * 4) >> ((lane >> 5) * 8);
+        }
         if constexpr (W4) {
 #pragma unroll
             for (int n4 = 0; n4 < NT4; ++n4)   // fragment (row >> 5)'s 256 bytes, lane-linear; this step's pair of bytes down to bits 0 .. 15
                 scw[n4] = *(const uint32_t *)(Bt + B_TILE + (wn * (TN / WNC / 32) + n4) * 256 + lane * 4) >> ((kb & 1) * 16);
         }
         auto frag = [&](const unsigned char *tile, int row, int kk) -> Frag {
-            if constexpr (FP8) {
+            if constexpr (F8W4) {   // the instruction's own k order of an 8-dword fp8 operand: dwords 0 .. 3 are k 16 h .. + 15, dwords 4 .. 7 k 32 + 16 h .. + 15
+                const int c0 = kk * 4 + (lane >> 5);
+                const u32x4 lo = *(const u32x4 *)(tile + row * (BK * 2) + ((c0 ^ KT::swz(row)) << 4));
+                const u32x4 hi = *(const u32x4 *)(tile + row * (BK * 2) + (((c0 + 2) ^ KT::swz(row)) << 4));
+                return (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+            } else if constexpr (FP8) {
                 const int c0 = kk * 4 + (lane >> 5) * 2;
                 const u32x4 lo = *(const u32x4 *)(tile + row * (BK * 2) + ((c0 ^ KT::swz(row)) << 4));
                 const u32x4 hi = *(const u32x4 *)(tile + row * (BK * 2) + (((c0 + 1) ^ KT::swz(row)) << 4));
@@ -559,7 +617,9 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
 #pragma unroll
             for (int n4 = 0; n4 < NT4; ++n4) {
                 const int row = wn * (TN / WNC) + n4 * 32 + (lane & 31);
-                if constexpr (W4)
+                if constexpr (F8W4)
+                    bq[set][n4] = *(const u32x4 *)(Bt + (row >> 4) * 1024 + (kk * 2 + (lane >> 5)) * 256 + (row & 15) * 16);
+                else if constexpr (W4)
                     bw4[set][n4] = *(const uint32_t *)(Bt + (row >> 6) * B_PAIR + ((row >> 4) & 1) * (1024 + 8) +
                                                        ((((row >> 5) & 1) * 2 + (kk >> 1)) * 16 + (row & 15)) * 16 + (kk & 1) * 8 + (lane >> 5) * 4);
                 else if constexpr (W8)
@@ -597,7 +657,12 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                 for (int n4 = 0; n4 < NT4; ++n4) {
-                    if constexpr (FP8)   // formats 0 / 0 = e4m3 x e4m3; literal zero scale operands select the unscaled encoding
+                    if constexpr (F8W4) {   // formats 0 / 4 = e4m3 x fp4; A scale the byte 127, B scale byte 2 kk of the lane's dword
+                        const u32x4 q = bq[kk & 1][n4];
+                        const i32x8 b8 = {(int)q[0], (int)q[1], (int)q[2], (int)q[3], 0, 0, 0, 0};
+                        if (kk == 0) acc[mt][n4] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[0][mt], b8, acc[mt][n4], 0, 4, 0, 127, 0, (int)scq[n4]);
+                        else acc[mt][n4] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[1][mt], b8, acc[mt][n4], 0, 4, 0, 127, 2, (int)scq[n4]);
+                    } else if constexpr (FP8)   // formats 0 / 0 = e4m3 x e4m3; literal zero scale operands select the unscaled encoding
                         acc[mt][n4] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[kk & 1][mt], bfr[kk & 1][n4], acc[mt][n4], 0, 0, 0, 0, 0, 0);
                     else
                         acc[mt][n4] = mfma32(af[kk & 1][mt], bfr[kk & 1][n4], acc[mt][n4]);
@@ -610,7 +675,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
     }
     MPROF_MARK(4);
 
-    if (!W4 && p.probe == 4) {  // timing probe: no epilogue
+    if (!NOPROBE && p.probe == 4) {  // timing probe: no epilogue
         float t = 0.f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -634,7 +699,24 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
         // RS: the reciprocal scales of the lane's rows, runs of four (ml .. ml + 3 per (mt, q4)), requested here so that they land under the
         // wait for the cache block.  M % 4 == 0 and a 16-byte aligned vector (wave-uniform): a run is live or dead as a whole and arrives as
         // one 16-byte read, a dead run re-reads the tile's last live one; otherwise four reads, each row clamped to the last live row.
-        f32x4 sa_row[RS ? MT : 1][RS ? 4 : 1];
+        f32x4 sa_row[RS || F8W4 ? MT : 1][RS || F8W4 ? 4 : 1];
+        if constexpr (F8W4) {   // as RS below; scale_n == 1: every row reads the one number
+            const bool rowwise = p.scale_n > 1;
+            const float *sap = p.scale_a + (rowwise ? g * BM + m_off : 0);
+            const bool vec = rowwise && (p.M & 3) == 0 && ((uintptr_t)p.scale_a & 15) == 0;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const int ml = wm * (TM / 2) + mt * 32 + q4 * 8 + (lane >> 5) * 4;
+                    if (vec) {
+                        sa_row[mt][q4] = *(const f32x4 *)(sap + min(ml, rows - 4));
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) sa_row[mt][q4][e] = sap[rowwise ? min(ml + e, rows - 1) : 0];
+                    }
+                }
+        }
         if constexpr (RS) {
             const float *sap = p.scale_a + (g * BM + m_off);
             const bool vec = (p.M & 3) == 0 && ((uintptr_t)p.scale_a & 15) == 0;
@@ -686,7 +768,12 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
                         const f32x2 c01 = unpack_bf16x2(c[0]), c23 = unpack_bf16x2(c[1]);
                         f32x2 a01 = {acc[mt][n4][q4 * 4 + 0], acc[mt][n4][q4 * 4 + 1]}, a23 = {acc[mt][n4][q4 * 4 + 2], acc[mt][n4][q4 * 4 + 3]};
                         uint32_t d01, d23, n01 = 0, n23 = 0;   // packed deltas as stored (bf16 pairs); the cache block's new values
-                        if constexpr (FP8 && GLU) {
+                        if constexpr (F8W4) {
+                            // sum * the row's scale, then + bias: two fp32 roundings (scale_then_bias2), then W8's one rounding
+                            const f32x2 s01 = {sa_row[mt][q4][0], sa_row[mt][q4][1]}, s23 = {sa_row[mt][q4][2], sa_row[mt][q4][3]}, bv = {bia, bia};
+                            d01 = pack_bf16x2_v(glu_act2<ACT>(scale_then_bias2(a01, s01, bv)) - c01);
+                            d23 = pack_bf16x2_v(glu_act2<ACT>(scale_then_bias2(a23, s23, bv)) - c23);
+                        } else if constexpr (FP8 && GLU) {
                             // each branch as the fp8 form makes its pre-activation, (acc * scale_a) * scale_b + bias, then the gated form's
                             // one rounding: fma(act(gate), up, -cache); a01 / a23 are the gate's sums, bias_v[1] the up projection's bias
                             const f32x2 u01 = {acc[mt][1][q4 * 4 + 0], acc[mt][1][q4 * 4 + 1]}, u23 = {acc[mt][1][q4 * 4 + 2], acc[mt][1][q4 * 4 + 3]};
@@ -738,7 +825,7 @@ __device__ __forceinline__ void mm1_tile(const P &p, unsigned char *smem, int g,
             }
         };
         if (p.update_cache == 0) arith(ic<0>{});
-        else if constexpr (GLU || W8 || W4) arith(ic<1>{});   // (the gated and the weight-only entries admit 0 and 1 only: no third copy of the epilogue)
+        else if constexpr (GLU || W8 || W4 || F8W4) arith(ic<1>{});   // (the gated and the weight-only entries admit 0 and 1 only: no third copy of the epilogue)
         else if (p.update_cache == 1) arith(ic<1>{});
         else arith(ic<2>{});
         __syncthreads();
@@ -1037,6 +1124,58 @@ __global__ __launch_bounds__(256, WPS) __attribute__((target("no-packed-fp32-ops
         }
         // the next tile's DMA lands where this tile's epilogue was reading (__syncthreads() written out: the header's function is compiled with
         // the packed forms and would stay a call from this kernel)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+}
+
+// e4m3 activations x MXFP4 fc1 on the block-scaled MFMA (mm1_tile's F8W4 form): c = bf16(act((sum_k f(a[m, k]) * W[i, k]) * scale_a[m or 0] +
+// bias[i]) - cache[i, m]), W as in mm1_w4_kernel; every product is exact in fp32, the accumulation order is the instruction's.  mm1_w4_kernel's
+// walk over 3 stages of mm1_f8w4_stage bytes (25 KiB; a sub-tile's stage is 13 KiB, 4 of them); a sequence of a batch starts M * K BYTES of a
+// and, with row scales, M floats of scale_a behind the one before.  Built without the packed fp32 forms like mm1_w4_kernel (see there).
+struct Mm1F8W4Batch : Mm1F8W4Params {
+    int B;
+    int64_t cache_bs;   // as Mm1Batch
+};
+template <int BN, int BK, int NST, int WPS, int ACT, bool BATCHED>
+__global__ __launch_bounds__(256, WPS) __attribute__((target("no-packed-fp32-ops"))) void mm1_fp8_w4_kernel(const typename std::conditional<BATCHED, Mm1F8W4Batch, Mm1F8W4Params>::type p) {
+    using P = Mm1F8W4Params;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int NSUB = 2 * (BN / 64);                                   // 64 x 64 sub-tiles per tile
+    constexpr int LDS = NST * mm1_f8w4_stage(BM, BN), SUB_STAGE = mm1_f8w4_stage(64, 64);
+    constexpr int SUB_NST = LDS / SUB_STAGE > 4 ? 4 : LDS / SUB_STAGE;    // inside the same LDS bytes
+    const int Gs = (p.M + BM - 1) / BM;   // groups of one sequence
+    int G = Gs;
+    if constexpr (BATCHED) G = p.B * Gs;  // the map runs over all B * Gs
+    const TilePlan pl = plan_tiles<BN>(p.counts, G, p.NT, p.NR, p.slots_per_xcd, NSUB);
+    const int nslots = pl.slots(), stride = (int)(gridDim.x >> 3);
+    for (int slot = blockIdx.x >> 3; slot < nslots; slot += stride) {
+        const TileMap tm = tile_at(pl, slot);
+        if (!tm.live) continue;
+        const int cnt = p.counts[tm.g];
+        int g = tm.g;
+        typename std::conditional<BATCHED, P, const P &>::type q = p;   // the tile sees its sequence's operands (one sequence: the kernel's own block)
+        if constexpr (BATCHED) {
+            const int seq = tm.g / Gs;
+            g = tm.g - seq * Gs;                      // group inside sequence seq
+            q.a = (const uint16_t *)((const unsigned char *)p.a + (int64_t)seq * p.M * p.K);
+            q.c = p.c + (int64_t)seq * p.M * p.F;
+            q.cache = p.cache + (int64_t)seq * p.cache_bs;
+            q.indices = p.indices + (int64_t)seq * Gs * p.F;
+            if (p.scale_n > 1) q.scale_a = p.scale_a + (int64_t)seq * p.M;   // [B, M]: the sequence's row scales
+        }
+        if (tm.sub < 0) {
+            const int n0 = tm.nt * BN;
+            if (n0 >= cnt) continue;  // tiles past counts[g] are skipped
+            mm1_tile<BM, BN, BK, NST, true, 4, false, ACT, P, true, false, false, false, true>(q, smem, g, 0, n0, cnt);
+        } else {
+            const int n0 = tm.nt * BN + (tm.sub >> 1) * 64;
+            if (n0 >= cnt) continue;
+            if (g * BM + (tm.sub & 1) * 64 >= p.M) continue;   // ragged last group: no row of this sub-tile exists
+            mm1_tile<64, 64, BK, SUB_NST, true, 4, false, ACT, P, true, false, false, false, true>(q, smem, g, (tm.sub & 1) * 64, n0, cnt);
+        }
+        // the next tile's DMA lands where this tile's epilogue was reading (written out as in mm1_w4_kernel)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -2772,6 +2911,74 @@ int mm1_w4_entry(const void *a, const void *b, const uint8_t *scale_b, void *c, 
 #endif
 }
 
+// e4m3 activations x MXFP4 fc1: mm1_fp8_w4_kernel at its one tile shape -- <128 columns, 128 k a stage, 3 stages, 2 workgroups per CU> --, grid
+// and tail split as launch_mm1_w8_kernel sets them
+#ifndef CHIPMUNK_MM1_PROBES
+template <int ACT, bool BATCHED>
+int launch_mm1_fp8_w4_kernel(Mm1F8W4Params p, hipStream_t s, int B, int64_t cache_bs) {
+    constexpr int BN = 128, BK = 64, NST = 3, WPS = 2;
+    constexpr int LDS = NST * mm1_f8w4_stage(BM, BN);
+    static_assert(LDS <= 80 * 1024, "two workgroups share a CU's 160 KiB");
+    static_assert(2 * BM * BN * 2 <= LDS, "the FLAT epilogue: cache block and output image inside the ring");
+    auto kern = mm1_fp8_w4_kernel<BN, BK, NST, WPS, ACT, BATCHED>;
+    static uint64_t lds_set = 0;
+    ensure_dynamic_lds((const void *)kern, LDS, lds_set);
+    p.NT = (p.F + BN - 1) / BN;
+    const int nr_option = chipmunk_get_option("mm1_nr");   // column tiles per walk: launch_mm1_variant's
+    p.NR = nr_option > 0 ? nr_option : 4;
+    if (p.NR > p.NT) p.NR = p.NT;
+    const int resident_per_xcd = WPS * device_cu_count() / 8;
+    p.slots_per_xcd = chipmunk_get_option("mm1_no_split") ? 0 : resident_per_xcd;
+    const int tiles_per_xcd = (B * ((p.M + BM - 1) / BM) * p.NT + 7) / 8;
+    const int per_xcd = tiles_per_xcd < resident_per_xcd ? tiles_per_xcd : resident_per_xcd;
+    if constexpr (BATCHED) {
+        Mm1F8W4Batch q;
+        static_cast<Mm1F8W4Params &>(q) = p;
+        q.B = B, q.cache_bs = cache_bs;
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(256), LDS, s, q);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(256), LDS, s, p);
+    }
+    CM_LAUNCH_CHECK();
+    return CHIPMUNK_OK;
+}
+template <bool BATCHED>
+int launch_mm1_fp8_w4(const Mm1F8W4Params &p, int act, hipStream_t s, int B, int64_t cache_bs) {
+    switch (act) {
+        case CHIPMUNK_ACT_GELU_TANH: return launch_mm1_fp8_w4_kernel<0, BATCHED>(p, s, B, cache_bs);
+        case CHIPMUNK_ACT_SILU: return launch_mm1_fp8_w4_kernel<1, BATCHED>(p, s, B, cache_bs);
+        default: return launch_mm1_fp8_w4_kernel<2, BATCHED>(p, s, B, cache_bs);
+    }
+}
+#endif
+
+// B > 0: the *_batched entry; gm: the *_gm entry, as mm1_w8_entry
+int mm1_fp8_w4_entry(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache, const int32_t *indices,
+                     const int32_t *counts, const float *scale_a, int scale_n, int M, int K, int F, int ldc, int act, int update_cache,
+                     hipStream_t stream, int B = 0, int64_t cache_bs = 0, bool gm = false) {
+#ifdef CHIPMUNK_MM1_PROBES
+    CM_CHECK(false, "csp_mlp_mm1_fp8_w4: not part of the probe-forms build");
+#else
+    CM_CHECK(a, "csp_mlp_mm1_fp8_w4: a is null");
+    CM_CHECK(b, "csp_mlp_mm1_fp8_w4: b is null");
+    CM_CHECK(scale_b, "csp_mlp_mm1_fp8_w4: scale_b is null");
+    CM_CHECK(c, "csp_mlp_mm1_fp8_w4: c is null");
+    CM_CHECK(pa_cache, "csp_mlp_mm1_fp8_w4: pa_cache is null");
+    CM_CHECK(scale_a, "csp_mlp_mm1_fp8_w4: scale_a is null");
+    CM_CHECK((((uintptr_t)b | (uintptr_t)scale_b | (uintptr_t)scale_a) & 3) == 0, "csp_mlp_mm1_fp8_w4: b, scale_b and scale_a must be 4-byte aligned");
+    CM_CHECK(scale_n == 1 || scale_n == M, "csp_mlp_mm1_fp8_w4: scale_n must be 1 (one reciprocal scale) or M = %d (one per token row), got %d", M,
+             scale_n);
+    // (K % 128: a stage is 128 k, and a row's e8m0 bytes are whole dwords, the unit they travel in)
+    if (int e = check_mm1("csp_mlp_mm1_fp8_w4", true, indices, counts, M, K, F, ldc, B, cache_bs, 128, true, act, update_cache, 1, gm)) return e;
+    Mm1F8W4Params p;
+    static_cast<Mm1Params &>(p) = {(const uint16_t *)a, (const uint16_t *)b, (const uint16_t *)bias, (uint16_t *)pa_cache,
+                                   (uint16_t *)c, indices, counts, M, K, F, 0, 0, 0, 0, update_cache, nullptr, nullptr, ldc};
+    p.scale_a = scale_a, p.scale_e8 = scale_b, p.scale_n = scale_n;
+    if (gm) p.gs = F * BM, B = B == 1 ? 0 : B;
+    return B > 0 ? launch_mm1_fp8_w4<true>(p, act, stream, B, cache_bs) : launch_mm1_fp8_w4<false>(p, act, stream, 1, 0);
+#endif
+}
+
 // Gated MXFP4 gate / up: mm1_glu_w4_kernel at its one tile shape -- <128 B rows = 64 packed columns, k step 64, 3 stages, 2 workgroups per CU> --,
 // the grid as launch_mm1_glu_w8_kernel sets it (no tail split)
 #ifndef CHIPMUNK_MM1_PROBES
@@ -2885,6 +3092,29 @@ extern "C" int chipmunk_csp_mlp_mm1_w4_gm(const void *a, const void *b, const ui
     if (int e = check_mlp_batch(B, M)) return e;
     return mm1_w4_entry(a, b, scale_b, c, bias, pa_cache, indices, counts, M, K, F, BM, act, update_cache, (hipStream_t)stream, B,
                         cache_batch_stride, true);
+}
+
+// ---- e4m3 activations x MXFP4 fc1 (include/chipmunk_hip.h, "MXFP4 fc1, e4m3 activations")
+extern "C" int chipmunk_csp_mlp_mm1_fp8_w4(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
+                                           const int32_t *indices, const int32_t *counts, const float *scale_a, int scale_n, int M, int K, int F,
+                                           int ldc, int act, int update_cache, void *stream) {
+    return mm1_fp8_w4_entry(a, b, scale_b, c, bias, pa_cache, indices, counts, scale_a, scale_n, M, K, F, ldc, act, update_cache,
+                            (hipStream_t)stream);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_w4_batched(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias,
+                                                   void *pa_cache, const int32_t *indices, const int32_t *counts, const float *scale_a,
+                                                   int scale_n, int M, int K, int F, int ldc, int act, int update_cache, int B,
+                                                   int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_fp8_w4_entry(a, b, scale_b, c, bias, pa_cache, indices, counts, scale_a, scale_n, M, K, F, ldc, act, update_cache,
+                            (hipStream_t)stream, B, cache_batch_stride);
+}
+extern "C" int chipmunk_csp_mlp_mm1_fp8_w4_gm(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
+                                              const int32_t *indices, const int32_t *counts, const float *scale_a, int scale_n, int M, int K,
+                                              int F, int act, int update_cache, int B, int64_t cache_batch_stride, void *stream) {
+    if (int e = check_mlp_batch(B, M)) return e;
+    return mm1_fp8_w4_entry(a, b, scale_b, c, bias, pa_cache, indices, counts, scale_a, scale_n, M, K, F, BM, act, update_cache,
+                            (hipStream_t)stream, B, cache_batch_stride, true);
 }
 
 // ---- gated weight-only e4m3 gate / up (include/chipmunk_hip.h, "gated fp8, weight-only")

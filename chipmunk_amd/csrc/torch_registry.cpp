@@ -747,6 +747,49 @@ void csp_mlp_mm1_w4(at::Tensor a, at::Tensor b, at::Tensor scale_b, at::Tensor c
                                       cur_stream(a)), who);
 }
 
+// addition: GEMM1 over the MXFP4 weight of csp_mlp_mm1_w4 with e4m3 activations on the block-scaled MFMA (chipmunk_csp_mlp_mm1_fp8_w4): a
+// float8_e4m3fn, b / scale_b as csp_mlp_mm1_w4 takes them, scale_a the float32 reciprocal scale of a -- one element, or one per token row ([M];
+// [B, M] for a batched a) --, c = bf16(act((f(a) W^T) * scale_a + bias) - cache).  update_cache is an integer (0 / 1) that the library checks.
+void csp_mlp_mm1_fp8_w4(at::Tensor a, at::Tensor b, at::Tensor scale_b, at::Tensor c, const c10::optional<at::Tensor> &bias, at::Tensor pa_cache,
+                        at::Tensor indices, at::Tensor counts, at::Tensor scale_a, std::string act, int64_t update_cache) {
+    const char *who = "csp_mlp_mm1_fp8_w4";
+    CHECK_DEV(a); CHECK_DEV(b); CHECK_DEV(scale_b); CHECK_DEV(c); CHECK_DEV(pa_cache); CHECK_DEV(indices); CHECK_DEV(counts); CHECK_DEV(scale_a);
+    TORCH_CHECK(a.scalar_type() == at::kFloat8_e4m3fn, who, ": a must be float8_e4m3fn (OCP; gfx950 has no fnuz)");
+    CHECK_BF16(c); CHECK_BF16(pa_cache);
+    CHECK_I32(indices); CHECK_I32(counts);
+    CHECK_CONTIG(a); CHECK_CONTIG(c); CHECK_CONTIG(indices); CHECK_CONTIG(counts);
+    const int64_t Kw = a.size(-1);
+    TORCH_CHECK(Kw % 128 == 0, who, ": K must be a multiple of 128 (got ", Kw, ")");
+    TORCH_CHECK(b.scalar_type() == at::kByte && b.dim() == 2 && b.size(1) * 2 == Kw && b.is_contiguous() && b.device() == a.device(), who,
+                ": b must be a contiguous uint8 tensor [F, K / 2] on the device of a (two e2m1 elements a byte)");
+    TORCH_CHECK(scale_b.scalar_type() == at::kByte && scale_b.dim() == 2 && scale_b.size(0) == b.size(0) && scale_b.size(1) * 32 == Kw &&
+                    scale_b.is_contiguous() && scale_b.device() == a.device(),
+                who, ": scale_b must be a contiguous uint8 tensor [F, K / 32] on the device of a (one e8m0 byte per 32 k)");
+    const Mm1Shape sh = mm1_shape(a, b, c, nullptr, pa_cache, indices, counts, true, 2);
+    TORCH_CHECK(scale_a.scalar_type() == at::kFloat && scale_a.is_contiguous() && scale_a.device() == a.device(), who,
+                ": scale_a must be a contiguous float32 tensor on the device of a");
+    TORCH_CHECK(scale_a.numel() == 1 || (a.dim() == 2 && scale_a.dim() == 1 && scale_a.size(0) == sh.M) ||
+                    (a.dim() == 3 && scale_a.dim() == 2 && scale_a.size(0) == sh.B && scale_a.size(1) == sh.M),
+                who, ": scale_a must have one element, or be [M] with one reciprocal scale per row of a ([B, M] for a batched a)");
+    const void *bp = optional_bias(bias, "bias", sh.F);
+    const int code = act_code(who, act);
+    c10::DeviceGuard guard(a.device());
+    int *ip = indices.data_ptr<int>(), *cp = counts.data_ptr<int>();
+    const int M = (int)sh.M, K = (int)sh.K, F = (int)sh.F, ldc = (int)sh.ldc, sn = scale_a.numel() == 1 ? 1 : M;
+    const int upd = (int)std::max<int64_t>(-1, std::min<int64_t>(update_cache, 2));   // (out of range stays out of range: the library refuses it)
+    const uint8_t *sp = scale_b.data_ptr<uint8_t>();
+    const float *ap = scale_a.data_ptr<float>();
+    if (sh.gm)
+        check(chipmunk_csp_mlp_mm1_fp8_w4_gm(a.data_ptr(), b.data_ptr(), sp, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, ap, sn, M, K, F, code,
+                                             upd, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else if (sh.batched())
+        check(chipmunk_csp_mlp_mm1_fp8_w4_batched(a.data_ptr(), b.data_ptr(), sp, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, ap, sn, M, K, F,
+                                                  ldc, code, upd, (int)sh.B, sh.cache_bs, cur_stream(a)), who);
+    else
+        check(chipmunk_csp_mlp_mm1_fp8_w4(a.data_ptr(), b.data_ptr(), sp, c.data_ptr(), bp, pa_cache.data_ptr(), ip, cp, ap, sn, M, K, F, ldc,
+                                          code, upd, cur_stream(a)), who);
+}
+
 // addition: csp_mlp_mm1_glu over e4m3 gate / up weights with bf16 activations (gated weight-only fp8, chipmunk_csp_mlp_mm1_glu_w8): scale_gate /
 // scale_up are the weights' float32 reciprocal scales -- one element, or [F] with one per row --,
 // c = bf16(fma(act((a f(b_gate)^T) * scale_gate + bias_gate), (a f(b_up)^T) * scale_up + bias_up, -cache))
@@ -1744,6 +1787,7 @@ TORCH_LIBRARY(chipmunk, m) {
     m.def("csp_mlp_mm1_w4(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_w8(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_w8(Tensor a, Tensor b_gate, Tensor b_up, Tensor scale_gate, Tensor scale_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
+    m.def("csp_mlp_mm1_fp8_w4(Tensor a, Tensor b, Tensor scale_b, Tensor(c!) c, Tensor? bias, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, Tensor scale_a, str act, int update_cache) -> ()");
     m.def("csp_mlp_mm1_glu_w4(Tensor a, Tensor b_gate, Tensor b_up, Tensor scale_gate, Tensor scale_up, Tensor(c!) c, Tensor? bias_gate, Tensor? bias_up, Tensor(pa!) pa_cache, Tensor indices, Tensor counts, str act, bool update_cache) -> ()");
     m.def("w8_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
     m.def("w4_linear(Tensor x, Tensor w, Tensor scale_b, Tensor? bias, Tensor(a!) y) -> ()");
@@ -1829,6 +1873,7 @@ TORCH_LIBRARY_IMPL(chipmunk, CUDA, m) {
     m.impl("csp_mlp_mm1_w8", &csp_mlp_mm1_w8);
     m.impl("csp_mlp_mm1_w4", &csp_mlp_mm1_w4);
     m.impl("csp_mlp_mm1_glu_w8", &csp_mlp_mm1_glu_w8);
+    m.impl("csp_mlp_mm1_fp8_w4", &csp_mlp_mm1_fp8_w4);
     m.impl("csp_mlp_mm1_glu_w4", &csp_mlp_mm1_glu_w4);
     m.impl("w8_linear", &w8_linear);
     m.impl("w4_linear", &w4_linear);

@@ -20,7 +20,9 @@ full steps and the block-mean probe call its forward (the bf16 linear layer over
 
 An MXFP4 ``fc1`` (``W4Linear``, ``mlp.mxfp4_fc1``: packed e2m1 weight with one e8m0 scale per 32 ``k``, ``in_features % 128 == 0``) is the same
 route one format down: forward on dense and full steps and for the probe, ``csp_mlp_mm1_w4`` with ``fc1.weight`` / ``fc1.block_scale`` on the
-sparse steps -- the bits of the bf16 layer over ``fc1.widened()``.  A ``W4Linear`` ``fc2`` is refused.
+sparse steps -- the bits of the bf16 layer over ``fc1.widened()``.  A ``W4Linear`` ``fc2`` is refused.  With ``mlp.mxfp4_fp8_act`` the sparse
+steps quantise ``x`` to e4m3, one scale per token (``fc1.quantize_input_rowwise``), and run ``csp_mlp_mm1_fp8_w4`` instead -- e4m3 x fp4 on the
+block-scaled MFMA; a recomputed column then carries the e4m3 error of its fresh value, and nothing accumulates.
 
 An MXFP4 ``fc2`` (``W4LinearT``, ``mlp.mxfp4_fc2``: ``fc2.weight^T`` packed, one e8m0 scale per 32 output features, ``out_features % 128 == 0``)
 is stored once, in the orientation GEMM2 gathers: ``fc2w_T`` IS ``fc2.weight_t``, the sparse steps run ``csp_mlp_mm2_w4`` with
@@ -360,6 +362,9 @@ class SparseDiffMlp(SparseDeltaMlp):
         scale_a = scale_b = fc1_scale = None
         if getattr(fc1, "weight_format", None) == "mxfp4":      # W4Linear: x stays bf16, GEMM1 gathers packed e2m1 rows of fc1.weight
             fc1_scale = fc1.block_scale                         # ... and their e8m0 block scales [F, K / 32]
+            if GLOBAL_CONFIG["mlp"]["mxfp4_fp8_act"]:           # ... or x in e4m3, one scale per token: csp_mlp_mm1_fp8_w4
+                x, scale_a = fc1.quantize_input_rowwise(x)      # [B, N]
+                scale_a = scale_a if batched else scale_a[0]
         elif getattr(fc1, "weight_only", False):                # W8Linear: x stays bf16, GEMM1 gathers e4m3 rows of fc1.weight
             fc1_scale = fc1.scale_reciprocal                    # one number, or one per fc1 column: [F]
         elif fc1.weight.dtype == torch.float8_e4m3fn and getattr(fc1, "scaling", "tensor") == "row":

@@ -397,6 +397,18 @@ class W4Linear(nn.Module):
         w = self.widened()
         return torch.nn.functional.linear(x, w if x.dtype == w.dtype else w.to(x.dtype), self.bias)
 
+    def quantize_input_rowwise(self, x: torch.Tensor):
+        """``x [..., K] -> (xq [..., K] float8_e4m3fn, scale_recip [...] fp32)``, one dynamic scale per row of the last dimension, for the
+        sparse steps under ``mlp.mxfp4_fp8_act`` (``csp_mlp_mm1_fp8_w4``): the one-pass kernel ``quantize_fp8_rowwise`` on the GPU, which takes
+        bf16 rows of ``K % 16 == 0``, ``K <= ROWWISE_MAX_K``; ``quantize_rowwise_torch`` (the same chain) everywhere else."""
+        if not x.is_cuda:
+            return quantize_rowwise_torch(x, 448.0)
+        K = x.shape[-1]
+        if x.dtype != torch.bfloat16 or K % 16 or not 0 < K <= ROWWISE_MAX_K or x.numel() == 0:
+            raise ValueError(f"W4Linear.quantize_input_rowwise: x must be a non-empty bfloat16 tensor with K % 16 == 0 and K <= ROWWISE_MAX_K = "
+                             f"{ROWWISE_MAX_K} columns on the GPU (got {x.dtype} {tuple(x.shape)})")
+        return torch.ops.chipmunk.quantize_fp8_rowwise(x, 448.0)
+
     @classmethod
     def from_mx(cls, weight: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor] = None) -> "W4Linear":
         """A layer over tensors already in the format: ``weight`` ``[out, in / 2]`` uint8 or ``float4_e2m1fn_x2``, ``scales``

@@ -328,6 +328,23 @@ def _register():
         torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_w4: unknown activation '{act}'")
         return None
 
+    @lib.register_fake("chipmunk::csp_mlp_mm1_fp8_w4")
+    def _(a, b, scale_b, c, bias, pa_cache, indices, counts, scale_a, act, update_cache):
+        # as csp_mlp_mm1_w4, with an e4m3 a and its float32 reciprocal scale: one element, or one per token row ([M]; [B, M] for a batch)
+        torch._check(a.dtype == torch.float8_e4m3fn and b.dtype == torch.uint8 and scale_b.dtype == torch.uint8,
+                     lambda: "a must be float8_e4m3fn, b and scale_b uint8")
+        torch._check(c.dtype == torch.bfloat16 and pa_cache.dtype == torch.bfloat16, lambda: "c and pa_cache must be bfloat16")
+        torch._check(a.ndim in (2, 3) and a.shape[-1] % 128 == 0, lambda: "K must be a multiple of 128")
+        torch._check(b.ndim == 2 and b.shape[1] * 2 == a.shape[-1], lambda: "b must be [F, K / 2]")
+        torch._check(scale_b.shape == (b.shape[0], a.shape[-1] // 32), lambda: "scale_b must be [F, K / 32]")
+        torch._check(c.shape == a.shape[:-1] + (b.shape[0],), lambda: "c must be [M, F] ([B, M, F] with the batch size of a)")
+        torch._check(bias is None or bias.numel() == b.shape[0], lambda: "bias must have F entries")
+        torch._check(scale_a.dtype == torch.float32 and (scale_a.numel() == 1 or scale_a.shape == a.shape[:-1]),
+                     lambda: "scale_a must be float32 with one element, or [M] ([B, M] with the batch size of a)")
+        torch._check(act in ("gelu_tanh", "silu", "gelu"), lambda: f"csp_mlp_mm1_fp8_w4: unknown activation '{act}'")
+        torch._check(update_cache in (0, 1), lambda: "update_cache must be 0 or 1")
+        return None
+
     @lib.register_fake("chipmunk::csp_mlp_mm1_glu_w8")
     def _(a, b_gate, b_up, scale_gate, scale_up, c, bias_gate, bias_up, pa_cache, indices, counts, act, update_cache):
         # as csp_mlp_mm1_glu, with e4m3 b_gate / b_up and their float32 reciprocal scales: one element each, or [F]

@@ -7,6 +7,7 @@ through the op as an int (``ops/mlp.py:42``) -- the argument is kept (value 0) a
 """
 from __future__ import annotations
 
+import functools
 from typing import Optional
 
 import torch
@@ -112,15 +113,23 @@ MXFP4_SCALES = tuple(t for t in (torch.uint8, getattr(torch, "float8_e8m0fnu", N
 def _check_mxfp4(who: str, x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, scale_a, scale_b,
                  names=("scale_a", "scale_b")) -> None:
     """The rules of an MXFP4 ``fc1`` (weight-only, ``W4Linear``): ``fc1w`` uint8 / ``float4_e2m1fn_x2`` ``[F, K / 2]`` with ``fc1_scale`` uint8 /
-    ``float8_e8m0fnu`` ``[F, K / 32]``, a bf16 ``x`` with ``K % 128 == 0``, no activation / weight scale pair.  Every violation raises
-    ``ValueError`` and names the argument."""
+    ``float8_e8m0fnu`` ``[F, K / 32]``, ``K % 128 == 0``, and either a bf16 ``x`` with no activation / weight scale pair (weight-only) or an
+    e4m3 ``x`` with ``scale_a`` -- one number, or one per token row -- and no ``scale_b``.  Every violation raises ``ValueError`` and names
+    the argument."""
     if fc1_scale.dtype not in MXFP4_SCALES:
         raise ValueError(f"{who}: fc1_scale of a {fc1w.dtype} fc1w (MXFP4) must be its e8m0 block scales, uint8 or float8_e8m0fnu; got {fc1_scale.dtype}")
-    if x.dtype != torch.bfloat16:
-        raise ValueError(f"{who}: with an MXFP4 fc1w x must be bfloat16 (got {x.dtype}): the activations are not quantised")
+    if x.dtype == torch.float8_e4m3fn:     # quantised activations (csp_mlp_mm1_fp8_w4): scale_a is theirs, one number or one per token row
+        if scale_a is None or not (scale_a.numel() == 1 or tuple(scale_a.shape) == tuple(x.shape[:-1])):
+            raise ValueError(f"{who}: a float8_e4m3fn x with an MXFP4 fc1w needs {names[0]}, its reciprocal scale: one number, or one per "
+                             f"token row {tuple(x.shape[:-1])}; got {None if scale_a is None else tuple(scale_a.shape)}")
+        if scale_a.device != x.device:
+            raise ValueError(f"{who}: {names[0]} must be on the device of x ({x.device}); got {scale_a.device}")
+        scale_a = None
+    elif x.dtype != torch.bfloat16:
+        raise ValueError(f"{who}: with an MXFP4 fc1w x must be bfloat16 (weight-only), or float8_e4m3fn with {names[0]} (got {x.dtype})")
     for name, t in zip(names, (scale_a, scale_b)):
         if t is not None:
-            raise ValueError(f"{who}: {name} must be None with an MXFP4 fc1w: a weight-only fc1 has no activation scale, and its block "
+            raise ValueError(f"{who}: {name} must be None with an MXFP4 fc1w: a bf16 x has no activation scale, and the weight's block "
                              "scales are fc1_scale")
     K = x.shape[-1]
     if K % 128:
@@ -154,12 +163,40 @@ def _launch_mm1_w4(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, in
                                       fc1b, sparse_act_T, indices, counts, act, bool(update_cache))
 
 
+def mm1_fp8_w4(x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
+               sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, scale_a: torch.Tensor, act: str = "gelu_tanh",
+               update_cache: bool = False) -> None:
+    """MXFP4 GEMM1 over QUANTISED activations on the block-scaled MFMA: ``packed = bf16(act((f(x) W^T) * scale_a + fc1b) - cache)`` on the
+    kept columns with e4m3 ``x``, ``W`` as in ``mm1_w4`` and ``scale_a`` the reciprocal scale of ``x`` -- one number, or one per token row
+    (``[M]``; ``[B, M]`` for a batch; ``W4Linear.quantize_input_rowwise``).  Every product is exact in fp32; ``update_cache`` also applies the
+    scatter-add of the packed deltas to ``sparse_act_T``.  Every cache layout and batch form of ``csp_mlp_mm1_act``."""
+    if act not in GLU_ACTS:
+        raise ValueError(f"mm1_fp8_w4: unknown activation {act!r} (one of {', '.join(GLU_ACTS)})")
+    if fc1w.dtype not in MXFP4_WEIGHTS:
+        raise ValueError(f"mm1_fp8_w4: fc1w must be uint8 or float4_e2m1fn_x2 (MXFP4, two e2m1 elements a byte); got {fc1w.dtype}")
+    if x.dtype != torch.float8_e4m3fn:
+        raise ValueError(f"mm1_fp8_w4: x must be float8_e4m3fn (got {x.dtype}); a bfloat16 x takes mm1_w4")
+    _check_mxfp4("mm1_fp8_w4", x, fc1w, fc1_scale, scale_a, None)
+    _launch_mm1_fp8_w4(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache, scale_a)
+
+
+def _launch_mm1_fp8_w4(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache, scale_a) -> None:
+    """``mm1_fp8_w4`` behind its argument rules: the byte views, the float32 scale and the operator"""
+    assert sparse_act_packed.dtype == torch.bfloat16 and sparse_act_T.dtype == torch.bfloat16
+    scale = scale_a.float().reshape(1) if scale_a.numel() == 1 else scale_a.float().contiguous()
+    torch.ops.chipmunk.csp_mlp_mm1_fp8_w4(x, fc1w.view(torch.uint8).contiguous(), fc1_scale.view(torch.uint8).contiguous(), sparse_act_packed,
+                                          fc1b, sparse_act_T, indices, counts, scale, act, int(update_cache))
+
+
 def _weight_only_gemm1(who: str, x: torch.Tensor, fc1w: torch.Tensor, fc1_scale: torch.Tensor, scale_a, scale_b,
                        names=("scale_a", "scale_b")):
-    """The GEMM1 of a weight-only ``fc1`` after its argument rules, reported under the caller's name: the MXFP4 launch for a uint8 /
-    ``float4_e2m1fn_x2`` ``fc1w``, ``mm1_w8`` for everything else ``fc1_scale`` comes with."""
+    """The GEMM1 of an ``fc1`` with ``fc1_scale`` after its argument rules, reported under the caller's name: the MXFP4 launch for a uint8 /
+    ``float4_e2m1fn_x2`` ``fc1w`` -- weight-only under a bf16 ``x``, ``csp_mlp_mm1_fp8_w4`` with ``scale_a`` under an e4m3 ``x`` --, ``mm1_w8``
+    for everything else ``fc1_scale`` comes with."""
     if fc1w.dtype in MXFP4_WEIGHTS:
         _check_mxfp4(who, x, fc1w, fc1_scale, scale_a, scale_b, names)
+        if x.dtype == torch.float8_e4m3fn:
+            return functools.partial(_launch_mm1_fp8_w4, scale_a=scale_a)
         return _launch_mm1_w4
     _check_fc1_scale(who, x, fc1w, fc1_scale, scale_a, scale_b, names)
     return mm1_w8
@@ -170,7 +207,8 @@ def mm1(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc
         scale_a: Optional[torch.Tensor] = None, scale_b: Optional[torch.Tensor] = None, fc1_scale: Optional[torch.Tensor] = None,
         act: str = "gelu_tanh") -> None:
     fc1_scale, act = _positional_act(fc1_scale, act)
-    if fc1_scale is not None:      # weight-only fc1 under a bf16 x: e4m3 fc1w (csp_mlp_mm1_w8) or MXFP4 (csp_mlp_mm1_w4); the cache is left to the scatter-add
+    if fc1_scale is not None:      # weight-only fc1 under a bf16 x: e4m3 fc1w (csp_mlp_mm1_w8) or MXFP4 (csp_mlp_mm1_w4); MXFP4 under an e4m3 x
+                                   # with scale_a: csp_mlp_mm1_fp8_w4; the cache is left to the scatter-add
         gemm1 = _weight_only_gemm1("mm1", x, fc1w, fc1_scale, scale_a, scale_b)
         return gemm1(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache=False)
     # (the reference asserts x is bf16 even on its fp8 branch, one of the reasons that branch cannot run as shipped)
@@ -210,9 +248,17 @@ def mm1_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Te
 
 def mm1_fp8_scatter(x: torch.Tensor, fc1w: torch.Tensor, sparse_act_packed: torch.Tensor, fc1b: Optional[torch.Tensor],
                     sparse_act_T: torch.Tensor, indices: torch.Tensor, counts: torch.Tensor, scale_a: torch.Tensor,
-                    scale_b: torch.Tensor, act: str = "gelu_tanh") -> None:
+                    scale_b: Optional[torch.Tensor], fc1_scale: Optional[torch.Tensor] = None, act: str = "gelu_tanh") -> None:
     """fp8 GEMM1 + ``csp_scatter_add`` of its output into ``sparse_act_T`` in one kernel (the fp8 counterpart of ``mm1_scatter``;
-    bit-identical in the packed deltas and in the cache to ``csp_mlp_mm1_fp8`` followed by the scatter-add)."""
+    bit-identical in the packed deltas and in the cache to ``csp_mlp_mm1_fp8`` followed by the scatter-add).  With ``fc1_scale`` -- the e8m0
+    block scales of an MXFP4 ``fc1w`` -- the GEMM1 is ``csp_mlp_mm1_fp8_w4``: ``scale_a`` one number or one per token row, ``scale_b`` None."""
+    fc1_scale, act = _positional_act(fc1_scale, act)
+    if fc1_scale is not None:
+        if x.dtype != torch.float8_e4m3fn or fc1w.dtype not in MXFP4_WEIGHTS:
+            raise ValueError(f"mm1_fp8_scatter: fc1_scale comes with a float8_e4m3fn x and an MXFP4 fc1w (uint8 / float4_e2m1fn_x2); got x "
+                             f"{x.dtype} and fc1w {fc1w.dtype}")
+        gemm1 = _weight_only_gemm1("mm1_fp8_scatter", x, fc1w, fc1_scale, scale_a, scale_b)
+        return gemm1(x, fc1w, fc1_scale, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act, update_cache=True)
     assert x.dtype == torch.float8_e4m3fn and fc1w.dtype == torch.float8_e4m3fn
     default = _default_form("mm1_fp8_scatter", act, fc1b) and not group_major(x, sparse_act_T)      # (the name is checked before anything else)
     if _row_scales("mm1_fp8_scatter", x, fc1w, scale_a, scale_b):   # update_cache 2: the scatter-add of the deltas
@@ -374,7 +420,8 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
     # fc1_scale (W8Linear.scale_reciprocal; the sibling of fc2_scale): fc1w is e4m3 under a bf16 x, weight-only -- GEMM1 is csp_mlp_mm1_w8, with
     # its own scatter-add or (mlp.fused_scatter off) the scatter-add behind it; mm1_scale_a / mm1_scale_b must then be None.
     # fc1w uint8 / float4_e2m1fn_x2 [F, K1 / 2] with fc1_scale uint8 / float8_e8m0fnu [F, K1 / 32] (W4Linear.weight / .block_scale): MXFP4,
-    # GEMM1 is csp_mlp_mm1_w4 in the same place.
+    # GEMM1 is csp_mlp_mm1_w4 in the same place.  The same fc1w / fc1_scale under an e4m3 x with mm1_scale_a -- one number, or one per token
+    # row -- and no mm1_scale_b: csp_mlp_mm1_fp8_w4, quantised activations x MXFP4 weights on the block-scaled MFMA.
     # sparse_act_T of one dimension more than x ([G, F, 128] / [B, G, F, 128]) is the group-major cache: see group_major.  Otherwise:
     # M is any positive row count (ceil(M / 128) groups, the last one short); sparse_act_T is [F, M], contiguous or -- required when
     # M % 8 != 0 -- the [:, :M] view of a [F, ldc] buffer with ldc % 8 == 0; x and cached_out may be row views of larger buffers.
@@ -402,7 +449,11 @@ def run_e2e(x: torch.Tensor, fc1w: torch.Tensor, fc1b: Optional[torch.Tensor], f
     if fc1_scale is not None:
         _weight_only_gemm1("run_e2e", x, fc1w, fc1_scale, mm1_scale_a, mm1_scale_b, ("mm1_scale_a", "mm1_scale_b"))
         fused = bool(x.is_cuda and amd_key("mlp", "fused_scatter"))
-        (mm1_scatter if fused else mm1)(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act=act, fc1_scale=fc1_scale)
+        if x.dtype == torch.float8_e4m3fn:   # (an MXFP4 fc1w: the rules above admit no other)
+            (mm1_fp8_scatter if fused else mm1)(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, mm1_scale_a, mm1_scale_b,
+                                                act=act, fc1_scale=fc1_scale)
+        else:
+            (mm1_scatter if fused else mm1)(x, fc1w, sparse_act_packed, fc1b, sparse_act_T, indices, counts, act=act, fc1_scale=fc1_scale)
         return _after_gemm1(fused, *tail)
     if (x.is_cuda and fc1w.dtype == torch.bfloat16
             and amd_key("mlp", "fused_scatter")):
@@ -573,5 +624,5 @@ def run_e2e_glu_w4(x: torch.Tensor, w_gate: torch.Tensor, w_up: torch.Tensor, sc
                    x, w_gate, w_up, fc2w_T, indices, counts, sparse_act_T, cached_out, num_sms_scatter_add, fc2_scale)
 
 
-__all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_w8", "mm1_w4", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
+__all__ = ["group_major", "scatter_add_gm", "mm1", "mm1_w8", "mm1_w4", "mm1_fp8_w4", "mm1_scatter", "mm1_fp8_scatter", "mm2_fused", "mm2_unfused", "run_e2e", "csp_mlp_mm2", "csp_mlp_mm1_fp8",
            "mm1_glu", "run_e2e_glu", "mm1_glu_fp8", "run_e2e_glu_fp8", "mm1_glu_w8", "run_e2e_glu_w8", "mm1_glu_w4", "run_e2e_glu_w4"]

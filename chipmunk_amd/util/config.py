@@ -148,6 +148,12 @@ AMD_EXTRA_KEYS: Dict[str, Any] = {
     # scale per 32 k, 4.25 bits a weight, bf16 activations -- and SparseDiffMlp's sparse steps gather those rows (csp_mlp_mm1_w4: the bits of
     # the bf16 GEMM1 on the widened weight).  Every other layer gets what it gets without the key.  Off by default: nothing changes.
     "mlp.mxfp4_fc1": False,
+    # e4m3 activations over an MXFP4 fc1 (not in the reference): SparseDiffMlp's sparse steps over a W4Linear fc1 quantise the step's x to
+    # e4m3 with one scale per token (W4Linear.quantize_input_rowwise) and run csp_mlp_mm1_fp8_w4 -- e4m3 x fp4 on the block-scaled MFMA, the
+    # e8m0 block scales in the instruction -- instead of csp_mlp_mm1_w4.  Dense and full steps and the block-mean probe keep calling the
+    # layer's forward on the bf16 x.  A recomputed column then carries the e4m3 quantisation error of its FRESH value; nothing accumulates,
+    # because cache += delta replaces the column with that value.  Off by default: nothing changes.
+    "mlp.mxfp4_fp8_act": False,
     # W4Linear.forward for few rows (not in the reference): a bf16 GPU input of at most this many rows (all leading dimensions flattened)
     # runs ops.w4_linear -- the packed e2m1 weight and its e8m0 bytes are read once and widened in registers, the block scale applied at the
     # conversion -- instead of building the whole bf16 weight for F.linear; what SparseDiffMlp's block-mean probe fc1(block_mean(x)) needs on
@@ -208,6 +214,7 @@ BASE_CONFIG["mlp"]["w8_stream_rows"] = AMD_EXTRA_KEYS["mlp.w8_stream_rows"]
 BASE_CONFIG["mlp"]["w8_gated"] = AMD_EXTRA_KEYS["mlp.w8_gated"]
 BASE_CONFIG["mlp"]["mxfp4_gated"] = AMD_EXTRA_KEYS["mlp.mxfp4_gated"]
 BASE_CONFIG["mlp"]["mxfp4_fc1"] =AMD_EXTRA_KEYS["mlp.mxfp4_fc1"]
+BASE_CONFIG["mlp"]["mxfp4_fp8_act"] = AMD_EXTRA_KEYS["mlp.mxfp4_fp8_act"]
 BASE_CONFIG["mlp"]["w4_stream_rows"] = AMD_EXTRA_KEYS["mlp.w4_stream_rows"]
 BASE_CONFIG["attn"]["top_p"] = AMD_EXTRA_KEYS["attn.top_p"]
 BASE_CONFIG["attn"]["top_p_min_keys"] = AMD_EXTRA_KEYS["attn.top_p_min_keys"]

@@ -396,6 +396,32 @@ int chipmunk_csp_mlp_mm1_w4_batched(const void *a, const void *b, const uint8_t 
                                     const int32_t *indices, const int32_t *counts, int M, int K, int F, int ldc, int act,
                                     int update_cache, int B, int64_t cache_batch_stride, void *stream);
 
+/* MXFP4 fc1, e4m3 activations (W4A8): GEMM1 over the MXFP4 weight of chipmunk_csp_mlp_mm1_w4 with QUANTISED activations, on the block-scaled
+ * matrix instruction v_mfma_scale_f32_32x32x64_f8f6f4 (no reference counterpart).  a [M,K] OCP e4m3 bytes (float8_e4m3fn); b [F, K/2] and
+ * scale_b [F, K/32] exactly as chipmunk_csp_mlp_mm1_w4 takes them (nibble order, e8m0 bytes); scale_a fp32 on the device, the RECIPROCAL
+ * quantisation scale of a: one number (scale_n == 1) or one per token row (scale_n == M; [B, M] for a batch); bias bf16 [F] or NULL (= zero).
+ * With i = idx[g,j], f the exact e4m3 -> fp32 widening and W[i,k] = e2m1(b[i,k]) * 2^(scale_b[i,k/32] - 127):
+ *   S[m,j] = sum_k f(a[m,k]) * W[i,k]                          fp32 accumulators from zero
+ *   t      = act( S * scale_a[m or 0] + bias[i] )              the scale, then the bias, each rounded in fp32, never an fma
+ *   c[m,j] = bf16( t - pa_cache[i, m] )                        one rounding
+ * Every product is exact in fp32 (e4m3 x e2m1 x a power of two); only the accumulation order is the hardware's.  The block scales are applied
+ * by the instruction's scale operand (one e8m0 byte per lane = per row and 32 k), not by a multiply or a conversion; the A-side scale operand
+ * is the byte 127 (1.0).  Scale byte 255 and e4m3 NaN bytes are outside the contract and not looked for.  act is CHIPMUNK_ACT_*; update_cache
+ * 0 leaves the cache, 1 also applies the scatter-add of c, as chipmunk_csp_mlp_mm1_w4.  Contract of chipmunk_csp_mlp_mm1_w4 and its
+ * *_batched / *_gm forms: any M >= 1 (ragged last group), ldc >= M, ldc % 8 == 0, F % 64 == 0, K % 128 == 0, F*K, M*K and F*ldc below 2^31.
+ * A null a / b / scale_b / c / pa_cache / scale_a (named in the message), b, scale_b or scale_a off 4-byte alignment, a scale_n other than 1
+ * or M, a K off its multiple, an unknown act or an update_cache outside 0 / 1 returns CHIPMUNK_ERR_INVALID with a message, before anything
+ * is enqueued.  No element of scale_a at or past scale_n (B * M for a batch with row scales) is read.  Not part of the probe-forms build. */
+int chipmunk_csp_mlp_mm1_fp8_w4(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
+                                const int32_t *indices, const int32_t *counts, const float *scale_a, int scale_n, int M, int K, int F,
+                                int ldc, int act, int update_cache, void *stream);
+int chipmunk_csp_mlp_mm1_fp8_w4_batched(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
+                                        const int32_t *indices, const int32_t *counts, const float *scale_a, int scale_n, int M, int K,
+                                        int F, int ldc, int act, int update_cache, int B, int64_t cache_batch_stride, void *stream);
+int chipmunk_csp_mlp_mm1_fp8_w4_gm(const void *a, const void *b, const uint8_t *scale_b, void *c, const void *bias, void *pa_cache,
+                                   const int32_t *indices, const int32_t *counts, const float *scale_a, int scale_n, int M, int K, int F,
+                                   int act, int update_cache, int B, int64_t cache_batch_stride, void *stream);
+
 /* gated fp8, weight-only: chipmunk_csp_mlp_mm1_glu[_batched|_gm] over e4m3 gate / up weights with bf16 activations (no reference
  * counterpart).  a [M,K] bf16; b_gate / b_up [F,K] OCP e4m3 bytes (float8_e4m3fn), row stride K: two weights, or the halves of one
  * fused [2F,K] projection in either order; scale_gate / scale_up fp32 on the device, each weight's RECIPROCAL quantisation scale: one

@@ -2,7 +2,7 @@
 """Per-kernel micro-benchmark at the BASELINE shapes: back-to-back launches inside one HIP-event bracket, so the
 number is kernel time (comparable with rocprofv3's average duration), not host launch latency.
 
-usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm2_w4 mm2_w4_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_glu_w8 mm1_glu_w4 w8_probe w8_probe_wan w8_probe_hunyuan w4_probe w4_probe_wan w4_probe_hv scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
+usage: python tools/kbench.py [mm1 mm1s mm1_act mm1_glu mm1_glu_fp8 mm2 mm2_w8 mm2_w8_wan mm2_w4 mm2_w4_wan mm1_w8 mm1_w8_wan mm1_w4 mm1_w4_wan mm1_fp8_w4 mm1_fp8_w4_wan mm1_glu_w8 mm1_glu_w4 w8_probe w8_probe_wan w8_probe_hunyuan w4_probe w4_probe_wan w4_probe_hv scatter fp8_wan fp8_rs_wan fp8_wan_groups mm1s_groups to_groups mm2_wan fp8_wan_ragged fp8_wan_ragged_pitched mm2_wan_ragged mm1s_hunyuan mm2_hunyuan csp_flux csp_hunyuan dense_flux colsum_flux maskstep_hunyuan topk m2i copy group_delta] [--variants 0,1,2]
 """
 import argparse
 import os
@@ -393,6 +393,67 @@ def bench_mm1_w4(M=4352, K=3072, F=12288, keep=3840):
     print(f"mm1_w4  mxfp4 rows: {med['w4']:8.1f} us  [{min(t['w4']):.1f} .. {max(t['w4']):.1f}]  {flops/med['w4']/1e6:7.1f} TFLOP/s   {tag}")
     print(f"mm1s    bf16 rows : {med['bf16']:8.1f} us  [{min(t['bf16']):.1f} .. {max(t['bf16']):.1f}]  {flops/med['bf16']/1e6:7.1f} TFLOP/s")
     print(f"mm1_w4 / mm1s     : {med['w4'] / med['bf16']:8.3f}")
+
+
+def bench_mm1_fp8_w4(M=4352, K=3072, F=12288, keep=3840):
+    """The e4m3 x MXFP4 GEMM1 with its scatter-add (csp_mlp_mm1_fp8_w4: row-quantised e4m3 activations, packed e2m1 rows + e8m0 block scales on
+    the block-scaled MFMA) against csp_mlp_mm1_w4 (bf16 activations, the same weight), the row-scaled e4m3 form csp_mlp_mm1_fp8_act_rs (e4m3
+    weight rows) and the bf16 csp_mlp_mm1_scatter on the widened weight: same index lists and shape, each with its scatter-add, the four
+    alternating as bench_mm1_w4 (KB_ROUNDS, KB_LAYERS)."""
+    from chipmunk_amd.modules import W4Linear
+    from chipmunk_amd.modules.mlp_fp8 import quantize_rowwise_torch
+    g = torch.Generator(device=dev).manual_seed(0)
+    L = int(os.environ.get("KB_LAYERS", "1"))
+    G = (M + 127) // 128
+    ldc = (M + 7) // 8 * 8
+    sets = []
+    for _ in range(L):
+        q = W4Linear.from_linear(torch.nn.Linear(K, F, bias=False, device=dev, dtype=torch.bfloat16))
+        x = torch.randn(M, K, device=dev, dtype=torch.bfloat16, generator=g) * 0.5
+        xq, sa = quantize_rowwise_torch(x, 448.0)
+        w16 = q.widened()
+        w8, sb = quantize_rowwise_torch(w16, 448.0)
+        sets.append(dict(w16=w16, w4=q.weight.data, sc=q.block_scale, w8=w8.contiguous(), sb=sb.contiguous(), x=x, xq=xq.contiguous(),
+                         sa=sa.contiguous(), bias=torch.randn(F, device=dev, dtype=torch.bfloat16, generator=g) * 0.1,
+                         cache=torch.zeros(F, ldc, device=dev, dtype=torch.bfloat16)[:, :M],
+                         out=torch.empty(M, F, device=dev, dtype=torch.bfloat16)))
+    inds = rand_rows(G, F, keep, g)
+    counts = torch.full((G,), keep, dtype=torch.int32, device=dev)
+    state = {"i": 0}
+
+    def nxt():
+        state["i"] = (state["i"] + 1) % L
+        return sets[state["i"]]
+
+    def run_fp8_w4():
+        s = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_fp8_w4(s["xq"], s["w4"], s["sc"], s["out"], s["bias"], s["cache"], inds, counts, s["sa"], "gelu_tanh", 1)
+
+    def run_w4():
+        s = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_w4(s["x"], s["w4"], s["sc"], s["out"], s["bias"], s["cache"], inds, counts, "gelu_tanh", True)
+
+    def run_fp8_rs():
+        s = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_fp8_act_rs(s["xq"], s["w8"], s["out"], s["bias"], s["cache"], inds, counts, s["sa"], s["sb"], "gelu_tanh", 2)
+
+    def run_bf16():
+        s = nxt()
+        torch.ops.chipmunk.csp_mlp_mm1_scatter(s["x"], s["w16"], s["out"], s["bias"], s["cache"], inds, counts)
+    rounds = int(os.environ.get("KB_ROUNDS", "5"))
+    runs = {"fp8_w4": run_fp8_w4, "w4": run_w4, "fp8_rs": run_fp8_rs, "bf16": run_bf16}
+    t = {k: [] for k in runs}
+    for _ in range(rounds):
+        for k, fn in runs.items():
+            t[k].append(timeit(fn) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    flops = 2.0 * M * K * keep
+    tag = f"(M={M} K={K} F={F} keep={keep} layers={L}, {rounds} alternating rounds)"
+    for k, name in (("fp8_w4", "mm1_fp8_w4 e4m3 x mxfp4"), ("w4", "mm1_w4     bf16 x mxfp4"), ("fp8_rs", "mm1_fp8_rs e4m3 x e4m3 "),
+                    ("bf16", "mm1s       bf16 x bf16 ")):
+        print(f"{name}: {med[k]:8.1f} us  [{min(t[k]):.1f} .. {max(t[k]):.1f}]  {flops/med[k]/1e6:7.1f} TFLOP/s   {tag if k == 'fp8_w4' else ''}")
+    for k in ("w4", "fp8_rs", "bf16"):
+        print(f"mm1_fp8_w4 / {k:7}: {med['fp8_w4'] / med[k]:8.3f}")
 
 
 def bench_mm1_w8(M=4352, K=3072, F=12288, keep=3840):
@@ -1015,6 +1076,10 @@ def main():
             bench_mm1_w4()
         elif w == "mm1_w4_wan":       # ... at the Wan2.1 1.3B shape (K = 1 536: 12 scale dwords a row)
             bench_mm1_w4(M=32760, K=1536, F=8960, keep=2816)
+        elif w == "mm1_fp8_w4":       # e4m3 x MXFP4 GEMM1 (+ scatter-add) against mm1_w4, the row-scaled e4m3 form and mm1s at the FLUX shape
+            bench_mm1_fp8_w4()
+        elif w == "mm1_fp8_w4_wan":   # ... at the Wan2.1 1.3B shape
+            bench_mm1_fp8_w4(M=32760, K=1536, F=8960, keep=2816)
         elif w == "mm1_w8":           # weight-only fp8 GEMM1 (+ scatter-add) against mm1s at the FLUX shape, 3 840 of 12 288 columns kept
             bench_mm1_w8()
         elif w == "mm1_w8_wan":       # ... at the Wan2.1 1.3B shape: 32 760 tokens (ragged last group), K = 1 536, F = 8 960, 2 816 kept
